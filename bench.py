@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- Mrays/s of the trace loop on MI355X for the BASELINE.json workload.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run does what the headline figure needs and nothing else: set-up (scene, upload, one untimed step that
+allocates the renderer's working state), W warm-up steps, K timed steps, the result line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, ...).  --dump-outputs DIR writes the accumulator of the last timed step to
+DIR as finite float32 arrays (dump_outputs).  Everything described below beyond the headline step -- the counting
+pass and rays_per_step, the HIP-event kernel times and the roofline block, frame_checksum and the comparison with the committed line, the
+live legs, the CPU baseline and parity_check -- runs only with --full.
 
 One *step* = one complete render of the workload frame: 1920x1080 pixels x 64 frames (spp) of the
 path integrator over BASELINE config 3 (unity.tri as two BLASes, 8 instances through the TLAS =
@@ -66,7 +73,14 @@ def main():
     ap.add_argument("--ooc-n", type=int, default=2048, help="out-of-cache leg: the terrain is 2 n^2 triangles (2048: 8.4 M, pairs + primitive records 0.94 GB)")
     ap.add_argument("--ooc-spp", type=int, default=16)
     ap.add_argument("--ooc-steps", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the counting pass (rays_per_step, all_rays_mrays_per_s), "
+                    "HIP-event kernel times and the roofline block, frame_checksum and the committed-line comparison, the live legs, the CPU baseline "
+                    "and parity_check (the --no-* / --force-legs / --ooc-* / --cpu-seconds options act on these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                    "(the accumulator, as finite float32 arrays with a class file for its non-finite entries) to DIR/*.npy: see dump_outputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: start the N ranks as a CHILD process (torch.distributed.run, one rank per GPU) before
@@ -189,19 +203,23 @@ def main():
         torch.cuda.synchronize()
         r.synchronize()
 
-    # ---- untimed: counting pass (algorithmic work of this rank's rows), then warmup ----
-    r.counters()
-    if not args.no_count:
-        r.set_counting(ha.RT_COUNT_EXECUTED)  # the walk the timed kernels make (same results, fewer TLAS / instance visits than the reference's)
-        step()
-    near, occl = r.counters_split()
-    r.set_counting(False)
+    # ---- untimed: counting pass (--full: algorithmic work of this rank's rows), then warmup ----
+    if args.full:
+        r.counters()
+        if not args.no_count:
+            r.set_counting(ha.RT_COUNT_EXECUTED)  # the walk the timed kernels make (same results, fewer TLAS / instance visits than the reference's)
+            step()
+        near, occl = r.counters_split()
+        r.set_counting(False)
+    else:
+        step()  # the first step allocates the renderer's working state: once, untimed, as the counting pass does under --full
     for _ in range(args.warmup):
         step()
 
     # ---- timed region: exactly K steps ----
-    r.set_profiling(True)
-    r.profile()
+    if args.full:
+        r.set_profiling(True)
+        r.profile()
     fence()
     timed[0] = True
     t0 = time.perf_counter()
@@ -210,33 +228,34 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     timed[0] = False
-    prof = r.profile()
-    r.set_profiling(False)
+    if args.full:
+        prof = r.profile()
+        r.set_profiling(False)
 
     red_dev = "cuda" if backend == "nccl" else "cpu"
     t = torch.tensor([dt], dtype=torch.float64, device=red_dev)
-    cnt = torch.tensor([near["rays_nearest"], occl["rays_occluded"]], dtype=torch.float64, device=red_dev)
+    if args.full:
+        cnt = torch.tensor([near["rays_nearest"], occl["rays_occluded"]], dtype=torch.float64, device=red_dev)
     split = torch.tensor([timing.get("render_s", 0.0), timing.get("gather_s", 0.0)], dtype=torch.float64, device=red_dev)
     split0 = split.clone()
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
+        if args.full:
+            dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
         dist.all_reduce(split, op=dist.ReduceOp.MAX)
     dt = float(t.item())
-    rays_all = float(cnt.sum().item())  # per step, all ranks
     seen = torch.ones(1, dtype=torch.int64, device=red_dev)  # the witness that the process group really had N ranks
     if world > 1:
         dist.all_reduce(seen, op=dist.ReduceOp.SUM)
 
     failures = []
     if rank == 0:
+        if args.dump_outputs:  # (before the --full legs below reuse the accumulator)
+            dump_outputs(args.dump_outputs, acc.cpu().numpy())
         sec_per_step = dt / args.steps
         value = W * H * spp / sec_per_step / 1e6
         if args.emulate_world > 1:  # a profiling line: only rank 0's rows of the N-rank shard were rendered
             value = W * shard.count * spp / sec_per_step / 1e6
-        ext = prof["extend"]
-        launches_per_step = ext["launches"] / args.steps
-        avg_ms = ext["ms"] / max(1, ext["launches"])  # HIP events on the kernel's own stream, inside the timed steps
         out = {
             "metric": ("Mrays/s at %d×%d×%dspp" % (W, H, spp)) + (" (rank %d's rows of a %d-rank shard only: a profiling line)" % (args.emulate_rank, args.emulate_world) if args.emulate_world > 1 else ""),
             "value": round(value, 3), "unit": "Mrays/s", "n_gpus": world, "ranks_seen": int(seen.item()), "backend": backend if world > 1 else None,
@@ -248,45 +267,51 @@ def main():
                        "sampler": ("Q-learning guided indirect bounce (Dahm & Keller 2017; no reference code: PARITY UNPINNED), 16^3 cells x 64 patches, "
                                    "table updated every %d frames, rewards from samples with stream state & %d == 0" % (args.qlearn, args.qlearn_mask)) if args.qlearn else "uniform hemisphere (renderer.cpp:181)",
                        "rays_definition": "value counts primary pixel samples (reference's Mrays/s, renderer.cpp:300); all_rays counts every FindNearest + IsOccluded query"},
-            "all_rays_mrays_per_s": round(rays_all / sec_per_step / 1e6, 3),
-            "rays_per_step": {"nearest": int(cnt[0].item()), "occluded": int(cnt[1].item())},
-            # several ranks: where a step's time goes on the host's clock -- render = until the rank's own rows are complete, gather =
-            # from there until the exchange has completed on the rank (it includes waiting for the slowest share); rank 0 and the
-            # maximum over the ranks.  null on one rank (nothing is gathered) and under --qlearn (the step is several batches).
-            "render_ms": ({"rank0": round(float(split0[0].item()) / args.steps * 1e3, 3), "max": round(float(split[0].item()) / args.steps * 1e3, 3)} if world > 1 and not args.qlearn else None),
-            "gather_ms": ({"rank0": round(float(split0[1].item()) / args.steps * 1e3, 3), "max": round(float(split[1].item()) / args.steps * 1e3, 3)} if world > 1 and not args.qlearn else None),
-            "roofline": roofline_block(args, ha, near, occl, avg_ms, launches_per_step, W, H, spp, args.emulate_world if args.emulate_world > 1 else world,
-                                       {k: round(v["ms"] / args.steps, 3) for k, v in prof.items() if v["launches"]},
-                                       r.build_info(), sec_per_step, prof["connect"]),
         }
-        out["frame_checksum"] = frame_checksum(acc)
+        if args.full:
+            ext = prof["extend"]
+            launches_per_step = ext["launches"] / args.steps
+            avg_ms = ext["ms"] / max(1, ext["launches"])  # HIP events on the kernel's own stream, inside the timed steps
+            out["all_rays_mrays_per_s"] = round(float(cnt.sum().item()) / sec_per_step / 1e6, 3)  # rays per step, all ranks
+            out["rays_per_step"] = {"nearest": int(cnt[0].item()), "occluded": int(cnt[1].item())}
+        # several ranks: where a step's time goes on the host's clock -- render = until the rank's own rows are complete, gather =
+        # from there until the exchange has completed on the rank (it includes waiting for the slowest share); rank 0 and the
+        # maximum over the ranks.  null on one rank (nothing is gathered) and under --qlearn (the step is several batches).
+        out["render_ms"] = {"rank0": round(float(split0[0].item()) / args.steps * 1e3, 3), "max": round(float(split[0].item()) / args.steps * 1e3, 3)} if world > 1 and not args.qlearn else None
+        out["gather_ms"] = {"rank0": round(float(split0[1].item()) / args.steps * 1e3, 3), "max": round(float(split[1].item()) / args.steps * 1e3, 3)} if world > 1 and not args.qlearn else None
+        if args.full:
+            out["roofline"] = roofline_block(args, ha, near, occl, avg_ms, launches_per_step, W, H, spp, args.emulate_world if args.emulate_world > 1 else world,
+                                             {k: round(v["ms"] / args.steps, 3) for k, v in prof.items() if v["launches"]},
+                                             r.build_info(), sec_per_step, prof["connect"])
+            out["frame_checksum"] = frame_checksum(acc)
         out["ranks_devices"] = ranks_devices  # PCI address of every rank's GPU, in rank order (one all-gather; distinct under RCCL or the run has ended above)
         out["ranks_devices_distinct"] = bool(devices_distinct)
         # several ranks: the gathered frame must be the one-GPU frame bit for bit (rows are independent, sums are in frame order); the
         # committed one-GPU line of the same workload is the witness (its own frame was compared with the oracle's: parity_check there)
-        try:
-            ref = json.loads(open(os.path.join(ROOT, "profiles", "final_bench.json")).read().strip().splitlines()[-1])
-            if ref["metric"] == out["metric"] and not args.qlearn and args.emulate_world <= 1:
-                out["frame_checksum_of_committed_1gpu_line"] = ref["frame_checksum"]
-                out["frame_equals_committed_1gpu_frame"] = ref["frame_checksum"] == out["frame_checksum"]
-                out["committed_1gpu_line_is_of_these_kernels"] = ref["roofline"]["pmc"]["kernel_hash"] == out["roofline"]["pmc"]["kernel_hash"]
-        except Exception:
-            pass
+        if args.full:
+            try:
+                ref = json.loads(open(os.path.join(ROOT, "profiles", "final_bench.json")).read().strip().splitlines()[-1])
+                if ref["metric"] == out["metric"] and not args.qlearn and args.emulate_world <= 1:
+                    out["frame_checksum_of_committed_1gpu_line"] = ref["frame_checksum"]
+                    out["frame_equals_committed_1gpu_frame"] = ref["frame_checksum"] == out["frame_checksum"]
+                    out["committed_1gpu_line_is_of_these_kernels"] = ref["roofline"]["pmc"]["kernel_hash"] == out["roofline"]["pmc"]["kernel_hash"]
+            except Exception:
+                pass
         if int(seen.item()) != world:
             failures.append("the process group held %d ranks, not %d" % (int(seen.item()), world))
         if world > 1 and out.get("frame_equals_committed_1gpu_frame") is False and out.get("committed_1gpu_line_is_of_these_kernels"):  # same kernels, another frame: the shard or the gather is wrong
             failures.append("the gathered %d-rank frame is not the committed one-GPU frame (%s vs %s)" % (world, out["frame_checksum"], out["frame_checksum_of_committed_1gpu_line"]))
-        # ---- live legs outside the timed region (one GPU, the default workload): what the driver cannot see otherwise ----
-        plain = world == 1 and not args.qlearn and args.emulate_world <= 1 and ((args.workload == "config3" and not (args.width or args.height or args.spp)) or args.force_legs)
+        # ---- live legs outside the timed region (--full; one GPU, the default workload): what the driver cannot see otherwise ----
+        default_shape = args.full and world == 1 and not args.qlearn and args.emulate_world <= 1 and ((args.workload == "config3" and not (args.width or args.height or args.spp)) or args.force_legs)
         terrain = None
-        if plain and not args.no_legs and not args.no_cpu_baseline:  # (profiling runs pass --no-cpu-baseline: their kernel statistics are the timed steps' alone)
+        if default_shape and not args.no_legs and not args.no_cpu_baseline:  # (profiling runs pass --no-cpu-baseline: their kernel statistics are the timed steps' alone)
             t_legs = time.perf_counter()
             out["share_ms"] = share_leg(dpar, r, acc, mode, spp, H, W, sec_per_step * 1e3)
             out["tick_ms"] = tick_leg(ha, scenes, device_index)
             ooc, terrain = out_of_cache_leg(args, ha, scenes, device_index)
             out["roofline"]["hbm"]["out_of_cache_live"] = ooc
             out["gpu_leg_s"] = round(time.perf_counter() - t_legs, 2)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             t_cpu = time.perf_counter()
             can_check = not args.qlearn and args.emulate_world <= 1
             out["cpu_baseline"], out["parity_check"] = cpu_baseline(args, cfg, W, H, spp, (r, acc, mode, out["frame_checksum"]) if can_check else None)
@@ -308,6 +333,34 @@ def main():
         dist.destroy_process_group()
     if rank == 0 and failures:
         raise SystemExit("bench.py: " + "; ".join(failures))
+
+
+def dump_outputs(dirname, acc, limit=64 << 20):
+    """--dump-outputs: what the timed path hands its caller, from the last timed step: the H x W x 4 float32 accumulator (rank 0's
+    gathered frame with several ranks).  Every file holds finite values only, and together they are lossless:
+      DIR/accumulator.npy            the accumulator, its non-finite entries written as 0
+      DIR/accumulator_nonfinite.npy  H x W float32: per pixel the sum over channels c of k_c * 4**c, k = 0 finite, 1 +inf, 2 -inf,
+                                     3 NaN (a path that sees an area light directly is +inf in the reference: SURVEY.md Q7)
+    A frame whose files would exceed `limit` bytes is written as a fixed, seeded sample of its pixels instead:
+    DIR/accumulator_sample.npy, DIR/accumulator_sample_nonfinite.npy and their flat pixel indices DIR/accumulator_sample_index.npy
+    (float64, exact).  The workload is deterministic, so equal arguments give equal inputs and the files of two builds compare
+    entry for entry."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    a = np.array(acc, dtype=np.float32)
+    cls = np.zeros(a.shape, dtype=np.float32)
+    cls[np.isposinf(a)], cls[np.isneginf(a)], cls[np.isnan(a)] = 1, 2, 3
+    a[cls != 0] = 0
+    code = (cls * (4.0 ** np.arange(a.shape[-1], dtype=np.float32))).sum(axis=-1, dtype=np.float32)
+    files = {"accumulator": a, "accumulator_nonfinite": code}
+    if a.nbytes + code.nbytes > limit:
+        px = a.reshape(-1, a.shape[-1])
+        n = limit // (px.shape[1] * 4 + 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(len(px), n, replace=False))
+        files = {"accumulator_sample": px[idx], "accumulator_sample_nonfinite": code.reshape(-1)[idx],
+                 "accumulator_sample_index": idx.astype(np.float64)}
+    for name, v in files.items():
+        np.save(os.path.join(dirname, name + ".npy"), v)
 
 
 def frame_checksum(acc, rows=None):

@@ -11,7 +11,7 @@ ARGS=${BENCH_ARGS:-}
 for ENVS in "$@"; do
   OUT=gpurun_out/${TAG}_${I}
   rm -rf $OUT
-  ( export $ENVS; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --steps $STEPS --warmup 1 --no-cpu-baseline $ARGS > $OUT.log 2>&1 )
+  ( export $ENVS; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --full --steps $STEPS --warmup 1 --no-cpu-baseline $ARGS > $OUT.log 2>&1 )
   cp $OUT/*/*kernel_stats.csv gpurun_out/${TAG}_${I}_kernel_stats.csv 2>/dev/null
   cp $OUT/*/*kernel_trace.csv gpurun_out/${TAG}_${I}_kernel_trace.csv 2>/dev/null
   echo "== $ENVS"

@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."
 export RT_FUSE=0 "$@"
 OUT=gpurun_out/${TAG}_pmcq
 rm -rf $OUT; mkdir -p $OUT
-ARGS="--steps 2 --warmup 0 --no-cpu-baseline --no-count ${BENCH_ARGS:-}"
+ARGS="--full --steps 2 --warmup 0 --no-cpu-baseline --no-count ${BENCH_ARGS:-}"
 run() { name=$1; shift; timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 bench.py $ARGS > $OUT/$name.log 2>&1 || echo "pass $name failed"; }
 run sq1 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY
 run fetch FETCH_SIZE

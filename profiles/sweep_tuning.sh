@@ -4,7 +4,7 @@
 # it as it is gives identical rows.  A sweep is a rebuild per value now: profiles/bisect.sh over trees built with make EXTRA=-DRT_...=N.
 # Sweep the traversal scheduling thresholds (and the 4-wide occlusion walk) on the bench workload, all on one box.
 # Usage: profiles/sweep_tuning.sh > log
-run() { echo "$1: $(env $1 python bench.py --no-cpu-baseline --steps 4 --warmup 1 2>/dev/null | grep -o 'ms_per_step.: [0-9.]*\|kernel_ms_per_step.: {[^}]*}' | tr '\n' ' ')"; }
+run() { echo "$1: $(env $1 python bench.py --full --no-cpu-baseline --steps 4 --warmup 1 2>/dev/null | grep -o 'ms_per_step.: [0-9.]*\|kernel_ms_per_step.: {[^}]*}' | tr '\n' ' ')"; }
 run "RT_NONE=0"
 for rf in 8 12 24; do run "RT_REFILL=$rf"; done
 for ra in 16 24 48; do run "RT_REFILL_ANY=$ra"; done

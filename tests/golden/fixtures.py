@@ -1,6 +1,6 @@
 """Definitions shared by the golden-vector generator (make_golden.py, which runs the oracle) and the tests that
 read the vectors (which must not need the oracle): fixture scene list, key naming, the ray generator and
-the single-primitive scenes.  Nothing here imports the oracle or the product."""
+the single-primitive scenes, and how the vectors are stored.  Nothing here imports the oracle or the product."""
 import numpy as np
 
 RNG_SEEDS = (0, 1, 2, 61, 0x12345678, 0xDEADBEEF, 0xFFFFFFFE, 1768515948)  # the last one hashes to 0 (replaced state)
@@ -37,3 +37,34 @@ def single_primitive(b, kind):
         b.mesh_raw(1, m, np.array([[50, 50, 50, 51, 50, 50, 50, 51, 50]], np.float32))  # far away: only the light is hit
         b.area_light(11, (0.0, 0.4, 0.0), 7.0, (1, 1, 1), 0.8, (0, -1, 0))
     b.build(0)
+
+
+# The vectors are stored in two files so that each stays small: the per-fixture-scene arrays in <stem>_scenes.npz, the rest in
+# <stem>.npz (the RNG streams, hemisphere and fresnel samples, and the single-primitive ray vectors).
+def _is_scene_key(k):
+    return any(k.startswith(scene_key(name, kw) + "_") for name, kw in FIXTURE_SCENES)
+
+
+def gold_paths(path):
+    return path, path[:-len(".npz")] + "_scenes.npz"
+
+
+class Golden(dict):
+    """Both files as one mapping, read like np.load's result (['key'], .files)."""
+    @property
+    def files(self):
+        return list(self)
+
+
+def save_gold(path, out):
+    first, scenes = gold_paths(path)
+    np.savez_compressed(first, **{k: v for k, v in out.items() if not _is_scene_key(k)})
+    np.savez_compressed(scenes, **{k: v for k, v in out.items() if _is_scene_key(k)})
+
+
+def load_gold(path):
+    g = Golden()
+    for p in gold_paths(path):
+        with np.load(p) as z:
+            g.update((k, z[k]) for k in z.files)
+    return g

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/oracle_vectors.npz from the oracle (oracle/), at the sizes SURVEY.md section 8(c) lists.
+"""Generate tests/golden/oracle_vectors.npz and oracle_vectors_scenes.npz from the oracle (oracle/), at the sizes SURVEY.md section 8(c) lists.
 
 The reference has no tests, fixtures or golden images and cannot be built in this
 image without stand-ins for Windows/MSVC headers, so these vectors do NOT come from the reference:
@@ -26,7 +26,7 @@ from oracle import oracle_api as oa  # noqa: E402
 scenes = importlib.import_module("ray-and-pathtracer_amd.scenes")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from fixtures import RNG_SEEDS, FIXTURE_SCENES, scene_key, unit_rays, single_primitive  # noqa: E402
+from fixtures import RNG_SEEDS, FIXTURE_SCENES, scene_key, unit_rays, single_primitive, save_gold, gold_paths  # noqa: E402
 
 
 def generate():
@@ -122,8 +122,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "oracle_vectors.npz"))
     args = ap.parse_args()
     out = generate()
-    np.savez_compressed(args.out, **out)
-    print("wrote %d arrays to %s" % (len(out), args.out))
+    save_gold(args.out, out)
+    print("wrote %d arrays to %s" % (len(out), " and ".join(gold_paths(args.out))))
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""The HIP path (through the C ABI) against the COMMITTED golden vectors (tests/golden/oracle_vectors.npz):
+"""The HIP path (through the C ABI) against the COMMITTED golden vectors (tests/golden/oracle_vectors*.npz):
 fixed expected values that were produced by the oracle once (tests/golden/make_golden.py), reproduce under two
 compilers (tests/test_oracle_cpu.py) and do not need the oracle at test time.  Bar as everywhere: ids, t,
 normals, occlusion flags bit-exact; radiance within 1e-4 relative, non-finite pixels by class."""
@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "gol
 import fixtures as fx  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vectors.npz"))
+GOLD = fx.load_gold(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vectors.npz"))
 
 
 @pytest.mark.parametrize("kind", ["triangle", "sphere", "plane", "disk"])

@@ -476,7 +476,7 @@ def test_bench_two_ranks_equal_one(host_api):
     import json, os, subprocess, sys
     from conftest import ROOT
     ndev = host_api.rt_lib().rt_device_count()
-    common = ["--steps", "2", "--warmup", "1", "--width", "320", "--height", "181", "--spp", "4", "--no-cpu-baseline"]  # (a warm-up step: the first step of a process pays torch's and HIP's first-call costs, which are neither render nor gather)
+    common = ["--steps", "2", "--warmup", "1", "--width", "320", "--height", "181", "--spp", "4", "--full", "--no-cpu-baseline"]  # (a warm-up step: the first step of a process pays torch's and HIP's first-call costs, which are neither render nor gather)
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     if ndev < 2:
         env["RAPT_DIST_BACKEND"] = "gloo"
@@ -509,7 +509,7 @@ def test_bench_line_witnesses_parity(host_api):
     accumulator with the device's as a whole: the JSON line carries parity_check, and the run fails above 1e-4."""
     import json, os, subprocess, sys
     from conftest import ROOT
-    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--width", "160", "--height", "90", "--spp", "3", "--cpu-seconds", "30"], cwd=ROOT, timeout=600)
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--width", "160", "--height", "90", "--spp", "3", "--full", "--cpu-seconds", "30"], cwd=ROOT, timeout=600)
     d = json.loads([l for l in out.decode().splitlines() if l.startswith("{")][-1])
     pc, cb = d["parity_check"], d["cpu_baseline"]
     assert pc["ok"] and pc["frames"] == 3 and pc["pixels"] == 160 * 90 and pc["max_rel_err"] <= 1e-4 and pc["nonfinite_class_equal"]
@@ -524,7 +524,7 @@ def test_bench_line_carries_its_live_legs(host_api):
     the split of the run into legs, every rank's device."""
     import json, os, subprocess, sys
     from conftest import ROOT
-    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--width", "160", "--height", "96", "--spp", "3", "--cpu-seconds", "30",
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--width", "160", "--height", "96", "--spp", "3", "--full", "--cpu-seconds", "30",
                                    "--force-legs", "--ooc-n", "96", "--ooc-spp", "2", "--ooc-steps", "2"], cwd=ROOT, timeout=600)
     d = json.loads([l for l in out.decode().splitlines() if l.startswith("{")][-1])
     r = d["roofline"]
@@ -538,6 +538,49 @@ def test_bench_line_carries_its_live_legs(host_api):
     assert tk["whitted"] > 0 and tk["path"] > 0 and tk["whitted_pixels_checksum"] != tk["path_pixels_checksum"]
     assert d["gpu_leg_s"] > 0 and d["cpu_leg_s"] > 0 and d["timed_region_s"] > 0 and len(d["ranks_devices"]) == 1 and ":" in d["ranks_devices"][0]
     assert d["parity_check"]["ok"] and d["cpu_baseline"]["kind"] == "port"
+
+
+def test_bench_plain_line_and_dumped_outputs(host_api, oracle_api, scenes, tmp_path):
+    """A plain bench run carries the headline figure and nothing that needs runs of its own (no roofline, legs, baseline or parity);
+    --dump-outputs writes the last timed step's accumulator as finite arrays (values, and the class of every non-finite entry), the
+    same files as a --full run of the same arguments, and decoded they are the oracle's frame (1e-4 relative, non-finite by class)."""
+    import json, os, subprocess, sys
+    from conftest import ROOT
+    W, H, spp = 160, 96, 3
+    common = ["--steps", "2", "--warmup", "1", "--width", str(W), "--height", str(H), "--spp", str(spp)]
+    def run(*extra):
+        out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py")] + common + list(extra), cwd=ROOT, timeout=600)
+        return json.loads([l for l in out.decode().splitlines() if l.startswith("{")][-1])
+    plain = run("--dump-outputs", str(tmp_path / "plain"))
+    assert plain["metric"] == "Mrays/s at 160×96×3spp" and plain["unit"] == "Mrays/s" and plain["higher_is_better"] is True and plain["dtype"] == "f32"
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0 and abs(plain["value"] * plain["ms_per_step"] - W * H * spp / 1e3) < 0.01 * W * H * spp / 1e3
+    assert not {"roofline", "rays_per_step", "frame_checksum", "share_ms", "tick_ms", "cpu_baseline", "parity_check"} & set(plain)
+    run("--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full"))
+    files = {}
+    for d in ("plain", "full"):
+        files[d] = [np.load(tmp_path / d / f) for f in ("accumulator.npy", "accumulator_nonfinite.npy")]
+        for x in files[d]:
+            assert x.dtype == np.float32 and np.isfinite(x).all()
+    (vals, code), (vals_f, code_f) = files["plain"], files["full"]
+    assert vals.shape == (H, W, 4) and code.shape == (H, W)
+    assert np.array_equal(vals.view(np.uint32), vals_f.view(np.uint32)) and np.array_equal(code, code_f)
+    got = vals.copy()
+    for c in range(4):
+        k = (code.astype(np.int64) >> (2 * c)) & 3
+        got[..., c][k == 1], got[..., c][k == 2], got[..., c][k == 3] = np.inf, -np.inf, np.nan
+    o = oracle_api.OracleScene()
+    cfg = scenes.REGISTRY["config3"](o)
+    o.set_raytracer(False)
+    orr = oracle_api.OracleRenderer(o, W, H)
+    c = cfg["camera"]
+    orr.set_camera(c["cam_pos"], c["top_left"], c["top_right"], c["bottom_left"])
+    orr.clear()
+    orr.render(0, spp, nthreads=0)
+    ref = orr.accumulator()
+    orr.close()
+    o.close()
+    err, cls_ok = rel_err(got[..., :3], ref[..., :3])
+    assert cls_ok and err.max() <= 1e-4 and (np.isfinite(ref[..., :3]).mean() > 0.5)
 
 
 @pytest.mark.parametrize("name,kw", [("tlas_test2", {"mesh": "BigB"}), ("pretty_tlas", {"n_instances": 4}), ("mixed_small", {})])

@@ -280,6 +280,44 @@ def test_bench_plumbing_without_a_gpu(tmp_path, monkeypatch):
     assert argv[-4:] == ["--gpus", "3", "--steps", "2"] and argv[-5].endswith("bench.py")
 
 
+def test_bench_dump_outputs_without_a_gpu(tmp_path):
+    """bench.py --dump-outputs: every file is finite float32 / float64, and together they are lossless -- the values, with 0 where the
+    accumulator is non-finite, and per pixel the class of each channel (+inf, -inf, NaN).  A frame above the limit is written as the
+    same seeded pixel sample every time (values, classes and float64 flat indices, within the limit together).  --steps below 1 is
+    refused before anything starts."""
+    import importlib, subprocess, sys
+    from conftest import ROOT
+    bench = importlib.import_module("bench")
+    acc = np.random.default_rng(5).random((30, 40, 4)).astype(np.float32)
+    acc[3, 4, 0], acc[3, 4, 2], acc[7, 1, 1], acc[9, 9, 3] = np.inf, np.nan, -np.inf, np.inf
+
+    def decode(vals, code):
+        out = vals.astype(np.float32)
+        for c in range(out.shape[-1]):
+            k = (code.astype(np.int64) >> (2 * c)) & 3
+            out[..., c][k == 1], out[..., c][k == 2], out[..., c][k == 3] = np.inf, -np.inf, np.nan
+        return out
+
+    bench.dump_outputs(str(tmp_path / "whole"), acc)
+    vals, code = np.load(tmp_path / "whole" / "accumulator.npy"), np.load(tmp_path / "whole" / "accumulator_nonfinite.npy")
+    assert vals.dtype == np.float32 and code.dtype == np.float32 and vals.shape == acc.shape and code.shape == acc.shape[:2]
+    assert np.isfinite(vals).all() and np.isfinite(code).all() and (code != 0).sum() == 3
+    assert vals[3, 4, 0] == 0 and code[3, 4] == 1 + 3 * 16 and code[7, 1] == 2 * 4 and code[9, 9] == 64
+    back = decode(vals, code)
+    assert np.array_equal(back, acc, equal_nan=True)
+    limit = 6000
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), acc, limit=limit)
+    svals, scode, idx = (np.load(tmp_path / "s1" / ("accumulator_sample%s.npy" % x)) for x in ("", "_nonfinite", "_index"))
+    assert not (tmp_path / "s1" / "accumulator.npy").exists() and svals.dtype == np.float32 and idx.dtype == np.float64
+    assert svals.nbytes + scode.nbytes + idx.nbytes <= limit and len(svals) == len(scode) == len(idx) > 100 and np.all(np.diff(idx) > 0)
+    assert np.isfinite(svals).all() and np.isfinite(scode).all()
+    assert np.array_equal(decode(svals, scode), acc.reshape(-1, 4)[idx.astype(np.int64)], equal_nan=True)
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "accumulator_sample_index.npy"))
+    rc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], cwd=ROOT, capture_output=True)
+    assert rc.returncode != 0 and b"--steps" in rc.stderr
+
+
 def test_committed_counter_files_are_of_these_kernel_sources():
     """bench.py quotes profiles/roofline_pmc.json and profiles/out_of_cache_pmc.json only while they were measured on the tree's kernel sources
     (kernel_hash over csrc/*.{h,hip,inc}, the Makefile and the library's build / tuning string).  The build string of the committed bench

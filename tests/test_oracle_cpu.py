@@ -1,16 +1,20 @@
 """CPU tier: the oracle against (a) independent restatements of the published algorithms it uses
 (Marsaglia xorshift32, Wang hash -- pure Python, written from the algorithm descriptions), (b) the
-committed golden vectors (tests/golden/oracle_vectors.npz, drift pin), (c) analytic cases.
+committed golden vectors (tests/golden/oracle_vectors*.npz, drift pin), (c) analytic cases.
 
 The reference ships no tests or fixtures: parity of the oracle with the reference
 itself is unpinned, see oracle/README.md."""
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 import pytest
 
-GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vectors.npz"))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+import fixtures as fx  # noqa: E402
+
+GOLD = fx.load_gold(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vectors.npz"))
 
 
 def xorshift32(s):
@@ -110,7 +114,7 @@ def test_goldens_do_not_depend_on_the_compiler(oracle_api, tmp_path):
     out = str(tmp_path / "clang.npz")
     env = dict(os.environ, ORACLE_LIB=so)
     subprocess.check_call([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_golden.py"), "--out", out], env=env)
-    other = np.load(out)
+    other = fx.load_gold(out)
     assert sorted(other.files) == sorted(GOLD.files)
     for k in GOLD.files:
         assert other[k].tobytes() == GOLD[k].tobytes(), k
