@@ -231,6 +231,34 @@ int rt_set_scene_raytracer(rt_ctx* ctx, int flag);
 /* The same with Trace / Sample's third argument: energy[3] instead of float3(1) */
 int rt_trace_batch_energy(rt_ctx* ctx, int mode, int n, const float* O, const float* D, int depth, uint32_t seed_base, const float* energy, float* rgb_out);
 
+/* ---- G-buffer and denoised preview ------------------------------------------------------------------
+ * rt_render_aovs: the G-buffer of the frame -- per pixel, Camera::GetPrimaryRay(x, y) + Scene::FindNearest(t_min) (the first hit of every
+ *   path sample of the pixel: Tick's jitter is truncated by GetPrimaryRay's int parameters) as the rt_hit record rt_intersect_batch gives,
+ *   an albedo (diffuse: col * albedo, metal / glass: col, a light: the light's col, a miss: 0) and the world position O + D * t (f32).
+ *   t_min: 0.001f is what Sample uses (renderer.cpp:133), 1e-6f what Trace uses.  The buffers belong to the context (allocated on first
+ *   use); the launch counts as a query in rt_get_profile.  The G-buffer goes stale with rt_upload_scene, rt_set_time and an rt_set_camera
+ *   whose record differs byte-wise from the current one (an unchanged camera sent every Tick keeps it); on a current G-buffer with the same
+ *   t_min the call returns at once without a launch.  Synchronous.
+ * rt_download_aovs: rows [y0, y1) of the G-buffer: hits_out (rt_hit per pixel) and / or albedo_rgb_out (3 floats per pixel); either NULL.
+ * rt_denoise: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) of the mean colour accumulator / iteration (whatever
+ *   accumulator is bound), on the whole frame, on the context's stream, without synchronising.  Definition (tests/denoise_ref.py restates it):
+ *     c_p = acc_p.xyz / iteration (f32, as rt_resolve); a pixel with a non-finite component is passed through and is no tap of any neighbour;
+ *     for i = 0 .. iterations - 1, step s = 2^i: taps at s * (dx, dy), dx, dy in [-2, 2], B3-spline h = (1/16, 1/4, 3/8, 1/4, 1/16),
+ *     taps outside the image or non-finite skipped, w = h[dx] h[dy] exp(-(|c_p - c_q|^2 kc_i + |n_p - n_q|^2 kn + |x_p - x_q|^2 / t_p^2 kx
+ *     + |a_p - a_q|^2 ka)), kc_i = 4^i / sigma_color^2, kn = 1 / sigma_normal^2, kx = 1 / sigma_position^2, ka = 1 / sigma_albedo^2 (f32;
+ *     sigma = +inf drops its term); two misses compare colour only, a hit and a miss do not mix (w = 0); out = sum w c_q / sum w, w channel 0.
+ *   params NULL: RT_DENOISE_DEFAULTS.  RT_E_ARG: iteration < 1, iterations outside 1..8, a sigma <= 0 or NaN.  RT_E_STATE: the G-buffer is
+ *   missing or stale (rt_render_aovs first).  The accumulator is not written.
+ * rt_download_denoised: rows [y0, y1) of the last rt_denoise result (float4 per pixel).
+ * rt_resolve_denoised: RGBF32_to_RGB8 of those rows (rt_resolve of the denoised mean, iteration 1). */
+typedef struct { int32_t iterations; float sigma_color, sigma_normal, sigma_position, sigma_albedo; } rt_denoise_params;
+#define RT_DENOISE_DEFAULTS { 5, 0.5f, 0.25f, 0.1f, 0.1f }
+int rt_render_aovs(rt_ctx* ctx, float t_min);
+int rt_download_aovs(rt_ctx* ctx, int y0, int y1, rt_hit* hits_out, float* albedo_rgb_out);
+int rt_denoise(rt_ctx* ctx, int iteration, const rt_denoise_params* params);
+int rt_download_denoised(rt_ctx* ctx, int y0, int y1, float* out);
+int rt_resolve_denoised(rt_ctx* ctx, int y0, int y1, uint32_t* rgb8_out);
+
 /* ---- Q-learning guided sampling ("next" row N4) ------------------------------------------------------
  * The reference snapshot has no code for it: README.md:36-42 names Dahm & Keller 2017, "Learning Light Transport
  * the Reinforced Way", and lists "initialize sampling positions; pick sampling direction according to the QValue of neighboring

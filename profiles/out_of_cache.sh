@@ -13,7 +13,7 @@ OUT=gpurun_out/${TAG}_ooc_spp$SPP
 rm -rf $OUT; mkdir -p $OUT
 timeout -k 10 900 python3 profiles/out_of_cache.py --n $N --spp $SPP --check --json $OUT/run.json > $OUT/run.log 2>&1 || { echo "plain run failed"; tail -5 $OUT/run.log; exit 1; }
 tail -2 $OUT/run.log | head -1
-run() { name=$1; shift; timeout -k 10 600 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 profiles/out_of_cache.py --n $N --spp $SPP --steps 2 > $OUT/$name.log 2>&1 || echo "pass $name failed"; }
+run() { name=$1; shift; timeout -k 10 600 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 profiles/out_of_cache.py --n $N --spp $SPP --steps 2 > $OUT/$name.log 2>&1 || { echo "pass $name failed: no further pass is started"; exit 1; }; }
 run fetch FETCH_SIZE
 run write WRITE_SIZE
 run grbm GRBM_GUI_ACTIVE GRBM_TA_BUSY TA_BUSY_avr TA_BUSY_max

@@ -4,7 +4,7 @@
 set -u
 OUT=$1; shift
 export TMPDIR=/tmp
-run() { name=$1; shift; timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 bench.py --full $BENCH_ARGS > $OUT/$name.log 2>&1 || echo "pass $name failed"; }
+run() { name=$1; shift; timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 bench.py --full $BENCH_ARGS > $OUT/$name.log 2>&1 || { echo "pass $name failed: no further pass is started"; exit 1; }; }
 BENCH_ARGS="${*:---steps 1 --warmup 0 --spp 8 --no-cpu-baseline}"
 mkdir -p $OUT
 run sq1 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY

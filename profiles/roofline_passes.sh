@@ -16,7 +16,7 @@ rm -f $RT_ROOFLINE_PMC_OUT
 for N in $WORLDS; do
   OUT=gpurun_out/${TAG}_w${N}_pmc
   EMU=""; [ "$N" != "1" ] && EMU="--emulate-world $N"
-  bash profiles/pmc_passes.sh $OUT --steps 2 --warmup 0 --no-cpu-baseline --no-count $EMU
+  bash profiles/pmc_passes.sh $OUT --steps 2 --warmup 0 --no-cpu-baseline --no-count $EMU || { echo "world $N: a pass failed, aborting (profiles/roofline_pmc.json untouched)"; exit 1; }
   python3 profiles/pmc_summary.py $OUT > gpurun_out/${TAG}_w${N}_pmc_summary.json
   KH=$(grep -o '"kernel_hash": "[0-9a-f]*"' $OUT/sq1.log | head -1 | grep -o '[0-9a-f]\{16\}')
   if [ -z "$KH" ]; then echo "no kernel_hash in $OUT/sq1.log (the bench did not finish): aborting, profiles/roofline_pmc.json untouched"; exit 1; fi

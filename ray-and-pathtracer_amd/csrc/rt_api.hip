@@ -79,6 +79,7 @@ rt_ctx* rt_create(int device, int width, int height)
 		                      (const void*)k_query_occluded<false, true>, (const void*)k_query_occluded<false, false, true>, (const void*)k_query_occluded<false, false, false, true> };
 		for (int i = 0; i < 9; i++) { const int r = resident(qk[i]); if (r < q) q = r; }
 		c->gridQuery = q;
+		c->gridAovs = std::min(q, std::min(resident((const void*)k_primary_aovs<false>), resident((const void*)k_primary_aovs<true>)));
 	}
 	ok = ok && hipMalloc((void**)&c->spill, (size_t)(RT_STACK_MAX - RT_STACK_ROWS_MIN) * c->gridBlocks * RT_BLOCK * sizeof(uint)) == hipSuccess;
 	ok = ok && hipMalloc((void**)&c->flags, (16 + RT_HEADS * RT_HEAD_STRIDE) * sizeof(int)) == hipSuccess;
@@ -131,6 +132,7 @@ void rt_destroy(rt_ctx* c)
 	if (c->spill) (void)hipFree(c->spill);
 	if (c->samples) (void)hipFree(c->samples);
 	if (c->resolveBuf) (void)hipFree(c->resolveBuf);
+	free_pool(c->denoiseAllocs);
 	if (c->gammaLut) (void)hipFree(c->gammaLut);
 	if (c->flags) (void)hipFree(c->flags);
 	if (c->counters) (void)hipFree(c->counters);
@@ -149,6 +151,9 @@ int rt_set_scene_raytracer(rt_ctx* c, int flag)
 int rt_set_camera(rt_ctx* c, const rt_camera* cam)
 {
 	if (!c || !cam) return fail(c, RT_E_ARG, "rt_set_camera: null argument");
+	// Renderer::SyncCamera sends the camera every Tick: only a record that differs byte-wise makes the G-buffer stale
+	if (!c->cameraSet || memcmp(&c->camRec, cam, sizeof(rt_camera)) != 0) c->sceneGen++;
+	memcpy(&c->camRec, cam, sizeof(rt_camera));
 	memcpy(c->C.camPos, cam->cam_pos, 12), memcpy(c->C.topLeft, cam->top_left, 12);
 	memcpy(c->C.topRight, cam->top_right, 12), memcpy(c->C.bottomLeft, cam->bottom_left, 12);
 	c->C.fisheye = cam->fisheye, c->C.viewAngle = cam->view_angle, c->C.yAngle = cam->y_angle;
@@ -204,6 +209,7 @@ int rt_bind_accumulator(rt_ctx* c, void* p)
 
 #include "rt_api_gather.inc"
 #include "rt_api_query.inc"
+#include "rt_api_denoise.inc"
 
 // ---- measurement ------------------------------------------------------------------------------
 int rt_set_counting(rt_ctx* c, int counting)

@@ -8,11 +8,13 @@
 //   rt_api_gather.inc   rt_gather_*
 //   rt_api_query.inc    batch queries
 //   rt_api_qlearn.inc   rt_qlearn_*
+//   rt_api_denoise.inc  rt_render_aovs, rt_denoise and their downloads
 #pragma once
 #include "rt_kernels.h"
 #include "rt_stream.h"
 #include "rt_mega.h"
 #include "rt_build.h"
+#include "rt_denoise.h"
 #include "../../include/rt_amd.h"
 #include <algorithm>
 #include <cstdarg>
@@ -167,6 +169,16 @@ struct rt_ctx {
 	std::vector<int> timerKind;
 	int* hostCounts = nullptr; // pinned
 	uint* resolveBuf = nullptr; // rt_resolve's device pixels (width * height), allocated on first use
+	// G-buffer + denoiser (rt_api_denoise.inc).  sceneGen counts what makes the G-buffer stale (rt_upload_scene, rt_set_time, a camera
+	// record that differs byte-wise): the G-buffer is current while aovGen == sceneGen
+	rt_camera camRec;
+	unsigned long long sceneGen = 1, aovGen = 0;
+	float aovTmin = 0.0f;
+	int gridAovs = 0;
+	std::vector<void*> denoiseAllocs;
+	float4* aovNrm = nullptr; float4* aovPos = nullptr; float4* aovAlb = nullptr; // width * height each, allocated on first use
+	float4* denoiseBuf[2] = { nullptr, nullptr }; // ping-pong of the filter's iterations
+	float4* denoised = nullptr; // the buffer holding the last rt_denoise result (null: none yet)
 	float4* samples = nullptr; // finished samples of the current batch, [frame][tile pixel]
 	size_t sampleCap = 0;
 };

@@ -1206,6 +1206,53 @@ __global__ void __launch_bounds__(RT_BLOCK) k_primary_hits(DScene S, DCamera C, 
 	if (COUNT) flush_counters(counters, lc, rays, 0);
 }
 
+// The G-buffer of a frame (rt_render_aovs): PrimaryPolicy's rays, and per pixel three float4 records the denoiser reads as
+// 16-byte vectors --
+//   nrm   hitNormal xyz, w = t                           (the rt_hit record is nrm + the two ids below)
+//   pos   O + D * t (f32, not contracted) xyz, w = objIdx bits (-1: a miss)
+//   alb   albedo rgb, w = material bits: col * albedo for a diffuse hit, col for metal / glass, the light's col for a
+//         light (objIdx in [11, 11 + nLights), the test the path kernels make), 0 for a miss
+struct AovPolicy {
+	const DScene& S; const DCamera& C; float4* nrm; float4* pos; float4* alb;
+	__device__ __forceinline__ int slot_of(int i) const { return i; }
+	__device__ __forceinline__ bool load(int i, f3& O, f3& D, float& tm, HitRef&) const { primary_ray(C, i % C.width, i / C.width, O, D); tm = 1e34f; return true; }
+	__device__ __forceinline__ void store(int i, const HitRef& hit, const f3&, const f3&) const
+	{
+		f3 O, D;
+		float tm;
+		HitRef unused;
+		load(i, O, D, tm, unused);
+		int objIdx, mat;
+		f3 normal;
+		resolve_hit(S, hit, O, D, objIdx, mat, normal);
+		f3 a(0.0f);
+		if (objIdx >= 11 && objIdx < 11 + S.nLights) {
+			const DLight& L = S.lights[objIdx - 11];
+			a = f3(L.col[0], L.col[1], L.col[2]);
+		} else if (objIdx != -1 && mat >= 0 && mat < S.nMats) {
+			const DMaterial& m = S.mats[mat];
+			a = f3(m.col[0], m.col[1], m.col[2]);
+			if (m.type == 1) a = a * f3(m.albedo[0], m.albedo[1], m.albedo[2]);
+		}
+		const f3 P = O + D * hit.t;
+		nrm[i] = mk4(normal, hit.t);
+		pos[i] = mk4(P, __int_as_float(objIdx));
+		alb[i] = mk4(a, __int_as_float(mat));
+	}
+};
+
+template <bool COUNT>
+__global__ void __launch_bounds__(RT_BLOCK) k_primary_aovs(DScene S, DCamera C, float t_min, int tuning, float4* nrm, float4* pos, float4* alb, uint* spill, int* work, DCounters* counters)
+{
+	__shared__ __attribute__((aligned(16))) uint ldsStack[RT_LDS_WORDS];
+	LaneCounters lc;
+	lc.clear();
+	uint rays = 0;
+	AovPolicy pol{ S, C, nrm, pos, alb };
+	trace_persistent<false, COUNT, true>(S, pol, C.width * C.height, work + 16, t_min, tuning, ldsStack, spill, &work[1], lc, rays);
+	if (COUNT) flush_counters(counters, lc, rays, 0);
+}
+
 // Scene::GetSkyColor (template/scene.h:1312-1327) for n directions
 __global__ void k_sky_color(DScene S, int n, const float* D3, float* rgb)
 {

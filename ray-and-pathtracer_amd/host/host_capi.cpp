@@ -255,6 +255,12 @@ int rth_renderer_qlearning(void* h, int grid, const float* lo, const float* hi, 
 	GUARD(r, if (grid > 0) r->r->EnableQLearning(grid, float3(lo[0], lo[1], lo[2]), float3(hi[0], hi[1], hi[2]), alpha, eps, qInit); else r->r->DisableQLearning());
 	return 0;
 }
+void rth_renderer_set_denoise(void* h, int on, const rt_denoise_params* params)
+{
+	Renderer* r = ((RthRenderer*)h)->r;
+	r->denoise = on != 0;
+	if (params) r->denoiseParams = *params;
+}
 const float* rth_renderer_accumulator(void* h) { return &((RthRenderer*)h)->r->accumulator[0].x; }
 const unsigned* rth_renderer_pixels(void* h) { return ((RthRenderer*)h)->r->screenPixels; }
 int rth_renderer_trace(void* h, int path, const float* O, const float* D, int depth, const float* energy, float* rgb)

@@ -372,6 +372,10 @@ public:
 	bool qlearning = false;
 	int qgrid = 0;
 	uint32_t qlearnMask = 0;          // rt_qlearn_params::learn_mask for the next EnableQLearning (0: every sample pays rewards)
+	// Denoised preview (path mode only): Tick refreshes the G-buffer when something changed (rt_render_aovs, 0.001f as Sample), filters the
+	// mean with rt_denoise and shows rt_resolve_denoised in screenPixels; 'accumulator' stays the raw download.  Off: Tick is unchanged.
+	bool denoise = false;
+	rt_denoise_params denoiseParams = RT_DENOISE_DEFAULTS;
 	float4* accumulator = nullptr; // host copy, refreshed by Tick
 	uint32_t* screenPixels = nullptr; // Surface::pixels analogue (template/precomp.h:134)
 	Scene scene;

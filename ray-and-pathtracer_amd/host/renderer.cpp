@@ -176,7 +176,13 @@ void Renderer::Tick(float /*deltaTime*/)
 		for (rt_ctx* k : ctxs) check(k, rt_qlearn_apply(k));
 	}
 	if (!scene.raytracer) frame++;
-	check(ctx, rt_resolve(ctx, it, 0, height, screenPixels));
+	if (!scene.raytracer && denoise) {
+		// context 0 holds the gathered accumulator (its stream already waits for every gather) and the synced camera
+		check(ctx, rt_render_aovs(ctx, 0.001f)); // a no-op unless the camera, the scene or the time changed
+		check(ctx, rt_denoise(ctx, it, &denoiseParams));
+		check(ctx, rt_resolve_denoised(ctx, 0, height, screenPixels));
+	} else
+		check(ctx, rt_resolve(ctx, it, 0, height, screenPixels));
 	if (downloadEachTick) check(ctx, rt_download_accumulator(ctx, 0, height, &accumulator[0].x));
 	if (!scene.raytracer && !camChanged) scene.SetIterationNumber(it + 1);
 	camera.SetChange(false);

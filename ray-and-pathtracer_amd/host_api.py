@@ -27,11 +27,28 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_build_bvh", "rt_build_bvh_split", "rt_build_tlas", "rt_gather_rows", "rt_gather_begin", "rt_device_of",
               "rt_intersect_scope", "rt_occluded_scope", "rt_sky_color_batch", "rt_trace_batch_energy", "rt_build_info", "rt_tuning_info",
               "rt_qlearn_enable", "rt_qlearn_apply", "rt_qlearn_get_sums", "rt_qlearn_set_sums", "rt_qlearn_get_table", "rt_qlearn_bind_sums",
-              "rt_device_pci_bus_id", "rt_set_scene_raytracer"]
+              "rt_device_pci_bus_id", "rt_set_scene_raytracer",
+              "rt_render_aovs", "rt_download_aovs", "rt_denoise", "rt_download_denoised", "rt_resolve_denoised"]
+
+RT_E_ARG, RT_E_STATE = -2, -5
+# include/rt_amd.h RT_DENOISE_DEFAULTS
+DENOISE_DEFAULTS = dict(iterations=5, sigma_color=0.5, sigma_normal=0.25, sigma_position=0.1, sigma_albedo=0.1)
 
 
 class RtQlearnParams(C.Structure):
     _fields_ = [("grid", C.c_int32), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("alpha", C.c_float), ("epsilon", C.c_float), ("q_init", C.c_float), ("learn_mask", C.c_uint32)]
+
+
+class RtDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float), ("sigma_albedo", C.c_float)]
+
+
+def denoise_params(params=None):
+    """rt_denoise_params from a dict of DENOISE_DEFAULTS' keys (missing keys: the defaults); None -> None (the library's defaults)"""
+    if params is None:
+        return None
+    p = dict(DENOISE_DEFAULTS, **params)
+    return RtDenoiseParams(int(p["iterations"]), p["sigma_color"], p["sigma_normal"], p["sigma_position"], p["sigma_albedo"])
 
 
 class RtCamera(C.Structure):
@@ -120,6 +137,11 @@ def rt_lib():
         L.rt_get_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.rt_set_profiling.argtypes = [C.c_void_p, C.c_int]
         L.rt_get_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rt_render_aovs.argtypes = [C.c_void_p, C.c_float]
+        L.rt_download_aovs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.rt_denoise.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rt_download_denoised.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.rt_resolve_denoised.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _rt = L
     return _rt
 
@@ -391,6 +413,11 @@ class HostRenderer:
         p = C.cast(self.L.rth_renderer_pixels(self.h), C.POINTER(C.c_uint32))
         return np.ctypeslib.as_array(p, shape=(self.hgt, self.w)).copy()
 
+    def set_denoise(self, on, params=None):
+        """rapt::Renderer::denoise / denoiseParams: Tick shows the denoised mean in path mode (params: dict, see denoise_params)"""
+        p = denoise_params(params)
+        self.L.rth_renderer_set_denoise(self.h, int(bool(on)), C.byref(p) if p is not None else None)
+
     def trace_one(self, O, D, depth, path=False, energy=(1, 1, 1)):
         rgb = (C.c_float * 3)()
         self._chk(self.L.rth_renderer_trace(self.h, int(path), _f3(O), _f3(D), depth, _f3(energy), rgb))
@@ -481,6 +508,35 @@ class HostRenderer:
         t = np.zeros((self.hgt, self.w), dtype=np.float32)
         self._rt(self.rt.rt_primary_hits(self.ctx, t_min, _p(obj), _p(t)))
         return obj, t
+
+    # ---- G-buffer and denoiser (include/rt_amd.h rt_render_aovs .. rt_resolve_denoised) ----
+    def render_aovs(self, t_min=0.001):
+        self._rt(self.rt.rt_render_aovs(self.ctx, t_min))
+
+    def aovs(self, y0=0, y1=None):
+        """rows [y0, y1) of the G-buffer: dict(t, obj, mat, normal, albedo) like find_nearest plus the albedo, shaped (rows, width[, 3])"""
+        y1 = self.hgt if y1 is None else y1
+        hits = np.zeros((y1 - y0, self.w), dtype=RT_HIT_DTYPE)
+        alb = np.zeros((y1 - y0, self.w, 3), dtype=np.float32)
+        self._rt(self.rt.rt_download_aovs(self.ctx, y0, y1, _p(hits), _p(alb)))
+        return dict(t=hits["t"].copy(), obj=hits["obj_idx"].copy(), mat=hits["material"].copy(), normal=hits["normal"].copy(), albedo=alb)
+
+    def denoise(self, it, params=None):
+        """rt_denoise of the accumulator / it (params: dict, see denoise_params; None: the library's defaults)"""
+        p = denoise_params(params)
+        self._rt(self.rt.rt_denoise(self.ctx, int(it), C.byref(p) if p is not None else None))
+
+    def denoised(self, y0=0, y1=None):
+        y1 = self.hgt if y1 is None else y1
+        out = np.zeros((y1 - y0, self.w, 4), dtype=np.float32)
+        self._rt(self.rt.rt_download_denoised(self.ctx, y0, y1, _p(out)))
+        return out
+
+    def resolve_denoised(self, y0=0, y1=None):
+        y1 = self.hgt if y1 is None else y1
+        out = np.zeros((y1 - y0, self.w), dtype=np.uint32)
+        self._rt(self.rt.rt_resolve_denoised(self.ctx, y0, y1, _p(out)))
+        return out
 
     def set_scene_raytracer(self, flag):
         """rt_set_scene_raytracer: -1 the flag follows the function (Trace: set, Sample: clear), 0 / 1 scene.raytracer as the caller holds it"""
