@@ -246,7 +246,9 @@ int rt_trace_batch_energy(rt_ctx* ctx, int mode, int n, const float* O, const fl
  *     for i = 0 .. iterations - 1, step s = 2^i: taps at s * (dx, dy), dx, dy in [-2, 2], B3-spline h = (1/16, 1/4, 3/8, 1/4, 1/16),
  *     taps outside the image or non-finite skipped, w = h[dx] h[dy] exp(-(|c_p - c_q|^2 kc_i + |n_p - n_q|^2 kn + |x_p - x_q|^2 / t_p^2 kx
  *     + |a_p - a_q|^2 ka)), kc_i = 4^i / sigma_color^2, kn = 1 / sigma_normal^2, kx = 1 / sigma_position^2, ka = 1 / sigma_albedo^2 (f32;
- *     sigma = +inf drops its term); two misses compare colour only, a hit and a miss do not mix (w = 0); out = sum w c_q / sum w, w channel 0.
+ *     sigma = +inf drops its term).  Every k is clamped to FLT_MAX where it overflows: kc_i as the f32 product (1 / sigma_color^2) 4^i,
+ *     kn, kx, ka, and kx / t_p^2 per pixel.  A zero distance then weighs exp(0) = 1 and a nonzero one under a tiny sigma about 0, so a
+ *     tiny sigma mixes only neighbours identical in that feature and never produces NaN; two misses compare colour only, a hit and a miss do not mix (w = 0); out = sum w c_q / sum w, w channel 0.
  *   params NULL: RT_DENOISE_DEFAULTS.  RT_E_ARG: iteration < 1, iterations outside 1..8, a sigma <= 0 or NaN.  RT_E_STATE: the G-buffer is
  *   missing or stale (rt_render_aovs first).  The accumulator is not written.
  * rt_download_denoised: rows [y0, y1) of the last rt_denoise result (float4 per pixel).

@@ -56,6 +56,16 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def resolve_values(rgba, it):
+    """Renderer::ResolvePixel of each float4 of rgba (shape (..., 4)) for iteration count it, without a renderer: uint32 of shape (...)"""
+    a = np.ascontiguousarray(rgba, dtype=np.float32)
+    out = np.zeros(a.shape[:-1], dtype=np.uint32)
+    L = lib()
+    L.orc_resolve_values.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    L.orc_resolve_values(_p(a), out.size, int(it), _p(out))
+    return out
+
+
 class OracleScene:
     """Scene builder + queries over the CPU restatement (oracle)."""
 

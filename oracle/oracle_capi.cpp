@@ -404,6 +404,11 @@ void orc_resolve(void* h, int it, unsigned* out)
 	const Renderer& r = ((OrcRenderer*)h)->r;
 	for (size_t i = 0; i < r.accumulator.size(); i++) out[i] = r.ResolvePixel(i, it);
 }
+// ResolvePixel of n caller-given float4 values (rgba: 4 floats each) for iteration count 'it', without a renderer
+void orc_resolve_values(const float* rgba, size_t n, int it, unsigned* out)
+{
+	for (size_t i = 0; i < n; i++) out[i] = Renderer::ResolveValue(float4{ rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2], rgba[4 * i + 3] }, it);
+}
 // primary rays only: GetPrimaryRay + FindNearest(t_min) per pixel
 void orc_primary_hits(void* h, float t_min, int* outObj, float* outT, unsigned long long* counters)
 {

@@ -349,20 +349,21 @@ struct Renderer {
 	}
 
 	// RGBF32_to_RGB8 of accumulator / it (:287-290, template/precomp.h:445-448, non-MSVC branch)
-	uint ResolvePixel(size_t idx, int it) const
+	uint ResolvePixel(size_t idx, int it) const { return ResolveValue(accumulator[idx], it); }
+	static uint ResolveValue(const float4& a, int it)
 	{
-		const float4& a = accumulator[idx];
 		float fx = a.x / it, fy = a.y / it, fz = a.z / it;
-		auto conv = [](float v) -> uint {
-			float m = std_min(1.0f, v);
-			float s = 255.0f * m;
-			// (uint) of a negative or NaN float is undefined in C++; x86-64 compilers emit cvttss2si
-			// to a 64-bit register and keep the low 32 bits
-			long long q = (s > -9.2e18f && s < 9.2e18f) ? (long long)s : (long long)0x8000000000000000ull;
-			return (uint)q;
-		};
-		uint r = conv(fx), g = conv(fy), b = conv(fz);
+		uint r = ResolveChannel(fx), g = ResolveChannel(fy), b = ResolveChannel(fz);
 		return (r << 16) + (g << 8) + b;
+	}
+	static uint ResolveChannel(float v)
+	{
+		float m = std_min(1.0f, v);
+		float s = 255.0f * m;
+		// (uint) of a negative or NaN float is undefined in C++; x86-64 compilers emit cvttss2si
+		// to a 64-bit register and keep the low 32 bits
+		long long q = (s > -9.2e18f && s < 9.2e18f) ? (long long)s : (long long)0x8000000000000000ull;
+		return (uint)q;
 	}
 };
 

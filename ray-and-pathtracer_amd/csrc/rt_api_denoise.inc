@@ -54,8 +54,9 @@ int rt_download_aovs(rt_ctx* c, int y0, int y1, rt_hit* hits_out, float* albedo_
 	return RT_OK;
 }
 
-// 1 / sigma^2 in f32; sigma = +inf gives 0 (the term is dropped)
-static float denoise_k(float sigma) { return 1.0f / (sigma * sigma); }
+// 1 / sigma^2 in f32; sigma = +inf gives 0 (the term is dropped), a k that overflows is FLT_MAX (so a zero distance adds 0, not 0 x inf = NaN)
+static float denoise_k_clamp(float k) { return std::min(k, FLT_MAX); }
+static float denoise_k(float sigma) { return denoise_k_clamp(1.0f / (sigma * sigma)); }
 static bool denoise_sigma_ok(float sigma) { return sigma > 0.0f; } // (false for NaN)
 
 int rt_denoise(rt_ctx* c, int iteration, const rt_denoise_params* params)
@@ -88,7 +89,7 @@ int rt_denoise(rt_ctx* c, int iteration, const rt_denoise_params* params)
 		A.in = i == 0 ? c->accum : c->denoiseBuf[(i - 1) & 1];
 		A.out = c->denoiseBuf[i & 1];
 		A.step = 1 << i;
-		A.kc = kc0 * (float)(1 << (2 * i)); // sigma_c halves every iteration (exact: a power of two)
+		A.kc = denoise_k_clamp(kc0 * (float)(1 << (2 * i))); // sigma_c halves every iteration (exact: a power of two, until it overflows)
 		if (i == 0) hipLaunchKernelGGL(k_denoise_atrous<true>, grid, block, 0, c->stream, A);
 		else hipLaunchKernelGGL(k_denoise_atrous<false>, grid, block, 0, c->stream, A);
 	}

@@ -7,9 +7,10 @@
 //   c_p = accum_p.xyz / it on the first iteration (k_resolve's f32 division), the previous iteration's output after that
 //   a non-finite c_p is passed through and is no tap of any neighbour
 //   w = h[dx] h[dy] exp(-(|c_p - c_q|^2 kc + |n_p - n_q|^2 kn + |x_p - x_q|^2 / t_p^2 kx + |a_p - a_q|^2 ka)), a zero k drops its term
-//   (sigma = inf), two misses compare colour only, a hit and a miss do not mix (w = 0); out = sum w c_q / sum w, w channel 0
+//   (sigma = inf), an overflowing k is FLT_MAX (kc, kn, kx, ka on the host, kx / t_p^2 here), two misses compare colour only, a hit and a miss do not mix (w = 0); out = sum w c_q / sum w, w channel 0
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cfloat>
 
 namespace rtd {
 
@@ -52,8 +53,8 @@ __global__ void __launch_bounds__(RT_DENOISE_TX * RT_DENOISE_TY) k_denoise_atrou
 	if (!finite4(cp)) { A.out[p] = make_float4(cp.x, cp.y, cp.z, 0.0f); return; }
 	const float4 xp = A.pos[p], np = A.nrm[p], ap = A.alb[p];
 	const bool hitP = __float_as_int(xp.w) != -1;
-	// the position term's scale 1 / t_p^2 is the centre's alone: folded into its k once
-	const float kxp = A.kx != 0.0f ? A.kx / (np.w * np.w) : 0.0f;
+	// the position term's scale 1 / t_p^2 is the centre's alone: folded into its k once, clamped like every k (a tiny t_p overflows it)
+	const float kxp = A.kx != 0.0f ? fminf(A.kx / (np.w * np.w), FLT_MAX) : 0.0f;
 	const float h[5] = { 1.0f / 16, 1.0f / 4, 3.0f / 8, 1.0f / 4, 1.0f / 16 };
 	float sw = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
 #pragma unroll

@@ -7,11 +7,32 @@ H = np.array([1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16])
 DEFAULTS = dict(iterations=5, sigma_color=0.5, sigma_normal=0.25, sigma_position=0.1, sigma_albedo=0.1)
 
 
+FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def clamp_k(k):
+    """every k, in f32, clamped to FLT_MAX: an overflowing k does not turn the zero distance of the centre tap into NaN"""
+    return np.minimum(np.float32(k), np.float32(FLT_MAX))
+
+
 def k_of(sigma):
-    """1 / sigma^2 as the host computes it (f32); sigma = inf -> 0"""
+    """1 / sigma^2 as the host computes it (f32, clamped); sigma = inf -> 0"""
     s = np.float32(sigma)
+    with np.errstate(over="ignore", under="ignore", divide="ignore"):
+        return float(clamp_k(np.float32(1) / (s * s)))
+
+
+def kc_of(kc0, i):
+    """iteration i's colour k: kc0 * 4^i as an f32 product, clamped"""
     with np.errstate(over="ignore"):
-        return float(np.float32(1) / (s * s))
+        return float(clamp_k(np.float32(kc0) * np.float32(4.0 ** i)))
+
+
+def kx_of(kx, t):
+    """the per-pixel position k: kx / t_p^2 in f32, clamped"""
+    t = np.asarray(t, np.float32)
+    with np.errstate(over="ignore", under="ignore", divide="ignore", invalid="ignore"):
+        return clamp_k(np.float32(kx) / (t * t)).astype(np.float64)
 
 
 def mean_color(acc, it):
@@ -35,11 +56,10 @@ def atrous(color, normal, pos, albedo, t, hit, params=None):
     hit = np.asarray(hit, bool)
     hgt, wid = c.shape[:2]
     kc0, kn, kx, ka = k_of(p["sigma_color"]), k_of(p["sigma_normal"]), k_of(p["sigma_position"]), k_of(p["sigma_albedo"])
-    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        kxp = np.where(hit, kx / (t * t), 0.0) if kx else np.zeros_like(t)
+    kxp = np.where(hit, kx_of(kx, t), 0.0) if kx else np.zeros_like(t)
     for i in range(int(p["iterations"])):
         s = 1 << i
-        kc = kc0 * 4.0 ** i
+        kc = kc_of(kc0, i)
         fin = np.all(np.isfinite(c), axis=-1)
         sw = np.zeros((hgt, wid))
         acc = np.zeros((hgt, wid, 3))

@@ -164,3 +164,44 @@ def test_mean_color_is_the_f32_division():
     c = dr.mean_color(acc, 3)
     assert np.array_equal(c[0, 0], (np.float32(1) / np.float32(3), np.float32(2) / np.float32(3), np.float32(1.0)))
     assert np.isposinf(c[0, 1, 0])
+
+
+@pytest.mark.parametrize("params", [dict(sigma_color=5e-19, iterations=5), dict(sigma_color=1e-30, iterations=8), dict(sigma_normal=1e-20),
+                                    dict(sigma_position=1e-20, iterations=8), dict(sigma_albedo=1e-20), dict(tiny_t=True)])
+def test_tiny_sigma_keeps_every_pixel_finite(params):
+    """a k that overflows f32 is clamped to FLT_MAX (include/rt_amd.h): the centre tap's zero distance weighs 1, not 0 x inf = NaN, and
+    where every neighbour differs in the tiny-sigma feature no neighbour mixes in -- the output is the input.  (Before the clamp every
+    hit pixel came out NaN, and with sigma_color = 5e-19 kc_4 = 4e36 x 256 overflowed on the fifth iteration.)  tiny_t: t_p = 1e-30 and
+    the default sigma_position, where kx / t_p^2 overflows per pixel."""
+    params = dict(params)
+    color, normal, pos, albedo, t, hit = _scene(19, 37, seed=3)
+    hit[:] = True
+    rng = np.random.default_rng(5)
+    # every pixel distinct from every other in every feature
+    color = rng.uniform(0.1, 1.0, color.shape)
+    normal = rng.standard_normal(normal.shape)
+    pos = rng.uniform(-1, 1, pos.shape)
+    albedo = rng.uniform(0, 1, albedo.shape)
+    if params.pop("tiny_t", False):
+        t = np.full(t.shape, 1e-30)
+    key = [k for k in params if k.startswith("sigma")]
+    # the other terms off, so that only the tiny sigma (or the tiny t) stands between the pixels
+    others = {k: INF for k in ("sigma_color", "sigma_normal", "sigma_position", "sigma_albedo") if k not in key and (key or k != "sigma_position")}
+    out = dr.atrous(color, normal, pos, albedo, t, hit, dict(others, **params))
+    assert np.all(np.isfinite(out))
+    assert np.allclose(out, color, rtol=1e-12, atol=0)
+    # pixels identical in that feature still mix: a constant guide with the colour test off is the plain blur
+    if key and key[0] != "sigma_color":
+        feat = {"sigma_normal": normal, "sigma_position": pos, "sigma_albedo": albedo}[key[0]]
+        feat[:] = feat[0, 0]
+        out = dr.atrous(color, normal, pos, albedo, t, hit, dict(others, **params))
+        assert np.allclose(out, _b3_blur(color, params.get("iterations", 5)), rtol=1e-12, atol=1e-15)
+
+
+def test_overflowing_k_is_clamped_in_f32():
+    fmax = float(np.finfo(np.float32).max)
+    assert dr.k_of(1e-20) == dr.k_of(1e-30) == fmax and dr.k_of(INF) == 0 and dr.k_of(1e30) == 0
+    assert dr.k_of(0.5) == 4.0 and dr.kc_of(dr.k_of(0.5), 3) == 256.0
+    kc0 = dr.k_of(5e-19)
+    assert kc0 < fmax and dr.kc_of(kc0, 3) < fmax and dr.kc_of(kc0, 4) == fmax  # 4e36 x 256 overflows
+    assert np.all(dr.kx_of(100.0, np.array([1e-30, 0.0, 2.0])) == (fmax, fmax, 25.0))

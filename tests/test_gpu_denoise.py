@@ -92,12 +92,13 @@ def check_aovs(o, orr, r, rec, t_min):
     return g
 
 
-@pytest.mark.parametrize("name,w,h", [("mixed_small", 64, 40), ("background_scene", 64, 40), ("tlas_test2", 64, 40), ("pretty_tlas", 960, 540)])
+@pytest.mark.parametrize("name,w,h", [("mixed_small", 64, 40), ("background_scene", 64, 40), ("tlas_test2", 64, 40), ("pretty_tlas", 960, 540)]
+                         + [(n, w, h) for n in ("mixed_small", "background_scene", "tlas_test2") for w, h in ((1, 1), (33, 9), (97, 41))])
 @pytest.mark.parametrize("t_min", [0.001, 1e-6])
 def test_aovs_equal_the_oracle(name, w, h, t_min, scenes, oracle_api, host_api):
     o, orr, r, rec = make(scenes, oracle_api, host_api, getattr(scenes, name), w, h)
     g = check_aovs(o, orr, r, rec, t_min)
-    assert (g["obj"] != -1).any()
+    assert (g["obj"] != -1).any() or w * h == 1  # (a single pixel of the two non-TLAS scenes is a miss)
     r.close()
 
 

@@ -305,3 +305,21 @@ def test_zero_hash_stream_does_not_hang(scenes, oracle_api):
     r.render(0, 1, seed_base=1768515948 - 40)  # pixel 40 of frame 0 gets the zero-hash index
     assert np.isfinite(r.accumulator()[..., 3]).all()
     r.close(); s.close()
+
+
+def test_resolve_restatement_equals_the_oracle(oracle_api):
+    """tests/resolve_ref.py (what tests/test_gpu_output_stages.py holds k_resolve to) against the oracle's ResolvePixel, bit for bit, on
+    every k/255 boundary, the specials, the int64 branch's edges, NaNs and 1M random bit patterns, three channels set independently"""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import resolve_ref as rr
+    px = rr.pixels(rr.value_set(), 3 << 19)
+    for it in rr.ITS:
+        got, ref = rr.resolve(px, it), oracle_api.resolve_values(px, it)
+        bad = np.flatnonzero(got != ref)
+        assert bad.size == 0, "it %d: %d pixels differ, first %s -> %#x, oracle %#x" % (it, bad.size, px[bad[0]], got[bad[0]], ref[bad[0]])
+    # a few by hand: 255 v truncated toward zero; a negative channel keeps the low half of its int64 (wrapping into the others);
+    # NaN and anything >= 1 clamp to 255; -inf and the out-of-range negatives are INT64_MIN, whose low half is 0
+    ch = rr.channel(np.array([1, 0.5, np.float32(254) / np.float32(255), -np.float32(1) / np.float32(255), np.nan, -np.inf, 3e30, -3e30], np.float32))
+    assert ch.tolist() == [255, 127, 254, 0xFFFFFFFF, 255, 0, 255, 0]
+    one = np.array([[0.5, -1 / 255, 1, 0]], np.float32)
+    assert rr.resolve(one, 1)[0] == oracle_api.resolve_values(one, 1)[0] == ((127 << 16) + (0xFFFFFFFF << 8) + 255) & 0xFFFFFFFF
