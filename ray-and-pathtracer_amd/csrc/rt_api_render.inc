@@ -358,8 +358,8 @@ static int ensure_stream_state(rt_ctx* c, int n)
 		HIPCHK(c, dalloc(A, &T.cls[b], cap));
 	}
 	HIPCHK(c, dalloc(A, &T.pos, cap / 64 + 64)); // a pair of bases per group of 64 entries
-	HIPCHK(c, dalloc(A, &T.shI, cap)); HIPCHK(c, dalloc(A, &T.shN, cap)); HIPCHK(c, dalloc(A, &T.shD, cap)); HIPCHK(c, dalloc(A, &T.shW, cap));
-	HIPCHK(c, dalloc(A, &T.shP, cap * nl));
+	HIPCHK(c, dalloc(A, &T.shI, cap)); HIPCHK(c, dalloc(A, &T.shX, cap)); // a shadow record: 24 B ...
+	HIPCHK(c, dalloc(A, &T.shP, cap * nl));                               // ... + 16 B per light for connect
 	HIPCHK(c, dalloc(A, &T.vis, cap * nl));
 	HIPCHK(c, dalloc(A, &T.traceQ, cap));
 	HIPCHK(c, dalloc(A, &T.leftover, wide ? cap * nl : (size_t)4));

@@ -62,11 +62,14 @@ struct StreamState {
 	float4* L[2];     // radiance so far xyz, w = sample id
 	unsigned char* cls[2]; // CL_* bits
 	int2* pos;        // current round, per GROUP of 64 entries: x = entry in the next round of the group's first CL_CONT entry, y = shadow record of its first CL_SHADOW entry (k_assign; k_shade_s counts inside the group)
-	float4* shI;      // shadow record: ray.IntersectionPoint() xyz, w = material
-	float4* shN;      //                hit normal xyz, w = continuation entry (holds this path's E and L)
-	float4* shD;      //                direction of the ray that hit xyz
-	float4* shW;      //                weight of the segment xyz
-	float4* shP;      // [light][cap]   sampled light position xyz
+	// A shadow record holds what exists nowhere else, and references into its round for the rest: the hit's normal, D, W and
+	// material stay in entry e of buffer p = round & 1 until shade(r + 1) writes that buffer, and shade(r + 1) starts only after
+	// light(r) on every schedule of run_rounds_stream.  light rebuilds the sampled light positions from the seed: it runs shade's
+	// loop of light_position calls again on the same operands, so the replay is bit for bit.  connect reads them from shP:
+	// replayed there, its double-precision cos / sin cost it more than the 16-B load (profiles/FINDINGS.md, finding 93).
+	float4* shI;      // shadow record: ray.IntersectionPoint() xyz, w = RNG state before the light loop (bits)
+	int2* shX;        //                x = entry e of round r, y = continuation entry (holds this path's E and L)
+	float4* shP;      // [light][cap]   sampled light position xyz: connect's alone (light replays the draws)
 	unsigned char* vis; // [light][cap] 1: occluded
 	uint* traceQ;     // entries with CL_TRACE, in order
 	uint* leftover;   // connect work items the 4-wide walk handed back
@@ -412,7 +415,7 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 			const f3 O = xyz(o4), D = xyz(d4), normal = xyz(hn);
 			const float t = hn.w;
 			f3 W = xyz(w4), E = xyz(e4), Lsum = xyz(l4);
-			uint seed = __float_as_uint(e4.w);
+			uint seed = __float_as_uint(e4.w), shadowSeed = 0;
 			const f3 I = O + t * D; // ray.IntersectionPoint()
 			const bool childTraces = !last; // Sample(depth - 1 < 0) = 0.05 (renderer.cpp:129)
 			bool segmentEnds = true, wantShadow = false;
@@ -474,9 +477,10 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 					else Lsum = Lsum + nW * f3(0.05f);
 				} else { // DIFFUSE, renderer.cpp:156-191
 					wantShadow = S.nLights > 0;
+					shadowSeed = seed; // light draws the light positions again from here
 					for (int i = 0; i < S.nLights; i++) {
 						const f3 pickedPos = light_position(S.lights[i], false, seed);
-						T.shP[(size_t)i * cap + (size_t)p.y] = mk4(pickedPos, 0.0f);
+						T.shP[(size_t)i * cap + (size_t)p.y] = mk4(pickedPos, 0.0f); // connect's
 					}
 					const f3 albedo(m.albedo[0], m.albedo[1], m.albedo[2]);
 					if constexpr (QL) {
@@ -508,10 +512,8 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 			// the class byte promised exactly these outputs
 			RT_CHECK(((c & CL_SHADOW) != 0) == wantShadow && ((c & CL_CONT) != 0) == (!segmentEnds || wantShadow), 22, &T.counts[SC_FLAG]);
 			if (wantShadow) {
-				T.shI[p.y] = mk4(I, __int_as_float(id.y));
-				T.shN[p.y] = mk4(normal, __int_as_float(p.x));
-				T.shD[p.y] = mk4(D, 0.0f);
-				T.shW[p.y] = mk4(W, 0.0f);
+				T.shI[p.y] = mk4(I, __uint_as_float(shadowSeed));
+				T.shX[p.y] = make_int2(e, p.x);
 			}
 			if (!segmentEnds || wantShadow) {
 				T.E[pout][p.x] = mk4(E, __uint_as_float(seed));
@@ -615,21 +617,27 @@ __global__ void RT_LIGHT_BOUNDS k_light_s(DScene S0, RenderParams R, StreamState
 	__shared__ ShadeTables tables;
 	DScene S = S0;
 	load_tables(S, tables, ldsTables);
-	const int pout = 1 - (round & 1);
+	const int p = round & 1, pout = 1 - p;
 	const int n = T.counts[SC_SHADOW + round % 3];
 	const size_t cap = (size_t)T.cap;
 	for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
-		const float4 i4 = T.shI[s], n4 = T.shN[s], d4 = T.shD[s], w4 = T.shW[s];
-		const int cp = __float_as_int(n4.w);
-		RT_CHECK(cp >= 0 && cp < T.cap, 24, &T.counts[SC_FLAG]);
+		const float4 i4 = T.shI[s];
+		const int2 x = T.shX[s];
+		const int e = x.x, cp = x.y;
+		RT_CHECK(e >= 0 && e < T.cap && cp >= 0 && cp < T.cap, 24, &T.counts[SC_FLAG]);
+		// the hit's own fields from entry e of this round (shade(round + 1) has not run yet); a round-0 entry has no W: shade took 1 (fresh)
+		const float4 n4 = T.hitN[p][e], d4 = T.D[p][e];
+		const int mat = T.hitId[p][e].y;
+		const f3 W = round == 0 ? f3(1.0f) : xyz(T.W[p][e]);
 		const float4 e4 = T.E[pout][cp], l4 = T.L[pout][cp];
-		const f3 I = xyz(i4), normal = xyz(n4), D = xyz(d4), W = xyz(w4);
+		const f3 I = xyz(i4), normal = xyz(n4), D = xyz(d4);
 		f3 E = xyz(e4), Lsum = xyz(l4);
-		const DMaterial m = S.mats[__float_as_int(i4.w)];
+		uint seed = __float_as_uint(i4.w); // shade's light loop, replayed
+		const DMaterial m = S.mats[mat];
 		const f3 col(m.col[0], m.col[1], m.col[2]);
 		f3 direct(0.0f);
 		for (int i = 0; i < S.nLights; i++) {
-			const f3 pickedPos = xyz(T.shP[(size_t)i * cap + (size_t)s]);
+			const f3 pickedPos = light_position(S.lights[i], false, seed);
 			const f3 lightRayDirection = normalize(pickedPos - I);
 			if (T.vis[(size_t)i * cap + (size_t)s] != 0) continue;
 			const f3 att = diffuse_scatter(m, D, lightRayDirection, light_intensity(S.lights[i], I, normal, pickedPos), normal, E);
