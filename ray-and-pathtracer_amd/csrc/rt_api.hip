@@ -37,17 +37,7 @@ rt_ctx* rt_create(int device, int width, int height)
 	if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) { fail(nullptr, RT_E_NODEVICE, "rt_create: device %d is %s, this library is built for gfx950 only", device, prop.gcnArchName); return nullptr; }
 	rt_ctx* c = new rt_ctx();
 	c->device = device, c->width = width, c->height = height;
-	memset(&c->S, 0, sizeof(c->S));
-	memset(&c->slot.P, 0, sizeof(PathState)), memset(&c->slot.Q, 0, sizeof(Queues));
 	read_knobs(c->knobs);
-	c->fuseTraversal = c->knobs.fuse, c->useStream = c->knobs.stream, c->decideRays = c->knobs.decide;
-	c->useMega = c->knobs.mega, c->megaLpt = c->knobs.megaLpt, c->megaLevels = c->knobs.megaLevels, c->deferGamma = c->knobs.deferGamma;
-	memset(&c->M, 0, sizeof(c->M));
-	memset(&c->Qt, 0, sizeof(c->Qt));
-	c->shadeLds = c->knobs.shadeLds;
-	memset(&c->T, 0, sizeof(c->T));
-	memset(&c->prof, 0, sizeof(c->prof));
-	memset(&c->C, 0, sizeof(c->C));
 	bool ok = hipStreamCreate(&c->stream) == hipSuccess;
 	ok = ok && hipMalloc((void**)&c->accum, (size_t)width * height * sizeof(float4)) == hipSuccess;
 	ok = ok && hipMemset(c->accum, 0, (size_t)width * height * sizeof(float4)) == hipSuccess;
@@ -61,20 +51,20 @@ rt_ctx* rt_create(int device, int width, int height)
 		auto resident = [&](const void* fn) { int b = 0; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, fn, RT_BLOCK, 0) != hipSuccess || b < 1) b = 1; if (b > 8) b = 8; if (capBlocks >= 1 && b > capBlocks) b = capBlocks; return b * prop.multiProcessorCount; };
 		const int e0 = std::min(resident((const void*)k_extend<false, false>), resident((const void*)k_extend<false, true>)), e1 = std::min(resident((const void*)k_extend<true, false>), resident((const void*)k_extend<true, true>));
 		const int c0 = resident((const void*)k_connect<false>), c1 = resident((const void*)k_connect<true>);
-		c->gridExtend = e0 < e1 ? e0 : e1, c->gridConnect = c0 < c1 ? c0 : c1;
-		c->gridConnectWide = resident((const void*)k_connect<false, true>);
-		c->gridLeftover = std::min(resident((const void*)k_connect<false, false, true>), prop.multiProcessorCount); // a short list: one block per CU is plenty
-		c->gridExtendS = std::min(resident((const void*)k_extend_s<false>), resident((const void*)k_extend_s<true>));
-		c->gridConnectS = std::min(resident((const void*)k_connect_s<false>), resident((const void*)k_connect_s<true>));
-		c->gridConnectWideS = resident((const void*)k_connect_s<false, true>);
-		c->gridLeftoverS = std::min(resident((const void*)k_connect_s<false, false, true>), prop.multiProcessorCount);
-		c->gridConnectWide8S = resident((const void*)k_connect_s<false, false, false, true>);
-		c->gridTraverseS = resident((const void*)k_traverse_s);
-		c->gridMega = resident((const void*)k_whitted_mega);
-		c->gridLevel = resident((const void*)k_whitted_level);
-		c->gridShadeS = std::min(resident((const void*)k_shade_s<false>), resident((const void*)k_shade_s<true>));
-		c->gridLightS = resident((const void*)k_light_s);
-		int q = c->gridConnect < c->gridExtend ? c->gridConnect : c->gridExtend;
+		c->slot.gridExtend = e0 < e1 ? e0 : e1, c->slot.gridConnect = c0 < c1 ? c0 : c1;
+		c->slot.gridConnectWide = resident((const void*)k_connect<false, true>);
+		c->slot.gridLeftover = std::min(resident((const void*)k_connect<false, false, true>), prop.multiProcessorCount); // a short list: one block per CU is plenty
+		c->dense.gridExtend = std::min(resident((const void*)k_extend_s<false>), resident((const void*)k_extend_s<true>));
+		c->dense.gridConnect = std::min(resident((const void*)k_connect_s<false>), resident((const void*)k_connect_s<true>));
+		c->dense.gridConnectWide = resident((const void*)k_connect_s<false, true>);
+		c->dense.gridLeftover = std::min(resident((const void*)k_connect_s<false, false, true>), prop.multiProcessorCount);
+		c->dense.gridConnectWide8 = resident((const void*)k_connect_s<false, false, false, true>);
+		c->dense.gridTraverse = resident((const void*)k_traverse_s);
+		c->mega.grid = resident((const void*)k_whitted_mega);
+		c->level.grid = resident((const void*)k_whitted_level);
+		c->dense.gridShade = std::min(resident((const void*)k_shade_s<false>), resident((const void*)k_shade_s<true>));
+		c->dense.gridLight = resident((const void*)k_light_s);
+		int q = std::min(c->slot.gridConnect, c->slot.gridExtend);
 		const void* qk[9] = { (const void*)k_query_nearest<false>, (const void*)k_query_nearest<true>, (const void*)k_query_occluded<false>, (const void*)k_query_occluded<true>, (const void*)k_primary_hits<false>, (const void*)k_primary_hits<true>,
 		                      (const void*)k_query_occluded<false, true>, (const void*)k_query_occluded<false, false, true>, (const void*)k_query_occluded<false, false, false, true> };
 		for (int i = 0; i < 9; i++) { const int r = resident(qk[i]); if (r < q) q = r; }
@@ -91,8 +81,6 @@ rt_ctx* rt_create(int device, int width, int height)
 	if (ok) {
 		const int exact = c->knobs.exactGamma; // rt_kernels.h gamma_powf
 		ok = hipMemcpyToSymbol(HIP_SYMBOL(g_exactGamma), &exact, sizeof(int), 0, hipMemcpyHostToDevice) == hipSuccess;
-		c->exactGamma = exact;
-		if (exact) c->deferGamma = 1; // the exact form lives where samples are read (k_accumulate), not in the shading kernels
 	}
 	if (ok) hipLaunchKernelGGL(k_gamma_lut, dim3(1), dim3(256), 0, c->stream, c->gammaLut);
 	if (!ok) { fail(nullptr, RT_E_HIP, "rt_create: device allocation failed: %s", hipGetErrorString(hipGetLastError())); rt_destroy(c); return nullptr; }
@@ -114,20 +102,14 @@ void rt_destroy(rt_ctx* c)
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
 	prof_collect(c);
 	free_pool(c->sceneAllocs);
-	free_pool(c->slot.allocs);
-	free_pool(c->streamAllocs);
-	free_pool(c->megaAllocs);
-	free_pool(c->megaOrderAllocs);
-	free_pool(c->levelAllocs);
+	c->slot.free_state();
+	c->dense.destroy();
+	c->mega.destroy();
+	c->level.free_state();
 	free_pool(c->qAllocs);
-	if (c->streamSide) { (void)hipStreamSynchronize(c->streamSide); (void)hipStreamDestroy(c->streamSide); }
-	if (c->streamSideSpill) (void)hipFree(c->streamSideSpill);
-	if (c->streamFork) (void)hipEventDestroy(c->streamFork);
-	if (c->streamJoin) (void)hipEventDestroy(c->streamJoin);
 	if (c->gatherDone) (void)hipEventDestroy(c->gatherDone);
 	if (c->gatherReady) (void)hipEventDestroy(c->gatherReady);
 	if (c->rowsFree) (void)hipEventDestroy(c->rowsFree);
-	for (int k = 0; k < 2; k++) if (c->megaEv[k]) (void)hipEventDestroy(c->megaEv[k]);
 	if (c->accum && c->accumOwned) (void)hipFree(c->accum);
 	if (c->spill) (void)hipFree(c->spill);
 	if (c->samples) (void)hipFree(c->samples);
@@ -270,8 +252,8 @@ const char* rt_tuning_info(rt_ctx* c)
 	if (!c) return "";
 	char buf[640];
 	snprintf(buf, sizeof(buf), "stream=%d decide=%d fuse=%d refill=%d refill_any=%d stepmin=%d stepmin_any=%d stepmin_xform=%d pairagain=%d pairagain_any=%d drain=%d drain_any=%d shade_lds=%d gamma_lut=%d exact_gamma=%d defer_gamma=%d wide=%d wide8=%d mega=%d mega_levels=%d mega_lpt=%d qlearn=%d tlas_lds=%d stack_rows=%d slots=%d",
-	         c->useStream, c->decideRays, c->fuseTraversal, RT_REFILL, RT_REFILL_ANY, RT_STEPMIN, RT_STEPMIN_ANY, RT_STEPMIN_XFORM,
-	         RT_PAIRAGAIN, RT_PAIRAGAIN_ANY, RT_DRAIN_LANES, RT_DRAIN_LANES_ANY, c->shadeLds, c->S.gammaLut ? 1 : 0, c->exactGamma, c->deferGamma, c->S.wide ? 1 : 0, c->S.wide8 ? 1 : 0, c->useMega, c->megaLevels, c->megaLpt, c->Qt.on,
+	         c->knobs.stream, c->knobs.decide, c->knobs.fuse, RT_REFILL, RT_REFILL_ANY, RT_STEPMIN, RT_STEPMIN_ANY, RT_STEPMIN_XFORM,
+	         RT_PAIRAGAIN, RT_PAIRAGAIN_ANY, RT_DRAIN_LANES, RT_DRAIN_LANES_ANY, c->knobs.shadeLds, c->S.gammaLut ? 1 : 0, c->knobs.exactGamma, c->knobs.deferGamma, c->S.wide ? 1 : 0, c->S.wide8 ? 1 : 0, c->knobs.mega, c->knobs.megaLevels, c->knobs.megaLpt, c->Qt.on,
 	         c->S.tlasLds, c->S.stackRows, slot_budget(c));
 	c->tuningInfo = buf;
 	return c->tuningInfo.c_str();

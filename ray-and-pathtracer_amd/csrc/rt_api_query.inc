@@ -1,14 +1,5 @@
 // Batch queries: Scene::FindNearest / IsOccluded / GetSkyColor and the members below scene level for n caller rays, primary-hit maps.  Included by rt_api.hip.
 // ---- batch queries -------------------------------------------------------------------------------
-static int check_overflow(rt_ctx* c)
-{
-	int f = 0;
-	HIPCHK(c, hipMemcpy(&f, c->flags + 1, sizeof(int), hipMemcpyDeviceToHost));
-	if (f == 199) { (void)hipMemset(c->flags, 0, 2 * sizeof(int)); return fail(c, RT_E_STATE, "a traversal launch met a link no step understands (corrupt tree?) and dropped rays"); }
-	if (f >= 100) { (void)hipMemset(c->flags, 0, 2 * sizeof(int)); return fail(c, RT_E_STATE, "debug check %d failed in a query kernel (RT_DEBUG_CHECKS build)", f - 100); }
-	if (f) { (void)hipMemset(c->flags, 0, 2 * sizeof(int)); return fail(c, RT_E_OVERFLOW, "traversal stack deeper than %d entries", RT_STACK_MAX); }
-	return RT_OK;
-}
 static int query_grid(rt_ctx* c, int n) { int g = (n + RT_CHUNK - 1) / RT_CHUNK / 4 + 1; return g > c->gridQuery ? c->gridQuery : g; }
 
 // the scene as a query of the given scope sees it: rooted at the accelerator, one BLAS or one instance
@@ -55,9 +46,7 @@ int rt_intersect_scope(rt_ctx* c, int scope, int index, int n, const float* O, c
 	if (e == hipSuccess && tmax) e = hipMemcpyAsync(dT, tmax, (size_t)4 * n, hipMemcpyHostToDevice, c->stream);
 	if (e == hipSuccess) {
 		(void)hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), c->stream); // work heads
-#ifdef RT_SECTION_PROBE
 		section_probe_reset(c->stream);
-#endif
 		prof_begin(c, K_QUERY);
 		const bool head = scope == RT_SCOPE_SCENE;
 		if (c->counting) {
@@ -68,9 +57,7 @@ int rt_intersect_scope(rt_ctx* c, int scope, int index, int n, const float* O, c
 			else hipLaunchKernelGGL((k_query_nearest<false, false>), dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, S, n, dO, dD, dT, t_min, tuning(c), dH, c->spill, c->flags, c->counters);
 		}
 		prof_end(c);
-#ifdef RT_SECTION_PROBE
 		if (!c->counting) section_probe_print(c->stream, "query", n);
-#endif
 		e = hipStreamSynchronize(c->stream);
 	}
 	static_assert(sizeof(QueryHit) == sizeof(rt_hit), "rt_hit layout");

@@ -1,7 +1,6 @@
-// rt_render[_rows], rt_trace_batch[_energy]: path state, the slot wavefront's round loop, Whitted frames as one launch / by tree levels, the dense
-// path-mode pipeline (run_rounds_stream), batches of frames and k_accumulate.  Included by rt_api.hip.
-static int check_overflow(rt_ctx* c);
-
+// rt_render[_rows], rt_trace_batch[_energy]: path state, the slot wavefront's round loop, Whitted frames by tree levels / as one launch, the dense
+// path-mode pipeline (run_rounds_stream), the dispatcher that puts a batch of samples on one of them (trace_samples), batches of frames and
+// k_accumulate.  Included by rt_api.hip.
 // ---- path state -------------------------------------------------------------------------------
 static int ensure_state(rt_ctx* c, int nSlots, bool pend)
 {
@@ -9,10 +8,8 @@ static int ensure_state(rt_ctx* c, int nSlots, bool pend)
 	const bool wide = c->S.wide != nullptr; // the 4-wide occlusion walk hands rays back through Q.leftover: allocated only for scenes that have it
 	if (pl.stateSlots >= nSlots && pl.stateLights == c->S.nLights && (pl.statePend || !pend) && (pl.stateWide || !wide)) { pl.P.nSlots = nSlots; return RT_OK; }
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	free_pool(pl.allocs);
-	pl.stateSlots = 0;
-	PathState P;
-	memset(&P, 0, sizeof(P));
+	pl.free_state();
+	PathState P{};
 	const size_t n = (size_t)nSlots;
 	for (int b = 0; b < 2; b++) { HIPCHK(c, dalloc(pl.allocs, &P.O[b], n)); HIPCHK(c, dalloc(pl.allocs, &P.D[b], n)); }
 	for (int b = 0; b < 2; b++) { HIPCHK(c, dalloc(pl.allocs, &P.hitN[b], n)); HIPCHK(c, dalloc(pl.allocs, &P.hitId[b], n)); }
@@ -26,8 +23,7 @@ static int ensure_state(rt_ctx* c, int nSlots, bool pend)
 		HIPCHK(c, dalloc(pl.allocs, &P.pend, n * RT_PEND_CAP * 4));
 		HIPCHK(c, dalloc(pl.allocs, &P.pendCount, n));
 	}
-	Queues Q;
-	memset(&Q, 0, sizeof(Q));
+	Queues Q{};
 	HIPCHK(c, dalloc(pl.allocs, &P.status, n + 16));
 	HIPCHK(c, dalloc(pl.allocs, &Q.active, n));
 	HIPCHK(c, dalloc(pl.allocs, &Q.shadow, n));
@@ -52,7 +48,29 @@ static int ensure_samples(rt_ctx* c, size_t count)
 	return RT_OK;
 }
 
-static int slot_budget(const rt_ctx* c);
+static int slot_budget(const rt_ctx* c)
+{
+	// slots in flight.  Every round pays a fixed tail: once the work head runs dry the waves of a traversal
+	// launch drain unevenly, and the longest rays finish alone at memory latency per step (0.3-0.8 ms per traversal
+	// launch whatever it held, DESIGN.md finding 38).  Fewer, larger rounds win until every sample of the batch has its
+	// own slot: 16M -> 64M -> 128M slots took the 1080p x 64 spp frame from 97.8 to 79.0 to 76.4 ms (round 1), and
+	// 128M -> 256M takes 1080p x 256 spp from 148 to 138.5 ms and 4K x 1024 spp from 2.96 to 2.88 s (32-frame instead
+	// of 16-frame batches).  ~250 B of state per slot: 256M slots = 67 GB of the 288 GB, allocated for the slots a batch
+	// really has.  The shadow rays of a round are counted in an int: slots x lights stays below 2^31.  RT_SLOTS overrides.
+	const long v = c ? c->knobs.slots : 0;
+	long b = v > 0 ? v : (1l << 28);
+	const long lights = c && c->S.nLights > 1 ? c->S.nLights : 1;
+	if (b > 0x7FFFFFFFl / lights) b = 0x7FFFFFFFl / lights;
+	return (int)b;
+}
+static int segments_per_sample(int mode, int depth, int nLights)
+{
+	// path: at most 5 segments (depth 4..0); Whitted: at most 2^depth - 1 glass segments, times the
+	// mirror branches of shiny diffuse hits
+	if (mode == RT_MODE_PATH) return depth + 1;
+	return (1 << (depth < 12 ? depth : 12)) * (1 + nLights);
+}
+
 // Scene::IsOccluded for the shadow queue.  Counting launches walk like the reference; timed launches take the 4-wide
 // walk when the scene has wide nodes, followed by the binary walk over the (normally empty) list of rays the wide
 // walk handed back because they are not clean.
@@ -60,12 +78,12 @@ static void launch_connect(rt_ctx* c, hipStream_t st, const PathState& P, const 
 {
 	// the any-hit walk has its own thresholds (RT_REFILL_ANY, RT_STEPMIN_ANY, RT_PAIRAGAIN_ANY)
 	const int tun = tuning(c);
-	if (c->counting) hipLaunchKernelGGL((k_connect<true>), dim3(c->gridConnect), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, tun, spill, c->counters + 1);
-	else if (!c->S.wide) hipLaunchKernelGGL((k_connect<false>), dim3(c->gridConnect), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, tun, spill, c->counters + 1);
+	if (c->counting) hipLaunchKernelGGL((k_connect<true>), dim3(c->slot.gridConnect), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, tun, spill, c->counters + 1);
+	else if (!c->S.wide) hipLaunchKernelGGL((k_connect<false>), dim3(c->slot.gridConnect), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, tun, spill, c->counters + 1);
 	else {
-		hipLaunchKernelGGL((k_connect<false, true>), dim3(c->gridConnectWide), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, tun, spill, c->counters + 1);
+		hipLaunchKernelGGL((k_connect<false, true>), dim3(c->slot.gridConnectWide), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, tun, spill, c->counters + 1);
 		hipLaunchKernelGGL(k_round_begin, dim3(1), dim3(1), 0, st, Q, 0, 0, 4);
-		hipLaunchKernelGGL((k_connect<false, false, true>), dim3(c->gridLeftover), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, tun, spill, c->counters + 1);
+		hipLaunchKernelGGL((k_connect<false, false, true>), dim3(c->slot.gridLeftover), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, tun, spill, c->counters + 1);
 	}
 }
 // The round loop of the slot wavefront (rt_kernels.h), shared by rt_render_rows and rt_trace_batch: Whitted rounds (RT_MEGA=0 and
@@ -95,49 +113,29 @@ static int run_rounds(rt_ctx* c, const RenderParams& R, int maxRounds, int known
 		const int allActive = round == 0 && R.finishInline ? P.nSlots : 0;
 		hipLaunchKernelGGL(k_round_begin, dim3(1), dim3(1), 0, st, Q, P.pendCount ? 0 : 1, allActive, 3);
 		if (!allActive) hipLaunchKernelGGL(k_compact, dim3(grid / 2), dim3(RT_COMPACT_BLOCK), 0, st, P, (int)ST_ACTIVE, Q.active, &Q.counts[0]);
-#ifdef RT_TAIL_PROBE
 		tail_probe_reset(st);
-#endif
-#ifdef RT_SECTION_PROBE
 		section_probe_reset(st);
-#endif
-#ifdef RT_STEP_COUNT
 		step_count_begin(c, st, P.nSlots);
-#endif
 		prof_begin(c, K_EXTEND, st);
 		{
 			auto extendKernel = c->counting ? (allActive ? k_extend<true, true> : k_extend<true, false>) : (allActive ? k_extend<false, true> : k_extend<false, false>);
-			hipLaunchKernelGGL(extendKernel, dim3(c->gridExtend), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, t_min, tuning(c), c->spill, c->counters);
+			hipLaunchKernelGGL(extendKernel, dim3(c->slot.gridExtend), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, t_min, tuning(c), c->spill, c->counters);
 		}
 		prof_end(c, st);
-#ifdef RT_TAIL_PROBE
 		tail_probe_print(st, "extend", round);
-#endif
-#ifdef RT_SECTION_PROBE
 		section_probe_print(st, "extend", round);
-#endif
-#ifdef RT_STEP_COUNT
 		step_count_print(c, st, P, parity, round, c->matTypes);
-#endif
 		prof_begin(c, K_SHADE, st);
 		hipLaunchKernelGGL(k_shade, dim3(grid), dim3(RT_BLOCK), 0, st, c->S, c->C, R, P, Q, parity, round == 0 && R.finishInline ? 1 : 0);
 		prof_end(c, st);
 		hipLaunchKernelGGL(k_compact, dim3(grid / 2), dim3(RT_COMPACT_BLOCK), 0, st, P, (int)ST_SHADOW, Q.shadow, &Q.counts[2]);
-#ifdef RT_TAIL_PROBE
 		tail_probe_reset(st);
-#endif
-#ifdef RT_SECTION_PROBE
 		section_probe_reset(st);
-#endif
 		prof_begin(c, K_CONNECT, st);
 		launch_connect(c, st, P, Q, parity, c->spill);
 		prof_end(c, st);
-#ifdef RT_TAIL_PROBE
 		tail_probe_print(st, "connect", round);
-#endif
-#ifdef RT_SECTION_PROBE
 		section_probe_print(st, "connect", round);
-#endif
 		prof_begin(c, K_SHADE, st);
 		hipLaunchKernelGGL(k_light, dim3(grid), dim3(RT_BLOCK), 0, st, c->S, R, P, Q, parity);
 		if (!R.finishInline) {
@@ -151,11 +149,8 @@ static int run_rounds(rt_ctx* c, const RenderParams& R, int maxRounds, int known
 			HIPCHK(c, hipMemcpyAsync(c->hostCounts, Q.counts, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
 			HIPCHK(c, hipStreamSynchronize(st));
 			const int* hc = c->hostCounts;
-			if (hc[3] == 1) rc = fail(c, RT_E_OVERFLOW, "traversal stack deeper than %d entries", RT_STACK_MAX);
-			else if (hc[3] == 2) rc = fail(c, RT_E_OVERFLOW, "more than %d pending Whitted branches in one pixel", RT_PEND_CAP);
-			else if (hc[3] == 199) rc = fail(c, RT_E_STATE, "a traversal launch met a link no step understands (corrupt tree?) and dropped rays");
-			else if (hc[3] >= 100) rc = fail(c, RT_E_STATE, "debug check %d failed in a wavefront kernel (RT_DEBUG_CHECKS build)", hc[3] - 100);
 			if (hc[3] != 0) (void)hipMemsetAsync(Q.counts + 3, 0, sizeof(int), st);
+			rc = decode_status(c, hc[3], FAM_WAVEFRONT);
 			if (rc != RT_OK || hc[0] == 0 || knownRounds > 0) break;
 			if (round + 1 == maxRounds) rc = fail(c, RT_E_STATE, "paths still active after %d rounds", maxRounds);
 		}
@@ -167,9 +162,60 @@ static int run_rounds(rt_ctx* c, const RenderParams& R, int maxRounds, int known
 
 // ---- Whitted frames as one persistent launch (rt_mega.h) -----------------------------------------------
 #define RT_LEVEL_SAMPLES_MAX (16u << 20) // larger batches keep the single launch: their drain is a small part of them, and the queues would take GBs
-static int run_levels(rt_ctx* c, const RenderParams& R, const MegaState& M0, int grid0, bool* redo);
+// the status word of a Whitted launch, read after it and cleared for the next one; 3 is run_levels' to answer
+static int whitted_status(rt_ctx* c, int& f)
+{
+	const int rc = read_flags(c, f);
+	if (rc == RT_OK && f != 0) (void)hipMemsetAsync(c->flags, 0, 2 * sizeof(int), c->stream);
+	return rc;
+}
+
+// Whitted frames by tree levels (rt_mega.h): depth launches of k_whitted_level + k_whitted_reduce.  *redo: a queue overflowed.
+static int run_levels(rt_ctx* c, const RenderParams& R, const MegaState& M0, int grid0, bool* redo)
+{
+	rt_ctx::LevelForm& lv = c->level;
+	const int levels = R.maxDepth;
+	const size_t cap = ((size_t)2 * R.nSamples + 65536 + 63) & ~(size_t)63;
+	if (lv.cap < cap || lv.levels < levels || lv.samples < (size_t)R.nSamples) {
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		lv.free_state();
+		LevelState V{};
+		std::vector<void*>& A = lv.allocs;
+		HIPCHK(c, dalloc(A, &V.seg[0], cap * 4)); HIPCHK(c, dalloc(A, &V.seg[1], cap * 4));
+		HIPCHK(c, dalloc(A, &V.count, (size_t)RT_LEVEL_MAX + 2));
+		HIPCHK(c, dalloc(A, &V.termKey, cap * (size_t)levels)); HIPCHK(c, dalloc(A, &V.termVal, cap * (size_t)levels));
+		HIPCHK(c, dalloc(A, &V.head, (size_t)R.nSamples));
+		V.cap = (int)cap;
+		lv.V = V, lv.cap = cap, lv.levels = levels, lv.samples = (size_t)R.nSamples;
+	}
+	LevelState V = lv.V;
+	V.qcap = V.cap;
+	if (c->knobs.levelCap >= 64 && c->knobs.levelCap < V.cap) V.qcap = c->knobs.levelCap & ~63; // tests: queues that overflow
+	(void)hipMemsetAsync(V.count, 0, (RT_LEVEL_MAX + 2) * sizeof(int), c->stream);
+	(void)hipMemsetAsync(V.head, 0xFF, (size_t)R.nSamples * sizeof(int), c->stream);
+	prof_begin(c, K_EXTEND);
+	for (int level = 0; level < levels; level++) {
+		if (level > 0) (void)hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), c->stream); // work heads
+		V.level = level;
+		const int grid = level == 0 ? std::min(grid0, lv.grid) : lv.grid;
+		hipLaunchKernelGGL(k_whitted_level, dim3(grid), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, R, M0, V, tuning(c), c->spill, c->flags);
+	}
+	hipLaunchKernelGGL(k_whitted_reduce, dim3((R.nSamples + 255) / 256), dim3(256), 0, c->stream, R, V);
+	prof_end(c);
+	int f = 0;
+	int rc = whitted_status(c, f);
+	if (rc != RT_OK) return rc;
+	*redo = f == 3;
+	if (f == 3) return RT_OK;
+	rc = decode_status(c, f, FAM_WHITTED);
+	if (rc != RT_OK) return rc;
+	HIPCHK(c, hipGetLastError());
+	return RT_OK;
+}
+
 static int run_mega(rt_ctx* c, const RenderParams& R0)
 {
+	rt_ctx::MegaForm& mg = c->mega;
 	RenderParams R = R0;
 	// deal the frame out in tiles of 64 pixels from all over it (rt_mega.h sample_of): the multiplier nearest nTiles / 61 that is coprime to nTiles
 	if (R.nSamples >= 16384) {
@@ -180,153 +226,97 @@ static int run_mega(rt_ctx* c, const RenderParams& R0)
 		while (gcd(p, nTiles) != 1) p += 2;
 		R.permMul = p;
 	}
-	const int gridMax = c->gridMega;
-	const int lanes = std::max(c->gridMega, c->gridLevel) * RT_BLOCK; // run_levels indexes the same arrays by lane of ITS grid
-	if (c->megaLanes < lanes) {
+	const int gridMax = mg.grid;
+	const int lanes = std::max(mg.grid, c->level.grid) * RT_BLOCK; // run_levels indexes the same arrays by lane of ITS grid
+	if (mg.lanes < lanes) {
 		HIPCHK(c, hipStreamSynchronize(c->stream));
-		free_pool(c->megaAllocs);
-		MegaState M;
-		memset(&M, 0, sizeof(M));
-		std::vector<void*>& A = c->megaAllocs;
+		mg.free_lanes();
+		MegaState M{};
+		std::vector<void*>& A = mg.allocs;
 		const size_t n = (size_t)lanes;
 		HIPCHK(c, dalloc(A, &M.O, n)); HIPCHK(c, dalloc(A, &M.D, n)); HIPCHK(c, dalloc(A, &M.W, n)); HIPCHK(c, dalloc(A, &M.E, n)); HIPCHK(c, dalloc(A, &M.L, n));
 		HIPCHK(c, dalloc(A, &M.hI, n)); HIPCHK(c, dalloc(A, &M.hN, n)); HIPCHK(c, dalloc(A, &M.hA, n)); HIPCHK(c, dalloc(A, &M.hS, n));
 		HIPCHK(c, dalloc(A, &M.pend, n * RT_PEND_CAP * 4));
 		M.lanes = lanes;
-		c->M = M, c->megaLanes = lanes;
+		mg.M = M, mg.lanes = lanes;
 	}
 	int grid = ((int)R.nSamples + RT_SHORT_QUEUE_RAYS * 64 - 1) / (RT_SHORT_QUEUE_RAYS * 64) + 1; // a short queue does not need the whole grid
 	if (grid > gridMax) grid = gridMax;
 	(void)hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), c->stream); // work heads
 	// longest first (rt_mega.h): a Whitted launch over the samples the last one rendered deals its tiles out by what they cost then
-	MegaState M = c->M;
+	MegaState M = mg.M;
 	M.cost = nullptr, M.order = nullptr;
 	M.nWork = (int)(((R.nSamples + (1u << R.permShift) - 1) >> R.permShift) << R.permShift);
-	bool useLevels = c->megaLevels && R.mode == RT_MODE_WHITTED && !R.customO && R.maxDepth >= 1 && R.maxDepth <= RT_LEVEL_MAX && R.nSamples <= RT_LEVEL_SAMPLES_MAX && c->S.nLights <= 32;
+	const int megaLevels = c->knobs.megaLevels;
+	bool useLevels = megaLevels && R.mode == RT_MODE_WHITTED && !R.customO && R.maxDepth >= 1 && R.maxDepth <= RT_LEVEL_MAX && R.nSamples <= RT_LEVEL_SAMPLES_MAX && c->S.nLights <= 32;
 	// RT_MEGA_LEVELS=2: both forms give the same frame, so the context may simply time them -- each form twice on the first four batches
 	// of a shape (the first run of a form pays its allocations and has no cost history), then whichever was faster
 	int probe = -1; // the form this batch is timed as
-	if (useLevels && c->megaLevels == 2) {
-		auto& A = c->megaAuto;
+	if (useLevels && megaLevels == 2) {
+		auto& A = mg.pick;
 		if (A.nSamples != R.nSamples || A.depth != R.maxDepth) A = {}, A.nSamples = R.nSamples, A.depth = R.maxDepth;
 		if (A.choice < 0) {
 			probe = A.tried[0] < 2 ? 0 : 1;
-			if (!c->megaEv[0]) { (void)hipEventCreate(&c->megaEv[0]); (void)hipEventCreate(&c->megaEv[1]); }
-			(void)hipEventRecord(c->megaEv[0], c->stream);
+			if (!mg.ev[0]) { (void)hipEventCreate(&mg.ev[0]); (void)hipEventCreate(&mg.ev[1]); }
+			(void)hipEventRecord(mg.ev[0], c->stream);
 		}
 		useLevels = A.choice >= 0 ? A.choice == 1 : probe == 1;
 	}
 	auto probe_end = [&]() {
 		if (probe < 0) return;
-		auto& A = c->megaAuto;
+		auto& A = mg.pick;
 		float ms = 0;
-		(void)hipEventRecord(c->megaEv[1], c->stream);
-		(void)hipEventSynchronize(c->megaEv[1]);
-		(void)hipEventElapsedTime(&ms, c->megaEv[0], c->megaEv[1]);
+		(void)hipEventRecord(mg.ev[1], c->stream);
+		(void)hipEventSynchronize(mg.ev[1]);
+		(void)hipEventElapsedTime(&ms, mg.ev[0], mg.ev[1]);
 		A.ms[probe] = ms, A.tried[probe]++;
 		if (A.tried[0] >= 2 && A.tried[1] >= 2) A.choice = A.ms[1] < A.ms[0] ? 1 : 0;
 	};
-	if (c->megaLpt && R.mode == RT_MODE_WHITTED && R.permMul && !R.customO) {
+	if (c->knobs.megaLpt && R.mode == RT_MODE_WHITTED && R.permMul && !R.customO) {
 		const unsigned tilesPerHead = RT_HEADS * 8u; // sub-queues of n / RT_HEADS entries, a multiple of 64 entries = 8 tiles of 8
 		const unsigned nTiles = (R.nSamples + (1u << R.permShift) - 1) >> R.permShift;
 		// k_mega_order's slot mapping is a bijection only when groups = nTilesPad / 8 is a multiple of RT_HEADS: pad to 8 * RT_HEADS tiles whatever the tile size
 		const unsigned unit = std::max(tilesPerHead * (64u >> R.permShift ? 64u >> R.permShift : 1u) / 8u, 8u * RT_HEADS);
 		const unsigned nTilesPad = (nTiles + unit - 1) / unit * unit;
-		if (c->megaCostCap < (size_t)R.nSamples) {
+		if (mg.costCap < (size_t)R.nSamples) {
 			HIPCHK(c, hipStreamSynchronize(c->stream));
-			free_pool(c->megaOrderAllocs);
-			c->megaCostCap = 0, c->megaCostSamples = 0;
-			HIPCHK(c, dalloc(c->megaOrderAllocs, &c->megaCost, (size_t)R.nSamples));
-			HIPCHK(c, dalloc(c->megaOrderAllocs, &c->megaOrder, (size_t)nTilesPad + 1024));
-			HIPCHK(c, dalloc(c->megaOrderAllocs, &c->megaHist, (size_t)2 * RT_MEGA_BUCKETS));
-			c->megaCostCap = (size_t)R.nSamples;
+			mg.free_order();
+			HIPCHK(c, dalloc(mg.orderAllocs, &mg.cost, (size_t)R.nSamples));
+			HIPCHK(c, dalloc(mg.orderAllocs, &mg.order, (size_t)nTilesPad + 1024));
+			HIPCHK(c, dalloc(mg.orderAllocs, &mg.hist, (size_t)2 * RT_MEGA_BUCKETS));
+			mg.costCap = (size_t)R.nSamples;
 		}
-		if (c->megaCostSamples == R.nSamples && c->megaCostFirst == R.sampleFirst) {
-			(void)hipMemsetAsync(c->megaHist, 0, 2 * RT_MEGA_BUCKETS * sizeof(uint), c->stream);
+		if (mg.costSamples == R.nSamples && mg.costFirst == R.sampleFirst) {
+			(void)hipMemsetAsync(mg.hist, 0, 2 * RT_MEGA_BUCKETS * sizeof(uint), c->stream);
 			const unsigned blocks = (nTilesPad + RT_MEGA_ORDER_BLOCK - 1) / RT_MEGA_ORDER_BLOCK;
-			hipLaunchKernelGGL(k_mega_hist, dim3(blocks), dim3(RT_MEGA_ORDER_BLOCK), 0, c->stream, c->megaCost, R.permShift, R.nSamples, nTilesPad, c->megaHist);
-			hipLaunchKernelGGL(k_mega_order, dim3(blocks), dim3(RT_MEGA_ORDER_BLOCK), 0, c->stream, c->megaCost, R.permShift, R.nSamples, nTilesPad, c->megaHist, c->megaOrder);
-			M.order = c->megaOrder;
+			hipLaunchKernelGGL(k_mega_hist, dim3(blocks), dim3(RT_MEGA_ORDER_BLOCK), 0, c->stream, mg.cost, R.permShift, R.nSamples, nTilesPad, mg.hist);
+			hipLaunchKernelGGL(k_mega_order, dim3(blocks), dim3(RT_MEGA_ORDER_BLOCK), 0, c->stream, mg.cost, R.permShift, R.nSamples, nTilesPad, mg.hist, mg.order);
+			M.order = mg.order;
 			M.nWork = (int)(nTilesPad << R.permShift);
 		}
-		M.cost = c->megaCost;
-		c->megaCostSamples = R.nSamples, c->megaCostFirst = R.sampleFirst;
+		M.cost = mg.cost;
+		mg.costSamples = R.nSamples, mg.costFirst = R.sampleFirst;
 	}
 	// a flush runs the body of Trace for the lanes that finished a query: it waits for more of them than a plain store does (32 instead of 16: 5.0 -> 4.85 ms)
 	if (useLevels) {
 		bool redo = false;
 		const int rc = run_levels(c, R, M, grid, &redo); // level 0 deals its tiles out like the single launch (M.order), and records what they cost
 		if (rc != RT_OK || !redo) { probe_end(); return rc; }
-		probe = -1, c->megaAuto.choice = 0; // this scene overflows the level queues: the single launch from now on
+		probe = -1, mg.pick.choice = 0; // this scene overflows the level queues: the single launch from now on
 		// a queue overflowed (more than two live branches per sample on average): the frame again, as one launch
 		(void)hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), c->stream);
 	}
-#ifdef RT_TAIL_PROBE
 	tail_probe_reset(c->stream);
-#endif
 	prof_begin(c, K_EXTEND);
 	hipLaunchKernelGGL(k_whitted_mega, dim3(grid), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, R, M, tuning(c), c->spill, c->flags);
 	prof_end(c);
-#ifdef RT_TAIL_PROBE
 	tail_probe_print(c->stream, "mega", 0);
-#endif
 	int f = 0;
-	HIPCHK(c, hipMemcpyAsync(c->hostCounts, c->flags + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	f = c->hostCounts[0];
-	if (f != 0) (void)hipMemsetAsync(c->flags, 0, 2 * sizeof(int), c->stream);
-	if (f == 2) return fail(c, RT_E_OVERFLOW, "more than %d pending Whitted branches in one pixel", RT_PEND_CAP);
-	if (f == 199) return fail(c, RT_E_STATE, "a traversal launch met a link no step understands (corrupt tree?) and dropped rays");
-	if (f >= 100) return fail(c, RT_E_STATE, "debug check %d failed in the Whitted kernel (RT_DEBUG_CHECKS build)", f - 100);
-	if (f) return fail(c, RT_E_OVERFLOW, "traversal stack deeper than %d entries", RT_STACK_MAX);
+	int rc = whitted_status(c, f);
+	if (rc == RT_OK) rc = decode_status(c, f, FAM_WHITTED);
+	if (rc != RT_OK) return rc;
 	HIPCHK(c, hipGetLastError());
 	probe_end();
-	return RT_OK;
-}
-
-// Whitted frames by tree levels (rt_mega.h): depth launches of k_whitted_level + k_whitted_reduce.  *redo: a queue overflowed.
-static int run_levels(rt_ctx* c, const RenderParams& R, const MegaState& M0, int grid0, bool* redo)
-{
-	const int levels = R.maxDepth;
-	const size_t cap = ((size_t)2 * R.nSamples + 65536 + 63) & ~(size_t)63;
-	if (c->levelCap < cap || c->levelLevels < levels || c->levelSamples < (size_t)R.nSamples) {
-		HIPCHK(c, hipStreamSynchronize(c->stream));
-		free_pool(c->levelAllocs);
-		c->levelCap = 0, c->levelLevels = 0, c->levelSamples = 0;
-		LevelState V;
-		memset(&V, 0, sizeof(V));
-		std::vector<void*>& A = c->levelAllocs;
-		HIPCHK(c, dalloc(A, &V.seg[0], cap * 4)); HIPCHK(c, dalloc(A, &V.seg[1], cap * 4));
-		HIPCHK(c, dalloc(A, &V.count, (size_t)RT_LEVEL_MAX + 2));
-		HIPCHK(c, dalloc(A, &V.termKey, cap * (size_t)levels)); HIPCHK(c, dalloc(A, &V.termVal, cap * (size_t)levels));
-		HIPCHK(c, dalloc(A, &V.head, (size_t)R.nSamples));
-		V.cap = (int)cap;
-		c->V = V, c->levelCap = cap, c->levelLevels = levels, c->levelSamples = (size_t)R.nSamples;
-	}
-	LevelState V = c->V;
-	V.qcap = V.cap;
-	if (c->knobs.levelCap >= 64 && c->knobs.levelCap < V.cap) V.qcap = c->knobs.levelCap & ~63; // tests: queues that overflow
-	(void)hipMemsetAsync(V.count, 0, (RT_LEVEL_MAX + 2) * sizeof(int), c->stream);
-	(void)hipMemsetAsync(V.head, 0xFF, (size_t)R.nSamples * sizeof(int), c->stream);
-	prof_begin(c, K_EXTEND);
-	for (int level = 0; level < levels; level++) {
-		if (level > 0) (void)hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), c->stream); // work heads
-		V.level = level;
-		const int grid = level == 0 ? std::min(grid0, c->gridLevel) : c->gridLevel;
-		hipLaunchKernelGGL(k_whitted_level, dim3(grid), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, R, M0, V, tuning(c), c->spill, c->flags);
-	}
-	hipLaunchKernelGGL(k_whitted_reduce, dim3((R.nSamples + 255) / 256), dim3(256), 0, c->stream, R, V);
-	prof_end(c);
-	HIPCHK(c, hipMemcpyAsync(c->hostCounts, c->flags + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	const int f = c->hostCounts[0];
-	if (f != 0) (void)hipMemsetAsync(c->flags, 0, 2 * sizeof(int), c->stream);
-	*redo = f == 3;
-	if (f == 3) return RT_OK;
-	if (f == 199) return fail(c, RT_E_STATE, "a traversal launch met a link no step understands (corrupt tree?) and dropped rays");
-	if (f >= 100) return fail(c, RT_E_STATE, "debug check %d failed in the Whitted kernel (RT_DEBUG_CHECKS build)", f - 100);
-	if (f) return fail(c, RT_E_OVERFLOW, "traversal stack deeper than %d entries", RT_STACK_MAX);
-	HIPCHK(c, hipGetLastError());
 	return RT_OK;
 }
 
@@ -334,23 +324,21 @@ static int run_levels(rt_ctx* c, const RenderParams& R, const MegaState& M0, int
 static int ensure_stream_state(rt_ctx* c, int n)
 {
 	const bool wide = c->S.wide != nullptr || c->S.wide8 != nullptr;
-	if (!c->streamSide) {
-		HIPCHK(c, hipStreamCreate(&c->streamSide));
-		HIPCHK(c, hipMalloc((void**)&c->streamSideSpill, (size_t)(RT_STACK_MAX - RT_STACK_ROWS_MIN) * c->gridBlocks * RT_BLOCK * sizeof(uint)));
-		HIPCHK(c, hipEventCreateWithFlags(&c->streamFork, hipEventDisableTiming));
-		HIPCHK(c, hipEventCreateWithFlags(&c->streamJoin, hipEventDisableTiming));
+	if (!c->dense.side) {
+		HIPCHK(c, hipStreamCreate(&c->dense.side));
+		HIPCHK(c, hipMalloc((void**)&c->dense.sideSpill, (size_t)(RT_STACK_MAX - RT_STACK_ROWS_MIN) * c->gridBlocks * RT_BLOCK * sizeof(uint)));
+		HIPCHK(c, hipEventCreateWithFlags(&c->dense.fork, hipEventDisableTiming));
+		HIPCHK(c, hipEventCreateWithFlags(&c->dense.join, hipEventDisableTiming));
 	}
-	if (c->streamCap >= n && c->streamLights == c->S.nLights && (c->streamWide || !wide)) return RT_OK;
+	if (c->dense.cap >= n && c->dense.lights == c->S.nLights && (c->dense.wide || !wide)) return RT_OK;
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->streamSide));
-	free_pool(c->streamAllocs);
-	c->streamCap = 0;
-	StreamState T;
-	memset(&T, 0, sizeof(T));
+	HIPCHK(c, hipStreamSynchronize(c->dense.side));
+	c->dense.free_state();
+	StreamState T{};
 	// k_assign writes the positions of whole 16-entry vectors and the compactions read whole 16-byte vectors of class bytes
 	const size_t cap = ((size_t)n + 1023) & ~(size_t)1023;
 	const size_t nl = (size_t)(c->S.nLights > 0 ? c->S.nLights : 1);
-	std::vector<void*>& A = c->streamAllocs;
+	std::vector<void*>& A = c->dense.allocs;
 	for (int b = 0; b < 2; b++) {
 		HIPCHK(c, dalloc(A, &T.O[b], cap)); HIPCHK(c, dalloc(A, &T.D[b], cap));
 		HIPCHK(c, dalloc(A, &T.hitN[b], cap)); HIPCHK(c, dalloc(A, &T.hitId[b], cap));
@@ -367,24 +355,24 @@ static int ensure_stream_state(rt_ctx* c, int n)
 	HIPCHK(c, dalloc(A, &T.heads, (size_t)2 * RT_HEADS * RT_HEAD_STRIDE));
 	HIPCHK(c, hipMemset(T.counts, 0, 16 * sizeof(int)));
 	T.cap = (int)cap;
-	c->T = T;
-	c->streamCap = (int)cap, c->streamLights = c->S.nLights, c->streamWide = wide;
+	c->dense.T = T;
+	c->dense.cap = (int)cap, c->dense.lights = c->S.nLights, c->dense.wide = wide;
 	return RT_OK;
 }
 static void launch_connect_s(rt_ctx* c, hipStream_t st, const StreamState& T, int round, uint* spill)
 {
 	const int tun = tuning(c);
-	if (c->counting) hipLaunchKernelGGL((k_connect_s<true>), dim3(c->gridConnectS), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
+	if (c->counting) hipLaunchKernelGGL((k_connect_s<true>), dim3(c->dense.gridConnect), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
 	else if (c->S.wide8) {
 		// the 8-wide quantised walk, then the binary walk over the rays it handed back (not clean: normally none)
-		hipLaunchKernelGGL((k_connect_s<false, false, false, true>), dim3(c->gridConnectWide8S), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
+		hipLaunchKernelGGL((k_connect_s<false, false, false, true>), dim3(c->dense.gridConnectWide8), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
 		hipLaunchKernelGGL(k_stream_begin, dim3(1), dim3(1), 0, st, T);
-		hipLaunchKernelGGL((k_connect_s<false, false, true>), dim3(c->gridLeftoverS), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
-	} else if (!c->S.wide) hipLaunchKernelGGL((k_connect_s<false>), dim3(c->gridConnectS), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
+		hipLaunchKernelGGL((k_connect_s<false, false, true>), dim3(c->dense.gridLeftover), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
+	} else if (!c->S.wide) hipLaunchKernelGGL((k_connect_s<false>), dim3(c->dense.gridConnect), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
 	else {
-		hipLaunchKernelGGL((k_connect_s<false, true>), dim3(c->gridConnectWideS), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
+		hipLaunchKernelGGL((k_connect_s<false, true>), dim3(c->dense.gridConnectWide), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
 		hipLaunchKernelGGL(k_stream_begin, dim3(1), dim3(1), 0, st, T);
-		hipLaunchKernelGGL((k_connect_s<false, false, true>), dim3(c->gridLeftoverS), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
+		hipLaunchKernelGGL((k_connect_s<false, false, true>), dim3(c->dense.gridLeftover), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
 	}
 }
 // Path mode, an entry per sample: 'rounds' = start depth + 1 rounds, no queue length is read back.  connect(r) and light(r)
@@ -407,56 +395,52 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 	// per round instead of two.
 	// Measured (profiles/r03_ab_one_launch_per_round.txt, 1080p x spp): 1: 3.73 -> 3.24 ms, 2: 4.50 -> 4.18, 4: 6.10 -> 6.02, 8: 9.00 -> 9.08, 16: 14.8 -> 15.8.
 	const unsigned mixedMax = c->knobs.mixedMax;
-	const bool mixed = !c->counting && (c->fuseTraversal == 1 || (c->fuseTraversal < 0 && R.nSamples < mixedMax)) &&
+	const bool mixed = !c->counting && (c->knobs.fuse == 1 || (c->knobs.fuse < 0 && R.nSamples < mixedMax)) &&
 	                   (unsigned long long)R.nSamples * (unsigned)(c->S.nLights + 1) < 0x7FFFFFFFull;
-	const bool twoStreams = !mixed && (c->fuseTraversal < 0 ? R.nSamples < 100000000u : c->fuseTraversal != 0);
-	const StreamState& T = c->T;
-	hipStream_t st = c->stream, sb = twoStreams ? c->streamSide : c->stream;
+	const bool twoStreams = !mixed && (c->knobs.fuse < 0 ? R.nSamples < 100000000u : c->knobs.fuse != 0);
+	const StreamState& T = c->dense.T;
+	hipStream_t st = c->stream, sb = twoStreams ? c->dense.side : c->stream;
 	const int cnt = c->counting ? 1 : 0;
 	const int n = (int)R.nSamples;
 	prof_begin(c, K_GENERATE, st);
-	hipLaunchKernelGGL(k_generate_s, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, rounds == 1 ? 1 : 0, c->decideRays, cnt);
+	hipLaunchKernelGGL(k_generate_s, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, rounds == 1 ? 1 : 0, c->knobs.decide, cnt);
 	prof_end(c, st);
 	bool pendingJoin = false;
 	for (int round = 0; round < rounds; round++) {
 		const int last = round + 1 == rounds ? 1 : 0, lastNext = round + 2 == rounds ? 1 : 0;
 		hipLaunchKernelGGL(k_compact_s, dim3(grid / 2), dim3(RT_COMPACT_BLOCK), 0, st, T, round);
-#ifdef RT_TAIL_PROBE
 		tail_probe_reset(st);
-#endif
 		prof_begin(c, K_EXTEND, st);
-		if (mixed && round > 0) hipLaunchKernelGGL(k_traverse_s, dim3(c->gridTraverseS), dim3(RT_BLOCK), 0, st, c->S, T, round, last, t_min, tuning(c), c->spill);
-		else if (c->counting) hipLaunchKernelGGL((k_extend_s<true>), dim3(c->gridExtendS), dim3(RT_BLOCK), 0, st, c->S, T, round & 1, last, t_min, tuning(c), c->spill, c->counters);
-		else hipLaunchKernelGGL((k_extend_s<false>), dim3(c->gridExtendS), dim3(RT_BLOCK), 0, st, c->S, T, round & 1, last, t_min, tuning(c), c->spill, c->counters);
+		if (mixed && round > 0) hipLaunchKernelGGL(k_traverse_s, dim3(c->dense.gridTraverse), dim3(RT_BLOCK), 0, st, c->S, T, round, last, t_min, tuning(c), c->spill);
+		else if (c->counting) hipLaunchKernelGGL((k_extend_s<true>), dim3(c->dense.gridExtend), dim3(RT_BLOCK), 0, st, c->S, T, round & 1, last, t_min, tuning(c), c->spill, c->counters);
+		else hipLaunchKernelGGL((k_extend_s<false>), dim3(c->dense.gridExtend), dim3(RT_BLOCK), 0, st, c->S, T, round & 1, last, t_min, tuning(c), c->spill, c->counters);
 		prof_end(c, st);
-#ifdef RT_TAIL_PROBE
 		tail_probe_print(st, "extend_s", round);
-#endif
 		if (mixed && round > 0) { // the shadow answers of the round before came with this round's hits
 			prof_begin(c, K_SHADE, st);
-			hipLaunchKernelGGL(k_light_s, dim3(c->gridLightS), dim3(RT_BLOCK), 0, st, c->S, R, T, round - 1, 0, c->shadeLds);
+			hipLaunchKernelGGL(k_light_s, dim3(c->dense.gridLight), dim3(RT_BLOCK), 0, st, c->S, R, T, round - 1, 0, c->knobs.shadeLds);
 			prof_end(c, st);
 		}
 		hipLaunchKernelGGL(k_assign, dim3(grid / 2), dim3(RT_COMPACT_BLOCK), 0, st, T, round);
-		if (pendingJoin) { HIPCHK(c, hipStreamWaitEvent(st, c->streamJoin, 0)); pendingJoin = false; }
+		if (pendingJoin) { HIPCHK(c, hipStreamWaitEvent(st, c->dense.join, 0)); pendingJoin = false; }
 		prof_begin(c, K_SHADE, st);
-		if (c->Qt.on) hipLaunchKernelGGL(k_shade_s<true>, dim3(c->gridShadeS), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->decideRays, c->shadeLds, cnt, c->Qt);
-		else hipLaunchKernelGGL(k_shade_s<false>, dim3(c->gridShadeS), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->decideRays, c->shadeLds, cnt, c->Qt);
+		if (c->Qt.on) hipLaunchKernelGGL(k_shade_s<true>, dim3(c->dense.gridShade), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt);
+		else hipLaunchKernelGGL(k_shade_s<false>, dim3(c->dense.gridShade), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt);
 		prof_end(c, st);
 		if (mixed && !last) continue; // this round's shadow rays ride in the next round's traversal launch
 		if (twoStreams) {
-			HIPCHK(c, hipEventRecord(c->streamFork, st));
-			HIPCHK(c, hipStreamWaitEvent(sb, c->streamFork, 0));
+			HIPCHK(c, hipEventRecord(c->dense.fork, st));
+			HIPCHK(c, hipStreamWaitEvent(sb, c->dense.fork, 0));
 		}
 		prof_begin(c, K_CONNECT, sb);
-		launch_connect_s(c, sb, T, round, twoStreams ? c->streamSideSpill : c->spill);
+		launch_connect_s(c, sb, T, round, twoStreams ? c->dense.sideSpill : c->spill);
 		prof_end(c, sb);
 		prof_begin(c, K_SHADE, sb);
-		hipLaunchKernelGGL(k_light_s, dim3(c->gridLightS), dim3(RT_BLOCK), 0, sb, c->S, R, T, round, last, c->shadeLds);
+		hipLaunchKernelGGL(k_light_s, dim3(c->dense.gridLight), dim3(RT_BLOCK), 0, sb, c->S, R, T, round, last, c->knobs.shadeLds);
 		prof_end(c, sb);
-		if (twoStreams) { HIPCHK(c, hipEventRecord(c->streamJoin, sb)); pendingJoin = true; }
+		if (twoStreams) { HIPCHK(c, hipEventRecord(c->dense.join, sb)); pendingJoin = true; }
 	}
-	if (pendingJoin) HIPCHK(c, hipStreamWaitEvent(st, c->streamJoin, 0));
+	if (pendingJoin) HIPCHK(c, hipStreamWaitEvent(st, c->dense.join, 0));
 	if (cnt) hipLaunchKernelGGL(k_fold_decided, dim3(1), dim3(1), 0, st, c->S, T.counts, c->counters);
 	HIPCHK(c, hipMemcpyAsync(c->hostCounts, T.counts, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
 	c->hostCounts[4] = 0;
@@ -468,15 +452,12 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 	}
 	HIPCHK(c, hipStreamSynchronize(st));
 	const int* hc = c->hostCounts;
-	int rc = RT_OK;
-	if (hc[4] != 0) {
+	if (hc[4] != 0) { // the sampler's own overflow word comes first
 		(void)hipMemsetAsync(c->Qt.ovf, 0, sizeof(int), st);
 		return fail(c, RT_E_OVERFLOW, "Q-learning sampler: more than %u rewards for one (cell, direction) within one batch of frames: render fewer frames per call", RT_Q_ACC_LIMIT);
 	}
-	if (hc[3] == 1) rc = fail(c, RT_E_OVERFLOW, "traversal stack deeper than %d entries", RT_STACK_MAX);
-	else if (hc[3] == 199) rc = fail(c, RT_E_STATE, "a traversal launch met a link no step understands (corrupt tree?) and dropped rays");
-	else if (hc[3] >= 100) rc = fail(c, RT_E_STATE, "debug check %d failed in a wavefront kernel (RT_DEBUG_CHECKS build)", hc[3] - 100);
 	if (hc[3] != 0) (void)hipMemsetAsync(T.counts + 3, 0, sizeof(int), st);
+	const int rc = decode_status(c, hc[3], FAM_WAVEFRONT);
 	if (rc != RT_OK) return rc;
 	HIPCHK(c, hipGetLastError());
 	return RT_OK;
@@ -485,40 +466,42 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 // (the reference's walk visits the root pair for every ray, which a producer-side decision skips)
 static bool stream_eligible(const rt_ctx* c, int mode, size_t samples)
 {
-	return (c->useStream || c->Qt.on) && mode == RT_MODE_PATH && !c->pathUnsupported && c->counting != RT_COUNT_REFERENCE && samples <= (size_t)slot_budget(c);
+	return (c->knobs.stream || c->Qt.on) && mode == RT_MODE_PATH && !c->pathUnsupported && c->counting != RT_COUNT_REFERENCE && samples <= (size_t)slot_budget(c);
 }
 
-// Size the slots of the slot wavefront for 'total' samples: one each while the budget lasts.
-static int setup_slots(rt_ctx* c, size_t total, bool pend, int& slots, bool& slotPerSample)
+// ---- one batch of samples ---------------------------------------------------------------------------
+// Trace / Sample as one lane per call tree (rt_kernels.h): the combinations the pipelines do not serve
+static int run_general(rt_ctx* c, const RenderParams& R, bool whitted)
 {
+	if (whitted) hipLaunchKernelGGL(k_trace_general, dim3(c->gridBlocks), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, R, c->spill, c->flags + 1);
+	else hipLaunchKernelGGL(k_sample_general, dim3(c->gridBlocks), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, R, c->spill, c->flags + 1);
+	return check_overflow(c);
+}
+// The batch R describes, on the pipeline that serves it; 'depth' is the depth its samples start at (Whitted: R.maxDepth).  Sets
+// R.finishInline: whether the samples were finished where they ended (an entry or slot each) or by k_finish.
+static int trace_samples(rt_ctx* c, RenderParams& R, int depth)
+{
+	const int mode = R.mode;
+	const size_t total = R.nSamples;
+	// random draws interleave with occlusion queries (shiny / raytracer == 0 diffuse): one lane per sample
+	if (mode == RT_MODE_PATH && c->pathUnsupported) return run_general(c, R, false);
+	if (c->knobs.mega && !c->counting && mode == RT_MODE_WHITTED) return run_mega(c, R);
+	if (stream_eligible(c, mode, total)) {
+		const int rc = ensure_stream_state(c, (int)total);
+		if (rc != RT_OK) return rc;
+		R.finishInline = 1;
+		return run_rounds_stream(c, R, depth + 1); // a round per hit level
+	}
+	// the slot wavefront: a slot per sample while the budget lasts
 	const size_t budget = (size_t)slot_budget(c);
-	slots = (int)(total < budget ? total : budget);
-	if (slots < 1) slots = 1;
-	slotPerSample = (size_t)slots >= total;
-	return ensure_state(c, slots, pend);
-}
-
-static int slot_budget(const rt_ctx* c)
-{
-	// slots in flight.  Every round pays a fixed tail: once the work head runs dry the waves of a traversal
-	// launch drain unevenly, and the longest rays finish alone at memory latency per step (0.3-0.8 ms per traversal
-	// launch whatever it held, DESIGN.md finding 38).  Fewer, larger rounds win until every sample of the batch has its
-	// own slot: 16M -> 64M -> 128M slots took the 1080p x 64 spp frame from 97.8 to 79.0 to 76.4 ms (round 1), and
-	// 128M -> 256M takes 1080p x 256 spp from 148 to 138.5 ms and 4K x 1024 spp from 2.96 to 2.88 s (32-frame instead
-	// of 16-frame batches).  ~250 B of state per slot: 256M slots = 67 GB of the 288 GB, allocated for the slots a batch
-	// really has.  The shadow rays of a round are counted in an int: slots x lights stays below 2^31.  RT_SLOTS overrides.
-	const long v = c ? c->knobs.slots : 0;
-	long b = v > 0 ? v : (1l << 28);
-	const long lights = c && c->S.nLights > 1 ? c->S.nLights : 1;
-	if (b > 0x7FFFFFFFl / lights) b = 0x7FFFFFFFl / lights;
-	return (int)b;
-}
-static int segments_per_sample(int mode, int depth, int nLights)
-{
-	// path: at most 5 segments (depth 4..0); Whitted: at most 2^depth - 1 glass segments, times the
-	// mirror branches of shiny diffuse hits
-	if (mode == RT_MODE_PATH) return depth + 1;
-	return (1 << (depth < 12 ? depth : 12)) * (1 + nLights);
+	const int slots = std::max(1, (int)std::min(total, budget));
+	const int rc = ensure_state(c, slots, mode == RT_MODE_WHITTED);
+	if (rc != RT_OK) return rc;
+	const int seg = segments_per_sample(mode, depth, c->S.nLights);
+	const int maxRounds = (int)((total + slots) / slots) * seg + seg + 4;
+	const bool direct = mode == RT_MODE_PATH && (size_t)slots >= total;
+	R.finishInline = direct ? 1 : 0;
+	return run_rounds(c, R, maxRounds, direct ? seg : 0);
 }
 
 int rt_render_rows(rt_ctx* c, int mode, uint32_t frame0, int nframes, uint32_t seed_base, int row_first, int row_stride, int row_count, int max_depth)
@@ -555,42 +538,11 @@ int rt_render_rows(rt_ctx* c, int mode, uint32_t frame0, int nframes, uint32_t s
 		memset(&R, 0, sizeof(R));
 		R.mode = mode, R.frame0 = frame0 + (uint)f, R.nSamples = (uint)total, R.tilePixels = (uint)tilePixels, R.samples = c->samples;
 		R.seedBase = seed_base, R.rowFirst = row_first, R.rowStride = row_stride, R.maxDepth = max_depth, R.accum = c->accum;
-		R.deferGamma = mode == RT_MODE_PATH ? c->deferGamma : 0;
+		R.deferGamma = mode == RT_MODE_PATH ? c->knobs.deferGamma : 0;
 		R.sceneRt = -1; // (rt_render is Tick's loop: the flag is what the mode says)
-		if (mode == RT_MODE_PATH && c->pathUnsupported) {
-			// random draws interleave with occlusion queries (shiny / raytracer == 0 diffuse): one lane per sample
-			hipLaunchKernelGGL(k_sample_general, dim3(c->gridBlocks), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, R, c->spill, c->flags + 1);
-			hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((tilePixels + 255) / 256)), dim3(256), 0, c->stream, c->C, R, bf);
-			rc = check_overflow(c);
-			if (rc != RT_OK) return rc;
-			continue;
-		}
-		if (mode == RT_MODE_PATH && c->Qt.on && !stream_eligible(c, mode, total))
+		if (mode == RT_MODE_PATH && c->Qt.on && !c->pathUnsupported && !stream_eligible(c, mode, total))
 			return fail(c, RT_E_UNSUPPORTED, "rt_render: the Q-learning sampler needs a path batch with an entry per sample (within the slot budget, no RT_COUNT_REFERENCE)");
-		if (c->useMega && !c->counting && mode == RT_MODE_WHITTED) {
-			rc = run_mega(c, R);
-			if (rc != RT_OK) return rc;
-			hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((tilePixels + 255) / 256)), dim3(256), 0, c->stream, c->C, R, bf);
-			continue;
-		}
-		if (stream_eligible(c, mode, total)) {
-			rc = ensure_stream_state(c, (int)total);
-			if (rc != RT_OK) return rc;
-			R.finishInline = 1;
-			rc = run_rounds_stream(c, R, 4 + 1); // Sample starts at depth 4 (renderer.cpp:278): five hit levels
-			if (rc != RT_OK) return rc;
-			hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((tilePixels + 255) / 256)), dim3(256), 0, c->stream, c->C, R, bf);
-			continue;
-		}
-		int slots = 1;
-		bool slotPerSample = false;
-		rc = setup_slots(c, total, mode == RT_MODE_WHITTED, slots, slotPerSample);
-		if (rc != RT_OK) return rc;
-		const int seg = segments_per_sample(mode, mode == RT_MODE_PATH ? 4 : max_depth, c->S.nLights);
-		const int maxRounds = (int)((total + slots) / slots) * seg + seg + 4;
-		const bool direct = mode == RT_MODE_PATH && slotPerSample;
-		R.finishInline = direct ? 1 : 0;
-		rc = run_rounds(c, R, maxRounds, direct ? seg : 0);
+		rc = trace_samples(c, R, mode == RT_MODE_PATH ? 4 : max_depth); // Sample starts at depth 4 (renderer.cpp:278): five hit levels
 		if (rc != RT_OK) return rc;
 		hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((tilePixels + 255) / 256)), dim3(256), 0, c->stream, c->C, R, bf);
 	}
@@ -644,28 +596,8 @@ int rt_trace_batch_energy(rt_ctx* c, int mode, int n, const float* O, const floa
 	if (traceUnflagged || sampleFlagged) {
 		if (c->Qt.on) return fail(c, RT_E_UNSUPPORTED, "rt_trace_batch: the Q-learning sampler is defined for Sample as Tick calls it only");
 		R.sceneRt = c->sceneRaytracer;
-		if (traceUnflagged) hipLaunchKernelGGL(k_trace_general, dim3(c->gridBlocks), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, R, c->spill, c->flags + 1);
-		else hipLaunchKernelGGL(k_sample_general, dim3(c->gridBlocks), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, R, c->spill, c->flags + 1);
-		rc = check_overflow(c);
-	} else
-	if (mode == RT_MODE_PATH && c->pathUnsupported) {
-		hipLaunchKernelGGL(k_sample_general, dim3(c->gridBlocks), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, R, c->spill, c->flags + 1);
-		rc = check_overflow(c);
-	} else if (c->useMega && !c->counting && mode == RT_MODE_WHITTED) {
-		rc = run_mega(c, R);
-	} else if (stream_eligible(c, mode, (size_t)n)) {
-		rc = ensure_stream_state(c, n);
-		R.finishInline = 1;
-		if (rc == RT_OK) rc = run_rounds_stream(c, R, depth + 1);
-	} else {
-		int slots = 1;
-		bool slotPerSample = false;
-		rc = setup_slots(c, (size_t)n, mode == RT_MODE_WHITTED, slots, slotPerSample);
-		const int seg = segments_per_sample(mode, depth, c->S.nLights);
-		const bool direct = mode == RT_MODE_PATH && slotPerSample;
-		R.finishInline = direct ? 1 : 0;
-		if (rc == RT_OK) rc = run_rounds(c, R, ((n + slots) / slots) * seg + seg + 4, direct ? seg : 0);
-	}
+		rc = run_general(c, R, traceUnflagged);
+	} else rc = trace_samples(c, R, depth);
 	if (rc == RT_OK) {
 		std::vector<float> out4((size_t)4 * n);
 		hipError_t e = hipMemcpy(out4.data(), dOut, (size_t)16 * n, hipMemcpyDeviceToHost);

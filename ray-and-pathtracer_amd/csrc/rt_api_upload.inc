@@ -46,7 +46,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
 		if (m.type < 1 || m.type > 3) return fail(c, RT_E_ARG, "rt_upload_scene: material %u has type %d", i, m.type);
 	}
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	c->megaAuto = {}; // another scene: the Whitted forms are timed again
+	c->mega.pick = {}; // another scene: the Whitted forms are timed again
 	free_pool(c->sceneAllocs);
 	c->sceneLoaded = false;
 	c->pathUnsupported = false;

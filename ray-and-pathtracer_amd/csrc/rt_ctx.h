@@ -48,7 +48,8 @@ struct Knobs {
 	int fuse = -1;         // RT_FUSE: 0 one kernel at a time, 1 one traversal launch per round, 2 connect + light on a second stream; < 0: by batch size
 	int stream = 1;        // RT_STREAM=0: the slot wavefront of rt_kernels.h instead of the dense pipeline
 	int decide = 1;        // RT_DECIDE: producers answer rays whose first traversal step leaves nothing to visit
-	int mega = 1, megaLpt = 1, megaLevels = 2; // RT_MEGA / RT_MEGA_LPT / RT_MEGA_LEVELS: the forms of a Whitted frame (rt_mega.h)
+	int mega = 1, megaLpt = 1, megaLevels = 2; // RT_MEGA / RT_MEGA_LPT / RT_MEGA_LEVELS: the forms of a Whitted frame (rt_mega.h); levels: frames up to
+	                       // RT_LEVEL_SAMPLES_MAX samples run one launch per tree level (1), as one launch (0), or as whichever was faster (2)
 	int deferGamma = 1;    // RT_DEFER_GAMMA=0: the gamma where a sample is stored instead of in k_accumulate
 	int shadeLds = 1;      // RT_SHADE_LDS=0: material / light tables from memory
 	int tlasLds = 1;       // RT_TLAS_LDS=0: the TLAS from global memory even when it fits a block's LDS
@@ -66,6 +67,7 @@ static void read_knobs(Knobs& k)
 	k.megaLevels = (int)num("RT_MEGA_LEVELS", 2), k.deferGamma = num("RT_DEFER_GAMMA", 1) != 0, k.shadeLds = num("RT_SHADE_LDS", 1) != 0;
 	k.tlasLds = num("RT_TLAS_LDS", 1) != 0, k.gammaLut = num("RT_GAMMA_LUT", 1) != 0, k.levelCap = (int)num("RT_LEVEL_CAP", 0);
 	k.mixedMax = (unsigned)num("RT_MIXED_MAX", 10000000);
+	if (k.exactGamma) k.deferGamma = 1; // the exact form lives where samples are read (k_accumulate), not in the shading kernels
 	// the scheduling thresholds are compile-time constants since round 4 (rt_scene_dev.h): a sweep script that still sets them in
 	// the environment would read as a flat sweep -- say so once
 	static bool warned = false;
@@ -74,13 +76,27 @@ static void read_knobs(Knobs& k)
 		if (!warned && getenv(name)) { fprintf(stderr, "rt_amd: %s is a compile-time constant (rebuild with make EXTRA=-D%s=N); the environment variable is ignored\n", name, name); warned = true; }
 }
 
+template <typename T>
+static hipError_t dalloc(std::vector<void*>& pool, T** p, size_t count)
+{
+	void* q = nullptr;
+	hipError_t e = hipMalloc(&q, count * sizeof(T) > 0 ? count * sizeof(T) : 16);
+	if (e == hipSuccess) { pool.push_back(q); *p = (T*)q; }
+	return e;
+}
+static void free_pool(std::vector<void*>& pool)
+{
+	for (void* p : pool) (void)hipFree(p);
+	pool.clear();
+}
+
 struct rt_ctx {
 	int device = 0, width = 0, height = 0;
 	Knobs knobs;
 	hipStream_t stream = nullptr;
 	std::string err, tuningInfo;
 	// scene
-	DScene S;
+	DScene S{};
 	bool sceneLoaded = false;
 	std::vector<void*> sceneAllocs;
 	int sceneRaytracer = -1; // rt_set_scene_raytracer: scene.raytracer as the caller's Scene holds it (-1: it follows the function called)
@@ -95,7 +111,7 @@ struct rt_ctx {
 	int refitLevels = 0, animSlots = 0;
 	std::vector<int> refitLevelHost; // levelStart[] on the host: which levels are wide enough for a launch of their own
 	// camera
-	DCamera C;
+	DCamera C{};
 	bool cameraSet = false;
 	// accumulator
 	float4* accum = nullptr;
@@ -103,68 +119,87 @@ struct rt_ctx {
 	// the slot wavefront of rt_kernels.h (Whitted rounds with RT_MEGA=0, path batches above the slot budget, RT_COUNT_REFERENCE
 	// launches, RT_STREAM=0): slots, status bytes, queues; it runs on the context's stream
 	struct SlotState {
-		PathState P;
-		Queues Q;
+		PathState P{};
+		Queues Q{};
 		int stateSlots = 0, stateLights = -1;
 		bool statePend = false, stateWide = false;
 		std::vector<void*> allocs;
+		int gridExtend = 0, gridConnect = 0, gridConnectWide = 0, gridLeftover = 0; // resident blocks of the persistent traversal kernels (every wave owns a first chunk: none may wait for a slot)
+		void free_state() { free_pool(allocs); stateSlots = 0; }
 	};
 	SlotState slot;
-	int fuseTraversal = -1;  // RT_FUSE: how connect(r) + light(r) share the machine with round r + 1 in the dense pipeline (run_rounds_stream)
-
-	// the dense path-mode pipeline (rt_stream.h): its state, the second stream for connect + light, and whether it is on
-	StreamState T;
-	std::vector<void*> streamAllocs;
-	int streamCap = 0, streamLights = -1;
-	bool streamWide = false;
-	hipStream_t streamSide = nullptr;
-	uint* streamSideSpill = nullptr;
-	hipEvent_t streamFork = nullptr, streamJoin = nullptr;
+	// the dense path-mode pipeline (rt_stream.h): its state, and the second stream for connect + light with its spill and events
+	struct DenseState {
+		StreamState T{};
+		std::vector<void*> allocs;
+		int cap = 0, lights = -1;
+		bool wide = false;
+		hipStream_t side = nullptr;
+		uint* sideSpill = nullptr;
+		hipEvent_t fork = nullptr, join = nullptr;
+		int gridExtend = 0, gridConnect = 0, gridConnectWide = 0, gridLeftover = 0, gridConnectWide8 = 0, gridTraverse = 0;
+		int gridShade = 0, gridLight = 0; // resident blocks of the grid-stride shading kernels (a second, partial round of blocks would run at low occupancy)
+		void free_state() { free_pool(allocs); cap = 0; }
+		void destroy()
+		{
+			free_state();
+			if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
+			if (sideSpill) (void)hipFree(sideSpill);
+			if (fork) (void)hipEventDestroy(fork);
+			if (join) (void)hipEventDestroy(join);
+		}
+	};
+	DenseState dense;
+	// Renderer::Trace as one persistent launch per frame (rt_mega.h).  With RT_MEGA_LEVELS=2 the context times this form against the level
+	// form on the first batches of a shape and keeps the faster (the frames are identical either way; deep glass trees gain 40 % by levels,
+	// shallow scenes lose 10 % to the extra launches)
+	struct MegaForm {
+		MegaState M{};
+		std::vector<void*> allocs;
+		int lanes = 0, grid = 0;
+		struct Auto { unsigned nSamples = 0; int depth = 0; int tried[2] = { 0, 0 }; float ms[2] = { 0, 0 }; int choice = -1; } pick; // [0] single launch, [1] levels
+		hipEvent_t ev[2] = { nullptr, nullptr };
+		// longest first: per-sample cost of the last Whitted launch and the tile order made from it
+		std::vector<void*> orderAllocs;
+		uint* cost = nullptr; uint* order = nullptr; uint* hist = nullptr;
+		size_t costCap = 0;
+		unsigned costSamples = 0, costFirst = 0; // the batch cost[] describes (0 samples: nothing yet)
+		void free_lanes() { free_pool(allocs); lanes = 0; }
+		void free_order() { free_pool(orderAllocs); costCap = 0, costSamples = 0; }
+		void destroy()
+		{
+			free_lanes(), free_order();
+			for (int k = 0; k < 2; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
+		}
+	};
+	MegaForm mega;
+	// Whitted frames by tree levels (rt_mega.h LevelState): queues, term log
+	struct LevelForm {
+		LevelState V{};
+		std::vector<void*> allocs;
+		size_t cap = 0, samples = 0;
+		int levels = 0, grid = 0;
+		void free_state() { free_pool(allocs); cap = 0, levels = 0, samples = 0; }
+	};
+	LevelForm level;
+	// row gathers between contexts (rt_api_gather.inc)
 	hipEvent_t gatherDone = nullptr; // rt_gather_rows with this context as the source: its rows have arrived at the destination
 	hipEvent_t gatherReady = nullptr; // ... and, recorded on the destination's stream before the push: what the destination had queued is done
 	hipEvent_t rowsFree = nullptr;    // this context as a DESTINATION: recorded by rt_gather_begin on its stream, once per frame, before its own share is queued
-	int useStream = 1;       // RT_STREAM: 1 the dense pipeline for path batches with an entry per sample (default), 0 the slot pipeline of rt_kernels.h
-	// Renderer::Trace as one persistent launch per frame (rt_mega.h)
-	MegaState M;
-	std::vector<void*> megaAllocs;
-	int megaLanes = 0, gridMega = 0, gridLevel = 0;
-	// Whitted frames by tree levels (rt_mega.h LevelState): queues, term log
-	std::vector<void*> levelAllocs;
-	LevelState V;
-	size_t levelCap = 0; int levelLevels = 0; size_t levelSamples = 0;
-	int megaLevels = 2;      // RT_MEGA_LEVELS: Whitted frames up to RT_LEVEL_SAMPLES_MAX samples run one launch per tree level (1), as one launch (0), or
-	                         // as whichever of the two was faster when this context last tried both on a batch of this shape (2, default: the frames
-	                         // are identical either way; deep glass trees gain 40 %, shallow scenes lose 10 % to the extra launches)
-	struct { unsigned nSamples = 0; int depth = 0; int tried[2] = { 0, 0 }; float ms[2] = { 0, 0 }; int choice = -1; } megaAuto; // [0] single launch, [1] levels
-	hipEvent_t megaEv[2] = { nullptr, nullptr };
-	// longest first (rt_mega.h): per-sample cost of the last Whitted launch and the tile order made from it
-	std::vector<void*> megaOrderAllocs;
-	uint* megaCost = nullptr; uint* megaOrder = nullptr; uint* megaHist = nullptr;
-	size_t megaCostCap = 0;
-	unsigned megaCostSamples = 0, megaCostFirst = 0; // the batch megaCost describes (0 samples: nothing yet)
-	int exactGamma = 0;      // RT_EXACT_GAMMA: the gamma of a finished sample as the reference's double-precision pow (rt_kernels.h gamma_powf)
-	int deferGamma = 1;      // RT_DEFER_GAMMA: path-mode samples get their gamma in k_accumulate (rt_kernels.h store_sample)
-	int megaLpt = 1;         // RT_MEGA_LPT: 0 keeps the multiplicative permutation
-	int useMega = 1;         // RT_MEGA: 1 Whitted frames as one launch (default), 0 the wavefront rounds of rt_kernels.h
 	// Q-learning guided sampling (rt_qlearn.h)
-	QTable Qt;
+	QTable Qt{};
 	std::vector<void*> qAllocs;
-	int shadeLds = 1;        // RT_SHADE_LDS: the shading kernels keep the material / brute-force primitive tables in LDS
-	int gridShadeS = 0, gridLightS = 0; // resident blocks of the grid-stride shading kernels (a second, partial round of blocks would run at low occupancy)
-	int decideRays = 1;      // RT_DECIDE: producers answer rays whose first traversal step leaves nothing to visit (rt_stream.h ray_decided)
-	int gridTraverseS = 0;
-	int gridExtendS = 0, gridConnectS = 0, gridConnectWideS = 0, gridLeftoverS = 0, gridConnectWide8S = 0;
 	// traversal stack spill of the context's stream (rounds and batch queries) + flags
 	uint* spill = nullptr;
 	int gridBlocks = 0;
 	std::vector<int> matTypes; // material types of the uploaded scene (measurement builds)
-	int gridExtend = 0, gridConnect = 0, gridQuery = 0, gridConnectWide = 0, gridLeftover = 0; // resident blocks of the persistent traversal kernels (every wave owns a first chunk: none may wait for a slot)
+	int gridQuery = 0; // resident blocks of the query kernels
 	float* gammaLut = nullptr; // DScene::gammaLut
-	int* flags = nullptr; // [0] overflow for batch queries
+	int* flags = nullptr; // [1] the status word of the Whitted, general and query kernels, [2] the leftover count of the wide occlusion query, [16..] their work heads
 	DCounters* counters = nullptr;
 	int counting = 0; // 0 off, 1 the reference's walk (RT_COUNT_REFERENCE), 2 the walk the timed kernels make (RT_COUNT_EXECUTED)
 	bool profiling = false;
-	rt_profile prof;
+	rt_profile prof{};
 	std::vector<Timer> timers; // pending event pairs, resolved lazily
 	std::vector<int> timerKind;
 	int* hostCounts = nullptr; // pinned
@@ -195,18 +230,38 @@ static int fail(rt_ctx* c, int code, const char* fmt, ...)
 }
 #define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(c, RT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
 
-template <typename T>
-static hipError_t dalloc(std::vector<void*>& pool, T** p, size_t count)
+// ---- the status word ---------------------------------------------------------------------------
+// Every traversal launch leaves at most one word of trouble: counts[3] of the round pipelines' queues, flags[1] of the Whitted, general and
+// query kernels.  This is the one place that knows its values; 'family' names the kernels in the debug-check message.
+//   1 traversal stack   2 pending Whitted branches (the general kernels: their call-frame stack, reported as a stack like the query side
+//   always did)   3 a level queue is full (run_levels repeats the frame as one launch before it gets here)   199 unknown link   100+ debug check
+enum StatusFamily { FAM_WAVEFRONT = 0, FAM_WHITTED, FAM_QUERY };
+static int decode_status(rt_ctx* c, int f, StatusFamily family)
 {
-	void* q = nullptr;
-	hipError_t e = hipMalloc(&q, count * sizeof(T) > 0 ? count * sizeof(T) : 16);
-	if (e == hipSuccess) { pool.push_back(q); *p = (T*)q; }
-	return e;
+	static const char* const name[] = { "a wavefront kernel", "the Whitted kernel", "a query kernel" };
+	if (f == 0) return RT_OK;
+	if (f == 199) return fail(c, RT_E_STATE, "a traversal launch met a link no step understands (corrupt tree?) and dropped rays");
+	if (f >= 100) return fail(c, RT_E_STATE, "debug check %d failed in %s (RT_DEBUG_CHECKS build)", f - 100, name[family]);
+	if (f == 3) return fail(c, RT_E_OVERFLOW, "a Whitted level queue overflowed");
+	if (f == 2 && family != FAM_QUERY) return fail(c, RT_E_OVERFLOW, "more than %d pending Whitted branches in one pixel", RT_PEND_CAP);
+	return fail(c, RT_E_OVERFLOW, "traversal stack deeper than %d entries", RT_STACK_MAX);
 }
-static void free_pool(std::vector<void*>& pool)
+// flags[1] after what is queued on the context's stream, in stream order (the pinned hostCounts, then one synchronisation)
+static int read_flags(rt_ctx* c, int& f)
 {
-	for (void* p : pool) (void)hipFree(p);
-	pool.clear();
+	HIPCHK(c, hipMemcpyAsync(c->hostCounts, c->flags + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	f = c->hostCounts[0];
+	return RT_OK;
+}
+// the general and query kernels' launches: did one of them report trouble?
+static int check_overflow(rt_ctx* c)
+{
+	int f = 0;
+	const int rc = read_flags(c, f);
+	if (rc != RT_OK) return rc;
+	if (f != 0) (void)hipMemset(c->flags, 0, 2 * sizeof(int));
+	return decode_status(c, f, FAM_QUERY);
 }
 
 static int tuning(const rt_ctx* c) { return c->counting == RT_COUNT_EXECUTED ? RT_TUNE_CULL_COUNTED : 0; } // the traversal kernels' one launch-time flag (the thresholds are constants: rt_scene_dev.h)
@@ -245,6 +300,7 @@ static void prof_collect(rt_ctx* c)
 	c->timerKind.clear();
 }
 
+// ---- the measurement builds' probes: empty in a default build -----------------------------------
 #ifdef RT_TAIL_PROBE
 // measurement build only: print, per traversal launch of the plain round loop (RT_FUSE=0), how long it ran with work left in
 // its queue and how long its drain was
@@ -260,6 +316,9 @@ static void tail_probe_print(hipStream_t st, const char* what, int round)
 	(void)hipMemcpyFromSymbol(v, HIP_SYMBOL(g_tailProbe), sizeof(v), 0, hipMemcpyDeviceToHost);
 	fprintf(stderr, "tail probe %s round %d: busy %.1f us, drain %.1f us\n", what, round, (double)(v[1] - v[0]) / 100.0, (double)(v[2] - v[1]) / 100.0);
 }
+#else
+static inline void tail_probe_reset(hipStream_t) {}
+static inline void tail_probe_print(hipStream_t, const char*, int) {}
 #endif
 
 #ifdef RT_STEP_COUNT
@@ -303,6 +362,9 @@ static void step_count_print(rt_ctx* c, hipStream_t st, const PathState& P, int 
 	for (int t = 0; t < 8; t++)
 		if (byType[t]) fprintf(stderr, "   left a surface of type %d: %llu rays (%.1f %%), mean %.1f steps, %llu with > 150 steps (%.2f %% of them)\n", t, byType[t], 100.0 * (double)byType[t] / (double)v.size(), (double)stepsByType[t] / (double)byType[t], longByType[t], 100.0 * (double)longByType[t] / (double)byType[t]);
 }
+#else
+static inline void step_count_begin(rt_ctx*, hipStream_t, int) {}
+static inline void step_count_print(rt_ctx*, hipStream_t, const PathState&, int, int, const std::vector<int>&) {}
 #endif
 #ifdef RT_SECTION_PROBE
 // measurement build only: per traversal launch of the plain round loop, the waves' cycles by section (rt_scene_dev.h)
@@ -322,5 +384,8 @@ static void section_probe_print(hipStream_t st, const char* what, int round)
 	        100 * v[3] / tot, 100 * v[4] / tot, v[10], v[10] ? (double)v[3] / v[10] : 0, v[10] ? (double)v[4] / v[10] : 0, 100 * v[5] / tot, v[11], v[11] ? (double)v[5] / v[11] : 0,
 	        100 * v[6] / tot, v[12], v[12] ? (double)v[6] / v[12] : 0, 100 * (tot - v[0] - v[1] - v[2] - v[3] - v[4] - v[5] - v[6]) / tot, v[8], v[8] ? tot / v[8] : 0);
 }
+#else
+static inline void section_probe_reset(hipStream_t) {}
+static inline void section_probe_print(hipStream_t, const char*, int) {}
 #endif
 
