@@ -315,7 +315,13 @@ int rt_build_tlas(rt_ctx* ctx, const float* bounds6, uint32_t n, rt_tlas_node* n
  *   RT_COUNT_REFERENCE  the walk bvh::BIntersect / tlas::Intersect make: the DataCollector tallies
  *                       (bvh.cpp:610-631), identical to the oracle's
  *   RT_COUNT_EXECUTED   the walk the timed kernels make: they skip TLAS children whose geometry the ray
- *                       cannot reach, so fewer instance / node visits; same results */
+ *                       cannot reach, so fewer instance / node visits; same results.  The camera rays of a dense
+ *                       path batch are answered from the context's primary-hit table when the timed launch
+ *                       would do so (RT_PRIMARY_TABLE, default on): every sample is still one rays_nearest
+ *                       query with its light_tests / brute_tests, but its walk is not repeated.  The table's own
+ *                       walk (inner_visits, prim_tests, tlas_inner, instance_visits of one ray per pixel of
+ *                       [-1, width] x [-1, height]) is tallied when the counting launch is the one that builds
+ *                       it; a table that was already current contributes none of these walk tallies */
 #define RT_COUNT_OFF 0
 #define RT_COUNT_REFERENCE 1
 #define RT_COUNT_EXECUTED 2

@@ -375,10 +375,44 @@ static void launch_connect_s(rt_ctx* c, hipStream_t st, const StreamState& T, in
 		hipLaunchKernelGGL((k_connect_s<false, false, true>), dim3(c->dense.gridLeftover), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
 	}
 }
+// Does round 0 of this batch read the primary-hit table (rt_stream.h)?  A current table is read; a stale one is rebuilt -- on the batch's
+// stream, before generate, with no synchronisation: its status word is the round pipeline's -- once the camera samples asked for since it
+// went stale are worth the build: one trace of (width + 2) x (height + 2) rays, always of the whole frame, so that row shards and
+// whole frames share it.  Below that a batch keeps today's round 0 (a one-frame Tick whose camera moves every call never builds).
+// The table outlives batches, calls and Ticks: a static camera accumulating frames is what a path tracer does (a camera change
+// resets the accumulator anyway).
+static int primary_table_for(rt_ctx* c, const RenderParams& R, hipStream_t st, bool* use)
+{
+	rt_ctx::DenseState& d = c->dense;
+	*use = false;
+	if (!c->knobs.primaryTable || R.customO) return RT_OK;
+	if (d.tableGen == c->sceneGen) { *use = true; return RT_OK; }
+	const size_t records = (size_t)(c->width + 2) * (size_t)(c->height + 2);
+	if (d.tablePendingGen != c->sceneGen) d.tablePendingGen = c->sceneGen, d.tablePending = 0;
+	d.tablePending += R.nSamples;
+	if (d.tablePending < (unsigned long long)c->knobs.tableMin * records) return RT_OK;
+	if (!d.tab.A) {
+		PrimaryTable P{};
+		HIPCHK(c, dalloc(d.tabAllocs, &P.A, records));
+		HIPCHK(c, dalloc(d.tabAllocs, &P.B, records));
+		P.w = c->width + 2, P.h = c->height + 2;
+		d.tab = P;
+	}
+	HIPCHK(c, hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), st)); // work heads
+	const int grid = std::min((int)((records + RT_CHUNK - 1) / RT_CHUNK / 4 + 1), d.gridTable); // a short queue does not need the whole grid
+	prof_begin(c, K_QUERY, st); // (the profile's query slot: a build is one launch there)
+	if (c->counting) hipLaunchKernelGGL(k_primary_table<true>, dim3(grid), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
+	else hipLaunchKernelGGL(k_primary_table<false>, dim3(grid), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
+	prof_end(c, st);
+	d.tableGen = c->sceneGen;
+	*use = true;
+	return RT_OK;
+}
 // Path mode, an entry per sample: 'rounds' = start depth + 1 rounds, no queue length is read back.  connect(r) and light(r)
 // run on the second stream beside compact / extend / assign of round r + 1 (twoStreams; light(r) is the last writer of
 // the E and L that shade(r + 1) reads, so the main stream joins before shade); RT_FUSE=0 keeps one kernel at a time.
 //   generate | begin compact extend(0) assign shade(0) | begin compact extend(1) assign {|| connect(0) light(0)} shade(1) | ...
+// With the primary-hit table round 0 is   [table] generate_t | assign shade(0)   on all three schedules.
 static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 {
 	const float t_min = 0.001f; // renderer.cpp:131
@@ -402,20 +436,28 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 	hipStream_t st = c->stream, sb = twoStreams ? c->dense.side : c->stream;
 	const int cnt = c->counting ? 1 : 0;
 	const int n = (int)R.nSamples;
+	bool table = false;
+	{
+		const int rc = primary_table_for(c, R, st, &table);
+		if (rc != RT_OK) return rc;
+	}
 	prof_begin(c, K_GENERATE, st);
-	hipLaunchKernelGGL(k_generate_s, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, rounds == 1 ? 1 : 0, c->knobs.decide, cnt);
+	if (table) hipLaunchKernelGGL(k_generate_t, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, c->dense.tab, rounds == 1 ? 1 : 0, cnt);
+	else hipLaunchKernelGGL(k_generate_s, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, rounds == 1 ? 1 : 0, c->knobs.decide, cnt);
 	prof_end(c, st);
 	bool pendingJoin = false;
 	for (int round = 0; round < rounds; round++) {
 		const int last = round + 1 == rounds ? 1 : 0, lastNext = round + 2 == rounds ? 1 : 0;
-		hipLaunchKernelGGL(k_compact_s, dim3(grid / 2), dim3(RT_COMPACT_BLOCK), 0, st, T, round);
-		tail_probe_reset(st);
-		prof_begin(c, K_EXTEND, st);
-		if (mixed && round > 0) hipLaunchKernelGGL(k_traverse_s, dim3(c->dense.gridTraverse), dim3(RT_BLOCK), 0, st, c->S, T, round, last, t_min, tuning(c), c->spill);
-		else if (c->counting) hipLaunchKernelGGL((k_extend_s<true>), dim3(c->dense.gridExtend), dim3(RT_BLOCK), 0, st, c->S, T, round & 1, last, t_min, tuning(c), c->spill, c->counters);
-		else hipLaunchKernelGGL((k_extend_s<false>), dim3(c->dense.gridExtend), dim3(RT_BLOCK), 0, st, c->S, T, round & 1, last, t_min, tuning(c), c->spill, c->counters);
-		prof_end(c, st);
-		tail_probe_print(st, "extend_s", round);
+		if (!(table && round == 0)) { // (the table's entries come with their hits: no queue, no traversal launch)
+			hipLaunchKernelGGL(k_compact_s, dim3(grid / 2), dim3(RT_COMPACT_BLOCK), 0, st, T, round);
+			tail_probe_reset(st);
+			prof_begin(c, K_EXTEND, st);
+			if (mixed && round > 0) hipLaunchKernelGGL(k_traverse_s, dim3(c->dense.gridTraverse), dim3(RT_BLOCK), 0, st, c->S, T, round, last, t_min, tuning(c), c->spill);
+			else if (c->counting) hipLaunchKernelGGL((k_extend_s<true>), dim3(c->dense.gridExtend), dim3(RT_BLOCK), 0, st, c->S, T, round & 1, last, t_min, tuning(c), c->spill, c->counters);
+			else hipLaunchKernelGGL((k_extend_s<false>), dim3(c->dense.gridExtend), dim3(RT_BLOCK), 0, st, c->S, T, round & 1, last, t_min, tuning(c), c->spill, c->counters);
+			prof_end(c, st);
+			tail_probe_print(st, "extend_s", round);
+		}
 		if (mixed && round > 0) { // the shadow answers of the round before came with this round's hits
 			prof_begin(c, K_SHADE, st);
 			hipLaunchKernelGGL(k_light_s, dim3(c->dense.gridLight), dim3(RT_BLOCK), 0, st, c->S, R, T, round - 1, 0, c->knobs.shadeLds);
@@ -458,7 +500,7 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 	}
 	if (hc[3] != 0) (void)hipMemsetAsync(T.counts + 3, 0, sizeof(int), st);
 	const int rc = decode_status(c, hc[3], FAM_WAVEFRONT);
-	if (rc != RT_OK) return rc;
+	if (rc != RT_OK) { c->dense.tableGen = 0; return rc; } // (the trouble may have been the table build's)
 	HIPCHK(c, hipGetLastError());
 	return RT_OK;
 }

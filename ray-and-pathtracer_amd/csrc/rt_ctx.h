@@ -54,6 +54,11 @@ struct Knobs {
 	int shadeLds = 1;      // RT_SHADE_LDS=0: material / light tables from memory
 	int tlasLds = 1;       // RT_TLAS_LDS=0: the TLAS from global memory even when it fits a block's LDS
 	int gammaLut = 1;      // RT_GAMMA_LUT=0: no 256-entry table for finished sky samples
+	int primaryTable = 1;  // RT_PRIMARY_TABLE=0: every camera ray of a dense path batch is traced (round 0 as generate + compact + extend) instead of
+	                       // read from the table of the frame's distinct camera rays (rt_stream.h k_primary_table)
+	int tableMin = 12;     // RT_PRIMARY_TABLE_MIN: a stale table is rebuilt once this many camera samples per table record have been asked for since it
+	                       // went stale (1080p, bench scene: the build is 0.49 ms; batches that rebuild every time are level with traced ones at
+	                       // 3-8 frames, 0.13 ms ahead at 12, 0.3 at 16, 2 at 32: profiles/ab_primary_table.txt)
 	int levelCap = 0;      // RT_LEVEL_CAP: (tests) level queues that overflow
 	unsigned mixedMax = 10000000u; // RT_MIXED_MAX: batches below this many samples run one traversal launch per round
 };
@@ -67,6 +72,7 @@ static void read_knobs(Knobs& k)
 	k.megaLevels = (int)num("RT_MEGA_LEVELS", 2), k.deferGamma = num("RT_DEFER_GAMMA", 1) != 0, k.shadeLds = num("RT_SHADE_LDS", 1) != 0;
 	k.tlasLds = num("RT_TLAS_LDS", 1) != 0, k.gammaLut = num("RT_GAMMA_LUT", 1) != 0, k.levelCap = (int)num("RT_LEVEL_CAP", 0);
 	k.mixedMax = (unsigned)num("RT_MIXED_MAX", 10000000);
+	k.primaryTable = num("RT_PRIMARY_TABLE", 1) != 0, k.tableMin = (int)std::max(0l, num("RT_PRIMARY_TABLE_MIN", 12));
 	if (k.exactGamma) k.deferGamma = 1; // the exact form lives where samples are read (k_accumulate), not in the shading kernels
 	// the scheduling thresholds are compile-time constants since round 4 (rt_scene_dev.h): a sweep script that still sets them in
 	// the environment would read as a flat sweep -- say so once
@@ -139,10 +145,18 @@ struct rt_ctx {
 		hipEvent_t fork = nullptr, join = nullptr;
 		int gridExtend = 0, gridConnect = 0, gridConnectWide = 0, gridLeftover = 0, gridConnectWide8 = 0, gridTraverse = 0;
 		int gridShade = 0, gridLight = 0; // resident blocks of the grid-stride shading kernels (a second, partial round of blocks would run at low occupancy)
+		// The primary-hit table (rt_stream.h PrimaryTable): Scene::FindNearest of every distinct camera ray of the frame, which round 0 of
+		// a batch fans out to its samples.  Current while tableGen == sceneGen (the G-buffer's rule below); it outlives batches and calls.
+		PrimaryTable tab{};
+		std::vector<void*> tabAllocs;
+		unsigned long long tableGen = 0;
+		unsigned long long tablePending = 0, tablePendingGen = 0; // camera samples asked for while the table was stale at generation tablePendingGen
+		int gridTable = 0;
 		void free_state() { free_pool(allocs); cap = 0; }
 		void destroy()
 		{
 			free_state();
+			free_pool(tabAllocs);
 			if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
 			if (sideSpill) (void)hipFree(sideSpill);
 			if (fork) (void)hipEventDestroy(fork);

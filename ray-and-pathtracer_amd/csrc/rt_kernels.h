@@ -382,6 +382,20 @@ __device__ __forceinline__ void sample_primary(const DCamera& C, const RenderPar
 		primary_ray(C, (int)newX, (int)newY, O, D); // jitter truncated by the int parameters (renderer.cpp:276-278)
 	}
 }
+// The pixel whose ray a path-mode camera sample gets: sample_primary up to its primary_ray call, on the same operands (seed: after
+// the two draws).  RandomFloat is uint * 2^-32 rounded to float: 0 gives 0 and 2^32 - 1 rounds to 1.0f, so the jitter r * 2 - 1 lies in
+// the CLOSED interval [-1, 1], x + jitter in [x - 1, x + 1], and the truncated pixel in [-1, width] x [-1, height]: (width + 2) x
+// (height + 2) distinct camera rays serve every sample of every frame (rt_stream.h PrimaryTable).
+__device__ __forceinline__ void sample_primary_pixel(const DCamera& C, const RenderParams& R, uint sid, int& px, int& py, uint& seed)
+{
+	const uint lp = sid % R.tilePixels, frame = R.frame0 + sid / R.tilePixels;
+	const int x = (int)(lp % (uint)C.width), y = R.rowFirst + (int)(lp / (uint)C.width) * R.rowStride;
+	const int pixel = y * C.width + x;
+	seed = StreamSeed(R.seedBase + (uint)pixel + frame * (uint)(C.width * C.height));
+	float newX = x + (RandomFloat(seed) * 2 - 1);
+	float newY = y + (RandomFloat(seed) * 2 - 1);
+	px = (int)newX, py = (int)newY;
+}
 // energy and RNG state a sample starts its first segment with
 __device__ __forceinline__ float4 fresh_energy(const DCamera& C, const RenderParams& R, uint sid)
 {

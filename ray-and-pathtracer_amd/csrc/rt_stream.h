@@ -235,6 +235,118 @@ __global__ void __launch_bounds__(RT_BLOCK) k_generate_s(DScene S, DCamera C, Re
 	if (counting) flush_decided(T.counts, decided ? 1u : 0u);
 }
 
+// ---- the primary-hit table ---------------------------------------------------------------------------------------------
+// sample_primary truncates the jittered pixel to ints before it builds the ray (renderer.cpp:276-278), so every camera ray of a
+// batch is the ray of an INTEGER pixel of [-1, width] x [-1, height] (sample_primary_pixel), and Scene::FindNearest of it --
+// head tests, the walk, resolve_hit -- is a function of that pixel, the camera and the scene alone.  A 64-frame batch asks
+// the same ~2 M queries 64 times each.  The table holds their answers; round 0 of a batch reads them (k_generate_t) and has no
+// traversal queue, no compaction and no extend launch.  Everything from assign(0) on sees what generate + extend(0) would have left.
+//   A   a surface hit: hit normal xyz, w = t (the entry's hitN).  Nothing / a light: the finished sample's radiance xyz, the
+//       Lsum k_generate_s hands to store_sample, computed once by the same expressions
+//   B   x objIdx, y material (the entry's hitId), z PT_* bits | hit_class of the hit for a round that is not the last (bits 0-3)
+//       and for one that is (bits 4-7), w the sky texel's bytes r | g << 8 | b << 16 (PT_TEXEL: generate's gamma table takes them)
+struct PrimaryTable {
+	float4* A;
+	int4* B;
+	int w, h; // (width + 2) x (height + 2) records, record (px + 1) + (py + 1) * w
+};
+#define PT_FINISHED 0x100 // the ray hits nothing or a light: Sample() returns at renderer.cpp:134 / :135-137
+#define PT_TEXEL 0x200    // ... nothing, and the scene has a sky texture
+struct TablePolicy {
+	const DScene& S; const DCamera& C; const PrimaryTable& P; float t_min;
+	__device__ __forceinline__ int slot_of(int i) const { return i; }
+	__device__ __forceinline__ void ray(int i, f3& O, f3& D) const { primary_ray(C, i % P.w - 1, i / P.w - 1, O, D); } // the call sample_primary makes, on the same ints
+	__device__ __forceinline__ bool load(int i, f3& O, f3& D, float& tm, HitRef& head) const
+	{
+		ray(i, O, D);
+		tm = 1e34f; // Ray constructor default, as emit_ray_s
+		LaneCounters unused;
+		find_nearest_head<false>(S, O, D, t_min, tm, head, unused);
+		return true;
+	}
+	__device__ __forceinline__ void store(int i, const HitRef& hit, const f3&, const f3&) const
+	{
+		f3 O, D;
+		ray(i, O, D);
+		int objIdx, mat, matType;
+		f3 normal;
+		resolve_hit(S, hit, O, D, objIdx, mat, normal, &matType);
+		int flags = hit_class(S, objIdx, mat, 0, matType) | (hit_class(S, objIdx, mat, 1, matType) << 4);
+		float4 a = mk4(normal, hit.t);
+		int texelBits = 0;
+		const bool none = objIdx == -1;
+		if (none || (objIdx >= 11 && objIdx < 11 + S.nLights)) {
+			// k_generate_s's finish of such a sample (the first shade with Lsum = 0 and W = 1)
+			f3 Lsum(0.0f);
+			const f3 W(1.0f);
+			flags |= PT_FINISHED;
+			if (none) {
+				const unsigned char* texel = sky_texel(S, D);
+				if (texel) {
+					Lsum = Lsum + W * (f3((float)texel[0], (float)texel[1], (float)texel[2]) / 255);
+					flags |= PT_TEXEL, texelBits = (int)texel[0] | ((int)texel[1] << 8) | ((int)texel[2] << 16);
+				}
+			} else {
+				const f3 I = O + hit.t * D;
+				Lsum = Lsum + W * light_intensity(S.lights[objIdx - 11], I, normal, I);
+			}
+			a = mk4(Lsum, 0.0f);
+		}
+		P.A[i] = a;
+		P.B[i] = make_int4(objIdx, mat, flags, texelBits);
+	}
+};
+// One launch per (camera, scene): its walk tallies go to the counters of a counting launch that happens to build; the queries themselves
+// are tallied by the samples that read the table (k_generate_t), so lc.light / lc.brute stay 0 here and no ray is counted.
+template <bool COUNT>
+__global__ void __launch_bounds__(RT_BLOCK) k_primary_table(DScene S, DCamera C, PrimaryTable P, float t_min, int tuning, uint* spill, int* heads, int* flag, DCounters* counters)
+{
+	__shared__ __attribute__((aligned(16))) uint ldsStack[RT_LDS_WORDS];
+	LaneCounters lc;
+	lc.clear();
+	uint rays = 0;
+	TablePolicy pol{ S, C, P, t_min };
+	trace_persistent<false, COUNT, false>(S, pol, P.w * P.h, heads, t_min, tuning, ldsStack, spill, flag, lc, rays);
+	if (COUNT) flush_counters(counters, lc, 0, 0);
+}
+
+// generate from the table: camera sample e of the batch -> entry e of round 0 WITH its hit, or the finished sample.  The seed and
+// the two draws are sample_primary's; no head test, no ray_decided, no resolve_hit and no sky lookup per sample.  Neighbouring
+// lanes are neighbouring pixels of one frame: their records are neighbours too.  No entry carries CL_TRACE.  A sample whose ray
+// hits nothing or a light is finished here whatever RT_DECIDE says: the value is the one shade(0) would store.
+// Counting launches: every sample is a Scene::FindNearest query answered by its producer (flush_decided).
+__global__ void __launch_bounds__(RT_BLOCK) k_generate_t(DScene S, DCamera C, RenderParams R, StreamState T, PrimaryTable P, int last, int counting)
+{
+	const int e = blockIdx.x * blockDim.x + threadIdx.x;
+	const bool valid = e < (int)R.nSamples;
+	prepare_round(T, 0, (int)R.nSamples);
+	if (valid) {
+		const uint sid = R.sampleFirst + (uint)e;
+		int px, py;
+		uint seed;
+		sample_primary_pixel(C, R, sid, px, py, seed);
+		RT_CHECK(px >= -1 && px <= C.width && py >= -1 && py <= C.height, 25, &T.counts[SC_FLAG]);
+		const size_t i = (size_t)(px + 1) + (size_t)(py + 1) * (size_t)P.w;
+		const int4 b = P.B[i];
+		const float4 a = P.A[i];
+		unsigned char cls = 0;
+		if (b.z & PT_FINISHED) {
+			if ((b.z & PT_TEXEL) && S.gammaLut) R.samples[sid] = make_float4(S.gammaLut[b.w & 255], S.gammaLut[(b.w >> 8) & 255], S.gammaLut[(b.w >> 16) & 255], 0.0f);
+			else store_sample(R, sid, xyz(a));
+		} else {
+			f3 O, D;
+			primary_ray(C, px, py, O, D);
+			T.O[0][e] = mk4(O, a.w);  // w (ray.t) and D.w (the head candidate) are extend's: nobody reads them now
+			T.D[0][e] = mk4(D, 0.0f);
+			T.hitN[0][e] = a;
+			T.hitId[0][e] = make_int2(b.x, b.y);
+			cls = (unsigned char)(CL_LIVE | ((last ? b.z >> 4 : b.z) & 15));
+		}
+		T.cls[0][e] = cls;
+	}
+	if (counting) flush_decided(T.counts, valid ? 1u : 0u);
+}
+
 // extend: Scene::FindNearest for the entries of the traversal queue
 struct StreamExtendPolicy {
 	const DScene& S;
