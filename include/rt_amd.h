@@ -261,6 +261,50 @@ int rt_denoise(rt_ctx* ctx, int iteration, const rt_denoise_params* params);
 int rt_download_denoised(rt_ctx* ctx, int y0, int y1, float* out);
 int rt_resolve_denoised(rt_ctx* ctx, int y0, int y1, uint32_t* rgb8_out);
 
+/* ---- adaptive sampling: per-pixel statistics and active-pixel batches --------------------------------------
+ * Path mode (RT_MODE_PATH), one context.  Unused, nothing else changes.  (This library's own addition: the reference samples every pixel alike.)
+ * rt_stats_enable(on != 0): allocates and zeroes three per-pixel buffers (12 B per pixel); while they exist every path-mode accumulation
+ *   (rt_render, rt_render_rows, rt_render_active) also keeps, per pixel, count (uint32: samples added), sum_y and sum_yy (f32): with
+ *   y = (0.2126f * r + 0.7152f * g) + 0.0722f * b of the sample exactly as it is added to the accumulator (after the gamma), f32 in that order
+ *   without contraction, y and y * y are added one at a time in frame order like the accumulator, so the values do not depend on how
+ *   frames are split into batches or calls.  rt_clear zeroes them with the accumulator; on == 0 frees them.  Whitted frames do not touch
+ *   them.  The accumulator's bits do not depend on whether they are on.
+ * rt_download_stats: rows [y0, y1) of the three buffers; any pointer may be NULL.  RT_E_STATE when statistics are off.
+ * rt_select_active: builds the context's active-pixel list on the device from the statistics.  Per pixel, all arithmetic f32 with IEEE
+ *   division and square root, ternaries as written (tests/adaptive_ref.py restates it and is compared exactly):
+ *     n = (float)count
+ *     m = sum_y / n
+ *     v = (sum_yy - sum_y * m) / (n - 1)
+ *     v = v > 0 ? v : 0
+ *     e = sqrtf(v / n)
+ *     d = m > floor ? m : floor
+ *     active = count < min_samples
+ *           || (count < max_samples && isfinite(sum_y) && isfinite(sum_yy) && e / d > threshold)
+ *   e is the standard error of the pixel's mean luminance, e / d its size relative to the mean (floor keeps dark pixels from asking for
+ *   samples for ever).  A pixel that views a light directly sums to +inf: once it has min_samples samples it is never active.  The list
+ *   holds pixel indices y * width + x in strictly ascending order; *n_active_out is its length, and reading those 4 bytes back is the
+ *   only synchronisation of the call.  params NULL: RT_ADAPTIVE_DEFAULTS (a starting point, NOT tuned).  RT_E_STATE: statistics off.
+ *   RT_E_ARG: min_samples < 2, max_samples < min_samples, a NaN or negative threshold, floor <= 0 or NaN.
+ * rt_set_active_pixels: installs a caller's list instead: n indices, strictly ascending, every one < width * height, else RT_E_ARG
+ *   (checked before anything is uploaded); n = 0 is allowed.  A list is only indices: it survives rt_clear, rt_set_camera and
+ *   rt_upload_scene.
+ * rt_download_active: the first min(cap, n) entries of the list to out; *n_out = n, the list's true length.  RT_E_STATE: no list.
+ * rt_render_active: adds frames [frame0, frame0 + nframes) of Renderer::Sample to the accumulator for the listed pixels only.  On every
+ *   listed pixel the accumulator and the statistics end bit-equal to what rt_render(ctx, RT_MODE_PATH, frame0, nframes, seed_base, 0,
+ *   height, max_depth) would have left there from the same starting state; every other pixel is not written at all.  An empty list:
+ *   RT_OK without a launch.  No list installed: RT_E_STATE.  With the Q-learning sampler on: RT_E_UNSUPPORTED (the rewards of a subset
+ *   are a different table).  Works with statistics off: it is also the region-of-interest render.
+ * rt_resolve_adaptive: rt_resolve with the pixel's own count as the divisor; count == 0 gives black.  RT_E_STATE: statistics off. */
+typedef struct { int32_t min_samples, max_samples; float threshold, floor; } rt_adaptive_params;
+#define RT_ADAPTIVE_DEFAULTS { 16, 1024, 0.05f, 1e-3f }
+int rt_stats_enable(rt_ctx* ctx, int on);
+int rt_download_stats(rt_ctx* ctx, int y0, int y1, uint32_t* count, float* sum_y, float* sum_yy);
+int rt_select_active(rt_ctx* ctx, const rt_adaptive_params* params, int* n_active_out);
+int rt_set_active_pixels(rt_ctx* ctx, const uint32_t* pixels, int n);
+int rt_download_active(rt_ctx* ctx, uint32_t* out, int cap, int* n_out);
+int rt_render_active(rt_ctx* ctx, uint32_t frame0, int nframes, uint32_t seed_base, int max_depth);
+int rt_resolve_adaptive(rt_ctx* ctx, int y0, int y1, uint32_t* rgb8_out);
+
 /* ---- Q-learning guided sampling ("next" row N4) ------------------------------------------------------
  * The reference snapshot has no code for it: README.md:36-42 names Dahm & Keller 2017, "Learning Light Transport
  * the Reinforced Way", and lists "initialize sampling positions; pick sampling direction according to the QValue of neighboring

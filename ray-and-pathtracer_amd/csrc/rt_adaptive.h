@@ -1,0 +1,107 @@
+// Adaptive sampling: the per-pixel statistics' consumers.  k_accumulate<true> (rt_kernels.h) keeps count / sum_y / sum_yy per pixel;
+// here the list of pixels that still need samples is made from them (rt_select_active), in ascending pixel order, and the frame is
+// resolved with every pixel's own count (rt_resolve_adaptive).  The predicate is defined in include/rt_amd.h (rt_select_active) and
+// restated in numpy in tests/adaptive_ref.py; the two follow each other operation by operation (f32, IEEE division and square root,
+// no contraction: the library is built with -ffp-contract=off).
+// The compaction is three launches on the context's stream -- a block's count, one block's scan of the block counts, the scatter --
+// so that no block ever waits for another one (the house pattern of compact_body / k_assign: counts first, positions from a scan).
+//   k_select_count    a block of RT_SELECT_BLOCK lanes owns RT_SELECT_BLOCK consecutive pixels: ballot per wave, the block's total
+//   k_select_scan     ONE block: exclusive scan of the block totals in place, the grand total to *nActive
+//   k_select_scatter  the predicate again (12 B per pixel: cheaper than keeping a flag array), rank inside the wave by mbcnt,
+//                     list[block base + waves before + rank] = pixel
+#pragma once
+#include "rt_kernels.h" // PixelStats, rgbf32_to_rgb8
+
+namespace rtd {
+
+#define RT_SELECT_BLOCK 256
+#define RT_SELECT_SCAN_BLOCK 1024
+
+struct AdaptiveArgs {
+	int minSamples, maxSamples;
+	float threshold, floor;
+};
+
+// include/rt_amd.h rt_select_active, line by line
+__device__ __forceinline__ bool pixel_active(uint count, float sumY, float sumYY, const AdaptiveArgs& A)
+{
+	if (count < (uint)A.minSamples) return true;
+	if (count >= (uint)A.maxSamples || !isfinite(sumY) || !isfinite(sumYY)) return false;
+	const float n = (float)count;
+	const float m = sumY / n;
+	float v = (sumYY - sumY * m) / (n - 1);
+	v = v > 0 ? v : 0;
+	const float e = sqrtf(v / n);
+	const float d = m > A.floor ? m : A.floor;
+	return e / d > A.threshold;
+}
+
+// lanes of this wave below the caller that are set in 'mask'
+__device__ __forceinline__ uint lanes_below(unsigned long long mask)
+{
+	return __builtin_amdgcn_mbcnt_hi((uint)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint)mask, 0u));
+}
+
+__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_select_count(PixelStats St, AdaptiveArgs A, int nPixels, uint* blockTotal)
+{
+	__shared__ uint waveTotal[RT_SELECT_BLOCK / 64];
+	const int p = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
+	const bool on = p < nPixels && pixel_active(St.count[p], St.sumY[p], St.sumYY[p], A);
+	const unsigned long long mask = __ballot(on);
+	if ((threadIdx.x & 63) == 0) waveTotal[threadIdx.x >> 6] = (uint)__popcll(mask);
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		uint sum = 0;
+		for (int w = 0; w < RT_SELECT_BLOCK / 64; w++) sum += waveTotal[w];
+		blockTotal[blockIdx.x] = sum;
+	}
+}
+
+// one block: blockTotal[0 .. nBlocks) -> its exclusive prefix sums, *nActive = the total.  A lane owns a run of consecutive entries.
+__global__ void __launch_bounds__(RT_SELECT_SCAN_BLOCK) k_select_scan(uint* blockTotal, int nBlocks, int* nActive)
+{
+	__shared__ uint waveSum[RT_SELECT_SCAN_BLOCK / 64];
+	const int per = (nBlocks + RT_SELECT_SCAN_BLOCK - 1) / RT_SELECT_SCAN_BLOCK;
+	const int first = min((int)threadIdx.x * per, nBlocks), last = min(first + per, nBlocks);
+	uint mine = 0;
+	for (int i = first; i < last; i++) mine += blockTotal[i];
+	const uint lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	uint incl = mine; // inclusive prefix sum over the wave
+	for (int o = 1; o < 64; o <<= 1) { const uint t = __shfl_up(incl, o); if ((int)lane >= o) incl += t; }
+	if (lane == 63) waveSum[wave] = incl;
+	__syncthreads();
+	uint base = 0, total = 0;
+	for (int w = 0; w < RT_SELECT_SCAN_BLOCK / 64; w++) { if (w < (int)wave) base += waveSum[w]; total += waveSum[w]; }
+	uint at = base + incl - mine;
+	for (int i = first; i < last; i++) { const uint t = blockTotal[i]; blockTotal[i] = at; at += t; }
+	if (threadIdx.x == 0) *nActive = (int)total;
+}
+
+__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_select_scatter(PixelStats St, AdaptiveArgs A, int nPixels, const uint* blockBase, uint* list)
+{
+	__shared__ uint waveTotal[RT_SELECT_BLOCK / 64];
+	const int p = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
+	const bool on = p < nPixels && pixel_active(St.count[p], St.sumY[p], St.sumYY[p], A);
+	const unsigned long long mask = __ballot(on);
+	const uint wave = threadIdx.x >> 6;
+	if ((threadIdx.x & 63) == 0) waveTotal[wave] = (uint)__popcll(mask);
+	__syncthreads();
+	if (!on) return;
+	uint at = blockBase[blockIdx.x] + lanes_below(mask);
+	for (uint w = 0; w < wave; w++) at += waveTotal[w];
+	list[at] = (uint)p; // at < the grand total <= nPixels: the three launches evaluate one predicate on the same statistics
+}
+
+// rt_resolve with the pixel's own sample count as the divisor; a pixel without samples is black
+__global__ void k_resolve_adaptive(const float4* accum, const uint* count, int first, int n, uint* out)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const uint k = count[first + i];
+	if (k == 0) { out[i] = 0; return; }
+	const float4 a = accum[first + i];
+	const float it = (float)k;
+	out[i] = rgbf32_to_rgb8(a.x / it, a.y / it, a.z / it);
+}
+
+} // namespace rtd

@@ -1,6 +1,6 @@
 // librt_amd.so: implementation of the C ABI in include/rt_amd.h for gfx950.
 // This file: context, camera, accumulator access, counters and timers, build / tuning info; the other units of the library
-// (scene upload, device builders, the render loops, gather, batch queries, the Q-learning sampler) are the rt_api_*.inc files
+// (scene upload, device builders, the render loops, gather, batch queries, the Q-learning sampler, the denoiser, adaptive sampling) are the rt_api_*.inc files
 // included below -- one translation unit, see rt_ctx.h.
 #include "rt_ctx.h"
 
@@ -116,6 +116,8 @@ void rt_destroy(rt_ctx* c)
 	if (c->samples) (void)hipFree(c->samples);
 	if (c->resolveBuf) (void)hipFree(c->resolveBuf);
 	free_pool(c->denoiseAllocs);
+	free_pool(c->adaptiveAllocs);
+	free_pool(c->activeAllocs);
 	if (c->gammaLut) (void)hipFree(c->gammaLut);
 	if (c->flags) (void)hipFree(c->flags);
 	if (c->counters) (void)hipFree(c->counters);
@@ -154,7 +156,7 @@ int rt_clear(rt_ctx* c)
 	if (!c) return RT_E_ARG;
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipMemsetAsync(c->accum, 0, (size_t)c->width * c->height * sizeof(float4), c->stream));
-	return RT_OK;
+	return stats_clear(c);
 }
 
 int rt_download_accumulator(rt_ctx* c, int y0, int y1, float* out)
@@ -193,6 +195,7 @@ int rt_bind_accumulator(rt_ctx* c, void* p)
 #include "rt_api_gather.inc"
 #include "rt_api_query.inc"
 #include "rt_api_denoise.inc"
+#include "rt_api_adaptive.inc"
 
 // ---- measurement ------------------------------------------------------------------------------
 int rt_set_counting(rt_ctx* c, int counting)

@@ -1,0 +1,138 @@
+// Adaptive sampling: rt_stats_enable, rt_download_stats, rt_select_active, rt_set_active_pixels, rt_download_active, rt_render_active,
+// rt_resolve_adaptive.  Included by rt_api.hip.  The statistics are kept by k_accumulate<true> (rt_kernels.h; launched by render_batches
+// of rt_api_render.inc while they are on), the selection and the per-count resolve are the kernels of rt_adaptive.h.
+int rt_stats_enable(rt_ctx* c, int on)
+{
+	if (!c) return RT_E_ARG;
+	HIPCHK(c, hipSetDevice(c->device));
+	if (!on) {
+		if (!c->stats.count) return RT_OK;
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		free_pool(c->adaptiveAllocs);
+		c->stats = PixelStats{};
+		return RT_OK;
+	}
+	if (!c->stats.count) {
+		const size_t n = (size_t)c->width * c->height;
+		PixelStats St{};
+		hipError_t e = dalloc(c->adaptiveAllocs, &St.count, n);
+		if (e == hipSuccess) e = dalloc(c->adaptiveAllocs, &St.sumY, n);
+		if (e == hipSuccess) e = dalloc(c->adaptiveAllocs, &St.sumYY, n);
+		if (e != hipSuccess) { free_pool(c->adaptiveAllocs); return fail(c, RT_E_HIP, "rt_stats_enable: %s", hipGetErrorString(e)); }
+		c->stats = St;
+	}
+	return stats_clear(c);
+}
+
+int rt_download_stats(rt_ctx* c, int y0, int y1, uint32_t* count, float* sum_y, float* sum_yy)
+{
+	if (!c || y0 < 0 || y1 > c->height || y0 >= y1) return fail(c, RT_E_ARG, "rt_download_stats: bad argument");
+	if (!c->stats.count) return fail(c, RT_E_STATE, "rt_download_stats: statistics are off (rt_stats_enable)");
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	const size_t first = (size_t)y0 * c->width, n = (size_t)(y1 - y0) * c->width;
+	if (count) HIPCHK(c, hipMemcpy(count, c->stats.count + first, n * sizeof(uint), hipMemcpyDeviceToHost));
+	if (sum_y) HIPCHK(c, hipMemcpy(sum_y, c->stats.sumY + first, n * sizeof(float), hipMemcpyDeviceToHost));
+	if (sum_yy) HIPCHK(c, hipMemcpy(sum_yy, c->stats.sumYY + first, n * sizeof(float), hipMemcpyDeviceToHost));
+	return RT_OK;
+}
+
+// the list's device storage: width * height indices, a total per block of the selection, the selected count
+static int ensure_active_list(rt_ctx* c)
+{
+	if (c->activeList) return RT_OK;
+	const size_t n = (size_t)c->width * c->height;
+	uint *list = nullptr, *totals = nullptr;
+	int* count = nullptr;
+	hipError_t e = dalloc(c->activeAllocs, &list, n);
+	if (e == hipSuccess) e = dalloc(c->activeAllocs, &totals, (n + RT_SELECT_BLOCK - 1) / RT_SELECT_BLOCK);
+	if (e == hipSuccess) e = dalloc(c->activeAllocs, &count, (size_t)1);
+	if (e != hipSuccess) { free_pool(c->activeAllocs); return fail(c, RT_E_HIP, "active-pixel list: %s", hipGetErrorString(e)); }
+	c->activeList = list, c->selectTotals = totals, c->activeCount = count;
+	return RT_OK;
+}
+
+int rt_select_active(rt_ctx* c, const rt_adaptive_params* params, int* n_active_out)
+{
+	const rt_adaptive_params P = params ? *params : rt_adaptive_params RT_ADAPTIVE_DEFAULTS;
+	if (P.min_samples < 2 || P.max_samples < P.min_samples) return fail(c, RT_E_ARG, "rt_select_active: min_samples %d (>= 2), max_samples %d (>= min_samples)", P.min_samples, P.max_samples);
+	if (!(P.threshold >= 0.0f) || !(P.floor > 0.0f)) return fail(c, RT_E_ARG, "rt_select_active: threshold must be >= 0 and floor > 0 (neither NaN)");
+	if (!c || !n_active_out) return fail(c, RT_E_ARG, "rt_select_active: null argument");
+	if (!c->stats.count) return fail(c, RT_E_STATE, "rt_select_active: statistics are off (rt_stats_enable)");
+	HIPCHK(c, hipSetDevice(c->device));
+	int rc = ensure_active_list(c);
+	if (rc != RT_OK) return rc;
+	AdaptiveArgs A;
+	A.minSamples = P.min_samples, A.maxSamples = P.max_samples, A.threshold = P.threshold, A.floor = P.floor;
+	const int n = c->width * c->height, blocks = (n + RT_SELECT_BLOCK - 1) / RT_SELECT_BLOCK;
+	c->nActive = -1; // no list until the count has come home
+	hipLaunchKernelGGL(k_select_count, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, n, c->selectTotals);
+	hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(RT_SELECT_SCAN_BLOCK), 0, c->stream, c->selectTotals, blocks, c->activeCount);
+	hipLaunchKernelGGL(k_select_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, n, c->selectTotals, c->activeList);
+	HIPCHK(c, hipGetLastError());
+	// the only synchronisation of the call: the selected count (pinned; the round pipelines use words 0..4)
+	HIPCHK(c, hipMemcpyAsync(c->hostCounts + 8, c->activeCount, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	const int got = c->hostCounts[8];
+	if (got < 0 || got > n) return fail(c, RT_E_STATE, "rt_select_active: %d pixels selected of %d", got, n);
+	c->nActive = got;
+	*n_active_out = got;
+	return RT_OK;
+}
+
+int rt_set_active_pixels(rt_ctx* c, const uint32_t* pixels, int n)
+{
+	if (!c || n < 0 || (n > 0 && !pixels)) return fail(c, RT_E_ARG, "rt_set_active_pixels: bad argument");
+	// refused before anything is uploaded: the list a batch walks must name every pixel once (two samples of one pixel in one
+	// k_accumulate launch would race) and inside the frame
+	const uint32_t limit = (uint32_t)c->width * (uint32_t)c->height;
+	for (int i = 0; i < n; i++) {
+		if (pixels[i] >= limit) return fail(c, RT_E_ARG, "rt_set_active_pixels: entry %d is pixel %u of %u", i, pixels[i], limit);
+		if (i > 0 && pixels[i] <= pixels[i - 1]) return fail(c, RT_E_ARG, "rt_set_active_pixels: entry %d (%u) does not ascend from entry %d (%u)", i, pixels[i], i - 1, pixels[i - 1]);
+	}
+	HIPCHK(c, hipSetDevice(c->device));
+	const int rc = ensure_active_list(c);
+	if (rc != RT_OK) return rc;
+	HIPCHK(c, hipStreamSynchronize(c->stream)); // (a batch over the list it replaces may still be accumulating)
+	if (n > 0) HIPCHK(c, hipMemcpy(c->activeList, pixels, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+	c->nActive = n;
+	return RT_OK;
+}
+
+int rt_download_active(rt_ctx* c, uint32_t* out, int cap, int* n_out)
+{
+	if (!c || cap < 0 || (cap > 0 && !out) || !n_out) return fail(c, RT_E_ARG, "rt_download_active: bad argument");
+	if (c->nActive < 0) return fail(c, RT_E_STATE, "rt_download_active: no active-pixel list (rt_select_active, rt_set_active_pixels)");
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	const int n = std::min(cap, c->nActive);
+	if (n > 0) HIPCHK(c, hipMemcpy(out, c->activeList, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	*n_out = c->nActive; // the list's true length, whatever fitted
+	return RT_OK;
+}
+
+int rt_render_active(rt_ctx* c, uint32_t frame0, int nframes, uint32_t seed_base, int max_depth)
+{
+	if (!c) return RT_E_ARG;
+	if (!c->sceneLoaded) return fail(c, RT_E_STATE, "rt_render_active: no scene uploaded");
+	if (nframes < 1) return fail(c, RT_E_ARG, "rt_render_active: nframes %d", nframes);
+	if (c->nActive < 0) return fail(c, RT_E_STATE, "rt_render_active: no active-pixel list (rt_select_active, rt_set_active_pixels)");
+	// the rewards of a pixel subset are a different table from the whole frame's: not defined here
+	if (c->Qt.on) return fail(c, RT_E_UNSUPPORTED, "rt_render_active: not with the Q-learning sampler on");
+	if (c->nActive == 0) return RT_OK;
+	HIPCHK(c, hipSetDevice(c->device));
+	return render_batches(c, RT_MODE_PATH, frame0, nframes, seed_base, 0, 1, (size_t)c->nActive, c->activeList, max_depth);
+}
+
+int rt_resolve_adaptive(rt_ctx* c, int y0, int y1, uint32_t* rgb8_out)
+{
+	if (!c || !rgb8_out || y0 < 0 || y1 > c->height || y0 >= y1) return fail(c, RT_E_ARG, "rt_resolve_adaptive: bad argument");
+	if (!c->stats.count) return fail(c, RT_E_STATE, "rt_resolve_adaptive: statistics are off (rt_stats_enable)");
+	HIPCHK(c, hipSetDevice(c->device));
+	const int n = (y1 - y0) * c->width;
+	if (!c->resolveBuf) HIPCHK(c, hipMalloc((void**)&c->resolveBuf, (size_t)c->width * c->height * 4));
+	hipLaunchKernelGGL(k_resolve_adaptive, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->accum, c->stats.count, y0 * c->width, n, c->resolveBuf);
+	HIPCHK(c, hipMemcpyAsync(rgb8_out, c->resolveBuf, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	return RT_OK;
+}

@@ -546,23 +546,22 @@ static int trace_samples(rt_ctx* c, RenderParams& R, int depth)
 	return run_rounds(c, R, maxRounds, direct ? seg : 0);
 }
 
-int rt_render_rows(rt_ctx* c, int mode, uint32_t frame0, int nframes, uint32_t seed_base, int row_first, int row_stride, int row_count, int max_depth)
+// the statistics' share of rt_clear (rt_api_adaptive.inc holds the rest of them)
+static int stats_clear(rt_ctx* c)
 {
-	if (!c) return RT_E_ARG;
-	if (!c->sceneLoaded) return fail(c, RT_E_STATE, "rt_render: no scene uploaded");
-	if (mode != RT_MODE_WHITTED && mode != RT_MODE_PATH) return fail(c, RT_E_ARG, "rt_render: mode %d", mode);
-	if (row_first < 0 || row_stride < 1 || row_count < 1 || row_first + (row_count - 1) * row_stride >= c->height)
-		return fail(c, RT_E_ARG, "rt_render: rows %d + k*%d (k < %d) outside 0..%d", row_first, row_stride, row_count, c->height);
-	if (nframes < 1 || (mode == RT_MODE_WHITTED && nframes != 1)) return fail(c, RT_E_ARG, "rt_render: nframes %d (Whitted frames overwrite the accumulator: 1 only)", nframes);
-	HIPCHK(c, hipSetDevice(c->device));
-	const int nSlots = c->width * row_count;
-	if (mode == RT_MODE_WHITTED && max_depth <= 0) { // Trace(depth <= 0) returns black without tracing
-		for (int k = 0; k < row_count; k++)
-			HIPCHK(c, hipMemsetAsync(c->accum + (size_t)(row_first + k * row_stride) * c->width, 0, (size_t)c->width * sizeof(float4), c->stream));
-		return RT_OK;
-	}
-	// batches of frames: the finished samples of a batch live in a [frame][pixel] buffer (<= 4 GiB)
-	const size_t tilePixels = (size_t)nSlots;
+	if (!c->stats.count) return RT_OK;
+	const size_t n = (size_t)c->width * c->height;
+	HIPCHK(c, hipMemsetAsync(c->stats.count, 0, n * sizeof(uint), c->stream));
+	HIPCHK(c, hipMemsetAsync(c->stats.sumY, 0, n * sizeof(float), c->stream));
+	HIPCHK(c, hipMemsetAsync(c->stats.sumYY, 0, n * sizeof(float), c->stream));
+	return RT_OK;
+}
+
+// Frames [frame0, frame0 + nframes) of one tile of pixels -- tilePixels of them: the rows row_first + k * row_stride of rt_render_rows, or
+// the entries of pixelList (rt_render_active) -- in batches of frames: the finished samples of a batch live in a [frame][tile pixel]
+// buffer (<= 4 GiB), which k_accumulate adds to the accumulator (and, with rt_stats_enable, to the pixels' statistics) in frame order.
+static int render_batches(rt_ctx* c, int mode, uint32_t frame0, int nframes, uint32_t seed_base, int row_first, int row_stride, size_t tilePixels, const uint* pixelList, int max_depth)
+{
 	const size_t sampleGiB = (size_t)c->knobs.sampleGiB;
 	int batchFrames = (int)((sampleGiB << 30) / (tilePixels * sizeof(float4)));
 	if (batchFrames < 1) batchFrames = 1;
@@ -580,16 +579,36 @@ int rt_render_rows(rt_ctx* c, int mode, uint32_t frame0, int nframes, uint32_t s
 		memset(&R, 0, sizeof(R));
 		R.mode = mode, R.frame0 = frame0 + (uint)f, R.nSamples = (uint)total, R.tilePixels = (uint)tilePixels, R.samples = c->samples;
 		R.seedBase = seed_base, R.rowFirst = row_first, R.rowStride = row_stride, R.maxDepth = max_depth, R.accum = c->accum;
+		R.pixelList = pixelList;
 		R.deferGamma = mode == RT_MODE_PATH ? c->knobs.deferGamma : 0;
 		R.sceneRt = -1; // (rt_render is Tick's loop: the flag is what the mode says)
 		if (mode == RT_MODE_PATH && c->Qt.on && !c->pathUnsupported && !stream_eligible(c, mode, total))
 			return fail(c, RT_E_UNSUPPORTED, "rt_render: the Q-learning sampler needs a path batch with an entry per sample (within the slot budget, no RT_COUNT_REFERENCE)");
 		rc = trace_samples(c, R, mode == RT_MODE_PATH ? 4 : max_depth); // Sample starts at depth 4 (renderer.cpp:278): five hit levels
 		if (rc != RT_OK) return rc;
-		hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((tilePixels + 255) / 256)), dim3(256), 0, c->stream, c->C, R, bf);
+		const dim3 grid((unsigned)((tilePixels + 255) / 256));
+		if (mode == RT_MODE_PATH && c->stats.count) hipLaunchKernelGGL(k_accumulate<true>, grid, dim3(256), 0, c->stream, c->C, R, bf, c->stats);
+		else hipLaunchKernelGGL(k_accumulate<false>, grid, dim3(256), 0, c->stream, c->C, R, bf, c->stats);
 	}
 	HIPCHK(c, hipGetLastError());
 	return RT_OK;
+}
+
+int rt_render_rows(rt_ctx* c, int mode, uint32_t frame0, int nframes, uint32_t seed_base, int row_first, int row_stride, int row_count, int max_depth)
+{
+	if (!c) return RT_E_ARG;
+	if (!c->sceneLoaded) return fail(c, RT_E_STATE, "rt_render: no scene uploaded");
+	if (mode != RT_MODE_WHITTED && mode != RT_MODE_PATH) return fail(c, RT_E_ARG, "rt_render: mode %d", mode);
+	if (row_first < 0 || row_stride < 1 || row_count < 1 || row_first + (row_count - 1) * row_stride >= c->height)
+		return fail(c, RT_E_ARG, "rt_render: rows %d + k*%d (k < %d) outside 0..%d", row_first, row_stride, row_count, c->height);
+	if (nframes < 1 || (mode == RT_MODE_WHITTED && nframes != 1)) return fail(c, RT_E_ARG, "rt_render: nframes %d (Whitted frames overwrite the accumulator: 1 only)", nframes);
+	HIPCHK(c, hipSetDevice(c->device));
+	if (mode == RT_MODE_WHITTED && max_depth <= 0) { // Trace(depth <= 0) returns black without tracing
+		for (int k = 0; k < row_count; k++)
+			HIPCHK(c, hipMemsetAsync(c->accum + (size_t)(row_first + k * row_stride) * c->width, 0, (size_t)c->width * sizeof(float4), c->stream));
+		return RT_OK;
+	}
+	return render_batches(c, mode, frame0, nframes, seed_base, row_first, row_stride, (size_t)c->width * row_count, nullptr, max_depth);
 }
 
 int rt_render(rt_ctx* c, int mode, uint32_t frame0, int nframes, uint32_t seed_base, int y0, int y1, int max_depth)

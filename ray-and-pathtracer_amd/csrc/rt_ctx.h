@@ -9,12 +9,14 @@
 //   rt_api_query.inc    batch queries
 //   rt_api_qlearn.inc   rt_qlearn_*
 //   rt_api_denoise.inc  rt_render_aovs, rt_denoise and their downloads
+//   rt_api_adaptive.inc rt_stats_*, rt_select_active, the active-pixel list, rt_render_active, rt_resolve_adaptive
 #pragma once
 #include "rt_kernels.h"
 #include "rt_stream.h"
 #include "rt_mega.h"
 #include "rt_build.h"
 #include "rt_denoise.h"
+#include "rt_adaptive.h"
 #include "../../include/rt_amd.h"
 #include <algorithm>
 #include <cstdarg>
@@ -230,6 +232,14 @@ struct rt_ctx {
 	float4* denoised = nullptr; // the buffer holding the last rt_denoise result (null: none yet)
 	float4* samples = nullptr; // finished samples of the current batch, [frame][tile pixel]
 	size_t sampleCap = 0;
+	// adaptive sampling (rt_api_adaptive.inc): per-pixel statistics kept by k_accumulate<true> while stats.count != nullptr, and the list of
+	// pixels rt_render_active renders (pixel indices, strictly ascending; nActive < 0: none installed).  The list is only indices: it
+	// survives rt_clear, rt_set_camera and rt_upload_scene.
+	PixelStats stats{};
+	std::vector<void*> adaptiveAllocs; // the statistics
+	std::vector<void*> activeAllocs;   // the list, the block totals of its compaction, its length on the device
+	uint* activeList = nullptr; uint* selectTotals = nullptr; int* activeCount = nullptr;
+	int nActive = -1;
 };
 
 static int fail(rt_ctx* c, int code, const char* fmt, ...)

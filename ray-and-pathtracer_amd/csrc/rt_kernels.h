@@ -74,6 +74,7 @@ struct RenderParams {
 	int sceneRt;       // rt_trace_batch with rt_set_scene_raytracer: scene.raytracer as the caller's Scene holds it, when it is NOT what the
 	                   // function called implies (Trace with the flag clear, Sample with it set: renderer.cpp:33-43, 107-121, 143-153) -- the
 	                   // general kernels below; -1: the flag follows the function, as Tick calls it
+	const uint* pixelList; // rt_render_active: tile pixel lp is pixel pixelList[lp] (tilePixels = the list's length); nullptr: the row mapping
 };
 
 #define ST_ACTIVE 1      // has a ray for extend + shade
@@ -368,11 +369,23 @@ __device__ __forceinline__ float mode_t_min(int mode) { return mode == 0 ? (floa
 // Put sample 'sid' of the pool into a slot: seed, jitter, primary ray (renderer.cpp:263-278)
 // depth a fresh sample starts with (renderer.cpp:269 / :278; rt_trace_batch: the caller's)
 __device__ __forceinline__ int start_depth(const RenderParams& R) { return R.customO ? R.customDepth : (R.mode == 0 ? R.maxDepth : 4); }
+// The ONE place that knows which pixel tile-local index lp of a batch is: pixel x = lp % width of row rowFirst + (lp / width) * rowStride,
+// or entry lp of the batch's pixel list (rt_render_active).  Everything a sample is made of follows from (pixel, frame) alone.
+__device__ __forceinline__ void tile_pixel(const DCamera& C, const RenderParams& R, uint lp, int& x, int& y)
+{
+	if (R.pixelList) {
+		const uint p = R.pixelList[lp];
+		x = (int)(p % (uint)C.width), y = (int)(p / (uint)C.width);
+		return;
+	}
+	x = (int)(lp % (uint)C.width), y = R.rowFirst + (int)(lp / (uint)C.width) * R.rowStride;
+}
 // camera sample 'sid' of the pool (renderer.cpp:263-278): its seed, jitter and primary ray; deterministic in (R, C, sid)
 __device__ __forceinline__ void sample_primary(const DCamera& C, const RenderParams& R, uint sid, f3& O, f3& D, uint& seed)
 {
 	const uint lp = sid % R.tilePixels, frame = R.frame0 + sid / R.tilePixels;
-	const int x = (int)(lp % (uint)C.width), y = R.rowFirst + (int)(lp / (uint)C.width) * R.rowStride;
+	int x, y;
+	tile_pixel(C, R, lp, x, y);
 	const int pixel = y * C.width + x;
 	seed = StreamSeed(R.seedBase + (uint)pixel + frame * (uint)(C.width * C.height));
 	if (R.mode == 0) primary_ray(C, x, y, O, D);
@@ -389,7 +402,8 @@ __device__ __forceinline__ void sample_primary(const DCamera& C, const RenderPar
 __device__ __forceinline__ void sample_primary_pixel(const DCamera& C, const RenderParams& R, uint sid, int& px, int& py, uint& seed)
 {
 	const uint lp = sid % R.tilePixels, frame = R.frame0 + sid / R.tilePixels;
-	const int x = (int)(lp % (uint)C.width), y = R.rowFirst + (int)(lp / (uint)C.width) * R.rowStride;
+	int x, y;
+	tile_pixel(C, R, lp, x, y);
 	const int pixel = y * C.width + x;
 	seed = StreamSeed(R.seedBase + (uint)pixel + frame * (uint)(C.width * C.height));
 	float newX = x + (RandomFloat(seed) * 2 - 1);
@@ -883,7 +897,8 @@ __global__ void __launch_bounds__(RT_BLOCK) k_sample_general(DScene S, DCamera C
 			seed = StreamSeed(R.seedBase + sid), depth = R.customDepth;
 		} else {
 			const uint lp = sid % R.tilePixels, frame = R.frame0 + sid / R.tilePixels;
-			const int x = (int)(lp % (uint)C.width), y = R.rowFirst + (int)(lp / (uint)C.width) * R.rowStride;
+			int x, y;
+			tile_pixel(C, R, lp, x, y);
 			seed = StreamSeed(R.seedBase + (uint)(y * C.width + x) + frame * (uint)(C.width * C.height));
 			float newX = x + (RandomFloat(seed) * 2 - 1);
 			float newY = y + (RandomFloat(seed) * 2 - 1);
@@ -1103,20 +1118,38 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_general(DScene S, DCamera C,
 
 // accumulate: add the finished samples of a batch to the accumulator in frame order
 // (renderer.cpp:270: overwrite in Whitted mode; :282: += in path mode)
-__global__ void k_accumulate(DCamera C, RenderParams R, int batchFrames)
+// STATS (rt_stats_enable, path mode): the pixel's sample count and the sums of the samples' luminance and of its square as well, the
+// luminance taken from the sample exactly as it is added (after the gamma), one sample at a time in frame order like the accumulator --
+// neither depends on how frames are split into batches or calls.  The accumulator's arithmetic is the same in both instantiations.
+struct PixelStats {
+	uint* count;   // samples accumulated into the pixel since the last clear
+	float* sumY;   // sum of the samples' luminance
+	float* sumYY;  // sum of its square
+};
+__device__ __forceinline__ float sample_luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+template <bool STATS>
+__global__ void k_accumulate(DCamera C, RenderParams R, int batchFrames, PixelStats St)
 {
 	const uint lp = blockIdx.x * blockDim.x + threadIdx.x;
 	if (lp >= R.tilePixels) return;
-	const int x = (int)(lp % (uint)C.width), y = R.rowFirst + (int)(lp / (uint)C.width) * R.rowStride;
+	int x, y;
+	tile_pixel(C, R, lp, x, y);
 	const int pixel = y * C.width + x;
 	if (R.mode == 0) { R.accum[pixel] = R.samples[lp]; return; }
 	float4 a = R.accum[pixel];
+	float sy = 0, syy = 0;
+	if (STATS) sy = St.sumY[pixel], syy = St.sumYY[pixel];
 	for (int f = 0; f < batchFrames; f++) {
 		float4 s = R.samples[(size_t)f * R.tilePixels + lp];
 		if (s.w != 0) s = g_exactGamma ? make_float4(x_powf(s.x * 1, RT_GAMMA), x_powf(s.y * 1, RT_GAMMA), x_powf(s.z * 1, RT_GAMMA), 0.0f) : gamma_sample(xyz(s)); // stored raw (R.deferGamma)
 		a.x += s.x, a.y += s.y, a.z += s.z, a.w += 0;
+		if (STATS) {
+			const float l = sample_luminance(s.x, s.y, s.z);
+			sy += l, syy += l * l;
+		}
 	}
 	R.accum[pixel] = a;
+	if (STATS) St.count[pixel] += (uint)batchFrames, St.sumY[pixel] = sy, St.sumYY[pixel] = syy;
 }
 
 // ---- batch queries -------------------------------------------------------------------------------
@@ -1374,13 +1407,10 @@ __global__ void k_wide_sync(float4* wide, const float4* pairs, int nWide)
 	w[0 + j] = lo.x, w[4 + j] = lo.y, w[8 + j] = lo.z, w[12 + j] = hi.x, w[16 + j] = hi.y, w[20 + j] = hi.z;
 }
 
-// RGBF32_to_RGB8(accumulator / it) (renderer.cpp:287-290, template/precomp.h:445-448)
-__global__ void k_resolve(const float4* accum, int first, int n, int it, uint* out)
+// RGBF32_to_RGB8 (template/precomp.h:445-448) of one mean colour
+__device__ __forceinline__ uint rgbf32_to_rgb8(float r, float g, float b)
 {
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const float4 a = accum[first + i];
-	const float v[3] = { a.x / it, a.y / it, a.z / it };
+	const float v[3] = { r, g, b };
 	uint c[3];
 	for (int k = 0; k < 3; k++) {
 		float m = std_min(1.0f, v[k]);
@@ -1389,7 +1419,15 @@ __global__ void k_resolve(const float4* accum, int first, int n, int it, uint* o
 		long long q = (s > -9.2e18f && s < 9.2e18f) ? (long long)s : (long long)0x8000000000000000ull;
 		c[k] = (uint)q;
 	}
-	out[i] = (c[0] << 16) + (c[1] << 8) + c[2];
+	return (c[0] << 16) + (c[1] << 8) + c[2];
+}
+// RGBF32_to_RGB8(accumulator / it) (renderer.cpp:287-290)
+__global__ void k_resolve(const float4* accum, int first, int n, int it, uint* out)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const float4 a = accum[first + i];
+	out[i] = rgbf32_to_rgb8(a.x / it, a.y / it, a.z / it);
 }
 
 } // namespace rtd

@@ -261,6 +261,13 @@ void rth_renderer_set_denoise(void* h, int on, const rt_denoise_params* params)
 	r->denoise = on != 0;
 	if (params) r->denoiseParams = *params;
 }
+void rth_renderer_set_adaptive(void* h, int on, const rt_adaptive_params* params)
+{
+	Renderer* r = ((RthRenderer*)h)->r;
+	r->adaptive = on != 0;
+	if (params) r->adaptiveParams = *params;
+}
+int rth_renderer_active_pixels(void* h) { return ((RthRenderer*)h)->r->activePixels; }
 const float* rth_renderer_accumulator(void* h) { return &((RthRenderer*)h)->r->accumulator[0].x; }
 const unsigned* rth_renderer_pixels(void* h) { return ((RthRenderer*)h)->r->screenPixels; }
 int rth_renderer_trace(void* h, int path, const float* O, const float* D, int depth, const float* energy, float* rgb)

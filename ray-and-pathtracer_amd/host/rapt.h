@@ -376,6 +376,15 @@ public:
 	// mean with rt_denoise and shows rt_resolve_denoised in screenPixels; 'accumulator' stays the raw download.  Off: Tick is unchanged.
 	bool denoise = false;
 	rt_denoise_params denoiseParams = RT_DENOISE_DEFAULTS;
+	// Adaptive sampling (path mode only, one context): Tick keeps per-pixel statistics (rt_stats_enable), renders whole frames until every
+	// pixel has adaptiveParams.min_samples samples, and from then on one frame of the pixels rt_select_active still finds noisy
+	// (rt_render_active); screenPixels is rt_resolve_adaptive (every pixel divided by its own count), 'accumulator' stays the raw download,
+	// activePixels is the number of pixels the last Tick sampled.  Switching it on clears the accumulator (the counts start with it); a
+	// camera change clears as ever.  Together with denoise (rt_denoise divides by ONE iteration count), with more than one device
+	// (the list is one context's) or with the Q-learning sampler, Tick throws.  Off: Tick is unchanged.
+	bool adaptive = false;
+	rt_adaptive_params adaptiveParams = RT_ADAPTIVE_DEFAULTS;
+	int activePixels = 0;
 	float4* accumulator = nullptr; // host copy, refreshed by Tick
 	uint32_t* screenPixels = nullptr; // Surface::pixels analogue (template/precomp.h:134)
 	Scene scene;
@@ -391,6 +400,9 @@ public:
 private:
 	struct Workers;                   // one parked host thread per context (several contexts only)
 	Workers* workers = nullptr;
+	void TickAdaptive();              // Tick's path-mode body with 'adaptive' set
+	bool adaptiveOn = false;          // the context's statistics were enabled by TickAdaptive
+	int wholeFrames = 0;              // whole frames rendered since the accumulator was last cleared
 };
 
 } // namespace rapt

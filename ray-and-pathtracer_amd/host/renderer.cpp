@@ -137,6 +137,15 @@ void Renderer::SyncCamera()
 void Renderer::Tick(float /*deltaTime*/)
 {
 	if (!ctx) Init();
+	if (adaptive) {
+		if (denoise) throw std::runtime_error("Renderer::Tick: adaptive with denoise: rt_denoise divides the whole frame by one iteration count");
+		if (ctxs.size() > 1) throw std::runtime_error("Renderer::Tick: adaptive with more than one device: the active-pixel list belongs to one context");
+		if (qlearning) throw std::runtime_error("Renderer::Tick: adaptive with the Q-learning sampler: the rewards of a pixel subset are not defined");
+		if (!scene.raytracer) { TickAdaptive(); return; }
+	} else if (adaptiveOn) {
+		check(ctx, rt_stats_enable(ctx, 0));
+		adaptiveOn = false;
+	}
 	scene.totIterationNumber++;
 	const int it = scene.GetIterationNumber();
 	const bool camChanged = camera.GetChange();
@@ -185,6 +194,37 @@ void Renderer::Tick(float /*deltaTime*/)
 		check(ctx, rt_resolve(ctx, it, 0, height, screenPixels));
 	if (downloadEachTick) check(ctx, rt_download_accumulator(ctx, 0, height, &accumulator[0].x));
 	if (!scene.raytracer && !camChanged) scene.SetIterationNumber(it + 1);
+	camera.SetChange(false);
+}
+
+// Tick in path mode with 'adaptive' set (one context): the iteration bookkeeping of Tick, whole frames until every pixel has min_samples
+// samples, then one frame of the pixels that are still noisy; every pixel is shown divided by its own count.
+void Renderer::TickAdaptive()
+{
+	scene.totIterationNumber++;
+	const int it = scene.GetIterationNumber();
+	bool reset = camera.GetChange();
+	if (!adaptiveOn) {
+		check(ctx, rt_stats_enable(ctx, 1));
+		adaptiveOn = true, reset = true; // the counts start now, so the accumulator does too
+	}
+	if (reset) {
+		scene.SetIterationNumber(1);
+		check(ctx, rt_clear(ctx)); // the statistics with the accumulator
+		wholeFrames = 0;
+	}
+	SyncCamera();
+	if (wholeFrames < adaptiveParams.min_samples) {
+		check(ctx, rt_render(ctx, RT_MODE_PATH, frame, 1, seedBase, 0, height, 4));
+		wholeFrames++, activePixels = width * height;
+	} else {
+		check(ctx, rt_select_active(ctx, &adaptiveParams, &activePixels));
+		check(ctx, rt_render_active(ctx, frame, 1, seedBase, 4));
+	}
+	frame++;
+	check(ctx, rt_resolve_adaptive(ctx, 0, height, screenPixels));
+	if (downloadEachTick) check(ctx, rt_download_accumulator(ctx, 0, height, &accumulator[0].x));
+	if (!reset) scene.SetIterationNumber(it + 1);
 	camera.SetChange(false);
 }
 

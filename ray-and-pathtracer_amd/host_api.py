@@ -28,9 +28,14 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_intersect_scope", "rt_occluded_scope", "rt_sky_color_batch", "rt_trace_batch_energy", "rt_build_info", "rt_tuning_info",
               "rt_qlearn_enable", "rt_qlearn_apply", "rt_qlearn_get_sums", "rt_qlearn_set_sums", "rt_qlearn_get_table", "rt_qlearn_bind_sums",
               "rt_device_pci_bus_id", "rt_set_scene_raytracer",
-              "rt_render_aovs", "rt_download_aovs", "rt_denoise", "rt_download_denoised", "rt_resolve_denoised"]
+              "rt_render_aovs", "rt_download_aovs", "rt_denoise", "rt_download_denoised", "rt_resolve_denoised",
+              "rt_stats_enable", "rt_download_stats", "rt_select_active", "rt_set_active_pixels", "rt_download_active",
+              "rt_render_active", "rt_resolve_adaptive"]
 
 RT_E_ARG, RT_E_STATE = -2, -5
+RT_E_UNSUPPORTED = -4
+# include/rt_amd.h RT_ADAPTIVE_DEFAULTS (a starting point, not tuned)
+ADAPTIVE_DEFAULTS = dict(min_samples=16, max_samples=1024, threshold=0.05, floor=1e-3)
 # include/rt_amd.h RT_DENOISE_DEFAULTS
 DENOISE_DEFAULTS = dict(iterations=5, sigma_color=0.5, sigma_normal=0.25, sigma_position=0.1, sigma_albedo=0.1)
 
@@ -49,6 +54,18 @@ def denoise_params(params=None):
         return None
     p = dict(DENOISE_DEFAULTS, **params)
     return RtDenoiseParams(int(p["iterations"]), p["sigma_color"], p["sigma_normal"], p["sigma_position"], p["sigma_albedo"])
+
+
+class RtAdaptiveParams(C.Structure):
+    _fields_ = [("min_samples", C.c_int32), ("max_samples", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float)]
+
+
+def adaptive_params(params=None):
+    """rt_adaptive_params from a dict of ADAPTIVE_DEFAULTS' keys (missing keys: the defaults); None -> None (the library's defaults)"""
+    if params is None:
+        return None
+    p = dict(ADAPTIVE_DEFAULTS, **params)
+    return RtAdaptiveParams(int(p["min_samples"]), int(p["max_samples"]), p["threshold"], p["floor"])
 
 
 class RtCamera(C.Structure):
@@ -142,6 +159,13 @@ def rt_lib():
         L.rt_denoise.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.rt_download_denoised.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.rt_resolve_denoised.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.rt_stats_enable.argtypes = [C.c_void_p, C.c_int]
+        L.rt_download_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_select_active.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_set_active_pixels.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rt_download_active.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.rt_render_active.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_int]
+        L.rt_resolve_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _rt = L
     return _rt
 
@@ -418,6 +442,15 @@ class HostRenderer:
         p = denoise_params(params)
         self.L.rth_renderer_set_denoise(self.h, int(bool(on)), C.byref(p) if p is not None else None)
 
+    def set_adaptive(self, on, params=None):
+        """rapt::Renderer::adaptive / adaptiveParams: path-mode Ticks sample only the pixels that are still noisy (params: dict, see adaptive_params)"""
+        p = adaptive_params(params)
+        self.L.rth_renderer_set_adaptive(self.h, int(bool(on)), C.byref(p) if p is not None else None)
+
+    def active_pixels(self):
+        """rapt::Renderer::activePixels: the pixels the last adaptive Tick sampled"""
+        return int(self.L.rth_renderer_active_pixels(self.h))
+
     def trace_one(self, O, D, depth, path=False, energy=(1, 1, 1)):
         rgb = (C.c_float * 3)()
         self._chk(self.L.rth_renderer_trace(self.h, int(path), _f3(O), _f3(D), depth, _f3(energy), rgb))
@@ -536,6 +569,47 @@ class HostRenderer:
         y1 = self.hgt if y1 is None else y1
         out = np.zeros((y1 - y0, self.w), dtype=np.uint32)
         self._rt(self.rt.rt_resolve_denoised(self.ctx, y0, y1, _p(out)))
+        return out
+
+    # ---- adaptive sampling (include/rt_amd.h rt_stats_enable .. rt_resolve_adaptive) ----
+    def stats_enable(self, on=True):
+        self._rt(self.rt.rt_stats_enable(self.ctx, int(bool(on))))
+
+    def stats(self, y0=0, y1=None):
+        """rows [y0, y1) of the per-pixel statistics: (count uint32, sum_y float32, sum_yy float32), shaped (rows, width)"""
+        y1 = self.hgt if y1 is None else y1
+        cnt = np.zeros((y1 - y0, self.w), dtype=np.uint32)
+        sy, syy = np.zeros((y1 - y0, self.w), dtype=np.float32), np.zeros((y1 - y0, self.w), dtype=np.float32)
+        self._rt(self.rt.rt_download_stats(self.ctx, y0, y1, _p(cnt), _p(sy), _p(syy)))
+        return cnt, sy, syy
+
+    def select_active(self, params=None):
+        """rt_select_active (params: dict, see adaptive_params; None: the library's defaults): the number of pixels selected"""
+        p = adaptive_params(params)
+        n = C.c_int(-1)
+        self._rt(self.rt.rt_select_active(self.ctx, C.byref(p) if p is not None else None, C.byref(n)))
+        return n.value
+
+    def set_active(self, pixels):
+        """rt_set_active_pixels: pixel indices y * width + x, strictly ascending"""
+        px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+        self._rt(self.rt.rt_set_active_pixels(self.ctx, _p(px) if len(px) else None, len(px)))
+
+    def active(self, cap=None):
+        """rt_download_active: (the first cap entries of the list, the list's true length); cap None: the whole frame's worth"""
+        cap = self.w * self.hgt if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint32)
+        n = C.c_int(-1)
+        self._rt(self.rt.rt_download_active(self.ctx, _p(out), cap, C.byref(n)))
+        return out[:min(cap, n.value)].copy(), n.value
+
+    def render_active(self, frame0=0, nframes=1, seed_base=0x12345678, max_depth=4):
+        self._rt(self.rt.rt_render_active(self.ctx, frame0, nframes, seed_base, max_depth))
+
+    def resolve_adaptive(self, y0=0, y1=None):
+        y1 = self.hgt if y1 is None else y1
+        out = np.zeros((y1 - y0, self.w), dtype=np.uint32)
+        self._rt(self.rt.rt_resolve_adaptive(self.ctx, y0, y1, _p(out)))
         return out
 
     def set_scene_raytracer(self, flag):
