@@ -305,6 +305,41 @@ int rt_download_active(rt_ctx* ctx, uint32_t* out, int cap, int* n_out);
 int rt_render_active(rt_ctx* ctx, uint32_t frame0, int nframes, uint32_t seed_base, int max_depth);
 int rt_resolve_adaptive(rt_ctx* ctx, int y0, int y1, uint32_t* rgb8_out);
 
+/* ---- variance-guided denoiser for an adaptively sampled frame ------------------------------------------------
+ * rt_denoise_variance: rt_denoise's a-trous filter for a frame whose pixels have different sample counts (the spatial half of SVGF,
+ *   Schied et al. 2017): every pixel's mean is accumulator / its own count, the colour edge-stopping term is a luminance difference scaled
+ *   by the local standard deviation of the mean, taken from the statistics (rt_stats_enable), and the variance is filtered along with the
+ *   colour.  On the whole frame, on the context's stream, without synchronising; neither the accumulator nor the statistics are written.
+ *   The result lies where rt_denoise leaves its own: rt_download_denoised and rt_resolve_denoised serve whichever of the two ran last.
+ *   (This library's own addition.)  All arithmetic f32 with IEEE division and square root, no contraction (tests/denoise_var_ref.py
+ *   restates it).  Inputs per pixel p, n = count_p:
+ *     n == 0 (empty): the output colour is (0, 0, 0), as rt_resolve_adaptive's black; p is no tap of any neighbour.
+ *     c_p = acc_p.xyz / (float)n.  If a component of c_p, sum_y or sum_yy is non-finite, p is passed through (c_p as it is) and is no tap
+ *       of any neighbour (rt_denoise's rule for a directly viewed light).
+ *     y_p = (0.2126f * r + 0.7152f * g) + 0.0722f * b of c_p (the statistics' luminance).
+ *     v_p, the variance of the mean:
+ *       n >= 2:  m = sum_y / n;  s = (sum_yy - sum_y * m) / (n - 1);  s = s > 0 ? s : 0;  v_p = s / n   (rt_select_active's e, squared)
+ *       n == 1:  v_p = y_p * y_p   (one sample says nothing about its spread; its own square lets the pixel be smoothed freely)
+ *       v_p = fminf(v_p, FLT_MAX)   (an overflowing variance is clamped like every k of rt_denoise: a tap of weight 0 adds 0, never 0 x inf)
+ *   Which pixels are filtered and may be taps is decided by these inputs once, for every iteration.
+ *   Iteration i = 0 .. iterations - 1, step s = 2^i, on the current (c, v), y_p the luminance of the current c_p:
+ *     g_p = the 3 x 3 prefilter of v: taps at ONE pixel's distance (not s), weights k3[dx] k3[dy], k3 = (1/4, 1/2, 1/4), over the taps inside
+ *       the image that are neither empty nor passed through and have p's hit class (hit or miss); normalised by the sum of the weights used.
+ *     kl_p = fminf(1 / (sigma_luminance * sqrtf(g_p) + epsilon), FLT_MAX) (a tiny epsilon on a zero variance: the centre tap's zero
+ *       difference weighs exp(0), never 0 x inf); sigma_luminance = +inf drops the term (kl_p = 0).
+ *     25 taps at s * (dx, dy), dx, dy in [-2, 2], h as rt_denoise; skipped: taps outside the image, empty, passed through, hit against miss.
+ *     w = h[dx] h[dy] exp(-(|y_p - y_q| * kl_p + |n_p - n_q|^2 kn + |x_p - x_q|^2 / t_p^2 kx + |a_p - a_q|^2 ka)), the last three terms
+ *       exactly rt_denoise's: k = 1 / sigma^2, clamped to FLT_MAX (kx / t_p^2 per pixel), sigma = +inf drops its term, two misses compare
+ *       colour only.  There is no 4^i on the colour term: the falling variance does that job.
+ *     c_out = sum w c_q / sum w,  v_out = fminf(sum w^2 v_q / (sum w)^2, FLT_MAX).
+ *   Result: float4 per pixel, xyz the filtered colour, w the filtered variance of a filtered pixel and 0 of an empty or passed-through one.
+ *   params NULL: RT_DENOISE_VAR_DEFAULTS (sigma_luminance 4 is SVGF's; a starting point, NOT tuned).  RT_E_ARG (checked before the context):
+ *   iterations outside 1..8, a sigma <= 0 or NaN, epsilon <= 0 or NaN.  RT_E_STATE: statistics off; the G-buffer missing or stale
+ *   (rt_render_aovs first, rt_denoise's rule). */
+typedef struct { int32_t iterations; float sigma_luminance, sigma_normal, sigma_position, sigma_albedo, epsilon; } rt_denoise_var_params;
+#define RT_DENOISE_VAR_DEFAULTS { 5, 4.0f, 0.25f, 0.1f, 0.1f, 1e-4f }
+int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_var_params* params);
+
 /* ---- Q-learning guided sampling ("next" row N4) ------------------------------------------------------
  * The reference snapshot has no code for it: README.md:36-42 names Dahm & Keller 2017, "Learning Light Transport
  * the Reinforced Way", and lists "initialize sampling positions; pick sampling direction according to the QValue of neighboring

@@ -196,6 +196,7 @@ int rt_bind_accumulator(rt_ctx* c, void* p)
 #include "rt_api_query.inc"
 #include "rt_api_denoise.inc"
 #include "rt_api_adaptive.inc"
+#include "rt_api_denoise_var.inc"
 
 // ---- measurement ------------------------------------------------------------------------------
 int rt_set_counting(rt_ctx* c, int counting)

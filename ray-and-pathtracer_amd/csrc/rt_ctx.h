@@ -10,6 +10,7 @@
 //   rt_api_qlearn.inc   rt_qlearn_*
 //   rt_api_denoise.inc  rt_render_aovs, rt_denoise and their downloads
 //   rt_api_adaptive.inc rt_stats_*, rt_select_active, the active-pixel list, rt_render_active, rt_resolve_adaptive
+//   rt_api_denoise_var.inc rt_denoise_variance
 #pragma once
 #include "rt_kernels.h"
 #include "rt_stream.h"
@@ -17,6 +18,7 @@
 #include "rt_build.h"
 #include "rt_denoise.h"
 #include "rt_adaptive.h"
+#include "rt_denoise_var.h"
 #include "../../include/rt_amd.h"
 #include <algorithm>
 #include <cstdarg>

@@ -267,6 +267,12 @@ void rth_renderer_set_adaptive(void* h, int on, const rt_adaptive_params* params
 	r->adaptive = on != 0;
 	if (params) r->adaptiveParams = *params;
 }
+void rth_renderer_set_denoise_variance(void* h, int on, const rt_denoise_var_params* params)
+{
+	Renderer* r = ((RthRenderer*)h)->r;
+	r->denoiseVariance = on != 0;
+	if (params) r->denoiseVarParams = *params;
+}
 int rth_renderer_active_pixels(void* h) { return ((RthRenderer*)h)->r->activePixels; }
 const float* rth_renderer_accumulator(void* h) { return &((RthRenderer*)h)->r->accumulator[0].x; }
 const unsigned* rth_renderer_pixels(void* h) { return ((RthRenderer*)h)->r->screenPixels; }

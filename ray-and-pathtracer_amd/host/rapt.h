@@ -385,6 +385,11 @@ public:
 	bool adaptive = false;
 	rt_adaptive_params adaptiveParams = RT_ADAPTIVE_DEFAULTS;
 	int activePixels = 0;
+	// Variance-guided denoised preview of the adaptive frame (needs 'adaptive': the filter reads its statistics; 'denoise' clear): every
+	// adaptive Tick ends with rt_render_aovs (0.001f, a no-op on a current G-buffer), rt_denoise_variance and rt_resolve_denoised into
+	// screenPixels; 'accumulator' stays the raw download.  Without 'adaptive', Tick throws.  Off: Tick is unchanged.
+	bool denoiseVariance = false;
+	rt_denoise_var_params denoiseVarParams = RT_DENOISE_VAR_DEFAULTS;
 	float4* accumulator = nullptr; // host copy, refreshed by Tick
 	uint32_t* screenPixels = nullptr; // Surface::pixels analogue (template/precomp.h:134)
 	Scene scene;

@@ -142,9 +142,12 @@ void Renderer::Tick(float /*deltaTime*/)
 		if (ctxs.size() > 1) throw std::runtime_error("Renderer::Tick: adaptive with more than one device: the active-pixel list belongs to one context");
 		if (qlearning) throw std::runtime_error("Renderer::Tick: adaptive with the Q-learning sampler: the rewards of a pixel subset are not defined");
 		if (!scene.raytracer) { TickAdaptive(); return; }
-	} else if (adaptiveOn) {
-		check(ctx, rt_stats_enable(ctx, 0));
-		adaptiveOn = false;
+	} else {
+		if (denoiseVariance) throw std::runtime_error("Renderer::Tick: denoiseVariance without adaptive: rt_denoise_variance needs the per-pixel statistics adaptive sampling keeps");
+		if (adaptiveOn) {
+			check(ctx, rt_stats_enable(ctx, 0));
+			adaptiveOn = false;
+		}
 	}
 	scene.totIterationNumber++;
 	const int it = scene.GetIterationNumber();
@@ -222,7 +225,12 @@ void Renderer::TickAdaptive()
 		check(ctx, rt_render_active(ctx, frame, 1, seedBase, 4));
 	}
 	frame++;
-	check(ctx, rt_resolve_adaptive(ctx, 0, height, screenPixels));
+	if (denoiseVariance) {
+		check(ctx, rt_render_aovs(ctx, 0.001f)); // a no-op unless the camera, the scene or the time changed
+		check(ctx, rt_denoise_variance(ctx, &denoiseVarParams));
+		check(ctx, rt_resolve_denoised(ctx, 0, height, screenPixels));
+	} else
+		check(ctx, rt_resolve_adaptive(ctx, 0, height, screenPixels));
 	if (downloadEachTick) check(ctx, rt_download_accumulator(ctx, 0, height, &accumulator[0].x));
 	if (!reset) scene.SetIterationNumber(it + 1);
 	camera.SetChange(false);

@@ -30,7 +30,7 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_device_pci_bus_id", "rt_set_scene_raytracer",
               "rt_render_aovs", "rt_download_aovs", "rt_denoise", "rt_download_denoised", "rt_resolve_denoised",
               "rt_stats_enable", "rt_download_stats", "rt_select_active", "rt_set_active_pixels", "rt_download_active",
-              "rt_render_active", "rt_resolve_adaptive"]
+              "rt_render_active", "rt_resolve_adaptive", "rt_denoise_variance"]
 
 RT_E_ARG, RT_E_STATE = -2, -5
 RT_E_UNSUPPORTED = -4
@@ -54,6 +54,23 @@ def denoise_params(params=None):
         return None
     p = dict(DENOISE_DEFAULTS, **params)
     return RtDenoiseParams(int(p["iterations"]), p["sigma_color"], p["sigma_normal"], p["sigma_position"], p["sigma_albedo"])
+
+
+# include/rt_amd.h RT_DENOISE_VAR_DEFAULTS (a starting point, not tuned)
+DENOISE_VAR_DEFAULTS = dict(iterations=5, sigma_luminance=4.0, sigma_normal=0.25, sigma_position=0.1, sigma_albedo=0.1, epsilon=1e-4)
+
+
+class RtDenoiseVarParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
+                ("sigma_albedo", C.c_float), ("epsilon", C.c_float)]
+
+
+def denoise_var_params(params=None):
+    """rt_denoise_var_params from a dict of DENOISE_VAR_DEFAULTS' keys (missing keys: the defaults); None -> None (the library's defaults)"""
+    if params is None:
+        return None
+    p = dict(DENOISE_VAR_DEFAULTS, **params)
+    return RtDenoiseVarParams(int(p["iterations"]), p["sigma_luminance"], p["sigma_normal"], p["sigma_position"], p["sigma_albedo"], p["epsilon"])
 
 
 class RtAdaptiveParams(C.Structure):
@@ -166,6 +183,7 @@ def rt_lib():
         L.rt_download_active.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.rt_render_active.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_int]
         L.rt_resolve_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.rt_denoise_variance.argtypes = [C.c_void_p, C.c_void_p]
         _rt = L
     return _rt
 
@@ -442,6 +460,11 @@ class HostRenderer:
         p = denoise_params(params)
         self.L.rth_renderer_set_denoise(self.h, int(bool(on)), C.byref(p) if p is not None else None)
 
+    def set_denoise_variance(self, on, params=None):
+        """rapt::Renderer::denoiseVariance / denoiseVarParams: adaptive Ticks show the variance-guided denoised frame (params: dict, see denoise_var_params)"""
+        p = denoise_var_params(params)
+        self.L.rth_renderer_set_denoise_variance(self.h, int(bool(on)), C.byref(p) if p is not None else None)
+
     def set_adaptive(self, on, params=None):
         """rapt::Renderer::adaptive / adaptiveParams: path-mode Ticks sample only the pixels that are still noisy (params: dict, see adaptive_params)"""
         p = adaptive_params(params)
@@ -558,6 +581,11 @@ class HostRenderer:
         """rt_denoise of the accumulator / it (params: dict, see denoise_params; None: the library's defaults)"""
         p = denoise_params(params)
         self._rt(self.rt.rt_denoise(self.ctx, int(it), C.byref(p) if p is not None else None))
+
+    def denoise_variance(self, params=None):
+        """rt_denoise_variance of the adaptively sampled frame (params: dict, see denoise_var_params; None: the library's defaults)"""
+        p = denoise_var_params(params)
+        self._rt(self.rt.rt_denoise_variance(self.ctx, C.byref(p) if p is not None else None))
 
     def denoised(self, y0=0, y1=None):
         y1 = self.hgt if y1 is None else y1
