@@ -159,3 +159,149 @@ def test_adaptive_loop_beats_uniform_on_the_oracle(scenes, oracle_api):
     assert most < q["stack_frames"], "the loop ran out of recorded frames"
     assert total <= q["budget_frames"] * w * h
     assert ratio <= 0.8, ratio
+
+
+# ---- the sizes, masks and lists of tests/test_gpu_adaptive_shapes.py ---------------------------------------------------------------
+import pytest  # noqa: E402
+
+import adaptive_shapes as sh  # noqa: E402
+
+LARGE_ONLY = ("full_to_1023", "full_from_1024", "scan_lane_mid", "scan_lane_last")
+
+
+def _per(mask, unit):
+    """(active pixels, pixels) of every run of 'unit' consecutive pixels (the last run may be short)"""
+    n = len(mask)
+    starts = np.arange(0, n, unit)
+    return np.add.reduceat(mask.astype(np.int64), starts), np.minimum(unit, n - starts)
+
+
+@pytest.mark.parametrize("size", list(sh.SIZES), ids=lambda s: "%dx%d" % s)
+def test_shape_sizes_reach_the_edges_they_are_listed_for(size):
+    w, h = size
+    n, blocks, per = sh.SIZES[size]
+    assert n == w * h
+    assert sh.geometry(n)[:2] == (blocks, per)
+    assert blocks == -(-n // 256) and per == -(-blocks // 1024)  # the library's two constants, written out
+    _, _, owners, last_owns = sh.geometry(n)
+    last_block = n - (blocks - 1) * 256
+    want = {(1, 1): (1, 1, 1), (63, 1): (1, 1, 63), (65, 1): (1, 1, 65), (255, 1): (1, 1, 255), (257, 3): (4, 1, 3), (97, 41): (16, 1, 137),
+            (641, 409): (513, 1, 25), (1280, 721): (902, 1, 256), (1279, 721): (901, 3, 47)}[size]
+    assert (owners, last_owns, last_block) == want
+    assert owners <= 1024 and (owners - 1) * per + last_owns == blocks
+    if size == (97, 41):
+        assert last_block % 64 != 0 and last_block > 64          # the last wave of the last block is partial, and not its only wave
+    if per > 1:
+        assert last_owns < per                                   # a last owning lane whose run is short
+        assert owners < 1024                                     # lanes past the end: first and last both clamped to blocks
+        assert sh.scan_lane_blocks(n, owners) == (blocks, blocks) and sh.scan_lane_blocks(n, 1023) == (blocks, blocks)
+        assert sh.scan_lane_blocks(n, owners - 1) == (blocks - last_owns, blocks)
+        assert sh.scan_lane_blocks(n, 64) == (64 * per, 65 * per)
+
+
+@pytest.mark.parametrize("size", list(sh.SIZES), ids=lambda s: "%dx%d" % s)
+def test_shape_masks_are_what_their_names_say(size):
+    w, h = size
+    n, blocks, per = sh.SIZES[size]
+    got = dict(sh.masks(w, h))
+    # which masks a size leaves out, and why: each would be another mask of the table
+    absent = set(sh.MASKS) - set(got)
+    want_absent = set()
+    if n == 1:
+        want_absent |= {"first", "last", "every_other", "seeded_30"}
+    if blocks == 1:
+        want_absent |= {"last_block", "all_but_last_block", "alternate_blocks"}
+    if n <= 64:
+        want_absent |= {"lane0"}
+    if n < 64:
+        want_absent |= {"lane63"}
+    if h == 1:
+        want_absent |= {"one_row"}
+    if n < 2000:
+        want_absent |= {"seeded_01"}
+    if per == 1:
+        want_absent |= set(LARGE_ONLY)
+    assert absent == want_absent
+    seen = {}
+    for name, m in got.items():
+        assert m.dtype == bool and m.shape == (n,), name
+        key = m.tobytes()
+        # no two masks of a size are the same mask; only the scan's own may repeat a block mask (1025 blocks: the block past the scan's
+        # lanes is the last one; a last scan lane that owns one entry owns the last block)
+        assert key not in seen or name in LARGE_ONLY, (name, seen.get(key))
+        seen[key] = name
+        lst = sh.complement_list(m)
+        assert sh.acceptable(lst, n) and len(lst) == n - int(m.sum()), name
+        assert np.array_equal(np.flatnonzero(m), np.setdiff1d(np.arange(n), lst)), name
+        b, bsize = _per(m, 256)
+        v, vsize = _per(m, 64)
+        assert len(b) == blocks
+        if name == "all":
+            assert np.array_equal(b, bsize) and np.array_equal(v, vsize)
+        elif name == "none":
+            assert not b.any()
+        elif name == "first":
+            assert m[0] and m.sum() == 1
+        elif name == "last":
+            assert m[n - 1] and m.sum() == 1 and b[-1] == 1
+        elif name == "last_block":
+            assert not b[:-1].any() and b[-1] == bsize[-1] == n - (blocks - 1) * 256
+        elif name == "all_but_last_block":
+            assert np.array_equal(b[:-1], bsize[:-1]) and b[-1] == 0
+        elif name == "alternate_blocks":
+            assert np.array_equal(b[0::2], bsize[0::2]) and not b[1::2].any()
+        elif name == "lane0":
+            assert np.all(v == 1) and m[::64].all()
+        elif name == "lane63":
+            assert np.array_equal(v, (vsize == 64).astype(np.int64)) and m[63::64].all()
+        elif name == "every_other":
+            assert np.array_equal(v, (vsize + 1) // 2) and m[::2].all()
+        elif name == "one_row":
+            assert m.sum() == w and m.reshape(h, w)[h // 2].all()
+        elif name == "seeded_30":
+            assert 0 < m.sum() < n and abs(m.mean() - 0.3) < 4 * np.sqrt(0.21 / n)
+            if blocks > 1:
+                assert np.all(b[:-1] > 0) and np.all(b < bsize)  # no block empty, none full: the middling totals
+        elif name == "seeded_01":
+            assert m.sum() == (n + 500) // 1000
+            if blocks > 16:
+                assert (b == 0).mean() > 0.5                     # most blocks total 0
+        elif name == "full_to_1023":
+            assert np.all(b[:1024] == 256) and not b[1024:].any() and blocks > 1024
+        elif name == "full_from_1024":
+            assert not b[:1024].any() and np.array_equal(b[1024:], bsize[1024:])
+        elif name == "scan_lane_mid":
+            assert np.all(b[64 * per:65 * per] == 256) and m.sum() == 256 * per
+        elif name == "scan_lane_last":
+            _, _, owners, last_owns = sh.geometry(n)
+            assert np.array_equal(b[blocks - last_owns:], bsize[blocks - last_owns:]) and not b[:blocks - last_owns].any()
+            assert last_owns == {(641, 409): 1, (1280, 721): 1, (1279, 721): 3}[size]
+        else:
+            raise AssertionError("no check for mask " + name)
+    # the acceptance rule itself
+    assert sh.acceptable(np.zeros(0, np.uint32), n) and not sh.acceptable(np.array([n], np.uint32), n)
+    assert not sh.acceptable(np.array([0, 0], np.uint32), max(n, 2)) and not sh.acceptable(np.array([1, 0], np.uint32), max(n, 2))
+
+
+def test_shape_lists():
+    for w, h in ((97, 41), (96, 64), (257, 3), (641, 409)):
+        n = w * h
+        for seed, density in ((5, 0.3), (9, 0.3), (11, 0.6)):
+            lst = sh.seeded_list(w, h, seed, density)
+            assert sh.acceptable(lst, n) and lst[0] == 0 and lst[-1] == n - 1
+            assert abs(len(lst) / n - density) < 0.05, (w, h, len(lst) / n)
+            row = np.arange((h // 3) * w, (h // 3 + 1) * w)
+            assert np.isin(row, lst).all()
+        row = sh.last_row_list(w, h)
+        assert sh.acceptable(row, n) and len(row) == w and np.all(row // w == h - 1)
+        cols = sh.side_columns_list(w, h)
+        assert sh.acceptable(cols, n) and len(cols) == 2 * h and set(np.unique(cols % w)) == {0, w - 1}
+    # the RT_SLOTS branches the device test asks for, from the lengths of its lists
+    for w, h in ((97, 41), (96, 64)):
+        k = len(sh.seeded_list(w, h))
+        assert k >= 1025                                         # the list lengths the device test cuts from it
+        assert sh.slots_branch(777, k, 4) == ("recycle", 4)
+        assert sh.slots_branch(2000, k, 4) == ("own", 1) and sh.slots_branch(2000, k, 7) == ("own", 1)
+        assert sh.slots_branch(4096, k, 4) == ("own", 2 if (w, h) == (96, 64) else 3)
+        assert sh.slots_branch(4096, k, 7)[1] in (2, 3)          # 7 frames: 2 + 2 + 2 + 1, or 3 + 3 + 1
+        assert sh.slots_branch(1 << 28, k, 4) == ("own", 4)
