@@ -10,7 +10,7 @@
 //   k_select_scatter  the predicate again (12 B per pixel: cheaper than keeping a flag array), rank inside the wave by mbcnt,
 //                     list[block base + waves before + rank] = pixel
 #pragma once
-#include "rt_kernels.h" // PixelStats, rgbf32_to_rgb8
+#include "rt_kernels.h" // PixelStats, resolve_pixel
 
 namespace rtd {
 
@@ -99,9 +99,7 @@ __global__ void k_resolve_adaptive(const float4* accum, const uint* count, int f
 	if (i >= n) return;
 	const uint k = count[first + i];
 	if (k == 0) { out[i] = 0; return; }
-	const float4 a = accum[first + i];
-	const float it = (float)k;
-	out[i] = rgbf32_to_rgb8(a.x / it, a.y / it, a.z / it);
+	out[i] = resolve_pixel(accum[first + i], (float)k);
 }
 
 } // namespace rtd

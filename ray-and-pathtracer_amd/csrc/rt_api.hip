@@ -1,6 +1,6 @@
 // librt_amd.so: implementation of the C ABI in include/rt_amd.h for gfx950.
 // This file: context, camera, accumulator access, counters and timers, build / tuning info; the other units of the library
-// (scene upload, device builders, the render loops, gather, batch queries, the Q-learning sampler, the denoiser, adaptive sampling) are the rt_api_*.inc files
+// (scene upload, device builders, the render loops, gather, batch queries, the Q-learning sampler, the output stage's helpers, the denoisers, adaptive sampling) are the rt_api_*.inc files
 // included below -- one translation unit, see rt_ctx.h.
 #include "rt_ctx.h"
 
@@ -150,6 +150,7 @@ int rt_set_camera(rt_ctx* c, const rt_camera* cam)
 #include "rt_api_upload.inc"
 #include "rt_api_build.inc"
 #include "rt_api_render.inc"
+#include "rt_api_output.inc"
 
 int rt_clear(rt_ctx* c)
 {
@@ -161,24 +162,14 @@ int rt_clear(rt_ctx* c)
 
 int rt_download_accumulator(rt_ctx* c, int y0, int y1, float* out)
 {
-	if (!c || !out || y0 < 0 || y1 > c->height || y0 >= y1) return fail(c, RT_E_ARG, "rt_download_accumulator: bad argument");
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	HIPCHK(c, hipMemcpy(out, c->accum + (size_t)y0 * c->width, (size_t)(y1 - y0) * c->width * sizeof(float4), hipMemcpyDeviceToHost));
-	return RT_OK;
+	if (!out || !rows_ok(c, y0, y1)) return fail(c, RT_E_ARG, "rt_download_accumulator: bad argument");
+	return download_rows(c, y0, y1, { { c->accum, out, sizeof(float4) } });
 }
 
 int rt_resolve(rt_ctx* c, int iteration, int y0, int y1, uint32_t* rgb8_out)
 {
-	if (!c || !rgb8_out || y0 < 0 || y1 > c->height || y0 >= y1 || iteration == 0) return fail(c, RT_E_ARG, "rt_resolve: bad argument");
-	HIPCHK(c, hipSetDevice(c->device));
-	const int n = (y1 - y0) * c->width;
-	// one frame-sized pixel buffer per context, kept: Tick resolves every frame
-	if (!c->resolveBuf) HIPCHK(c, hipMalloc((void**)&c->resolveBuf, (size_t)c->width * c->height * 4));
-	hipLaunchKernelGGL(k_resolve, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->accum, y0 * c->width, n, iteration, c->resolveBuf);
-	HIPCHK(c, hipMemcpyAsync(rgb8_out, c->resolveBuf, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	return RT_OK;
+	if (!rgb8_out || !rows_ok(c, y0, y1) || iteration == 0) return fail(c, RT_E_ARG, "rt_resolve: bad argument");
+	return resolve_rows(c, c->accum, nullptr, iteration, y0, y1, rgb8_out);
 }
 
 void* rt_accumulator_device_ptr(rt_ctx* c) { return c ? c->accum : nullptr; }
@@ -196,7 +187,6 @@ int rt_bind_accumulator(rt_ctx* c, void* p)
 #include "rt_api_query.inc"
 #include "rt_api_denoise.inc"
 #include "rt_api_adaptive.inc"
-#include "rt_api_denoise_var.inc"
 
 // ---- measurement ------------------------------------------------------------------------------
 int rt_set_counting(rt_ctx* c, int counting)

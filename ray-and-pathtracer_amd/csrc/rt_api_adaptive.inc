@@ -26,15 +26,9 @@ int rt_stats_enable(rt_ctx* c, int on)
 
 int rt_download_stats(rt_ctx* c, int y0, int y1, uint32_t* count, float* sum_y, float* sum_yy)
 {
-	if (!c || y0 < 0 || y1 > c->height || y0 >= y1) return fail(c, RT_E_ARG, "rt_download_stats: bad argument");
+	if (!rows_ok(c, y0, y1)) return fail(c, RT_E_ARG, "rt_download_stats: bad argument");
 	if (!c->stats.count) return fail(c, RT_E_STATE, "rt_download_stats: statistics are off (rt_stats_enable)");
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	const size_t first = (size_t)y0 * c->width, n = (size_t)(y1 - y0) * c->width;
-	if (count) HIPCHK(c, hipMemcpy(count, c->stats.count + first, n * sizeof(uint), hipMemcpyDeviceToHost));
-	if (sum_y) HIPCHK(c, hipMemcpy(sum_y, c->stats.sumY + first, n * sizeof(float), hipMemcpyDeviceToHost));
-	if (sum_yy) HIPCHK(c, hipMemcpy(sum_yy, c->stats.sumYY + first, n * sizeof(float), hipMemcpyDeviceToHost));
-	return RT_OK;
+	return download_rows(c, y0, y1, { { c->stats.count, count, sizeof(uint) }, { c->stats.sumY, sum_y, sizeof(float) }, { c->stats.sumYY, sum_yy, sizeof(float) } });
 }
 
 // the list's device storage: width * height indices, a total per block of the selection, the selected count
@@ -126,13 +120,7 @@ int rt_render_active(rt_ctx* c, uint32_t frame0, int nframes, uint32_t seed_base
 
 int rt_resolve_adaptive(rt_ctx* c, int y0, int y1, uint32_t* rgb8_out)
 {
-	if (!c || !rgb8_out || y0 < 0 || y1 > c->height || y0 >= y1) return fail(c, RT_E_ARG, "rt_resolve_adaptive: bad argument");
+	if (!rgb8_out || !rows_ok(c, y0, y1)) return fail(c, RT_E_ARG, "rt_resolve_adaptive: bad argument");
 	if (!c->stats.count) return fail(c, RT_E_STATE, "rt_resolve_adaptive: statistics are off (rt_stats_enable)");
-	HIPCHK(c, hipSetDevice(c->device));
-	const int n = (y1 - y0) * c->width;
-	if (!c->resolveBuf) HIPCHK(c, hipMalloc((void**)&c->resolveBuf, (size_t)c->width * c->height * 4));
-	hipLaunchKernelGGL(k_resolve_adaptive, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->accum, c->stats.count, y0 * c->width, n, c->resolveBuf);
-	HIPCHK(c, hipMemcpyAsync(rgb8_out, c->resolveBuf, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	return RT_OK;
+	return resolve_rows(c, c->accum, c->stats.count, 0, y0, y1, rgb8_out);
 }

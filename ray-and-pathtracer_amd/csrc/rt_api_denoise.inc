@@ -1,6 +1,6 @@
-// G-buffer (primary-hit AOVs) and the edge-avoiding a-trous denoiser: rt_render_aovs, rt_download_aovs, rt_denoise, rt_download_denoised,
-// rt_resolve_denoised.  Included by rt_api.hip.  The kernels are k_primary_aovs (rt_kernels.h) and k_denoise_atrous (rt_denoise.h).
-static bool aovs_current(const rt_ctx* c) { return c->aovNrm && c->aovGen == c->sceneGen; }
+// G-buffer (primary-hit AOVs) and the two edge-avoiding a-trous denoisers: rt_render_aovs, rt_download_aovs, rt_denoise, rt_denoise_variance,
+// rt_download_denoised, rt_resolve_denoised.  Included by rt_api.hip after rt_api_output.inc (the helpers they share).  The kernels are
+// k_primary_aovs (rt_kernels.h), k_denoise_atrous (rt_denoise.h) and k_denoise_var_init, k_denoise_var_atrous (rt_denoise_var.h).
 
 int rt_render_aovs(rt_ctx* c, float t_min)
 {
@@ -34,15 +34,12 @@ int rt_render_aovs(rt_ctx* c, float t_min)
 
 int rt_download_aovs(rt_ctx* c, int y0, int y1, rt_hit* hits_out, float* albedo_rgb_out)
 {
-	if (!c || y0 < 0 || y1 > c->height || y0 >= y1) return fail(c, RT_E_ARG, "rt_download_aovs: bad argument");
+	if (!rows_ok(c, y0, y1)) return fail(c, RT_E_ARG, "rt_download_aovs: bad argument");
 	if (!c->aovNrm || c->aovGen == 0) return fail(c, RT_E_STATE, "rt_download_aovs: no G-buffer (rt_render_aovs)");
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	const size_t first = (size_t)y0 * c->width, n = (size_t)(y1 - y0) * c->width;
+	const size_t n = (size_t)(y1 - y0) * c->width;
 	std::vector<float4> nrm(n), pos(hits_out ? n : 0), alb(n);
-	HIPCHK(c, hipMemcpy(nrm.data(), c->aovNrm + first, n * sizeof(float4), hipMemcpyDeviceToHost));
-	HIPCHK(c, hipMemcpy(alb.data(), c->aovAlb + first, n * sizeof(float4), hipMemcpyDeviceToHost));
-	if (hits_out) HIPCHK(c, hipMemcpy(pos.data(), c->aovPos + first, n * sizeof(float4), hipMemcpyDeviceToHost));
+	const int rc = download_rows(c, y0, y1, { { c->aovNrm, nrm.data(), sizeof(float4) }, { c->aovAlb, alb.data(), sizeof(float4) }, { c->aovPos, hits_out ? pos.data() : nullptr, sizeof(float4) } });
+	if (rc != RT_OK) return rc;
 	for (size_t i = 0; i < n; i++) {
 		if (hits_out) {
 			rt_hit& h = hits_out[i];
@@ -54,69 +51,56 @@ int rt_download_aovs(rt_ctx* c, int y0, int y1, rt_hit* hits_out, float* albedo_
 	return RT_OK;
 }
 
-// 1 / sigma^2 in f32; sigma = +inf gives 0 (the term is dropped), a k that overflows is FLT_MAX (so a zero distance adds 0, not 0 x inf = NaN)
-static float denoise_k_clamp(float k) { return std::min(k, FLT_MAX); }
-static float denoise_k(float sigma) { return denoise_k_clamp(1.0f / (sigma * sigma)); }
-static bool denoise_sigma_ok(float sigma) { return sigma > 0.0f; } // (false for NaN)
-
 int rt_denoise(rt_ctx* c, int iteration, const rt_denoise_params* params)
 {
-	// the arguments are checked before the context (a null context reports them through rt_last_error(NULL))
 	const rt_denoise_params P = params ? *params : rt_denoise_params RT_DENOISE_DEFAULTS;
 	if (iteration < 1) return fail(c, RT_E_ARG, "rt_denoise: iteration %d (>= 1)", iteration);
-	if (P.iterations < 1 || P.iterations > 8) return fail(c, RT_E_ARG, "rt_denoise: %d iterations (1..8)", P.iterations);
-	if (!denoise_sigma_ok(P.sigma_color) || !denoise_sigma_ok(P.sigma_normal) || !denoise_sigma_ok(P.sigma_position) || !denoise_sigma_ok(P.sigma_albedo))
-		return fail(c, RT_E_ARG, "rt_denoise: every sigma must be > 0 (+inf drops its term)");
+	int rc = atrous_check(c, "rt_denoise", P.iterations, P.sigma_color, P.sigma_normal, P.sigma_position, P.sigma_albedo);
+	if (rc != RT_OK) return rc;
 	if (!c) return fail(c, RT_E_ARG, "rt_denoise: null context");
-	if (!aovs_current(c)) return fail(c, RT_E_STATE, "rt_denoise: the G-buffer is %s (rt_render_aovs)", c->aovNrm ? "stale" : "missing");
-	HIPCHK(c, hipSetDevice(c->device));
-	const size_t n = (size_t)c->width * c->height;
-	if (!c->denoiseBuf[0]) {
-		float4 *b0 = nullptr, *b1 = nullptr;
-		hipError_t e = dalloc(c->denoiseAllocs, &b0, n);
-		if (e == hipSuccess) e = dalloc(c->denoiseAllocs, &b1, n);
-		if (e != hipSuccess) return fail(c, RT_E_HIP, "rt_denoise: %s", hipGetErrorString(e));
-		c->denoiseBuf[0] = b0, c->denoiseBuf[1] = b1;
-	}
 	DenoiseArgs A;
-	A.nrm = c->aovNrm, A.pos = c->aovPos, A.alb = c->aovAlb;
-	A.width = c->width, A.height = c->height;
+	rc = atrous_begin(c, "rt_denoise", A, P.sigma_normal, P.sigma_position, P.sigma_albedo);
+	if (rc != RT_OK) return rc;
 	A.it = (float)iteration;
-	A.kn = denoise_k(P.sigma_normal), A.kx = denoise_k(P.sigma_position), A.ka = denoise_k(P.sigma_albedo);
 	const float kc0 = denoise_k(P.sigma_color);
-	const dim3 grid((c->width + RT_DENOISE_TX - 1) / RT_DENOISE_TX, (c->height + RT_DENOISE_TY - 1) / RT_DENOISE_TY), block(RT_DENOISE_TX, RT_DENOISE_TY);
-	for (int i = 0; i < P.iterations; i++) {
-		A.in = i == 0 ? c->accum : c->denoiseBuf[(i - 1) & 1];
-		A.out = c->denoiseBuf[i & 1];
-		A.step = 1 << i;
+	return atrous_run(c, A, P.iterations, c->accum, [&](int i, dim3 grid, dim3 block) {
 		A.kc = denoise_k_clamp(kc0 * (float)(1 << (2 * i))); // sigma_c halves every iteration (exact: a power of two, until it overflows)
 		if (i == 0) hipLaunchKernelGGL(k_denoise_atrous<true>, grid, block, 0, c->stream, A);
 		else hipLaunchKernelGGL(k_denoise_atrous<false>, grid, block, 0, c->stream, A);
-	}
-	HIPCHK(c, hipGetLastError());
-	c->denoised = c->denoiseBuf[(P.iterations - 1) & 1];
-	return RT_OK;
+	});
+}
+
+// the variance-guided filter of an adaptively sampled frame: init writes buffer 1, the iterations follow; served like rt_denoise's result
+int rt_denoise_variance(rt_ctx* c, const rt_denoise_var_params* params)
+{
+	const rt_denoise_var_params P = params ? *params : rt_denoise_var_params RT_DENOISE_VAR_DEFAULTS;
+	int rc = atrous_check(c, "rt_denoise_variance", P.iterations, P.sigma_luminance, P.sigma_normal, P.sigma_position, P.sigma_albedo);
+	if (rc != RT_OK) return rc;
+	if (!(P.epsilon > 0.0f)) return fail(c, RT_E_ARG, "rt_denoise_variance: epsilon must be > 0");
+	if (!c) return fail(c, RT_E_ARG, "rt_denoise_variance: null context");
+	if (!c->stats.count) return fail(c, RT_E_STATE, "rt_denoise_variance: statistics are off (rt_stats_enable)");
+	DenoiseVarArgs A;
+	rc = atrous_begin(c, "rt_denoise_variance", A, P.sigma_normal, P.sigma_position, P.sigma_albedo);
+	if (rc != RT_OK) return rc;
+	A.sl = P.sigma_luminance, A.eps = P.epsilon;
+	const int n = c->width * c->height;
+	hipLaunchKernelGGL(k_denoise_var_init, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->accum, c->stats, n, c->denoiseBuf[1]);
+	return atrous_run(c, A, P.iterations, c->denoiseBuf[1], [&](int i, dim3 grid, dim3 block) {
+		A.last = i == P.iterations - 1;
+		hipLaunchKernelGGL(k_denoise_var_atrous, grid, block, 0, c->stream, A);
+	});
 }
 
 int rt_download_denoised(rt_ctx* c, int y0, int y1, float* out)
 {
-	if (!c || !out || y0 < 0 || y1 > c->height || y0 >= y1) return fail(c, RT_E_ARG, "rt_download_denoised: bad argument");
+	if (!out || !rows_ok(c, y0, y1)) return fail(c, RT_E_ARG, "rt_download_denoised: bad argument");
 	if (!c->denoised) return fail(c, RT_E_STATE, "rt_download_denoised: nothing denoised (rt_denoise)");
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	HIPCHK(c, hipMemcpy(out, c->denoised + (size_t)y0 * c->width, (size_t)(y1 - y0) * c->width * sizeof(float4), hipMemcpyDeviceToHost));
-	return RT_OK;
+	return download_rows(c, y0, y1, { { c->denoised, out, sizeof(float4) } });
 }
 
 int rt_resolve_denoised(rt_ctx* c, int y0, int y1, uint32_t* rgb8_out)
 {
-	if (!c || !rgb8_out || y0 < 0 || y1 > c->height || y0 >= y1) return fail(c, RT_E_ARG, "rt_resolve_denoised: bad argument");
+	if (!rgb8_out || !rows_ok(c, y0, y1)) return fail(c, RT_E_ARG, "rt_resolve_denoised: bad argument");
 	if (!c->denoised) return fail(c, RT_E_STATE, "rt_resolve_denoised: nothing denoised (rt_denoise)");
-	HIPCHK(c, hipSetDevice(c->device));
-	const int n = (y1 - y0) * c->width;
-	if (!c->resolveBuf) HIPCHK(c, hipMalloc((void**)&c->resolveBuf, (size_t)c->width * c->height * 4));
-	hipLaunchKernelGGL(k_resolve, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->denoised, y0 * c->width, n, 1, c->resolveBuf);
-	HIPCHK(c, hipMemcpyAsync(rgb8_out, c->resolveBuf, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	return RT_OK;
+	return resolve_rows(c, c->denoised, nullptr, 1, y0, y1, rgb8_out);
 }

@@ -8,9 +8,9 @@
 //   rt_api_gather.inc   rt_gather_*
 //   rt_api_query.inc    batch queries
 //   rt_api_qlearn.inc   rt_qlearn_*
-//   rt_api_denoise.inc  rt_render_aovs, rt_denoise and their downloads
+//   rt_api_output.inc   the output stage's shared helpers: row ranges, row downloads, the resolve, the a-trous drivers' common part
+//   rt_api_denoise.inc  rt_render_aovs, rt_denoise, rt_denoise_variance and their downloads
 //   rt_api_adaptive.inc rt_stats_*, rt_select_active, the active-pixel list, rt_render_active, rt_resolve_adaptive
-//   rt_api_denoise_var.inc rt_denoise_variance
 #pragma once
 #include "rt_kernels.h"
 #include "rt_stream.h"

@@ -1421,13 +1421,13 @@ __device__ __forceinline__ uint rgbf32_to_rgb8(float r, float g, float b)
 	}
 	return (c[0] << 16) + (c[1] << 8) + c[2];
 }
-// RGBF32_to_RGB8(accumulator / it) (renderer.cpp:287-290)
+// RGBF32_to_RGB8(accumulator / it) (renderer.cpp:287-290) of one record: the body of k_resolve and k_resolve_adaptive
+__device__ __forceinline__ uint resolve_pixel(const float4& a, float it) { return rgbf32_to_rgb8(a.x / it, a.y / it, a.z / it); }
 __global__ void k_resolve(const float4* accum, int first, int n, int it, uint* out)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	const float4 a = accum[first + i];
-	out[i] = rgbf32_to_rgb8(a.x / it, a.y / it, a.z / it);
+	out[i] = resolve_pixel(accum[first + i], (float)it);
 }
 
 } // namespace rtd

@@ -496,15 +496,18 @@ class HostRenderer:
     def synchronize(self):
         self._rt(self.rt.rt_synchronize(self.ctx))
 
-    def accumulator(self, y0=0, y1=None):
+    def _rows(self, y0, y1, dtype, *tail):
+        """rows [y0, y1) (y1 None: to the last row): (y1, a zeroed array of those rows, shaped (rows, width) + tail)"""
         y1 = self.hgt if y1 is None else y1
-        out = np.zeros((y1 - y0, self.w, 4), dtype=np.float32)
+        return y1, np.zeros((y1 - y0, self.w) + tail, dtype=dtype)
+
+    def accumulator(self, y0=0, y1=None):
+        y1, out = self._rows(y0, y1, np.float32, 4)
         self._rt(self.rt.rt_download_accumulator(self.ctx, y0, y1, _p(out)))
         return out
 
     def resolve(self, it=1, y0=0, y1=None):
-        y1 = self.hgt if y1 is None else y1
-        out = np.zeros((y1 - y0, self.w), dtype=np.uint32)
+        y1, out = self._rows(y0, y1, np.uint32)
         self._rt(self.rt.rt_resolve(self.ctx, it, y0, y1, _p(out)))
         return out
 
@@ -571,9 +574,8 @@ class HostRenderer:
 
     def aovs(self, y0=0, y1=None):
         """rows [y0, y1) of the G-buffer: dict(t, obj, mat, normal, albedo) like find_nearest plus the albedo, shaped (rows, width[, 3])"""
-        y1 = self.hgt if y1 is None else y1
-        hits = np.zeros((y1 - y0, self.w), dtype=RT_HIT_DTYPE)
-        alb = np.zeros((y1 - y0, self.w, 3), dtype=np.float32)
+        y1, hits = self._rows(y0, y1, RT_HIT_DTYPE)
+        alb = self._rows(y0, y1, np.float32, 3)[1]
         self._rt(self.rt.rt_download_aovs(self.ctx, y0, y1, _p(hits), _p(alb)))
         return dict(t=hits["t"].copy(), obj=hits["obj_idx"].copy(), mat=hits["material"].copy(), normal=hits["normal"].copy(), albedo=alb)
 
@@ -588,14 +590,12 @@ class HostRenderer:
         self._rt(self.rt.rt_denoise_variance(self.ctx, C.byref(p) if p is not None else None))
 
     def denoised(self, y0=0, y1=None):
-        y1 = self.hgt if y1 is None else y1
-        out = np.zeros((y1 - y0, self.w, 4), dtype=np.float32)
+        y1, out = self._rows(y0, y1, np.float32, 4)
         self._rt(self.rt.rt_download_denoised(self.ctx, y0, y1, _p(out)))
         return out
 
     def resolve_denoised(self, y0=0, y1=None):
-        y1 = self.hgt if y1 is None else y1
-        out = np.zeros((y1 - y0, self.w), dtype=np.uint32)
+        y1, out = self._rows(y0, y1, np.uint32)
         self._rt(self.rt.rt_resolve_denoised(self.ctx, y0, y1, _p(out)))
         return out
 
@@ -605,9 +605,8 @@ class HostRenderer:
 
     def stats(self, y0=0, y1=None):
         """rows [y0, y1) of the per-pixel statistics: (count uint32, sum_y float32, sum_yy float32), shaped (rows, width)"""
-        y1 = self.hgt if y1 is None else y1
-        cnt = np.zeros((y1 - y0, self.w), dtype=np.uint32)
-        sy, syy = np.zeros((y1 - y0, self.w), dtype=np.float32), np.zeros((y1 - y0, self.w), dtype=np.float32)
+        y1, cnt = self._rows(y0, y1, np.uint32)
+        sy, syy = self._rows(y0, y1, np.float32)[1], self._rows(y0, y1, np.float32)[1]
         self._rt(self.rt.rt_download_stats(self.ctx, y0, y1, _p(cnt), _p(sy), _p(syy)))
         return cnt, sy, syy
 
@@ -635,8 +634,7 @@ class HostRenderer:
         self._rt(self.rt.rt_render_active(self.ctx, frame0, nframes, seed_base, max_depth))
 
     def resolve_adaptive(self, y0=0, y1=None):
-        y1 = self.hgt if y1 is None else y1
-        out = np.zeros((y1 - y0, self.w), dtype=np.uint32)
+        y1, out = self._rows(y0, y1, np.uint32)
         self._rt(self.rt.rt_resolve_adaptive(self.ctx, y0, y1, _p(out)))
         return out
 

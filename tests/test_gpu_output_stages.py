@@ -191,6 +191,49 @@ def test_resolve_equals_the_restatement(w, h, host_api):
     r.close()
 
 
+# ---- the row range [y0, y1) of every entry point that takes one ----
+def test_every_row_range_is_checked_alike(scenes, host_api):
+    """the seven entry points that take rows [y0, y1) share one range check: a range outside the frame, an empty or a reversed one, and a
+    null output where one is required, is RT_E_ARG and writes nothing; the last row alone is served by each"""
+    w, h = 33, 9
+    r, _ = make(scenes, host_api, "mixed_small", w, h)
+    r.stats_enable(True)
+    r.render(host_api.RT_MODE_PATH, 0, 2)
+    r.render_aovs(0.001)
+    r.denoise(2)
+    L = host_api.rt_lib()
+
+    def buf(dtype, *tail):  # a row more than the frame, so that rows [0, h + 1) would fit
+        a = np.zeros((h + 1, w) + tail, dtype)
+        a.view(np.uint8)[...] = 0xA5
+        return a
+
+    # (name, the call on (y0, y1, outputs), the output arrays, whether a null output is an error)
+    entries = [
+        ("rt_download_accumulator", lambda y0, y1, o: L.rt_download_accumulator(r.ctx, y0, y1, *o), [buf(np.float32, 4)], True),
+        ("rt_resolve", lambda y0, y1, o: L.rt_resolve(r.ctx, 2, y0, y1, *o), [buf(np.uint32)], True),
+        ("rt_download_aovs", lambda y0, y1, o: L.rt_download_aovs(r.ctx, y0, y1, *o), [buf(host_api.RT_HIT_DTYPE), buf(np.float32, 3)], False),
+        ("rt_download_denoised", lambda y0, y1, o: L.rt_download_denoised(r.ctx, y0, y1, *o), [buf(np.float32, 4)], True),
+        ("rt_resolve_denoised", lambda y0, y1, o: L.rt_resolve_denoised(r.ctx, y0, y1, *o), [buf(np.uint32)], True),
+        ("rt_download_stats", lambda y0, y1, o: L.rt_download_stats(r.ctx, y0, y1, *o), [buf(np.uint32), buf(np.float32), buf(np.float32)], False),
+        ("rt_resolve_adaptive", lambda y0, y1, o: L.rt_resolve_adaptive(r.ctx, y0, y1, *o), [buf(np.uint32)], True),
+    ]
+    for name, call, outs, null_is_error in entries:
+        ptrs = [host_api._p(a) for a in outs]
+        for y0, y1 in [(-1, 1), (0, h + 1), (2, 2), (3, 2)]:
+            assert call(y0, y1, ptrs) == host_api.RT_E_ARG, "%s rows [%d, %d)" % (name, y0, y1)
+        if null_is_error:
+            assert call(0, h, [None] * len(outs)) == host_api.RT_E_ARG, name + ": null output"
+        r.synchronize()
+        assert all(np.all(a.view(np.uint8) == 0xA5) for a in outs), name + ": a refused call wrote"
+        assert call(h - 1, h, ptrs) == 0, name + ": the last row"  # RT_OK
+        for a in outs:  # one row arrived, at the start of the output, and nothing after it
+            row = a.view(np.uint8).reshape(h + 1, -1)
+            assert np.any(row[0] != 0xA5) and np.all(row[1:] == 0xA5), name + ": the last row's output"
+    assert np.array_equal(bits(entries[0][2][0][0]), bits(r.accumulator(h - 1, h)[0]))
+    r.close()
+
+
 # ---- k_denoise_atrous on crafted colours ----
 DENOISE_SHAPES = [(1, 1), (1, 37), (37, 1), (31, 7), (33, 9), (65, 17), (97, 41), (130, 67)]
 DENOISE_SCENES = ["mixed_small", "background_scene", "tlas_test2"]
