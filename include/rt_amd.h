@@ -340,6 +340,55 @@ typedef struct { int32_t iterations; float sigma_luminance, sigma_normal, sigma_
 #define RT_DENOISE_VAR_DEFAULTS { 5, 4.0f, 0.25f, 0.1f, 0.1f, 1e-4f }
 int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_var_params* params);
 
+/* ---- reprojection: carrying samples and statistics across a camera move ----------------------------------------
+ * A camera move need not throw every sample away: the radiance a diffuse surface point sends does not depend on the view, so the pixel
+ * that sees the point after the move may keep the samples of the pixel that saw it before.  Pinhole cameras only; nearest history pixel,
+ * no interpolation; statistics (rt_stats_enable) required.  (This library's own addition.)  The caller's sequence:
+ *   rt_render_aovs (old camera) - rt_history_capture - rt_set_camera - rt_render_aovs - rt_reproject - rt_select_active / rt_render_active
+ * rt_download_aov_positions: rows [y0, y1) of the G-buffer's world positions, 3 floats per pixel: O + D * t as k_primary_aovs stored it
+ *   (a restatement of rt_reproject must start from these bits, not from a product recomputed on the host).  Errors as rt_download_aovs.
+ * rt_history_capture: copies the bound accumulator, the three statistics arrays, the three G-buffer arrays and the current camera record
+ *   into history buffers of the context (allocated on first use, freed by rt_destroy): device to device on the context's stream, without
+ *   synchronising.  RT_E_STATE: statistics off; the G-buffer missing or stale (rt_render_aovs first).  RT_E_UNSUPPORTED: the current
+ *   camera is a fisheye.  A history stays valid until rt_upload_scene, rt_set_time or rt_stats_enable(ctx, 0); rt_clear and rt_set_camera
+ *   do not touch it.
+ * rt_reproject: rewrites the accumulator and the statistics of EVERY pixel: carried from the history, or zeroed (a zero float4, count 0,
+ *   sums 0).  On the context's stream; *n_carried_out (may be NULL) receives the number of carried pixels, and reading those 4 bytes back
+ *   is the only synchronisation of the call.  The history is not modified (a second call gives the same result), the active-pixel list
+ *   and the G-buffer are not touched.  All arithmetic f32 with IEEE division, no contraction (tests/reproject_ref.py restates it):
+ *     dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z
+ *     cross(a, b) = (a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x)
+ *     dist2(a, b) = dot(a - b, a - b)
+ *   Primed values are the history's; W, H the frame's size.  For the current pixel p, (n_p, t_p) the G-buffer's normal and distance,
+ *   x_p its position, obj_p its object (-1: a miss), mat_p its material index:
+ *     eligible = obj_p != -1 && (carry_view_dependent
+ *                || (0 <= mat_p < n_materials && material[mat_p].type == RT_MAT_DIFFUSE && material[mat_p].shinieness == 0))
+ *     A = TR' - TL';  B = BL' - TL';  N = cross(A, B);  E = TL' - cam';  d = x_p - cam'
+ *     lam = dot(E, N) / dot(d, N)                        needs isfinite(lam) && lam > 0 (the point lies in front of the history camera)
+ *     Q = lam * d - E  (per component)                   the point's image on the history's screen plane, from its top left corner
+ *     nn = dot(N, N);  u = dot(cross(Q, B), N) / nn;  v = dot(cross(A, Q), N) / nn
+ *     rx = floorf(u * (float)W + 0.5f);  ry = floorf(v * (float)H + 0.5f)     needs 0 <= rx < W, 0 <= ry < H, compared as floats (NaN fails)
+ *     q = (int)ry * W + (int)rx                          (pixel x's ray passes through u = x / W: the nearest pixel, not a truncation)
+ *     carried = eligible && the above
+ *            && count'_q > 0 && obj'_q == obj_p && mat'_q == mat_p
+ *            && dist2(n_p, n'_q) <= normal_tolerance * normal_tolerance
+ *            && fabsf(dot(n'_q, x_p - x'_q)) <= plane_tolerance * t_p
+ *   The last test is the distance of x_p from the history pixel's TANGENT PLANE, not from its point: snapping to the nearest pixel moves
+ *   the history point by up to half a pixel's footprint along the surface, which a point distance would reject at small frames.
+ *   A carried pixel takes acc'_q, count'_q, sum_y'_q, sum_yy'_q unchanged, unless max_history > 0 && count'_q > max_history: then
+ *   f = (float)max_history / (float)count'_q multiplies the four accumulator channels and both sums, and the count becomes max_history
+ *   (the mean stays, the old samples weigh less against new ones).
+ *   View dependence: a diffuse material with shinieness == 0 is what Renderer::Sample shades independently of the view; everything else
+ *   (metal, glass, shiny diffuse, a light seen directly) starts empty unless carry_view_dependent is set; a miss is never carried.
+ *   params NULL: RT_REPROJECT_DEFAULTS.  RT_E_ARG (checked before the context): a tolerance that is negative or NaN, max_history < 0.
+ *   RT_E_STATE: statistics off; no valid history; the current G-buffer missing or stale.  RT_E_UNSUPPORTED: the current camera is a
+ *   fisheye.  With rt_set_profiling on, rt_history_capture's copies and k_reproject are each one launch of rt_profile.query. */
+typedef struct { float normal_tolerance, plane_tolerance; int32_t max_history; int32_t carry_view_dependent; } rt_reproject_params;
+#define RT_REPROJECT_DEFAULTS { 0.25f, 0.01f, 0, 0 }   /* a starting point, NOT tuned */
+int rt_history_capture(rt_ctx* ctx);
+int rt_reproject(rt_ctx* ctx, const rt_reproject_params* params, int* n_carried_out);
+int rt_download_aov_positions(rt_ctx* ctx, int y0, int y1, float* xyz_out);
+
 /* ---- Q-learning guided sampling ("next" row N4) ------------------------------------------------------
  * The reference snapshot has no code for it: README.md:36-42 names Dahm & Keller 2017, "Learning Light Transport
  * the Reinforced Way", and lists "initialize sampling positions; pick sampling direction according to the QValue of neighboring

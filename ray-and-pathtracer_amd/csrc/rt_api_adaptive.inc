@@ -6,6 +6,7 @@ int rt_stats_enable(rt_ctx* c, int on)
 	if (!c) return RT_E_ARG;
 	HIPCHK(c, hipSetDevice(c->device));
 	if (!on) {
+		c->hist.gen = 0; // a captured history (rt_history_capture) belongs to the statistics it was taken with
 		if (!c->stats.count) return RT_OK;
 		HIPCHK(c, hipStreamSynchronize(c->stream));
 		free_pool(c->adaptiveAllocs);

@@ -1,0 +1,88 @@
+// Carrying samples across a camera move: rt_history_capture, rt_reproject, rt_download_aov_positions.  Included by rt_api.hip after
+// rt_api_adaptive.inc.  The kernel is k_reproject (rt_reproject.h).
+int rt_download_aov_positions(rt_ctx* c, int y0, int y1, float* xyz_out)
+{
+	if (!xyz_out || !rows_ok(c, y0, y1)) return fail(c, RT_E_ARG, "rt_download_aov_positions: bad argument");
+	if (!c->aovNrm || c->aovGen == 0) return fail(c, RT_E_STATE, "rt_download_aov_positions: no G-buffer (rt_render_aovs)");
+	const size_t n = (size_t)(y1 - y0) * c->width;
+	std::vector<float4> pos(n);
+	const int rc = download_rows(c, y0, y1, { { c->aovPos, pos.data(), sizeof(float4) } });
+	if (rc != RT_OK) return rc;
+	for (size_t i = 0; i < n; i++) xyz_out[3 * i] = pos[i].x, xyz_out[3 * i + 1] = pos[i].y, xyz_out[3 * i + 2] = pos[i].z;
+	return RT_OK;
+}
+
+static bool history_valid(const rt_ctx* c) { return c->hist.acc && c->hist.gen != 0 && c->hist.gen == c->geomGen; }
+
+int rt_history_capture(rt_ctx* c)
+{
+	if (!c) return fail(c, RT_E_ARG, "rt_history_capture: null context");
+	if (!c->stats.count) return fail(c, RT_E_STATE, "rt_history_capture: statistics are off (rt_stats_enable)");
+	if (!aovs_current(c)) return fail(c, RT_E_STATE, "rt_history_capture: the G-buffer is %s (rt_render_aovs)", c->aovNrm ? "stale" : "missing");
+	if (c->camRec.fisheye) return fail(c, RT_E_UNSUPPORTED, "rt_history_capture: the camera is a fisheye (the projection is the pinhole's)");
+	HIPCHK(c, hipSetDevice(c->device));
+	const size_t n = (size_t)c->width * c->height;
+	rt_ctx::History& H = c->hist;
+	if (!H.acc) {
+		rt_ctx::History B{};
+		hipError_t e = dalloc(c->historyAllocs, &B.acc, n);
+		if (e == hipSuccess) e = dalloc(c->historyAllocs, &B.nrm, n);
+		if (e == hipSuccess) e = dalloc(c->historyAllocs, &B.pos, n);
+		if (e == hipSuccess) e = dalloc(c->historyAllocs, &B.alb, n);
+		if (e == hipSuccess) e = dalloc(c->historyAllocs, &B.stats.count, n);
+		if (e == hipSuccess) e = dalloc(c->historyAllocs, &B.stats.sumY, n);
+		if (e == hipSuccess) e = dalloc(c->historyAllocs, &B.stats.sumYY, n);
+		if (e == hipSuccess) e = dalloc(c->historyAllocs, &B.nCarried, (size_t)1);
+		if (e != hipSuccess) { free_pool(c->historyAllocs); return fail(c, RT_E_HIP, "rt_history_capture: %s", hipGetErrorString(e)); }
+		H = B;
+	}
+	H.gen = 0; // not a history until every copy is queued
+	const struct { void* dst; const void* src; size_t elem; } copies[7] = {
+		{ H.acc, c->accum, sizeof(float4) }, { H.nrm, c->aovNrm, sizeof(float4) }, { H.pos, c->aovPos, sizeof(float4) }, { H.alb, c->aovAlb, sizeof(float4) },
+		{ H.stats.count, c->stats.count, sizeof(uint) }, { H.stats.sumY, c->stats.sumY, sizeof(float) }, { H.stats.sumYY, c->stats.sumYY, sizeof(float) } };
+	prof_begin(c, K_QUERY); // (with rt_set_profiling on: the seven copies are timed as one entry of rt_profile.query, k_reproject as another)
+	hipError_t copied = hipSuccess;
+	for (const auto& k : copies)
+		if (copied == hipSuccess) copied = hipMemcpyAsync(k.dst, k.src, n * k.elem, hipMemcpyDeviceToDevice, c->stream);
+	prof_end(c);
+	HIPCHK(c, copied);
+	H.cam = c->camRec;
+	H.gen = c->geomGen;
+	return RT_OK;
+}
+
+int rt_reproject(rt_ctx* c, const rt_reproject_params* params, int* n_carried_out)
+{
+	const rt_reproject_params P = params ? *params : rt_reproject_params RT_REPROJECT_DEFAULTS;
+	if (!(P.normal_tolerance >= 0.0f) || !(P.plane_tolerance >= 0.0f)) return fail(c, RT_E_ARG, "rt_reproject: the tolerances must be >= 0 (neither NaN)");
+	if (P.max_history < 0) return fail(c, RT_E_ARG, "rt_reproject: max_history %d (>= 0)", P.max_history);
+	if (!c) return fail(c, RT_E_ARG, "rt_reproject: null context");
+	if (!c->stats.count) return fail(c, RT_E_STATE, "rt_reproject: statistics are off (rt_stats_enable)");
+	if (!history_valid(c)) return fail(c, RT_E_STATE, "rt_reproject: no valid history (rt_history_capture; the scene, the time or the statistics changed since)");
+	if (!aovs_current(c)) return fail(c, RT_E_STATE, "rt_reproject: the G-buffer is %s (rt_render_aovs)", c->aovNrm ? "stale" : "missing");
+	if (c->camRec.fisheye) return fail(c, RT_E_UNSUPPORTED, "rt_reproject: the camera is a fisheye (the projection is the pinhole's)");
+	HIPCHK(c, hipSetDevice(c->device));
+	const rt_ctx::History& H = c->hist;
+	ReprojectArgs R;
+	R.nrm = c->aovNrm, R.pos = c->aovPos, R.alb = c->aovAlb;
+	R.hNrm = H.nrm, R.hPos = H.pos, R.hAlb = H.alb, R.hAcc = H.acc, R.hSt = H.stats;
+	R.acc = c->accum, R.St = c->stats;
+	R.mats = c->S.mats, R.nMats = c->S.nMats;
+	memcpy(R.cam, H.cam.cam_pos, 12), memcpy(R.TL, H.cam.top_left, 12), memcpy(R.TR, H.cam.top_right, 12), memcpy(R.BL, H.cam.bottom_left, 12);
+	R.width = c->width, R.height = c->height;
+	R.normalTol2 = P.normal_tolerance * P.normal_tolerance, R.planeTol = P.plane_tolerance;
+	R.maxHistory = P.max_history, R.carryViewDependent = P.carry_view_dependent != 0;
+	R.nCarried = H.nCarried;
+	HIPCHK(c, hipMemsetAsync(H.nCarried, 0, sizeof(int), c->stream));
+	prof_begin(c, K_QUERY);
+	hipLaunchKernelGGL(k_reproject, dim3((c->width + RT_DENOISE_TX - 1) / RT_DENOISE_TX, (c->height + RT_DENOISE_TY - 1) / RT_DENOISE_TY), dim3(RT_DENOISE_TX, RT_DENOISE_TY), 0, c->stream, R);
+	prof_end(c);
+	HIPCHK(c, hipGetLastError());
+	if (n_carried_out) {
+		// the only synchronisation of the call (pinned; the round pipelines use words 0..4, rt_select_active word 8)
+		HIPCHK(c, hipMemcpyAsync(c->hostCounts + 9, H.nCarried, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		*n_carried_out = c->hostCounts[9];
+	}
+	return RT_OK;
+}

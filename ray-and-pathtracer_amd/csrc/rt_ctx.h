@@ -11,6 +11,7 @@
 //   rt_api_output.inc   the output stage's shared helpers: row ranges, row downloads, the resolve, the a-trous drivers' common part
 //   rt_api_denoise.inc  rt_render_aovs, rt_denoise, rt_denoise_variance and their downloads
 //   rt_api_adaptive.inc rt_stats_*, rt_select_active, the active-pixel list, rt_render_active, rt_resolve_adaptive
+//   rt_api_reproject.inc rt_history_capture, rt_reproject, rt_download_aov_positions
 #pragma once
 #include "rt_kernels.h"
 #include "rt_stream.h"
@@ -19,6 +20,7 @@
 #include "rt_denoise.h"
 #include "rt_adaptive.h"
 #include "rt_denoise_var.h"
+#include "rt_reproject.h"
 #include "../../include/rt_amd.h"
 #include <algorithm>
 #include <cstdarg>
@@ -242,6 +244,19 @@ struct rt_ctx {
 	std::vector<void*> activeAllocs;   // the list, the block totals of its compaction, its length on the device
 	uint* activeList = nullptr; uint* selectTotals = nullptr; int* activeCount = nullptr;
 	int nActive = -1;
+	// reprojection (rt_api_reproject.inc): copies of the accumulator, the statistics, the G-buffer and the camera record taken by
+	// rt_history_capture, which rt_reproject gathers from.  geomGen counts what changes the surfaces (rt_upload_scene, rt_set_time) and,
+	// unlike sceneGen, not the camera: the history is valid while hist.gen == geomGen (0: none; rt_stats_enable(ctx, 0) drops it).
+	struct History {
+		float4* acc; float4* nrm; float4* pos; float4* alb;
+		PixelStats stats;
+		int* nCarried; // rt_reproject's count of carried pixels
+		rt_camera cam;
+		unsigned long long gen;
+	};
+	History hist{};
+	std::vector<void*> historyAllocs;
+	unsigned long long geomGen = 1;
 };
 
 static int fail(rt_ctx* c, int code, const char* fmt, ...)

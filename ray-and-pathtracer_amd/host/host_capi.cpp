@@ -273,6 +273,13 @@ void rth_renderer_set_denoise_variance(void* h, int on, const rt_denoise_var_par
 	r->denoiseVariance = on != 0;
 	if (params) r->denoiseVarParams = *params;
 }
+void rth_renderer_set_reproject(void* h, int on, const rt_reproject_params* params)
+{
+	Renderer* r = ((RthRenderer*)h)->r;
+	r->reproject = on != 0;
+	if (params) r->reprojectParams = *params;
+}
+int rth_renderer_carried_pixels(void* h) { return ((RthRenderer*)h)->r->carriedPixels; }
 int rth_renderer_active_pixels(void* h) { return ((RthRenderer*)h)->r->activePixels; }
 const float* rth_renderer_accumulator(void* h) { return &((RthRenderer*)h)->r->accumulator[0].x; }
 const unsigned* rth_renderer_pixels(void* h) { return ((RthRenderer*)h)->r->screenPixels; }

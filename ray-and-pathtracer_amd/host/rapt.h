@@ -390,6 +390,15 @@ public:
 	// screenPixels; 'accumulator' stays the raw download.  Without 'adaptive', Tick throws.  Off: Tick is unchanged.
 	bool denoiseVariance = false;
 	rt_denoise_var_params denoiseVarParams = RT_DENOISE_VAR_DEFAULTS;
+	// Samples carried across a camera move (needs 'adaptive': rt_reproject rewrites the per-pixel statistics).  An adaptive Tick that finds
+	// the camera changed, straight after another adaptive Tick (a Whitted Tick in between overwrites the accumulator), with statistics already on and
+	// neither the old nor the new camera a fisheye, does not clear: it runs
+	// rt_render_aovs under the camera of the last Tick (a no-op on a current G-buffer), rt_history_capture, SyncCamera, rt_render_aovs, rt_reproject, and goes
+	// straight on to rt_select_active / rt_render_active (a pixel below min_samples is active by definition).  Otherwise the Tick clears
+	// as ever.  Without 'adaptive', Tick throws.  Never set: Tick is unchanged.
+	bool reproject = false;
+	rt_reproject_params reprojectParams = RT_REPROJECT_DEFAULTS;
+	int carriedPixels = 0;            // the pixels the last reprojecting Tick carried
 	float4* accumulator = nullptr; // host copy, refreshed by Tick
 	uint32_t* screenPixels = nullptr; // Surface::pixels analogue (template/precomp.h:134)
 	Scene scene;
@@ -408,6 +417,9 @@ private:
 	void TickAdaptive();              // Tick's path-mode body with 'adaptive' set
 	bool adaptiveOn = false;          // the context's statistics were enabled by TickAdaptive
 	int wholeFrames = 0;              // whole frames rendered since the accumulator was last cleared
+	rt_camera syncedCam{};            // the record of the last SyncCamera
+	bool lastTickAdaptive = false;    // the last Tick was TickAdaptive: the accumulator holds its samples, taken under sampledCam
+	rt_camera sampledCam{};           // ... and of the last adaptive Tick: the camera the accumulator's samples were taken with
 };
 
 } // namespace rapt

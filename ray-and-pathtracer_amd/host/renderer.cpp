@@ -129,6 +129,7 @@ void Renderer::SyncCamera()
 	c.bottom_left[0] = camera.bottomLeft.x, c.bottom_left[1] = camera.bottomLeft.y, c.bottom_left[2] = camera.bottomLeft.z;
 	c.fisheye = camera.fishEye ? 1 : 0, c.view_angle = camera.viewAngle, c.y_angle = camera.yAngle;
 	for (rt_ctx* k : ctxs) check(k, rt_set_camera(k, &c));
+	syncedCam = c;
 }
 
 // renderer.cpp:240-305 without the animation, input and printf parts.  As in the reference, 'it' is read before a
@@ -144,11 +145,13 @@ void Renderer::Tick(float /*deltaTime*/)
 		if (!scene.raytracer) { TickAdaptive(); return; }
 	} else {
 		if (denoiseVariance) throw std::runtime_error("Renderer::Tick: denoiseVariance without adaptive: rt_denoise_variance needs the per-pixel statistics adaptive sampling keeps");
+		if (reproject) throw std::runtime_error("Renderer::Tick: reproject without adaptive: rt_reproject rewrites the per-pixel statistics adaptive sampling keeps");
 		if (adaptiveOn) {
 			check(ctx, rt_stats_enable(ctx, 0));
 			adaptiveOn = false;
 		}
 	}
+	lastTickAdaptive = false;
 	scene.totIterationNumber++;
 	const int it = scene.GetIterationNumber();
 	const bool camChanged = camera.GetChange();
@@ -207,16 +210,29 @@ void Renderer::TickAdaptive()
 	scene.totIterationNumber++;
 	const int it = scene.GetIterationNumber();
 	bool reset = camera.GetChange();
+	// a camera move with 'reproject' set (statistics already on, pinhole before and after): the samples follow their surface points
+	// (only straight after an adaptive Tick: a Whitted Tick in between has overwritten the accumulator under cameras of its own)
+	const bool carry = reset && reproject && adaptiveOn && lastTickAdaptive && !sampledCam.fisheye && !camera.fishEye;
 	if (!adaptiveOn) {
 		check(ctx, rt_stats_enable(ctx, 1));
 		adaptiveOn = true, reset = true; // the counts start now, so the accumulator does too
 	}
-	if (reset) {
+	if (carry) {
+		scene.SetIterationNumber(1);
+		check(ctx, rt_set_camera(ctx, &sampledCam)); // the camera of the samples: already the context's unless a caller synced the new one early
+		check(ctx, rt_render_aovs(ctx, 0.001f));     // a no-op when the G-buffer is current
+		check(ctx, rt_history_capture(ctx));
+		SyncCamera();
+		check(ctx, rt_render_aovs(ctx, 0.001f));
+		check(ctx, rt_reproject(ctx, &reprojectParams, &carriedPixels));
+		wholeFrames = adaptiveParams.min_samples; // straight to the selection: a pixel below min_samples is active by definition
+	} else if (reset) {
 		scene.SetIterationNumber(1);
 		check(ctx, rt_clear(ctx)); // the statistics with the accumulator
 		wholeFrames = 0;
 	}
-	SyncCamera();
+	if (!carry) SyncCamera();
+	sampledCam = syncedCam, lastTickAdaptive = true;
 	if (wholeFrames < adaptiveParams.min_samples) {
 		check(ctx, rt_render(ctx, RT_MODE_PATH, frame, 1, seedBase, 0, height, 4));
 		wholeFrames++, activePixels = width * height;

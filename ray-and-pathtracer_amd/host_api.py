@@ -30,7 +30,8 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_device_pci_bus_id", "rt_set_scene_raytracer",
               "rt_render_aovs", "rt_download_aovs", "rt_denoise", "rt_download_denoised", "rt_resolve_denoised",
               "rt_stats_enable", "rt_download_stats", "rt_select_active", "rt_set_active_pixels", "rt_download_active",
-              "rt_render_active", "rt_resolve_adaptive", "rt_denoise_variance"]
+              "rt_render_active", "rt_resolve_adaptive", "rt_denoise_variance",
+              "rt_history_capture", "rt_reproject", "rt_download_aov_positions"]
 
 RT_E_ARG, RT_E_STATE = -2, -5
 RT_E_UNSUPPORTED = -4
@@ -83,6 +84,22 @@ def adaptive_params(params=None):
         return None
     p = dict(ADAPTIVE_DEFAULTS, **params)
     return RtAdaptiveParams(int(p["min_samples"]), int(p["max_samples"]), p["threshold"], p["floor"])
+
+
+# include/rt_amd.h RT_REPROJECT_DEFAULTS (a starting point, not tuned)
+REPROJECT_DEFAULTS = dict(normal_tolerance=0.25, plane_tolerance=0.01, max_history=0, carry_view_dependent=0)
+
+
+class RtReprojectParams(C.Structure):
+    _fields_ = [("normal_tolerance", C.c_float), ("plane_tolerance", C.c_float), ("max_history", C.c_int32), ("carry_view_dependent", C.c_int32)]
+
+
+def reproject_params(params=None):
+    """rt_reproject_params from a dict of REPROJECT_DEFAULTS' keys (missing keys: the defaults); None -> None (the library's defaults)"""
+    if params is None:
+        return None
+    p = dict(REPROJECT_DEFAULTS, **params)
+    return RtReprojectParams(p["normal_tolerance"], p["plane_tolerance"], int(p["max_history"]), int(p["carry_view_dependent"]))
 
 
 class RtCamera(C.Structure):
@@ -184,6 +201,9 @@ def rt_lib():
         L.rt_render_active.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_int]
         L.rt_resolve_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.rt_denoise_variance.argtypes = [C.c_void_p, C.c_void_p]
+        L.rt_history_capture.argtypes = [C.c_void_p]
+        L.rt_reproject.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_download_aov_positions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         _rt = L
     return _rt
 
@@ -470,6 +490,15 @@ class HostRenderer:
         p = adaptive_params(params)
         self.L.rth_renderer_set_adaptive(self.h, int(bool(on)), C.byref(p) if p is not None else None)
 
+    def set_reproject(self, on, params=None):
+        """rapt::Renderer::reproject / reprojectParams: an adaptive Tick answers a camera move by carrying the samples (params: dict, see reproject_params)"""
+        p = reproject_params(params)
+        self.L.rth_renderer_set_reproject(self.h, int(bool(on)), C.byref(p) if p is not None else None)
+
+    def carried_pixels(self):
+        """rapt::Renderer::carriedPixels: the pixels the last reprojecting Tick carried"""
+        return int(self.L.rth_renderer_carried_pixels(self.h))
+
     def active_pixels(self):
         """rapt::Renderer::activePixels: the pixels the last adaptive Tick sampled"""
         return int(self.L.rth_renderer_active_pixels(self.h))
@@ -637,6 +666,23 @@ class HostRenderer:
         y1, out = self._rows(y0, y1, np.uint32)
         self._rt(self.rt.rt_resolve_adaptive(self.ctx, y0, y1, _p(out)))
         return out
+
+    # ---- reprojection (include/rt_amd.h rt_history_capture .. rt_download_aov_positions) ----
+    def aov_positions(self, y0=0, y1=None):
+        """rows [y0, y1) of the G-buffer's world positions as the device stored them, shaped (rows, width, 3)"""
+        y1, out = self._rows(y0, y1, np.float32, 3)
+        self._rt(self.rt.rt_download_aov_positions(self.ctx, y0, y1, _p(out)))
+        return out
+
+    def history_capture(self):
+        self._rt(self.rt.rt_history_capture(self.ctx))
+
+    def reproject(self, params=None):
+        """rt_reproject (params: dict, see reproject_params; None: the library's defaults): the number of pixels carried"""
+        p = reproject_params(params)
+        n = C.c_int(-1)
+        self._rt(self.rt.rt_reproject(self.ctx, C.byref(p) if p is not None else None, C.byref(n)))
+        return n.value
 
     def set_scene_raytracer(self, flag):
         """rt_set_scene_raytracer: -1 the flag follows the function (Trace: set, Sample: clear), 0 / 1 scene.raytracer as the caller holds it"""
