@@ -305,6 +305,53 @@ int rt_download_active(rt_ctx* ctx, uint32_t* out, int cap, int* n_out);
 int rt_render_active(rt_ctx* ctx, uint32_t frame0, int nframes, uint32_t seed_base, int max_depth);
 int rt_resolve_adaptive(rt_ctx* ctx, int y0, int y1, uint32_t* rgb8_out);
 
+/* ---- budgeted adaptive passes: per-pixel sample counts in one batch -------------------------------------------
+ * rt_render_active gives every listed pixel the same number of frames; these calls give each active pixel ITS OWN number of samples,
+ * predicted from its variance, and run them all as one batch -- the fixed costs of a pass are paid once however uneven the need is.
+ * Sample k of a pixel is always frame frame_base + k, so a pixel's value depends only on how many samples it has (see rt_render_budget).
+ * rt_select_budget: builds the active-pixel list exactly as rt_select_active(ctx, &params->select, ...) would (same storage, same
+ *   ascending order: rt_download_active and rt_render_active serve it afterwards) and the PLAN: a budget b per list entry.  All arithmetic
+ *   f32 with IEEE division and no contraction, ternaries as written (a NaN falls to the last branch); n, m, v, d are rt_select_active's
+ *   (v after its clamp to >= 0), cap the effective cap of the fit rule below (tests/budget_ref.py restates it and is compared exactly):
+ *     count < min_samples:  b = min_samples - count
+ *     otherwise (the pixel is active because it is noisy):
+ *         g    = threshold * d
+ *         t    = v / (g * g)           the sample count at which sqrtf(v / n) / d == threshold, were v and m to stay
+ *         need = t - n
+ *         b    = need >= (float)cap ? cap : (need >= 1.0f ? (int)ceilf(need) : 1)
+ *     then, both branches:  b = min(b, cap);  b = min(b, max_samples - count)
+ *   b >= 1 on every listed pixel (an active pixel has count < max_samples).  The plan also records each entry's count at selection time
+ *   (the pixel's first frame) and the exclusive prefix sums of the budgets.  *n_samples_out is the sum of the budgets, formed in 64 bits
+ *   on the device.
+ *   The fit rule: the limit is max_pass_samples, or, when that is 0, the capacity of the finished-sample buffer (RT_SAMPLE_GIB GiB / 16 B);
+ *   either way at most 2^31 - 1 (sample ids are ints).  cap = pass_cap >> k for the smallest k >= 0 whose total fits the limit; each
+ *   attempt is one more count pass and one more small read-back (the normal case is one); *cap_used_out reports cap.  If even cap = 1
+ *   does not fit (n_active > limit): RT_E_UNSUPPORTED, *n_active_out is set, no plan is installed, and the list stays installed
+ *   (rt_render_active can still serve it).  The read-backs of n_active and the total are the call's only synchronisation.
+ *   params NULL: RT_BUDGET_DEFAULTS.  RT_E_ARG (checked before the context): everything rt_select_active refuses, pass_cap outside
+ *   1..1024, a null output pointer.  RT_E_STATE: statistics off.
+ * rt_download_budgets: the first min(cap, n) budgets in list order; *n_out = n.  RT_E_STATE without a plan.
+ * rt_render_budget: for list entry i (pixel p, first frame c, budget b) adds frames frame_base + c ... frame_base + c + b - 1 of
+ *   Renderer::Sample to the accumulator and the statistics of p, in frame order, with the seeds rt_render uses for (p, that frame);
+ *   frame numbers wrap as rt_render's do.  Unlisted pixels are not written.  The guarantee: start from rt_clear; run any sequence of
+ *   whole-frame renders that begins at frame_base with every frame numbered consecutively in the order it is added, and of budgeted
+ *   passes with the same frame_base and seed_base; then a pixel with count n holds accumulator and statistics bit-equal to
+ *   rt_render(ctx, RT_MODE_PATH, frame_base, n, seed_base, 0, height, max_depth) at that pixel.  The pass is ONE batch, on whichever
+ *   pipeline serves that many samples, by the rules of every path batch (the primary-hit table included).
+ *   The plan is consumed: a second call without a new selection is RT_E_STATE.  It is also dropped by anything that changes counts or
+ *   the list: rt_render / rt_render_rows / rt_render_active in path mode, rt_clear, rt_stats_enable, rt_reproject, rt_select_active,
+ *   rt_set_active_pixels.  An empty list: RT_OK without a launch.  With the Q-learning sampler on: RT_E_UNSUPPORTED (rt_render_active's
+ *   rule).  Statistics off: RT_E_STATE. */
+typedef struct {
+    rt_adaptive_params select;   /* which pixels: exactly rt_select_active's predicate */
+    int32_t  pass_cap;           /* most samples one pixel may get in one pass, 1..1024 */
+    uint32_t max_pass_samples;   /* most samples of the whole pass; 0: the context's own limit */
+} rt_budget_params;
+#define RT_BUDGET_DEFAULTS { RT_ADAPTIVE_DEFAULTS, 64, 0 }   /* a starting point, NOT tuned */
+int rt_select_budget(rt_ctx* ctx, const rt_budget_params* params, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out);
+int rt_download_budgets(rt_ctx* ctx, uint32_t* out, int cap, int* n_out);
+int rt_render_budget(rt_ctx* ctx, uint32_t frame_base, uint32_t seed_base, int max_depth);
+
 /* ---- variance-guided denoiser for an adaptively sampled frame ------------------------------------------------
  * rt_denoise_variance: rt_denoise's a-trous filter for a frame whose pixels have different sample counts (the spatial half of SVGF,
  *   Schied et al. 2017): every pixel's mean is accumulator / its own count, the colour edge-stopping term is a luminance difference scaled

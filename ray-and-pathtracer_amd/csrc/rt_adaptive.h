@@ -22,18 +22,30 @@ struct AdaptiveArgs {
 	float threshold, floor;
 };
 
-// include/rt_amd.h rt_select_active, line by line
+// include/rt_amd.h rt_select_active, line by line: n, m, v (after its clamp) and d of a pixel with samples, shared with the budget
+// of rt_budget.h, so that the list and the plan cannot come apart
+struct PixelMoments { float n, m, v, d; };
+__device__ __forceinline__ PixelMoments pixel_moments(uint count, float sumY, float sumYY, const AdaptiveArgs& A)
+{
+	PixelMoments M;
+	M.n = (float)count;
+	M.m = sumY / M.n;
+	M.v = (sumYY - sumY * M.m) / (M.n - 1);
+	M.v = M.v > 0 ? M.v : 0;
+	M.d = M.m > A.floor ? M.m : A.floor;
+	return M;
+}
+// a pixel at or above min_samples: is it still noisy?
+__device__ __forceinline__ bool pixel_noisy(uint count, float sumY, float sumYY, const AdaptiveArgs& A, const PixelMoments& M)
+{
+	if (count >= (uint)A.maxSamples || !isfinite(sumY) || !isfinite(sumYY)) return false;
+	const float e = sqrtf(M.v / M.n);
+	return e / M.d > A.threshold;
+}
 __device__ __forceinline__ bool pixel_active(uint count, float sumY, float sumYY, const AdaptiveArgs& A)
 {
 	if (count < (uint)A.minSamples) return true;
-	if (count >= (uint)A.maxSamples || !isfinite(sumY) || !isfinite(sumYY)) return false;
-	const float n = (float)count;
-	const float m = sumY / n;
-	float v = (sumYY - sumY * m) / (n - 1);
-	v = v > 0 ? v : 0;
-	const float e = sqrtf(v / n);
-	const float d = m > A.floor ? m : A.floor;
-	return e / d > A.threshold;
+	return pixel_noisy(count, sumY, sumYY, A, pixel_moments(count, sumY, sumYY, A));
 }
 
 // lanes of this wave below the caller that are set in 'mask'

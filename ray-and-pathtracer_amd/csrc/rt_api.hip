@@ -1,6 +1,6 @@
 // librt_amd.so: implementation of the C ABI in include/rt_amd.h for gfx950.
 // This file: context, camera, accumulator access, counters and timers, build / tuning info; the other units of the library
-// (scene upload, device builders, the render loops, gather, batch queries, the Q-learning sampler, the output stage's helpers, the denoisers, adaptive sampling, reprojection) are the rt_api_*.inc files
+// (scene upload, device builders, the render loops, gather, batch queries, the Q-learning sampler, the output stage's helpers, the denoisers, adaptive sampling, budgeted passes, reprojection) are the rt_api_*.inc files
 // included below -- one translation unit, see rt_ctx.h.
 #include "rt_ctx.h"
 
@@ -118,6 +118,8 @@ void rt_destroy(rt_ctx* c)
 	free_pool(c->denoiseAllocs);
 	free_pool(c->adaptiveAllocs);
 	free_pool(c->activeAllocs);
+	free_pool(c->planAllocs);
+	free_pool(c->recordAllocs);
 	free_pool(c->historyAllocs);
 	if (c->gammaLut) (void)hipFree(c->gammaLut);
 	if (c->flags) (void)hipFree(c->flags);
@@ -188,6 +190,7 @@ int rt_bind_accumulator(rt_ctx* c, void* p)
 #include "rt_api_query.inc"
 #include "rt_api_denoise.inc"
 #include "rt_api_adaptive.inc"
+#include "rt_api_budget.inc"
 #include "rt_api_reproject.inc"
 
 // ---- measurement ------------------------------------------------------------------------------

@@ -61,6 +61,7 @@ int rt_select_active(rt_ctx* c, const rt_adaptive_params* params, int* n_active_
 	A.minSamples = P.min_samples, A.maxSamples = P.max_samples, A.threshold = P.threshold, A.floor = P.floor;
 	const int n = c->width * c->height, blocks = (n + RT_SELECT_BLOCK - 1) / RT_SELECT_BLOCK;
 	c->nActive = -1; // no list until the count has come home
+	drop_plan(c);
 	hipLaunchKernelGGL(k_select_count, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, n, c->selectTotals);
 	hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(RT_SELECT_SCAN_BLOCK), 0, c->stream, c->selectTotals, blocks, c->activeCount);
 	hipLaunchKernelGGL(k_select_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, n, c->selectTotals, c->activeList);
@@ -88,6 +89,7 @@ int rt_set_active_pixels(rt_ctx* c, const uint32_t* pixels, int n)
 	HIPCHK(c, hipSetDevice(c->device));
 	const int rc = ensure_active_list(c);
 	if (rc != RT_OK) return rc;
+	drop_plan(c); // a plan belongs to the list it was made with
 	HIPCHK(c, hipStreamSynchronize(c->stream)); // (a batch over the list it replaces may still be accumulating)
 	if (n > 0) HIPCHK(c, hipMemcpy(c->activeList, pixels, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
 	c->nActive = n;

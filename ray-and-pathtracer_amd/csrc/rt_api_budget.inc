@@ -1,0 +1,131 @@
+// Budgeted adaptive passes: rt_select_budget, rt_download_budgets, rt_render_budget.  Included by rt_api.hip after rt_api_adaptive.inc
+// (the list's storage and ensure_active_list are its).  The kernels are rt_budget.h's; the batch itself runs on whichever round pipeline
+// trace_samples (rt_api_render.inc) picks for that many samples -- a plan only changes which (pixel, frame) a sample id names.
+// The plan is dropped (drop_plan, rt_ctx.h) by whatever moves the counts or the list: a path-mode render_batches, stats_clear,
+// rt_reproject, rt_select_active, rt_set_active_pixels.
+
+// the per-entry arrays (an entry per pixel at most), the block totals of the budgets, the 64-bit total
+static int ensure_plan(rt_ctx* c)
+{
+	if (c->plan.budget) return RT_OK;
+	const size_t n = (size_t)c->width * c->height;
+	BudgetPlan B{};
+	uint* totals = nullptr;
+	unsigned long long* total = nullptr;
+	hipError_t e = dalloc(c->planAllocs, &B.budget, n);
+	if (e == hipSuccess) e = dalloc(c->planAllocs, &B.first, n);
+	if (e == hipSuccess) e = dalloc(c->planAllocs, &B.offset, n);
+	if (e == hipSuccess) e = dalloc(c->planAllocs, &totals, (n + RT_SELECT_BLOCK - 1) / RT_SELECT_BLOCK);
+	if (e == hipSuccess) e = dalloc(c->planAllocs, &total, (size_t)1);
+	if (e != hipSuccess) { free_pool(c->planAllocs); return fail(c, RT_E_HIP, "budget plan: %s", hipGetErrorString(e)); }
+	c->plan = B, c->budgetTotals = totals, c->planTotal = total;
+	return RT_OK;
+}
+// the per-sample records of a pass of 'count' samples (the caller has synchronised the stream: nothing reads the old ones)
+static int ensure_records(rt_ctx* c, size_t count)
+{
+	if (c->recordCap >= count) return RT_OK;
+	free_pool(c->recordAllocs);
+	c->plan.records = nullptr, c->recordCap = 0;
+	const hipError_t e = dalloc(c->recordAllocs, &c->plan.records, count);
+	if (e != hipSuccess) return fail(c, RT_E_HIP, "budget plan: %zu sample records: %s", count, hipGetErrorString(e));
+	c->recordCap = count;
+	return RT_OK;
+}
+
+#define RT_PASS_SAMPLES_MAX 0x7FFFFFFFull // sample ids are ints on the round pipelines
+
+int rt_select_budget(rt_ctx* c, const rt_budget_params* params, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out)
+{
+	const rt_budget_params B = params ? *params : rt_budget_params RT_BUDGET_DEFAULTS;
+	const rt_adaptive_params& P = B.select;
+	if (P.min_samples < 2 || P.max_samples < P.min_samples) return fail(c, RT_E_ARG, "rt_select_budget: min_samples %d (>= 2), max_samples %d (>= min_samples)", P.min_samples, P.max_samples);
+	if (!(P.threshold >= 0.0f) || !(P.floor > 0.0f)) return fail(c, RT_E_ARG, "rt_select_budget: threshold must be >= 0 and floor > 0 (neither NaN)");
+	if (B.pass_cap < 1 || B.pass_cap > 1024) return fail(c, RT_E_ARG, "rt_select_budget: pass_cap %d (1..1024)", B.pass_cap);
+	if (!c || !n_active_out || !n_samples_out || !cap_used_out) return fail(c, RT_E_ARG, "rt_select_budget: null argument");
+	if (!c->stats.count) return fail(c, RT_E_STATE, "rt_select_budget: statistics are off (rt_stats_enable)");
+	HIPCHK(c, hipSetDevice(c->device));
+	int rc = ensure_active_list(c);
+	if (rc == RT_OK) rc = ensure_plan(c);
+	if (rc != RT_OK) return rc;
+	AdaptiveArgs A;
+	A.minSamples = P.min_samples, A.maxSamples = P.max_samples, A.threshold = P.threshold, A.floor = P.floor;
+	const int n = c->width * c->height, blocks = (n + RT_SELECT_BLOCK - 1) / RT_SELECT_BLOCK;
+	unsigned long long limit = B.max_pass_samples ? (unsigned long long)B.max_pass_samples : ((unsigned long long)c->knobs.sampleGiB << 30) / sizeof(float4);
+	if (limit > RT_PASS_SAMPLES_MAX) limit = RT_PASS_SAMPLES_MAX;
+	c->nActive = -1; // no list until the count has come home
+	drop_plan(c);
+	// the fit rule: the largest cap = pass_cap >> k whose total fits; the list does not depend on the cap
+	int cap = B.pass_cap, got = 0;
+	unsigned long long total = 0;
+	for (;; cap >>= 1) {
+		hipLaunchKernelGGL(k_budget_count, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, cap, n, c->selectTotals, c->budgetTotals);
+		hipLaunchKernelGGL(k_budget_scan, dim3(1), dim3(RT_SELECT_SCAN_BLOCK), 0, c->stream, c->selectTotals, c->budgetTotals, blocks, c->activeCount, c->planTotal);
+		HIPCHK(c, hipGetLastError());
+		// the call's only synchronisation, once per cap tried (pinned; words 8 and 10..11: the round pipelines use 0..4, rt_reproject 9)
+		HIPCHK(c, hipMemcpyAsync(c->hostCounts + 8, c->activeCount, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(c, hipMemcpyAsync(c->hostCounts + 10, c->planTotal, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		got = c->hostCounts[8];
+		memcpy(&total, c->hostCounts + 10, sizeof(total));
+		if (got < 0 || got > n || total < (unsigned long long)got || total > (unsigned long long)got * (unsigned)cap)
+			return fail(c, RT_E_STATE, "rt_select_budget: %d pixels of %d selected, %llu samples at cap %d", got, n, total, cap);
+		if (total <= limit || cap == 1) break;
+	}
+	*n_active_out = got;
+	if (total > limit) {
+		// not even one sample per active pixel fits: the list alone, for rt_render_active (selectTotals holds the pixels' prefix sums)
+		hipLaunchKernelGGL(k_select_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, n, c->selectTotals, c->activeList);
+		HIPCHK(c, hipGetLastError());
+		c->nActive = got;
+		return fail(c, RT_E_UNSUPPORTED, "rt_select_budget: %d active pixels do not fit a pass of %llu samples", got, limit);
+	}
+	if (got > 0) {
+		rc = ensure_records(c, (size_t)total);
+		if (rc != RT_OK) return rc;
+		hipLaunchKernelGGL(k_budget_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, cap, n, c->selectTotals, c->budgetTotals, c->activeList, c->plan);
+		HIPCHK(c, hipGetLastError());
+	}
+	c->nActive = got, c->planSamples = (long long)total;
+	*n_samples_out = (uint32_t)total, *cap_used_out = cap;
+	return RT_OK;
+}
+
+int rt_download_budgets(rt_ctx* c, uint32_t* out, int cap, int* n_out)
+{
+	if (!c || cap < 0 || (cap > 0 && !out) || !n_out) return fail(c, RT_E_ARG, "rt_download_budgets: bad argument");
+	if (c->planSamples < 0 || c->nActive < 0) return fail(c, RT_E_STATE, "rt_download_budgets: no budget plan (rt_select_budget)");
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	const int n = std::min(cap, c->nActive);
+	if (n > 0) HIPCHK(c, hipMemcpy(out, c->plan.budget, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	*n_out = c->nActive;
+	return RT_OK;
+}
+
+int rt_render_budget(rt_ctx* c, uint32_t frame_base, uint32_t seed_base, int max_depth)
+{
+	if (!c) return RT_E_ARG;
+	if (!c->sceneLoaded) return fail(c, RT_E_STATE, "rt_render_budget: no scene uploaded");
+	if (!c->stats.count) return fail(c, RT_E_STATE, "rt_render_budget: statistics are off (rt_stats_enable)");
+	if (c->Qt.on) return fail(c, RT_E_UNSUPPORTED, "rt_render_budget: not with the Q-learning sampler on"); // rt_render_active's rule
+	if (c->planSamples < 0 || c->nActive < 0) return fail(c, RT_E_STATE, "rt_render_budget: no budget plan (rt_select_budget; a plan serves one pass, and a render, a clear, a reprojection or a new list drops it)");
+	const size_t total = (size_t)c->planSamples;
+	drop_plan(c); // consumed: the counts move
+	if (total == 0) return RT_OK;
+	HIPCHK(c, hipSetDevice(c->device));
+	int rc = ensure_samples(c, total);
+	if (rc != RT_OK) return rc;
+	RenderParams R;
+	memset(&R, 0, sizeof(R));
+	R.mode = RT_MODE_PATH, R.frame0 = frame_base, R.nSamples = (uint)total, R.tilePixels = (uint)total, R.samples = c->samples;
+	R.seedBase = seed_base, R.rowFirst = 0, R.rowStride = 1, R.maxDepth = max_depth, R.accum = c->accum;
+	R.plan = c->plan.records; // sample sid is (pixel, frame_base + first + k) of its entry; the pool is entry-major
+	R.deferGamma = c->knobs.deferGamma;
+	R.sceneRt = -1;
+	rc = trace_samples(c, R, 4); // Sample starts at depth 4 (renderer.cpp:278)
+	if (rc != RT_OK) return rc;
+	hipLaunchKernelGGL(k_accumulate_budget, dim3((unsigned)((c->nActive + 255) / 256)), dim3(256), 0, c->stream, R, c->activeList, c->plan, c->nActive, c->stats);
+	HIPCHK(c, hipGetLastError());
+	return RT_OK;
+}

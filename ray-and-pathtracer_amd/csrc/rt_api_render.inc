@@ -549,6 +549,7 @@ static int trace_samples(rt_ctx* c, RenderParams& R, int depth)
 // the statistics' share of rt_clear (rt_api_adaptive.inc holds the rest of them)
 static int stats_clear(rt_ctx* c)
 {
+	drop_plan(c); // the counts a budget plan was made from are gone
 	if (!c->stats.count) return RT_OK;
 	const size_t n = (size_t)c->width * c->height;
 	HIPCHK(c, hipMemsetAsync(c->stats.count, 0, n * sizeof(uint), c->stream));
@@ -562,6 +563,7 @@ static int stats_clear(rt_ctx* c)
 // buffer (<= 4 GiB), which k_accumulate adds to the accumulator (and, with rt_stats_enable, to the pixels' statistics) in frame order.
 static int render_batches(rt_ctx* c, int mode, uint32_t frame0, int nframes, uint32_t seed_base, int row_first, int row_stride, size_t tilePixels, const uint* pixelList, int max_depth)
 {
+	if (mode == RT_MODE_PATH) drop_plan(c); // the batch moves the counts a budget plan was made from
 	const size_t sampleGiB = (size_t)c->knobs.sampleGiB;
 	int batchFrames = (int)((sampleGiB << 30) / (tilePixels * sizeof(float4)));
 	if (batchFrames < 1) batchFrames = 1;

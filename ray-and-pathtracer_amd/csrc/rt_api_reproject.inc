@@ -62,6 +62,7 @@ int rt_reproject(rt_ctx* c, const rt_reproject_params* params, int* n_carried_ou
 	if (!aovs_current(c)) return fail(c, RT_E_STATE, "rt_reproject: the G-buffer is %s (rt_render_aovs)", c->aovNrm ? "stale" : "missing");
 	if (c->camRec.fisheye) return fail(c, RT_E_UNSUPPORTED, "rt_reproject: the camera is a fisheye (the projection is the pinhole's)");
 	HIPCHK(c, hipSetDevice(c->device));
+	drop_plan(c); // every pixel's count is rewritten
 	const rt_ctx::History& H = c->hist;
 	ReprojectArgs R;
 	R.nrm = c->aovNrm, R.pos = c->aovPos, R.alb = c->aovAlb;

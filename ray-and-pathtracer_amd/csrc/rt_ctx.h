@@ -19,6 +19,7 @@
 #include "rt_build.h"
 #include "rt_denoise.h"
 #include "rt_adaptive.h"
+#include "rt_budget.h"
 #include "rt_denoise_var.h"
 #include "rt_reproject.h"
 #include "../../include/rt_amd.h"
@@ -244,6 +245,15 @@ struct rt_ctx {
 	std::vector<void*> activeAllocs;   // the list, the block totals of its compaction, its length on the device
 	uint* activeList = nullptr; uint* selectTotals = nullptr; int* activeCount = nullptr;
 	int nActive = -1;
+	// budgeted passes (rt_api_budget.inc, rt_budget.h): the plan rt_select_budget made for the installed list -- per entry a budget, a first
+	// frame and an offset into the pool, per sample of the pass a (pixel, frame) record.  planSamples < 0: no plan (never made, consumed by
+	// rt_render_budget, or dropped by drop_plan because the counts or the list changed).
+	BudgetPlan plan{};
+	std::vector<void*> planAllocs;   // the per-entry arrays, the block totals of the budgets, the 64-bit total
+	std::vector<void*> recordAllocs; // the per-sample records, grown to the largest pass
+	uint* budgetTotals = nullptr; unsigned long long* planTotal = nullptr;
+	size_t recordCap = 0;
+	long long planSamples = -1;
 	// reprojection (rt_api_reproject.inc): copies of the accumulator, the statistics, the G-buffer and the camera record taken by
 	// rt_history_capture, which rt_reproject gathers from.  geomGen counts what changes the surfaces (rt_upload_scene, rt_set_time) and,
 	// unlike sceneGen, not the camera: the history is valid while hist.gen == geomGen (0: none; rt_stats_enable(ctx, 0) drops it).
@@ -258,6 +268,9 @@ struct rt_ctx {
 	std::vector<void*> historyAllocs;
 	unsigned long long geomGen = 1;
 };
+
+// whatever changes a pixel's count or the installed list takes the budget plan made from them along (rt_api_budget.inc)
+static void drop_plan(rt_ctx* c) { c->planSamples = -1; }
 
 static int fail(rt_ctx* c, int code, const char* fmt, ...)
 {

@@ -75,6 +75,7 @@ struct RenderParams {
 	                   // function called implies (Trace with the flag clear, Sample with it set: renderer.cpp:33-43, 107-121, 143-153) -- the
 	                   // general kernels below; -1: the flag follows the function, as Tick calls it
 	const uint* pixelList; // rt_render_active: tile pixel lp is pixel pixelList[lp] (tilePixels = the list's length); nullptr: the row mapping
+	const uint2* plan;     // rt_render_budget (rt_budget.h): sample sid is { pixel, frame - frame0 } = plan[sid]; nullptr: frame-major over the tile
 };
 
 #define ST_ACTIVE 1      // has a ray for extend + shade
@@ -380,12 +381,26 @@ __device__ __forceinline__ void tile_pixel(const DCamera& C, const RenderParams&
 	}
 	x = (int)(lp % (uint)C.width), y = R.rowFirst + (int)(lp / (uint)C.width) * R.rowStride;
 }
+// The ONE place that knows which (pixel, frame) sample 'sid' of a batch is: frame-major over the tile (sample sid is tile pixel
+// sid % tilePixels of frame frame0 + sid / tilePixels), or, with a budget plan bound (rt_render_budget), whatever the plan's record of
+// the sample says -- one 8-byte load; the frame number wraps like the frame-major one.
+__device__ __forceinline__ void sample_pixel_frame(const DCamera& C, const RenderParams& R, uint sid, int& x, int& y, uint& frame)
+{
+	if (R.plan) {
+		const uint2 r = R.plan[sid];
+		x = (int)(r.x % (uint)C.width), y = (int)(r.x / (uint)C.width), frame = R.frame0 + r.y;
+		return;
+	}
+	const uint lp = sid % R.tilePixels;
+	frame = R.frame0 + sid / R.tilePixels;
+	tile_pixel(C, R, lp, x, y);
+}
 // camera sample 'sid' of the pool (renderer.cpp:263-278): its seed, jitter and primary ray; deterministic in (R, C, sid)
 __device__ __forceinline__ void sample_primary(const DCamera& C, const RenderParams& R, uint sid, f3& O, f3& D, uint& seed)
 {
-	const uint lp = sid % R.tilePixels, frame = R.frame0 + sid / R.tilePixels;
 	int x, y;
-	tile_pixel(C, R, lp, x, y);
+	uint frame;
+	sample_pixel_frame(C, R, sid, x, y, frame);
 	const int pixel = y * C.width + x;
 	seed = StreamSeed(R.seedBase + (uint)pixel + frame * (uint)(C.width * C.height));
 	if (R.mode == 0) primary_ray(C, x, y, O, D);
@@ -401,9 +416,9 @@ __device__ __forceinline__ void sample_primary(const DCamera& C, const RenderPar
 // (height + 2) distinct camera rays serve every sample of every frame (rt_stream.h PrimaryTable).
 __device__ __forceinline__ void sample_primary_pixel(const DCamera& C, const RenderParams& R, uint sid, int& px, int& py, uint& seed)
 {
-	const uint lp = sid % R.tilePixels, frame = R.frame0 + sid / R.tilePixels;
 	int x, y;
-	tile_pixel(C, R, lp, x, y);
+	uint frame;
+	sample_pixel_frame(C, R, sid, x, y, frame);
 	const int pixel = y * C.width + x;
 	seed = StreamSeed(R.seedBase + (uint)pixel + frame * (uint)(C.width * C.height));
 	float newX = x + (RandomFloat(seed) * 2 - 1);
@@ -896,9 +911,9 @@ __global__ void __launch_bounds__(RT_BLOCK) k_sample_general(DScene S, DCamera C
 			D = f3(R.customD[3 * sid], R.customD[3 * sid + 1], R.customD[3 * sid + 2]);
 			seed = StreamSeed(R.seedBase + sid), depth = R.customDepth;
 		} else {
-			const uint lp = sid % R.tilePixels, frame = R.frame0 + sid / R.tilePixels;
 			int x, y;
-			tile_pixel(C, R, lp, x, y);
+			uint frame;
+			sample_pixel_frame(C, R, sid, x, y, frame);
 			seed = StreamSeed(R.seedBase + (uint)(y * C.width + x) + frame * (uint)(C.width * C.height));
 			float newX = x + (RandomFloat(seed) * 2 - 1);
 			float newY = y + (RandomFloat(seed) * 2 - 1);
@@ -1127,6 +1142,17 @@ struct PixelStats {
 	float* sumYY;  // sum of its square
 };
 __device__ __forceinline__ float sample_luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+// one finished sample into a pixel's running accumulator value and luminance sums (k_accumulate, k_accumulate_budget of rt_budget.h)
+template <bool STATS>
+__device__ __forceinline__ void add_sample(float4 s, float4& a, float& sy, float& syy)
+{
+	if (s.w != 0) s = g_exactGamma ? make_float4(x_powf(s.x * 1, RT_GAMMA), x_powf(s.y * 1, RT_GAMMA), x_powf(s.z * 1, RT_GAMMA), 0.0f) : gamma_sample(xyz(s)); // stored raw (R.deferGamma)
+	a.x += s.x, a.y += s.y, a.z += s.z, a.w += 0;
+	if (STATS) {
+		const float l = sample_luminance(s.x, s.y, s.z);
+		sy += l, syy += l * l;
+	}
+}
 template <bool STATS>
 __global__ void k_accumulate(DCamera C, RenderParams R, int batchFrames, PixelStats St)
 {
@@ -1140,13 +1166,7 @@ __global__ void k_accumulate(DCamera C, RenderParams R, int batchFrames, PixelSt
 	float sy = 0, syy = 0;
 	if (STATS) sy = St.sumY[pixel], syy = St.sumYY[pixel];
 	for (int f = 0; f < batchFrames; f++) {
-		float4 s = R.samples[(size_t)f * R.tilePixels + lp];
-		if (s.w != 0) s = g_exactGamma ? make_float4(x_powf(s.x * 1, RT_GAMMA), x_powf(s.y * 1, RT_GAMMA), x_powf(s.z * 1, RT_GAMMA), 0.0f) : gamma_sample(xyz(s)); // stored raw (R.deferGamma)
-		a.x += s.x, a.y += s.y, a.z += s.z, a.w += 0;
-		if (STATS) {
-			const float l = sample_luminance(s.x, s.y, s.z);
-			sy += l, syy += l * l;
-		}
+		add_sample<STATS>(R.samples[(size_t)f * R.tilePixels + lp], a, sy, syy);
 	}
 	R.accum[pixel] = a;
 	if (STATS) St.count[pixel] += (uint)batchFrames, St.sumY[pixel] = sy, St.sumYY[pixel] = syy;

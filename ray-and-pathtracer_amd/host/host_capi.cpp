@@ -279,6 +279,12 @@ void rth_renderer_set_reproject(void* h, int on, const rt_reproject_params* para
 	r->reproject = on != 0;
 	if (params) r->reprojectParams = *params;
 }
+void rth_renderer_set_adaptive_budget(void* h, int passCap, unsigned maxPassSamples)
+{
+	Renderer* r = ((RthRenderer*)h)->r;
+	r->adaptivePassCap = passCap, r->adaptiveMaxPassSamples = maxPassSamples;
+}
+int rth_renderer_pass_samples(void* h) { return ((RthRenderer*)h)->r->passSamples; }
 int rth_renderer_carried_pixels(void* h) { return ((RthRenderer*)h)->r->carriedPixels; }
 int rth_renderer_active_pixels(void* h) { return ((RthRenderer*)h)->r->activePixels; }
 const float* rth_renderer_accumulator(void* h) { return &((RthRenderer*)h)->r->accumulator[0].x; }

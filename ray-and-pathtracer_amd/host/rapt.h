@@ -385,6 +385,18 @@ public:
 	bool adaptive = false;
 	rt_adaptive_params adaptiveParams = RT_ADAPTIVE_DEFAULTS;
 	int activePixels = 0;
+	// Budgeted adaptive Ticks (adaptivePassCap > 0): every adaptive Tick is one rt_select_budget + rt_render_budget -- each active pixel
+	// gets its own number of samples, at most adaptivePassCap of them (and the pass at most adaptiveMaxPassSamples; 0: the context's own
+	// limit), in one batch.  There is no whole-frame phase: after a clear every pixel is below min_samples and gets min(min_samples, cap).
+	// The passes' frame_base is the value of 'frame' at the last clear or the last reprojection carry, so a pixel's sample k is frame
+	// frame_base + k (counted from the carried count after a carry); 'frame' still advances by one per Tick.  passSamples is the number of
+	// samples the last Tick took.  0: TickAdaptive is unchanged.  Set it at a clear (before the first adaptive Tick, or together with a
+	// camera change that clears): "count n = n frames from frame_base" and the independence of a pixel's samples hold only when every
+	// sample since the last clear or carry came from budgeted passes.  Switched on mid-run after frame-by-frame Ticks that followed a carry,
+	// a pixel may already hold frame numbers above frame_base + count, and a pass would draw one of them again.
+	int adaptivePassCap = 0;
+	uint32_t adaptiveMaxPassSamples = 0;
+	int passSamples = 0;
 	// Variance-guided denoised preview of the adaptive frame (needs 'adaptive': the filter reads its statistics; 'denoise' clear): every
 	// adaptive Tick ends with rt_render_aovs (0.001f, a no-op on a current G-buffer), rt_denoise_variance and rt_resolve_denoised into
 	// screenPixels; 'accumulator' stays the raw download.  Without 'adaptive', Tick throws.  Off: Tick is unchanged.
@@ -417,6 +429,7 @@ private:
 	void TickAdaptive();              // Tick's path-mode body with 'adaptive' set
 	bool adaptiveOn = false;          // the context's statistics were enabled by TickAdaptive
 	int wholeFrames = 0;              // whole frames rendered since the accumulator was last cleared
+	uint32_t frameBase = 0;           // 'frame' at the last clear or reprojection carry: rt_render_budget's frame_base
 	rt_camera syncedCam{};            // the record of the last SyncCamera
 	bool lastTickAdaptive = false;    // the last Tick was TickAdaptive: the accumulator holds its samples, taken under sampledCam
 	rt_camera sampledCam{};           // ... and of the last adaptive Tick: the camera the accumulator's samples were taken with

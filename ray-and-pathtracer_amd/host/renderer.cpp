@@ -204,7 +204,8 @@ void Renderer::Tick(float /*deltaTime*/)
 }
 
 // Tick in path mode with 'adaptive' set (one context): the iteration bookkeeping of Tick, whole frames until every pixel has min_samples
-// samples, then one frame of the pixels that are still noisy; every pixel is shown divided by its own count.
+// samples, then one frame of the pixels that are still noisy; every pixel is shown divided by its own count.  With adaptivePassCap > 0
+// every Tick is a budgeted pass instead (rt_select_budget + rt_render_budget).
 void Renderer::TickAdaptive()
 {
 	scene.totIterationNumber++;
@@ -226,19 +227,32 @@ void Renderer::TickAdaptive()
 		check(ctx, rt_render_aovs(ctx, 0.001f));
 		check(ctx, rt_reproject(ctx, &reprojectParams, &carriedPixels));
 		wholeFrames = adaptiveParams.min_samples; // straight to the selection: a pixel below min_samples is active by definition
+		frameBase = frame;
 	} else if (reset) {
 		scene.SetIterationNumber(1);
 		check(ctx, rt_clear(ctx)); // the statistics with the accumulator
 		wholeFrames = 0;
+		frameBase = frame;
 	}
 	if (!carry) SyncCamera();
 	sampledCam = syncedCam, lastTickAdaptive = true;
-	if (wholeFrames < adaptiveParams.min_samples) {
+	if (adaptivePassCap > 0) {
+		// a budgeted pass: every active pixel's own number of samples as one batch (no whole-frame phase: a pixel below min_samples is active)
+		rt_budget_params bp;
+		bp.select = adaptiveParams, bp.pass_cap = adaptivePassCap, bp.max_pass_samples = adaptiveMaxPassSamples;
+		uint32_t taken = 0;
+		int capUsed = 0;
+		check(ctx, rt_select_budget(ctx, &bp, &activePixels, &taken, &capUsed));
+		check(ctx, rt_render_budget(ctx, frameBase, seedBase, 4));
+		passSamples = (int)taken;
+		wholeFrames = adaptiveParams.min_samples; // (switching the cap off mid-run goes on with selections: the counts are uneven)
+	} else if (wholeFrames < adaptiveParams.min_samples) {
 		check(ctx, rt_render(ctx, RT_MODE_PATH, frame, 1, seedBase, 0, height, 4));
-		wholeFrames++, activePixels = width * height;
+		wholeFrames++, activePixels = width * height, passSamples = activePixels;
 	} else {
 		check(ctx, rt_select_active(ctx, &adaptiveParams, &activePixels));
 		check(ctx, rt_render_active(ctx, frame, 1, seedBase, 4));
+		passSamples = activePixels;
 	}
 	frame++;
 	if (denoiseVariance) {

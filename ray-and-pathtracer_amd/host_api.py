@@ -31,6 +31,7 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_render_aovs", "rt_download_aovs", "rt_denoise", "rt_download_denoised", "rt_resolve_denoised",
               "rt_stats_enable", "rt_download_stats", "rt_select_active", "rt_set_active_pixels", "rt_download_active",
               "rt_render_active", "rt_resolve_adaptive", "rt_denoise_variance",
+              "rt_select_budget", "rt_download_budgets", "rt_render_budget",
               "rt_history_capture", "rt_reproject", "rt_download_aov_positions"]
 
 RT_E_ARG, RT_E_STATE = -2, -5
@@ -84,6 +85,22 @@ def adaptive_params(params=None):
         return None
     p = dict(ADAPTIVE_DEFAULTS, **params)
     return RtAdaptiveParams(int(p["min_samples"]), int(p["max_samples"]), p["threshold"], p["floor"])
+
+
+# include/rt_amd.h RT_BUDGET_DEFAULTS (a starting point, not tuned); 'select' is a dict of ADAPTIVE_DEFAULTS' keys
+BUDGET_DEFAULTS = dict(select=None, pass_cap=64, max_pass_samples=0)
+
+
+class RtBudgetParams(C.Structure):
+    _fields_ = [("select", RtAdaptiveParams), ("pass_cap", C.c_int32), ("max_pass_samples", C.c_uint32)]
+
+
+def budget_params(params=None):
+    """rt_budget_params from a dict of BUDGET_DEFAULTS' keys (missing keys: the defaults; 'select': see adaptive_params); None -> None"""
+    if params is None:
+        return None
+    p = dict(BUDGET_DEFAULTS, **params)
+    return RtBudgetParams(adaptive_params(p["select"] or {}), int(p["pass_cap"]), int(p["max_pass_samples"]))
 
 
 # include/rt_amd.h RT_REPROJECT_DEFAULTS (a starting point, not tuned)
@@ -201,6 +218,9 @@ def rt_lib():
         L.rt_render_active.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_int]
         L.rt_resolve_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.rt_denoise_variance.argtypes = [C.c_void_p, C.c_void_p]
+        L.rt_select_budget.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_download_budgets.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.rt_render_budget.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
         L.rt_history_capture.argtypes = [C.c_void_p]
         L.rt_reproject.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_download_aov_positions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -490,6 +510,14 @@ class HostRenderer:
         p = adaptive_params(params)
         self.L.rth_renderer_set_adaptive(self.h, int(bool(on)), C.byref(p) if p is not None else None)
 
+    def set_adaptive_budget(self, pass_cap, max_pass_samples=0):
+        """rapt::Renderer::adaptivePassCap / adaptiveMaxPassSamples: adaptive Ticks are budgeted passes (pass_cap 0: one frame per Tick, as ever)"""
+        self.L.rth_renderer_set_adaptive_budget(self.h, int(pass_cap), C.c_uint32(int(max_pass_samples)))
+
+    def pass_samples(self):
+        """rapt::Renderer::passSamples: the samples the last adaptive Tick took"""
+        return int(self.L.rth_renderer_pass_samples(self.h))
+
     def set_reproject(self, on, params=None):
         """rapt::Renderer::reproject / reprojectParams: an adaptive Tick answers a camera move by carrying the samples (params: dict, see reproject_params)"""
         p = reproject_params(params)
@@ -666,6 +694,25 @@ class HostRenderer:
         y1, out = self._rows(y0, y1, np.uint32)
         self._rt(self.rt.rt_resolve_adaptive(self.ctx, y0, y1, _p(out)))
         return out
+
+    # ---- budgeted adaptive passes (include/rt_amd.h rt_select_budget .. rt_render_budget) ----
+    def select_budget(self, params=None):
+        """rt_select_budget (params: dict, see budget_params; None: the library's defaults): (pixels selected, samples of the pass, cap used)"""
+        p = budget_params(params)
+        n, total, cap = C.c_int(-1), C.c_uint32(0), C.c_int(-1)
+        self._rt(self.rt.rt_select_budget(self.ctx, C.byref(p) if p is not None else None, C.byref(n), C.byref(total), C.byref(cap)))
+        return n.value, total.value, cap.value
+
+    def budgets(self, cap=None):
+        """rt_download_budgets: (the first cap budgets in list order, the list's true length); cap None: the whole frame's worth"""
+        cap = self.w * self.hgt if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint32)
+        n = C.c_int(-1)
+        self._rt(self.rt.rt_download_budgets(self.ctx, _p(out), cap, C.byref(n)))
+        return out[:min(cap, n.value)].copy(), n.value
+
+    def render_budget(self, frame_base=0, seed_base=0x12345678, max_depth=4):
+        self._rt(self.rt.rt_render_budget(self.ctx, frame_base, seed_base, max_depth))
 
     # ---- reprojection (include/rt_amd.h rt_history_capture .. rt_download_aov_positions) ----
     def aov_positions(self, y0=0, y1=None):
