@@ -190,9 +190,25 @@ int rt_bind_accumulator(rt_ctx* ctx, void* device_ptr);
  * and every rt_gather_rows into dst until the next rt_gather_begin waits for that mark only -- not for dst's own rendering of
  * the frame, and not for the pushes of the sources that called earlier: the pushes then run side by side, each over its own
  * xGMI link.  Without it (never called on dst) every gather orders itself behind all that dst's stream held when it was
- * called, which is correct and serialises the pushes behind dst's rendering. */
+ * called, which is correct and serialises the pushes behind dst's rendering.
+ * rt_gather_stats_rows: rt_gather_rows for the accumulator AND the three statistics arrays (count, sum_y, sum_yy: 28 B per pixel) of
+ *   those rows -- what dst needs to run rt_resolve_adaptive, rt_denoise_variance or rt_reproject on a gathered frame.  The same ordering
+ *   (the rt_gather_begin mark, or "behind all dst holds now"), errors on src, RT_OK without work when dst == src.  RT_E_STATE: statistics
+ *   off on either context.  Either direction: a push from the context that holds the frame to the one that renders those rows is how
+ *   rows rewritten there (rt_reproject) get back to their owner.
+ * rt_gather_active: pushes accumulator, count, sum_y and sum_yy of the pixels on src's installed active-pixel list (rt_select_active,
+ *   rt_select_budget, their _rows forms, rt_set_active_pixels), and nothing else, into the same pixels of dst: after a pass over the list
+ *   only they have changed on src.  One kernel on src's stream, a lane per entry, stores through dst's pointers (the same device, or a
+ *   peer: access is enabled on first use); ordering as above.  Every pixel of dst that is not on the list is not written.  The caller's
+ *   part: the listed pixels must not be written by dst's own queued work in the meantime (disjoint row shards give this for free).
+ *   dst's own list and plan are not touched.  src's list outlives rt_render_budget, which consumes only the plan, so the call serves after
+ *   either kind of pass.  An empty list: RT_OK without a launch.  RT_E_STATE: no list on src, statistics off on either context.
+ *   RT_E_ARG: the sizes differ.  RT_E_UNSUPPORTED (never a silent fallback): dst lives on another device that src's device cannot access
+ *   as a peer -- the caller then pushes the rows with rt_gather_stats_rows. */
 int rt_gather_begin(rt_ctx* dst);
 int rt_gather_rows(rt_ctx* dst, rt_ctx* src, int row_first, int row_stride, int row_count);
+int rt_gather_stats_rows(rt_ctx* dst, rt_ctx* src, int row_first, int row_stride, int row_count);
+int rt_gather_active(rt_ctx* dst, rt_ctx* src);
 int rt_device_of(const rt_ctx* ctx);
 /* PCI address ("0000:c1:00.0") of HIP device 'device' into out[cap >= 16]: the ranks of a multi-process run exchange these to
  * prove that no two of them render on the same GPU (bench.py ranks_devices). */
@@ -262,7 +278,9 @@ int rt_download_denoised(rt_ctx* ctx, int y0, int y1, float* out);
 int rt_resolve_denoised(rt_ctx* ctx, int y0, int y1, uint32_t* rgb8_out);
 
 /* ---- adaptive sampling: per-pixel statistics and active-pixel batches --------------------------------------
- * Path mode (RT_MODE_PATH), one context.  Unused, nothing else changes.  (This library's own addition: the reference samples every pixel alike.)
+ * Path mode (RT_MODE_PATH).  A list belongs to one context; several contexts that shard the frame by rows each select over their own
+ * rows (rt_select_active_rows) and push what they sampled to the context that holds the frame (rt_gather_stats_rows, rt_gather_active,
+ * below).  Unused, nothing else changes.  (This library's own addition: the reference samples every pixel alike.)
  * rt_stats_enable(on != 0): allocates and zeroes three per-pixel buffers (12 B per pixel); while they exist every path-mode accumulation
  *   (rt_render, rt_render_rows, rt_render_active) also keeps, per pixel, count (uint32: samples added), sum_y and sum_yy (f32): with
  *   y = (0.2126f * r + 0.7152f * g) + 0.0722f * b of the sample exactly as it is added to the accumulator (after the gamma), f32 in that order
@@ -285,6 +303,13 @@ int rt_resolve_denoised(rt_ctx* ctx, int y0, int y1, uint32_t* rgb8_out);
  *   holds pixel indices y * width + x in strictly ascending order; *n_active_out is its length, and reading those 4 bytes back is the
  *   only synchronisation of the call.  params NULL: RT_ADAPTIVE_DEFAULTS (a starting point, NOT tuned).  RT_E_STATE: statistics off.
  *   RT_E_ARG: min_samples < 2, max_samples < min_samples, a NaN or negative threshold, floor <= 0 or NaN.
+ * rt_select_active_rows: rt_select_active over the pixels of rows row_first + k*row_stride, k < row_count, only (the rows
+ *   rt_render_rows renders with the same three numbers): the same predicate, storage and order, and the list holds exactly the pixels
+ *   of rt_select_active's list that lie in those rows.  No pixel of another row is read: a context that renders one share of the rows has
+ *   count 0 elsewhere, which the whole-frame call would list.  On the device, lane i < row_count * width of the compaction owns pixel
+ *     p = (row_first + (i / width) * row_stride) * width + i % width
+ *   which ascends with i.  RT_E_ARG also for a row set outside the frame, by rt_gather_rows' rule: row_first < 0, row_stride < 1,
+ *   row_count < 1 or row_first + (row_count - 1) * row_stride >= height.  rt_select_active is the case (0, 1, height) of the same code.
  * rt_set_active_pixels: installs a caller's list instead: n indices, strictly ascending, every one < width * height, else RT_E_ARG
  *   (checked before anything is uploaded); n = 0 is allowed.  A list is only indices: it survives rt_clear, rt_set_camera and
  *   rt_upload_scene.
@@ -300,6 +325,7 @@ typedef struct { int32_t min_samples, max_samples; float threshold, floor; } rt_
 int rt_stats_enable(rt_ctx* ctx, int on);
 int rt_download_stats(rt_ctx* ctx, int y0, int y1, uint32_t* count, float* sum_y, float* sum_yy);
 int rt_select_active(rt_ctx* ctx, const rt_adaptive_params* params, int* n_active_out);
+int rt_select_active_rows(rt_ctx* ctx, const rt_adaptive_params* params, int row_first, int row_stride, int row_count, int* n_active_out);
 int rt_set_active_pixels(rt_ctx* ctx, const uint32_t* pixels, int n);
 int rt_download_active(rt_ctx* ctx, uint32_t* out, int cap, int* n_out);
 int rt_render_active(rt_ctx* ctx, uint32_t frame0, int nframes, uint32_t seed_base, int max_depth);
@@ -330,6 +356,11 @@ int rt_resolve_adaptive(rt_ctx* ctx, int y0, int y1, uint32_t* rgb8_out);
  *   (rt_render_active can still serve it).  The read-backs of n_active and the total are the call's only synchronisation.
  *   params NULL: RT_BUDGET_DEFAULTS.  RT_E_ARG (checked before the context): everything rt_select_active refuses, pass_cap outside
  *   1..1024, a null output pointer.  RT_E_STATE: statistics off.
+ * rt_select_budget_rows: rt_select_budget over the pixels of rows row_first + k*row_stride, k < row_count, only, as
+ *   rt_select_active_rows is rt_select_active over them: the same predicate, budgets, storage, order and plan (a record names the frame's
+ *   pixel index, so rt_download_active, rt_download_budgets, rt_render_active and rt_render_budget serve the result unchanged).  The fit
+ *   rule sees the total of THESE rows: a shard's budgets equal the whole-frame call's at its pixels whenever neither call lowered its cap.
+ *   RT_E_ARG also for a row set outside the frame (rt_select_active_rows' rule).  rt_select_budget is the case (0, 1, height).
  * rt_download_budgets: the first min(cap, n) budgets in list order; *n_out = n.  RT_E_STATE without a plan.
  * rt_render_budget: for list entry i (pixel p, first frame c, budget b) adds frames frame_base + c ... frame_base + c + b - 1 of
  *   Renderer::Sample to the accumulator and the statistics of p, in frame order, with the seeds rt_render uses for (p, that frame);
@@ -349,6 +380,7 @@ typedef struct {
 } rt_budget_params;
 #define RT_BUDGET_DEFAULTS { RT_ADAPTIVE_DEFAULTS, 64, 0 }   /* a starting point, NOT tuned */
 int rt_select_budget(rt_ctx* ctx, const rt_budget_params* params, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out);
+int rt_select_budget_rows(rt_ctx* ctx, const rt_budget_params* params, int row_first, int row_stride, int row_count, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out);
 int rt_download_budgets(rt_ctx* ctx, uint32_t* out, int cap, int* n_out);
 int rt_render_budget(rt_ctx* ctx, uint32_t frame_base, uint32_t seed_base, int max_depth);
 
@@ -504,7 +536,9 @@ int rt_set_counting(rt_ctx* ctx, int counting);
 int rt_get_counters(rt_ctx* ctx, rt_counters* out, int reset);
 /* the same tallies kept apart: nearest-hit queries (extend kernel) / occlusion queries (connect) */
 int rt_get_counters_split(rt_ctx* ctx, rt_counters* nearest, rt_counters* occluded, int reset);
-/* profiling != 0: HIP events bracket every kernel launch on the context's stream */
+/* profiling != 0: HIP events bracket every kernel launch on the context's stream (rt_profile.query also takes one entry per
+ * rt_select_active / rt_select_active_rows -- its three launches -- and, on the SOURCE context, one per rt_gather_rows,
+ * rt_gather_stats_rows or rt_gather_active: the push's copies or kernel, behind its wait) */
 int rt_set_profiling(rt_ctx* ctx, int profiling);
 int rt_get_profile(rt_ctx* ctx, rt_profile* out, int reset);
 int rt_synchronize(rt_ctx* ctx);

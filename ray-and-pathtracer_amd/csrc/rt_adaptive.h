@@ -5,10 +5,13 @@
 // no contraction: the library is built with -ffp-contract=off).
 // The compaction is three launches on the context's stream -- a block's count, one block's scan of the block counts, the scatter --
 // so that no block ever waits for another one (the house pattern of compact_body / k_assign: counts first, positions from a scan).
-//   k_select_count    a block of RT_SELECT_BLOCK lanes owns RT_SELECT_BLOCK consecutive pixels: ballot per wave, the block's total
+//   k_select_count    a block of RT_SELECT_BLOCK lanes owns RT_SELECT_BLOCK consecutive pixels of the row set: ballot per wave, the block's total
 //   k_select_scan     ONE block: exclusive scan of the block totals in place, the grand total to *nActive
 //   k_select_scatter  the predicate again (12 B per pixel: cheaper than keeping a flag array), rank inside the wave by mbcnt,
 //                     list[block base + waves before + rank] = pixel
+// The launches walk a ROW SET (RowMap: rows rowFirst + k * rowStride, k < rowCount -- the share of the frame a context renders when the
+// rows are interleaved over several contexts, rt_select_active_rows): lane i owns the i-th pixel of the set in ascending pixel order, so
+// a shard reads only its own rows' statistics and its list ascends.  The whole frame is the set (0, 1, height), where i is the pixel.
 #pragma once
 #include "rt_kernels.h" // PixelStats, resolve_pixel
 
@@ -21,6 +24,18 @@ struct AdaptiveArgs {
 	int minSamples, maxSamples;
 	float threshold, floor;
 };
+
+struct RowMap {
+	int rowFirst, rowStride, width;
+	int nPixels; // rowCount * width
+};
+// lane i < nPixels -> its pixel; strictly ascending in i (rowStride >= 1).  Consecutive rows need no division.
+__device__ __forceinline__ int row_map_pixel(const RowMap& M, int i)
+{
+	if (M.rowStride == 1) return M.rowFirst * M.width + i;
+	const int k = i / M.width;
+	return (M.rowFirst + k * M.rowStride) * M.width + (i - k * M.width);
+}
 
 // include/rt_amd.h rt_select_active, line by line: n, m, v (after its clamp) and d of a pixel with samples, shared with the budget
 // of rt_budget.h, so that the list and the plan cannot come apart
@@ -54,11 +69,12 @@ __device__ __forceinline__ uint lanes_below(unsigned long long mask)
 	return __builtin_amdgcn_mbcnt_hi((uint)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint)mask, 0u));
 }
 
-__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_select_count(PixelStats St, AdaptiveArgs A, int nPixels, uint* blockTotal)
+__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_select_count(PixelStats St, AdaptiveArgs A, RowMap M, uint* blockTotal)
 {
 	__shared__ uint waveTotal[RT_SELECT_BLOCK / 64];
-	const int p = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
-	const bool on = p < nPixels && pixel_active(St.count[p], St.sumY[p], St.sumYY[p], A);
+	const int i = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
+	const int p = i < M.nPixels ? row_map_pixel(M, i) : 0;
+	const bool on = i < M.nPixels && pixel_active(St.count[p], St.sumY[p], St.sumYY[p], A);
 	const unsigned long long mask = __ballot(on);
 	if ((threadIdx.x & 63) == 0) waveTotal[threadIdx.x >> 6] = (uint)__popcll(mask);
 	__syncthreads();
@@ -89,11 +105,12 @@ __global__ void __launch_bounds__(RT_SELECT_SCAN_BLOCK) k_select_scan(uint* bloc
 	if (threadIdx.x == 0) *nActive = (int)total;
 }
 
-__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_select_scatter(PixelStats St, AdaptiveArgs A, int nPixels, const uint* blockBase, uint* list)
+__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_select_scatter(PixelStats St, AdaptiveArgs A, RowMap M, const uint* blockBase, uint* list)
 {
 	__shared__ uint waveTotal[RT_SELECT_BLOCK / 64];
-	const int p = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
-	const bool on = p < nPixels && pixel_active(St.count[p], St.sumY[p], St.sumYY[p], A);
+	const int i = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
+	const int p = i < M.nPixels ? row_map_pixel(M, i) : 0;
+	const bool on = i < M.nPixels && pixel_active(St.count[p], St.sumY[p], St.sumYY[p], A);
 	const unsigned long long mask = __ballot(on);
 	const uint wave = threadIdx.x >> 6;
 	if ((threadIdx.x & 63) == 0) waveTotal[wave] = (uint)__popcll(mask);
@@ -101,7 +118,7 @@ __global__ void __launch_bounds__(RT_SELECT_BLOCK) k_select_scatter(PixelStats S
 	if (!on) return;
 	uint at = blockBase[blockIdx.x] + lanes_below(mask);
 	for (uint w = 0; w < wave; w++) at += waveTotal[w];
-	list[at] = (uint)p; // at < the grand total <= nPixels: the three launches evaluate one predicate on the same statistics
+	list[at] = (uint)p; // at < the grand total <= M.nPixels: the three launches evaluate one predicate on the same statistics
 }
 
 // rt_resolve with the pixel's own sample count as the divisor; a pixel without samples is black

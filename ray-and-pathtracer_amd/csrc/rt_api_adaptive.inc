@@ -1,5 +1,5 @@
-// Adaptive sampling: rt_stats_enable, rt_download_stats, rt_select_active, rt_set_active_pixels, rt_download_active, rt_render_active,
-// rt_resolve_adaptive.  Included by rt_api.hip.  The statistics are kept by k_accumulate<true> (rt_kernels.h; launched by render_batches
+// Adaptive sampling: rt_stats_enable, rt_download_stats, rt_select_active, rt_select_active_rows, rt_set_active_pixels, rt_download_active,
+// rt_render_active, rt_resolve_adaptive.  Included by rt_api.hip.  The statistics are kept by k_accumulate<true> (rt_kernels.h; launched by render_batches
 // of rt_api_render.inc while they are on), the selection and the per-count resolve are the kernels of rt_adaptive.h.
 int rt_stats_enable(rt_ctx* c, int on)
 {
@@ -47,33 +47,56 @@ static int ensure_active_list(rt_ctx* c)
 	return RT_OK;
 }
 
-int rt_select_active(rt_ctx* c, const rt_adaptive_params* params, int* n_active_out)
+// the row set of rt_select_active_rows / rt_select_budget_rows as the kernels take it (row_set_ok: rt_gather_rows' rule for what lies in the frame)
+static bool row_map_of(const rt_ctx* c, int row_first, int row_stride, int row_count, RowMap& M)
+{
+	if (!row_set_ok(c, row_first, row_stride, row_count)) return false;
+	M.rowFirst = row_first, M.rowStride = row_stride, M.width = c->width, M.nPixels = row_count * c->width;
+	return true;
+}
+
+// rt_select_active (what = its name, the rows (0, 1, height)) and rt_select_active_rows
+static int select_active_rows(rt_ctx* c, const char* what, const rt_adaptive_params* params, int row_first, int row_stride, int row_count, int* n_active_out)
 {
 	const rt_adaptive_params P = params ? *params : rt_adaptive_params RT_ADAPTIVE_DEFAULTS;
-	if (P.min_samples < 2 || P.max_samples < P.min_samples) return fail(c, RT_E_ARG, "rt_select_active: min_samples %d (>= 2), max_samples %d (>= min_samples)", P.min_samples, P.max_samples);
-	if (!(P.threshold >= 0.0f) || !(P.floor > 0.0f)) return fail(c, RT_E_ARG, "rt_select_active: threshold must be >= 0 and floor > 0 (neither NaN)");
-	if (!c || !n_active_out) return fail(c, RT_E_ARG, "rt_select_active: null argument");
-	if (!c->stats.count) return fail(c, RT_E_STATE, "rt_select_active: statistics are off (rt_stats_enable)");
+	if (P.min_samples < 2 || P.max_samples < P.min_samples) return fail(c, RT_E_ARG, "%s: min_samples %d (>= 2), max_samples %d (>= min_samples)", what, P.min_samples, P.max_samples);
+	if (!(P.threshold >= 0.0f) || !(P.floor > 0.0f)) return fail(c, RT_E_ARG, "%s: threshold must be >= 0 and floor > 0 (neither NaN)", what);
+	if (!c || !n_active_out) return fail(c, RT_E_ARG, "%s: null argument", what);
+	RowMap M;
+	if (!row_map_of(c, row_first, row_stride, row_count, M)) return fail(c, RT_E_ARG, "%s: rows %d + k*%d (k < %d) outside 0..%d", what, row_first, row_stride, row_count, c->height);
+	if (!c->stats.count) return fail(c, RT_E_STATE, "%s: statistics are off (rt_stats_enable)", what);
 	HIPCHK(c, hipSetDevice(c->device));
 	int rc = ensure_active_list(c);
 	if (rc != RT_OK) return rc;
 	AdaptiveArgs A;
 	A.minSamples = P.min_samples, A.maxSamples = P.max_samples, A.threshold = P.threshold, A.floor = P.floor;
-	const int n = c->width * c->height, blocks = (n + RT_SELECT_BLOCK - 1) / RT_SELECT_BLOCK;
+	const int n = M.nPixels, blocks = (n + RT_SELECT_BLOCK - 1) / RT_SELECT_BLOCK;
 	c->nActive = -1; // no list until the count has come home
 	drop_plan(c);
-	hipLaunchKernelGGL(k_select_count, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, n, c->selectTotals);
+	prof_begin(c, K_QUERY); // (with rt_set_profiling on: the three launches are one entry of rt_profile.query)
+	hipLaunchKernelGGL(k_select_count, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, M, c->selectTotals);
 	hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(RT_SELECT_SCAN_BLOCK), 0, c->stream, c->selectTotals, blocks, c->activeCount);
-	hipLaunchKernelGGL(k_select_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, n, c->selectTotals, c->activeList);
+	hipLaunchKernelGGL(k_select_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, M, c->selectTotals, c->activeList);
+	prof_end(c);
 	HIPCHK(c, hipGetLastError());
 	// the only synchronisation of the call: the selected count (pinned; the round pipelines use words 0..4)
 	HIPCHK(c, hipMemcpyAsync(c->hostCounts + 8, c->activeCount, sizeof(int), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	const int got = c->hostCounts[8];
-	if (got < 0 || got > n) return fail(c, RT_E_STATE, "rt_select_active: %d pixels selected of %d", got, n);
+	if (got < 0 || got > n) return fail(c, RT_E_STATE, "%s: %d pixels selected of %d", what, got, n);
 	c->nActive = got;
 	*n_active_out = got;
 	return RT_OK;
+}
+
+int rt_select_active(rt_ctx* c, const rt_adaptive_params* params, int* n_active_out)
+{
+	return select_active_rows(c, "rt_select_active", params, 0, 1, c ? c->height : 1, n_active_out);
+}
+
+int rt_select_active_rows(rt_ctx* c, const rt_adaptive_params* params, int row_first, int row_stride, int row_count, int* n_active_out)
+{
+	return select_active_rows(c, "rt_select_active_rows", params, row_first, row_stride, row_count, n_active_out);
 }
 
 int rt_set_active_pixels(rt_ctx* c, const uint32_t* pixels, int n)

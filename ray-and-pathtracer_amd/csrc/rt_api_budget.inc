@@ -1,4 +1,4 @@
-// Budgeted adaptive passes: rt_select_budget, rt_download_budgets, rt_render_budget.  Included by rt_api.hip after rt_api_adaptive.inc
+// Budgeted adaptive passes: rt_select_budget, rt_select_budget_rows, rt_download_budgets, rt_render_budget.  Included by rt_api.hip after rt_api_adaptive.inc
 // (the list's storage and ensure_active_list are its).  The kernels are rt_budget.h's; the batch itself runs on whichever round pipeline
 // trace_samples (rt_api_render.inc) picks for that many samples -- a plan only changes which (pixel, frame) a sample id names.
 // The plan is dropped (drop_plan, rt_ctx.h) by whatever moves the counts or the list: a path-mode render_batches, stats_clear,
@@ -35,22 +35,25 @@ static int ensure_records(rt_ctx* c, size_t count)
 
 #define RT_PASS_SAMPLES_MAX 0x7FFFFFFFull // sample ids are ints on the round pipelines
 
-int rt_select_budget(rt_ctx* c, const rt_budget_params* params, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out)
+// rt_select_budget (what = its name, the rows (0, 1, height)) and rt_select_budget_rows
+static int select_budget_rows(rt_ctx* c, const char* what, const rt_budget_params* params, int row_first, int row_stride, int row_count, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out)
 {
 	const rt_budget_params B = params ? *params : rt_budget_params RT_BUDGET_DEFAULTS;
 	const rt_adaptive_params& P = B.select;
-	if (P.min_samples < 2 || P.max_samples < P.min_samples) return fail(c, RT_E_ARG, "rt_select_budget: min_samples %d (>= 2), max_samples %d (>= min_samples)", P.min_samples, P.max_samples);
-	if (!(P.threshold >= 0.0f) || !(P.floor > 0.0f)) return fail(c, RT_E_ARG, "rt_select_budget: threshold must be >= 0 and floor > 0 (neither NaN)");
-	if (B.pass_cap < 1 || B.pass_cap > 1024) return fail(c, RT_E_ARG, "rt_select_budget: pass_cap %d (1..1024)", B.pass_cap);
-	if (!c || !n_active_out || !n_samples_out || !cap_used_out) return fail(c, RT_E_ARG, "rt_select_budget: null argument");
-	if (!c->stats.count) return fail(c, RT_E_STATE, "rt_select_budget: statistics are off (rt_stats_enable)");
+	if (P.min_samples < 2 || P.max_samples < P.min_samples) return fail(c, RT_E_ARG, "%s: min_samples %d (>= 2), max_samples %d (>= min_samples)", what, P.min_samples, P.max_samples);
+	if (!(P.threshold >= 0.0f) || !(P.floor > 0.0f)) return fail(c, RT_E_ARG, "%s: threshold must be >= 0 and floor > 0 (neither NaN)", what);
+	if (B.pass_cap < 1 || B.pass_cap > 1024) return fail(c, RT_E_ARG, "%s: pass_cap %d (1..1024)", what, B.pass_cap);
+	if (!c || !n_active_out || !n_samples_out || !cap_used_out) return fail(c, RT_E_ARG, "%s: null argument", what);
+	RowMap M;
+	if (!row_map_of(c, row_first, row_stride, row_count, M)) return fail(c, RT_E_ARG, "%s: rows %d + k*%d (k < %d) outside 0..%d", what, row_first, row_stride, row_count, c->height);
+	if (!c->stats.count) return fail(c, RT_E_STATE, "%s: statistics are off (rt_stats_enable)", what);
 	HIPCHK(c, hipSetDevice(c->device));
 	int rc = ensure_active_list(c);
 	if (rc == RT_OK) rc = ensure_plan(c);
 	if (rc != RT_OK) return rc;
 	AdaptiveArgs A;
 	A.minSamples = P.min_samples, A.maxSamples = P.max_samples, A.threshold = P.threshold, A.floor = P.floor;
-	const int n = c->width * c->height, blocks = (n + RT_SELECT_BLOCK - 1) / RT_SELECT_BLOCK;
+	const int n = M.nPixels, blocks = (n + RT_SELECT_BLOCK - 1) / RT_SELECT_BLOCK;
 	unsigned long long limit = B.max_pass_samples ? (unsigned long long)B.max_pass_samples : ((unsigned long long)c->knobs.sampleGiB << 30) / sizeof(float4);
 	if (limit > RT_PASS_SAMPLES_MAX) limit = RT_PASS_SAMPLES_MAX;
 	c->nActive = -1; // no list until the count has come home
@@ -59,7 +62,7 @@ int rt_select_budget(rt_ctx* c, const rt_budget_params* params, int* n_active_ou
 	int cap = B.pass_cap, got = 0;
 	unsigned long long total = 0;
 	for (;; cap >>= 1) {
-		hipLaunchKernelGGL(k_budget_count, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, cap, n, c->selectTotals, c->budgetTotals);
+		hipLaunchKernelGGL(k_budget_count, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, cap, M, c->selectTotals, c->budgetTotals);
 		hipLaunchKernelGGL(k_budget_scan, dim3(1), dim3(RT_SELECT_SCAN_BLOCK), 0, c->stream, c->selectTotals, c->budgetTotals, blocks, c->activeCount, c->planTotal);
 		HIPCHK(c, hipGetLastError());
 		// the call's only synchronisation, once per cap tried (pinned; words 8 and 10..11: the round pipelines use 0..4, rt_reproject 9)
@@ -69,26 +72,36 @@ int rt_select_budget(rt_ctx* c, const rt_budget_params* params, int* n_active_ou
 		got = c->hostCounts[8];
 		memcpy(&total, c->hostCounts + 10, sizeof(total));
 		if (got < 0 || got > n || total < (unsigned long long)got || total > (unsigned long long)got * (unsigned)cap)
-			return fail(c, RT_E_STATE, "rt_select_budget: %d pixels of %d selected, %llu samples at cap %d", got, n, total, cap);
+			return fail(c, RT_E_STATE, "%s: %d pixels of %d selected, %llu samples at cap %d", what, got, n, total, cap);
 		if (total <= limit || cap == 1) break;
 	}
 	*n_active_out = got;
 	if (total > limit) {
 		// not even one sample per active pixel fits: the list alone, for rt_render_active (selectTotals holds the pixels' prefix sums)
-		hipLaunchKernelGGL(k_select_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, n, c->selectTotals, c->activeList);
+		hipLaunchKernelGGL(k_select_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, M, c->selectTotals, c->activeList);
 		HIPCHK(c, hipGetLastError());
 		c->nActive = got;
-		return fail(c, RT_E_UNSUPPORTED, "rt_select_budget: %d active pixels do not fit a pass of %llu samples", got, limit);
+		return fail(c, RT_E_UNSUPPORTED, "%s: %d active pixels do not fit a pass of %llu samples", what, got, limit);
 	}
 	if (got > 0) {
 		rc = ensure_records(c, (size_t)total);
 		if (rc != RT_OK) return rc;
-		hipLaunchKernelGGL(k_budget_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, cap, n, c->selectTotals, c->budgetTotals, c->activeList, c->plan);
+		hipLaunchKernelGGL(k_budget_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, cap, M, c->selectTotals, c->budgetTotals, c->activeList, c->plan);
 		HIPCHK(c, hipGetLastError());
 	}
 	c->nActive = got, c->planSamples = (long long)total;
 	*n_samples_out = (uint32_t)total, *cap_used_out = cap;
 	return RT_OK;
+}
+
+int rt_select_budget(rt_ctx* c, const rt_budget_params* params, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out)
+{
+	return select_budget_rows(c, "rt_select_budget", params, 0, 1, c ? c->height : 1, n_active_out, n_samples_out, cap_used_out);
+}
+
+int rt_select_budget_rows(rt_ctx* c, const rt_budget_params* params, int row_first, int row_stride, int row_count, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out)
+{
+	return select_budget_rows(c, "rt_select_budget_rows", params, row_first, row_stride, row_count, n_active_out, n_samples_out, cap_used_out);
 }
 
 int rt_download_budgets(rt_ctx* c, uint32_t* out, int cap, int* n_out)

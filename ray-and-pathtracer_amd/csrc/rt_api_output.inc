@@ -1,6 +1,11 @@
 // The host helpers of the stage between the accumulator and the screen, written once for the four row downloads, the three resolves and
 // the two a-trous drivers (rt_denoise, rt_denoise_variance).  Included by rt_api.hip before the first of them.
 static bool rows_ok(const rt_ctx* c, int y0, int y1) { return c && y0 >= 0 && y1 <= c->height && y0 < y1; } // rows [y0, y1) of c's frame
+// rows row_first + k*row_stride, k < row_count, of c's frame: the one rule of rt_gather_rows, rt_gather_stats_rows and the _rows selections
+static bool row_set_ok(const rt_ctx* c, int row_first, int row_stride, int row_count)
+{
+	return c && row_first >= 0 && row_stride >= 1 && row_count >= 1 && (long long)row_first + (long long)(row_count - 1) * row_stride < c->height;
+}
 
 // rows [y0, y1) of frame-sized device arrays, after everything the stream has queued; a null dst is an output the caller did not ask for
 struct RowCopy { const void* src; void* dst; size_t elem; };

@@ -6,7 +6,8 @@
 // k_accumulate_budget reads a contiguous run.  Sample sid of the pool is the (pixel, frame) pair its 8-byte record names -- the one
 // load sample_pixel_frame (rt_kernels.h) makes for a budgeted batch.
 // The house pattern of rt_adaptive.h, no block waits on another:
-//   k_budget_count    a block of RT_SELECT_BLOCK lanes owns that many consecutive pixels: its active pixels and the sum of their budgets
+//   k_budget_count    a block of RT_SELECT_BLOCK lanes owns that many consecutive pixels of the row set (rt_adaptive.h RowMap): its active
+//                     pixels and the sum of their budgets
 //   k_budget_scan     ONE block: exclusive scans of both block totals in place; the grand totals (pixels: int, budgets: 64 bit)
 //   k_budget_scatter  predicate and budget again; list / budget / first frame / offset per entry, then the wave expands its entries'
 //                     records TOGETHER: lanes stride over the wave's range of the pool and find their entry in the wave's prefix sums
@@ -50,11 +51,12 @@ __device__ __forceinline__ uint wave_inclusive(uint v, uint lane)
 	return v;
 }
 
-__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_budget_count(PixelStats St, AdaptiveArgs A, int cap, int nPixels, uint* blockPixels, uint* blockBudget)
+__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_budget_count(PixelStats St, AdaptiveArgs A, int cap, RowMap M, uint* blockPixels, uint* blockBudget)
 {
 	__shared__ uint wavePixels[RT_SELECT_BLOCK / 64], waveBudget[RT_SELECT_BLOCK / 64];
-	const int p = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
-	const uint b = p < nPixels ? pixel_budget(St.count[p], St.sumY[p], St.sumYY[p], A, cap) : 0u;
+	const int i = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
+	const int p = i < M.nPixels ? row_map_pixel(M, i) : 0;
+	const uint b = i < M.nPixels ? pixel_budget(St.count[p], St.sumY[p], St.sumYY[p], A, cap) : 0u;
 	const uint lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const unsigned long long mask = __ballot(b != 0);
 	const uint incl = wave_inclusive(b, lane);
@@ -106,13 +108,14 @@ __global__ void __launch_bounds__(RT_SELECT_SCAN_BLOCK) k_budget_scan(uint* bloc
 }
 
 // Runs only after the host has seen that the total of the budgets fits the pool (nSamples records).  Entries: at < the total of the
-// pixels <= nPixels; records: below the total of the budgets -- the count and this kernel evaluate one function on the same statistics.
-__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_budget_scatter(PixelStats St, AdaptiveArgs A, int cap, int nPixels, const uint* pixelBase, const uint* budgetBase, uint* list, BudgetPlan B)
+// pixels <= M.nPixels; records: below the total of the budgets -- the count and this kernel evaluate one function on the same statistics.
+__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_budget_scatter(PixelStats St, AdaptiveArgs A, int cap, RowMap M, const uint* pixelBase, const uint* budgetBase, uint* list, BudgetPlan B)
 {
 	__shared__ uint wavePixels[RT_SELECT_BLOCK / 64], waveBudget[RT_SELECT_BLOCK / 64];
-	const int p = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
-	const uint count = p < nPixels ? St.count[p] : 0u;
-	const uint b = p < nPixels ? pixel_budget(count, St.sumY[p], St.sumYY[p], A, cap) : 0u;
+	const int i = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
+	const int p = i < M.nPixels ? row_map_pixel(M, i) : 0; // the mapped pixel: what the list and the records name
+	const uint count = i < M.nPixels ? St.count[p] : 0u;
+	const uint b = i < M.nPixels ? pixel_budget(count, St.sumY[p], St.sumYY[p], A, cap) : 0u;
 	const uint lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const unsigned long long mask = __ballot(b != 0);
 	const uint incl = wave_inclusive(b, lane); // non-decreasing over the lanes: an inactive lane adds 0

@@ -22,6 +22,7 @@
 #include "rt_budget.h"
 #include "rt_denoise_var.h"
 #include "rt_reproject.h"
+#include "rt_gather.h"
 #include "../../include/rt_amd.h"
 #include <algorithm>
 #include <cstdarg>
@@ -203,8 +204,8 @@ struct rt_ctx {
 		void free_state() { free_pool(allocs); cap = 0, levels = 0, samples = 0; }
 	};
 	LevelForm level;
-	// row gathers between contexts (rt_api_gather.inc)
-	hipEvent_t gatherDone = nullptr; // rt_gather_rows with this context as the source: its rows have arrived at the destination
+	// pushes between contexts (rt_api_gather.inc: rt_gather_rows, rt_gather_stats_rows, rt_gather_active)
+	hipEvent_t gatherDone = nullptr; // a push with this context as the source: its rows or pixels have arrived at the destination
 	hipEvent_t gatherReady = nullptr; // ... and, recorded on the destination's stream before the push: what the destination had queued is done
 	hipEvent_t rowsFree = nullptr;    // this context as a DESTINATION: recorded by rt_gather_begin on its stream, once per frame, before its own share is queued
 	// Q-learning guided sampling (rt_qlearn.h)

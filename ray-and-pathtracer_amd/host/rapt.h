@@ -376,12 +376,19 @@ public:
 	// mean with rt_denoise and shows rt_resolve_denoised in screenPixels; 'accumulator' stays the raw download.  Off: Tick is unchanged.
 	bool denoise = false;
 	rt_denoise_params denoiseParams = RT_DENOISE_DEFAULTS;
-	// Adaptive sampling (path mode only, one context): Tick keeps per-pixel statistics (rt_stats_enable), renders whole frames until every
+	// Adaptive sampling (path mode only): Tick keeps per-pixel statistics (rt_stats_enable), renders whole frames until every
 	// pixel has adaptiveParams.min_samples samples, and from then on one frame of the pixels rt_select_active still finds noisy
 	// (rt_render_active); screenPixels is rt_resolve_adaptive (every pixel divided by its own count), 'accumulator' stays the raw download,
 	// activePixels is the number of pixels the last Tick sampled.  Switching it on clears the accumulator (the counts start with it); a
-	// camera change clears as ever.  Together with denoise (rt_denoise divides by ONE iteration count), with more than one device
-	// (the list is one context's) or with the Q-learning sampler, Tick throws.  Off: Tick is unchanged.
+	// camera change clears as ever.  Together with denoise (rt_denoise divides by ONE iteration count) or with the Q-learning sampler, Tick
+	// throws.  Off: Tick is unchanged.
+	// With several contexts every context keeps statistics and does all of this for its own interleaved rows: rt_render_rows and
+	// rt_gather_stats_rows in the whole-frame phase, then rt_select_active_rows / rt_select_budget_rows, the pass, and rt_gather_active
+	// (the listed pixels alone; rt_gather_stats_rows where the devices are no peers) into context 0, which holds the gathered frame WITH its
+	// statistics and resolves, denoises and reprojects it; after a reprojection carry rt_gather_stats_rows pushes each context's rows back
+	// to it.  activePixels and passSamples are the sums over the contexts.  The frame, the statistics and both numbers equal the
+	// one-context run's bit for bit, with one proviso: adaptiveMaxPassSamples is each CONTEXT's own limit (the fit rule of
+	// rt_select_budget_rows sees its shard's total), so the equality holds whenever no fit rule lowered a cap, in either run.
 	bool adaptive = false;
 	rt_adaptive_params adaptiveParams = RT_ADAPTIVE_DEFAULTS;
 	int activePixels = 0;

@@ -140,14 +140,13 @@ void Renderer::Tick(float /*deltaTime*/)
 	if (!ctx) Init();
 	if (adaptive) {
 		if (denoise) throw std::runtime_error("Renderer::Tick: adaptive with denoise: rt_denoise divides the whole frame by one iteration count");
-		if (ctxs.size() > 1) throw std::runtime_error("Renderer::Tick: adaptive with more than one device: the active-pixel list belongs to one context");
 		if (qlearning) throw std::runtime_error("Renderer::Tick: adaptive with the Q-learning sampler: the rewards of a pixel subset are not defined");
 		if (!scene.raytracer) { TickAdaptive(); return; }
 	} else {
 		if (denoiseVariance) throw std::runtime_error("Renderer::Tick: denoiseVariance without adaptive: rt_denoise_variance needs the per-pixel statistics adaptive sampling keeps");
 		if (reproject) throw std::runtime_error("Renderer::Tick: reproject without adaptive: rt_reproject rewrites the per-pixel statistics adaptive sampling keeps");
 		if (adaptiveOn) {
-			check(ctx, rt_stats_enable(ctx, 0));
+			for (rt_ctx* k : ctxs) check(k, rt_stats_enable(k, 0));
 			adaptiveOn = false;
 		}
 	}
@@ -203,19 +202,25 @@ void Renderer::Tick(float /*deltaTime*/)
 	camera.SetChange(false);
 }
 
-// Tick in path mode with 'adaptive' set (one context): the iteration bookkeeping of Tick, whole frames until every pixel has min_samples
-// samples, then one frame of the pixels that are still noisy; every pixel is shown divided by its own count.  With adaptivePassCap > 0
-// every Tick is a budgeted pass instead (rt_select_budget + rt_render_budget).
+// Tick in path mode with 'adaptive' set: the iteration bookkeeping of Tick, whole frames until every pixel has min_samples samples, then
+// one frame of the pixels that are still noisy; every pixel is shown divided by its own count.  With adaptivePassCap > 0 every Tick is a
+// budgeted pass instead (rt_select_budget + rt_render_budget).
+// Several contexts: context k renders, selects and samples the rows k, k + n, ... only (rt_render_rows, rt_select_active_rows /
+// rt_select_budget_rows: the predicate is per pixel and a sample a function of (seed, pixel, frame), so the shards' lists are the
+// one-context list cut by rows and the frame is the one-context frame bit for bit) and pushes what it wrote to context 0: whole rows with
+// their statistics after a whole frame (rt_gather_stats_rows), the listed pixels alone after a pass (rt_gather_active).  Context 0 holds
+// the gathered frame and its statistics: the carry, the resolve and the denoiser run there.
 void Renderer::TickAdaptive()
 {
 	scene.totIterationNumber++;
 	const int it = scene.GetIterationNumber();
+	const int n = (int)ctxs.size();
 	bool reset = camera.GetChange();
 	// a camera move with 'reproject' set (statistics already on, pinhole before and after): the samples follow their surface points
 	// (only straight after an adaptive Tick: a Whitted Tick in between has overwritten the accumulator under cameras of its own)
 	const bool carry = reset && reproject && adaptiveOn && lastTickAdaptive && !sampledCam.fisheye && !camera.fishEye;
 	if (!adaptiveOn) {
-		check(ctx, rt_stats_enable(ctx, 1));
+		for (rt_ctx* k : ctxs) check(k, rt_stats_enable(k, 1));
 		adaptiveOn = true, reset = true; // the counts start now, so the accumulator does too
 	}
 	if (carry) {
@@ -226,27 +231,68 @@ void Renderer::TickAdaptive()
 		SyncCamera();
 		check(ctx, rt_render_aovs(ctx, 0.001f));
 		check(ctx, rt_reproject(ctx, &reprojectParams, &carriedPixels));
+		// every pixel of context 0 is rewritten: each context gets its own rows back before it selects over them
+		for (int k = 1; k < n; k++) {
+			const int count = (height - k + n - 1) / n;
+			if (count > 0) check(ctx, rt_gather_stats_rows(ctxs[k], ctx, k, n, count)); // (context 0 is the source: its errors are reported there)
+		}
 		wholeFrames = adaptiveParams.min_samples; // straight to the selection: a pixel below min_samples is active by definition
 		frameBase = frame;
 	} else if (reset) {
 		scene.SetIterationNumber(1);
-		check(ctx, rt_clear(ctx)); // the statistics with the accumulator
+		for (rt_ctx* k : ctxs) check(k, rt_clear(k)); // the statistics with the accumulator
 		wholeFrames = 0;
 		frameBase = frame;
 	}
 	if (!carry) SyncCamera();
 	sampledCam = syncedCam, lastTickAdaptive = true;
-	if (adaptivePassCap > 0) {
+	rt_budget_params bp;
+	bp.select = adaptiveParams, bp.pass_cap = adaptivePassCap, bp.max_pass_samples = adaptiveMaxPassSamples;
+	const bool budgeted = adaptivePassCap > 0, whole = !budgeted && wholeFrames < adaptiveParams.min_samples;
+	if (n > 1) {
+		// context 0's pixels are free from here on: after the clear or the carry above (its pushes to the other contexts included) and the
+		// resolve of the Tick before; the pushes of this Tick wait for this mark alone
+		check(ctx, rt_gather_begin(ctx));
+		std::vector<int> active((size_t)n, 0);
+		std::vector<uint32_t> taken((size_t)n, 0);
+		workers->run([&](int k) {
+			rt_ctx* c = ctxs[(size_t)k];
+			const int count = (height - k + n - 1) / n;
+			if (count <= 0) return;
+			if (whole) {
+				check(c, rt_render_rows(c, RT_MODE_PATH, frame, 1, seedBase, k, n, count, 4));
+				active[(size_t)k] = count * width, taken[(size_t)k] = (uint32_t)(count * width);
+				if (k > 0) check(c, rt_gather_stats_rows(ctx, c, k, n, count));
+				return;
+			}
+			if (budgeted) {
+				int capUsed = 0;
+				check(c, rt_select_budget_rows(c, &bp, k, n, count, &active[(size_t)k], &taken[(size_t)k], &capUsed));
+				check(c, rt_render_budget(c, frameBase, seedBase, 4));
+			} else {
+				check(c, rt_select_active_rows(c, &adaptiveParams, k, n, count, &active[(size_t)k]));
+				check(c, rt_render_active(c, frame, 1, seedBase, 4));
+				taken[(size_t)k] = (uint32_t)active[(size_t)k];
+			}
+			if (k > 0) {
+				int rc = rt_gather_active(ctx, c); // the list outlives the pass
+				if (rc == RT_E_UNSUPPORTED) rc = rt_gather_stats_rows(ctx, c, k, n, count); // no peer access from this context's device: its rows whole
+				check(c, rc);
+			}
+		});
+		activePixels = passSamples = 0;
+		for (int k = 0; k < n; k++) activePixels += active[(size_t)k], passSamples += (int)taken[(size_t)k];
+		if (whole) wholeFrames++;
+		else wholeFrames = adaptiveParams.min_samples;
+	} else if (budgeted) {
 		// a budgeted pass: every active pixel's own number of samples as one batch (no whole-frame phase: a pixel below min_samples is active)
-		rt_budget_params bp;
-		bp.select = adaptiveParams, bp.pass_cap = adaptivePassCap, bp.max_pass_samples = adaptiveMaxPassSamples;
 		uint32_t taken = 0;
 		int capUsed = 0;
 		check(ctx, rt_select_budget(ctx, &bp, &activePixels, &taken, &capUsed));
 		check(ctx, rt_render_budget(ctx, frameBase, seedBase, 4));
 		passSamples = (int)taken;
 		wholeFrames = adaptiveParams.min_samples; // (switching the cap off mid-run goes on with selections: the counts are uneven)
-	} else if (wholeFrames < adaptiveParams.min_samples) {
+	} else if (whole) {
 		check(ctx, rt_render(ctx, RT_MODE_PATH, frame, 1, seedBase, 0, height, 4));
 		wholeFrames++, activePixels = width * height, passSamples = activePixels;
 	} else {

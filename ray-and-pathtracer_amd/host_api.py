@@ -32,7 +32,8 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_stats_enable", "rt_download_stats", "rt_select_active", "rt_set_active_pixels", "rt_download_active",
               "rt_render_active", "rt_resolve_adaptive", "rt_denoise_variance",
               "rt_select_budget", "rt_download_budgets", "rt_render_budget",
-              "rt_history_capture", "rt_reproject", "rt_download_aov_positions"]
+              "rt_history_capture", "rt_reproject", "rt_download_aov_positions",
+              "rt_select_active_rows", "rt_select_budget_rows", "rt_gather_stats_rows", "rt_gather_active"]
 
 RT_E_ARG, RT_E_STATE = -2, -5
 RT_E_UNSUPPORTED = -4
@@ -224,6 +225,10 @@ def rt_lib():
         L.rt_history_capture.argtypes = [C.c_void_p]
         L.rt_reproject.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_download_aov_positions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.rt_select_active_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.rt_select_budget_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_gather_stats_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.rt_gather_active.argtypes = [C.c_void_p, C.c_void_p]
         _rt = L
     return _rt
 
@@ -713,6 +718,38 @@ class HostRenderer:
 
     def render_budget(self, frame_base=0, seed_base=0x12345678, max_depth=4):
         self._rt(self.rt.rt_render_budget(self.ctx, frame_base, seed_base, max_depth))
+
+    # ---- adaptive sampling over several contexts (include/rt_amd.h rt_select_active_rows, rt_select_budget_rows, rt_gather_stats_rows, rt_gather_active)
+    def select_active_rows(self, row_first, row_stride, row_count, params=None):
+        """rt_select_active_rows: select_active over the pixels of rows row_first + k * row_stride, k < row_count, only"""
+        p = adaptive_params(params)
+        n = C.c_int(-1)
+        self._rt(self.rt.rt_select_active_rows(self.ctx, C.byref(p) if p is not None else None, row_first, row_stride, row_count, C.byref(n)))
+        return n.value
+
+    def select_budget_rows(self, row_first, row_stride, row_count, params=None):
+        """rt_select_budget_rows: select_budget over those rows only: (pixels selected, samples of the pass, cap used)"""
+        p = budget_params(params)
+        n, total, cap = C.c_int(-1), C.c_uint32(0), C.c_int(-1)
+        self._rt(self.rt.rt_select_budget_rows(self.ctx, C.byref(p) if p is not None else None, row_first, row_stride, row_count,
+                                               C.byref(n), C.byref(total), C.byref(cap)))
+        return n.value, total.value, cap.value
+
+    def _rt_src(self, src, rc):
+        if rc != 0:  # the gathers report on the source context
+            raise RuntimeError("rt_amd error %d: %s" % (rc, self.rt.rt_last_error(src.ctx).decode()))
+
+    def gather_rows(self, src, row_first, row_stride, row_count):
+        """rt_gather_rows: the accumulator rows row_first + k * row_stride, k < row_count, of HostRenderer 'src' into this renderer's context"""
+        self._rt_src(src, self.rt.rt_gather_rows(self.ctx, src.ctx, row_first, row_stride, row_count))
+
+    def gather_stats_rows(self, src, row_first, row_stride, row_count):
+        """rt_gather_stats_rows: accumulator and statistics of those rows of HostRenderer 'src' into this renderer's context"""
+        self._rt_src(src, self.rt.rt_gather_stats_rows(self.ctx, src.ctx, row_first, row_stride, row_count))
+
+    def gather_active(self, src):
+        """rt_gather_active: accumulator and statistics of the pixels on src's active-pixel list into this renderer's context"""
+        self._rt_src(src, self.rt.rt_gather_active(self.ctx, src.ctx))
 
     # ---- reprojection (include/rt_amd.h rt_history_capture .. rt_download_aov_positions) ----
     def aov_positions(self, y0=0, y1=None):
