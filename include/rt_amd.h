@@ -371,7 +371,7 @@ int rt_resolve_adaptive(rt_ctx* ctx, int y0, int y1, uint32_t* rgb8_out);
  *   pipeline serves that many samples, by the rules of every path batch (the primary-hit table included).
  *   The plan is consumed: a second call without a new selection is RT_E_STATE.  It is also dropped by anything that changes counts or
  *   the list: rt_render / rt_render_rows / rt_render_active in path mode, rt_clear, rt_stats_enable, rt_reproject, rt_select_active,
- *   rt_set_active_pixels.  An empty list: RT_OK without a launch.  With the Q-learning sampler on: RT_E_UNSUPPORTED (rt_render_active's
+ *   rt_select_active_dilated, rt_set_active_pixels.  An empty list: RT_OK without a launch.  With the Q-learning sampler on: RT_E_UNSUPPORTED (rt_render_active's
  *   rule).  Statistics off: RT_E_STATE. */
 typedef struct {
     rt_adaptive_params select;   /* which pixels: exactly rt_select_active's predicate */
@@ -383,6 +383,36 @@ int rt_select_budget(rt_ctx* ctx, const rt_budget_params* params, int* n_active_
 int rt_select_budget_rows(rt_ctx* ctx, const rt_budget_params* params, int row_first, int row_stride, int row_count, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out);
 int rt_download_budgets(rt_ctx* ctx, uint32_t* out, int cap, int* n_out);
 int rt_render_budget(rt_ctx* ctx, uint32_t frame_base, uint32_t seed_base, int max_depth);
+
+/* ---- dilated adaptive selection: also sample the neighbours of noisy pixels -----------------------------------
+ * rt_select_active decides per pixel, from that pixel's own statistics: a pixel that has not yet seen a rare bright path looks
+ * converged, is dropped, and can never come back because its statistics no longer change.  These calls also list the pixels around
+ * an active one, as production renderers grow their active mask by a few pixels.  Whole frame only: a context that holds one row shard
+ * has no statistics for its neighbours' rows, so there are no _rows forms.
+ * rt_select_active_dilated: with raw_q the unchanged predicate of rt_select_active on pixel q (same params), radius r and p = (x, y)
+ *   (tests/dilate_ref.py restates it and is compared exactly):
+ *     win(p)     = { (x + dx, y + dy) : |dx| <= r, |dy| <= r, 0 <= x + dx < width, 0 <= y + dy < height }
+ *     eligible_p = count_p < max_samples && isfinite(sum_y_p) && isfinite(sum_yy_p)
+ *     active_p   = raw_p || (eligible_p && OR over q in win(p) of raw_q)
+ *   The window is clipped to the frame per axis: a source at the end of one row never lights the start of the next.  A pixel that views
+ *   a light (sums +inf) or sits at max_samples is never listed by dilation alone.  r = 0 gives rt_select_active's list entry for entry.
+ *   The list is empty exactly when rt_select_active's is, so a loop that stops on *n_active_out == 0 stops under the same condition as
+ *   before, and after at most max_samples passes (every listed pixel is below max_samples and gains a sample per pass).  Same list
+ *   storage, ascending order and single read-back as rt_select_active: rt_download_active, rt_render_active and rt_gather_active serve
+ *   the result unchanged.  An existing plan is dropped.  On the device the predicate is evaluated once per pixel and kept as a bit;
+ *   the dilation works on bitmasks (width * height / 8 bytes each, allocated with the list) and reads no neighbour's statistics.
+ *   RT_E_ARG (checked before the context): everything rt_select_active refuses, radius outside 0..RT_DILATE_MAX_RADIUS, a null output
+ *   pointer.  RT_E_STATE: statistics off.
+ * rt_select_budget_dilated: rt_select_active_dilated(ctx, &params->select, radius, ...)'s list with rt_select_budget's plan: an entry
+ *   that is raw-active gets exactly rt_select_budget's budget b at the effective cap; an entry listed by dilation alone gets b = 1; either
+ *   way the entry's first frame is its count.  The fit rule (on the total of THESE budgets), RT_E_UNSUPPORTED when even cap = 1 does not
+ *   fit (the list stays installed, no plan), *cap_used_out and the 64-bit total are rt_select_budget's; rt_download_budgets and
+ *   rt_render_budget (with its guarantee: a pixel's value depends only on its count) serve the plan unchanged.
+ *   RT_E_ARG (checked before the context): everything rt_select_budget refuses and a radius outside 0..RT_DILATE_MAX_RADIUS.
+ *   RT_E_STATE: statistics off. */
+#define RT_DILATE_MAX_RADIUS 16
+int rt_select_active_dilated(rt_ctx* ctx, const rt_adaptive_params* params, int radius, int* n_active_out);
+int rt_select_budget_dilated(rt_ctx* ctx, const rt_budget_params* params, int radius, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out);
 
 /* ---- variance-guided denoiser for an adaptively sampled frame ------------------------------------------------
  * rt_denoise_variance: rt_denoise's a-trous filter for a frame whose pixels have different sample counts (the spatial half of SVGF,
@@ -537,7 +567,8 @@ int rt_get_counters(rt_ctx* ctx, rt_counters* out, int reset);
 /* the same tallies kept apart: nearest-hit queries (extend kernel) / occlusion queries (connect) */
 int rt_get_counters_split(rt_ctx* ctx, rt_counters* nearest, rt_counters* occluded, int reset);
 /* profiling != 0: HIP events bracket every kernel launch on the context's stream (rt_profile.query also takes one entry per
- * rt_select_active / rt_select_active_rows -- its three launches -- and, on the SOURCE context, one per rt_gather_rows,
+ * rt_select_active / rt_select_active_rows -- its three launches --, one per rt_select_active_dilated (its five launches) and per
+ * rt_select_budget_dilated (the whole call, its read-backs included) and, on the SOURCE context, one per rt_gather_rows,
  * rt_gather_stats_rows or rt_gather_active: the push's copies or kernel, behind its wait) */
 int rt_set_profiling(rt_ctx* ctx, int profiling);
 int rt_get_profile(rt_ctx* ctx, rt_profile* out, int reset);

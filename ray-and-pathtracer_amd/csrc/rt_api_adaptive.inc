@@ -32,7 +32,8 @@ int rt_download_stats(rt_ctx* c, int y0, int y1, uint32_t* count, float* sum_y, 
 	return download_rows(c, y0, y1, { { c->stats.count, count, sizeof(uint) }, { c->stats.sumY, sum_y, sizeof(float) }, { c->stats.sumYY, sum_yy, sizeof(float) } });
 }
 
-// the list's device storage: width * height indices, a total per block of the selection, the selected count
+// the list's device storage: width * height indices, a total per block of the selection, the selected count, and the four bitmasks of
+// the dilated selection (rt_dilate.h: a bit per pixel each, 259 KB at 1080p)
 static int ensure_active_list(rt_ctx* c)
 {
 	if (c->activeList) return RT_OK;
@@ -42,8 +43,14 @@ static int ensure_active_list(rt_ctx* c)
 	hipError_t e = dalloc(c->activeAllocs, &list, n);
 	if (e == hipSuccess) e = dalloc(c->activeAllocs, &totals, (n + RT_SELECT_BLOCK - 1) / RT_SELECT_BLOCK);
 	if (e == hipSuccess) e = dalloc(c->activeAllocs, &count, (size_t)1);
+	DilateMasks D{};
+	const size_t words = (n + 63) / 64;
+	if (e == hipSuccess) e = dalloc(c->activeAllocs, &D.raw, words);
+	if (e == hipSuccess) e = dalloc(c->activeAllocs, &D.eligible, words);
+	if (e == hipSuccess) e = dalloc(c->activeAllocs, &D.rows, words);
+	if (e == hipSuccess) e = dalloc(c->activeAllocs, &D.listed, words);
 	if (e != hipSuccess) { free_pool(c->activeAllocs); return fail(c, RT_E_HIP, "active-pixel list: %s", hipGetErrorString(e)); }
-	c->activeList = list, c->selectTotals = totals, c->activeCount = count;
+	c->activeList = list, c->selectTotals = totals, c->activeCount = count, c->dilate = D;
 	return RT_OK;
 }
 

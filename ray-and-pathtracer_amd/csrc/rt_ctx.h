@@ -20,6 +20,7 @@
 #include "rt_denoise.h"
 #include "rt_adaptive.h"
 #include "rt_budget.h"
+#include "rt_dilate.h"
 #include "rt_denoise_var.h"
 #include "rt_reproject.h"
 #include "rt_gather.h"
@@ -243,8 +244,9 @@ struct rt_ctx {
 	// survives rt_clear, rt_set_camera and rt_upload_scene.
 	PixelStats stats{};
 	std::vector<void*> adaptiveAllocs; // the statistics
-	std::vector<void*> activeAllocs;   // the list, the block totals of its compaction, its length on the device
+	std::vector<void*> activeAllocs;   // the list, the block totals of its compaction, its length on the device, the dilation's bitmasks
 	uint* activeList = nullptr; uint* selectTotals = nullptr; int* activeCount = nullptr;
+	DilateMasks dilate{};              // rt_select_active_dilated / rt_select_budget_dilated (rt_dilate.h): width * height bits each
 	int nActive = -1;
 	// budgeted passes (rt_api_budget.inc, rt_budget.h): the plan rt_select_budget made for the installed list -- per entry a budget, a first
 	// frame and an offset into the pool, per sample of the pass a (pixel, frame) record.  planSamples < 0: no plan (never made, consumed by

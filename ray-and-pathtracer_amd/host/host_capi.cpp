@@ -284,6 +284,7 @@ void rth_renderer_set_adaptive_budget(void* h, int passCap, unsigned maxPassSamp
 	Renderer* r = ((RthRenderer*)h)->r;
 	r->adaptivePassCap = passCap, r->adaptiveMaxPassSamples = maxPassSamples;
 }
+void rth_renderer_set_adaptive_dilate(void* h, int radius) { ((RthRenderer*)h)->r->adaptiveDilate = radius; }
 int rth_renderer_pass_samples(void* h) { return ((RthRenderer*)h)->r->passSamples; }
 int rth_renderer_carried_pixels(void* h) { return ((RthRenderer*)h)->r->carriedPixels; }
 int rth_renderer_active_pixels(void* h) { return ((RthRenderer*)h)->r->activePixels; }

@@ -404,6 +404,12 @@ public:
 	int adaptivePassCap = 0;
 	uint32_t adaptiveMaxPassSamples = 0;
 	int passSamples = 0;
+	// Dilated selection (adaptiveDilate > 0, at most RT_DILATE_MAX_RADIUS): the adaptive Ticks' selections also list the pixels within that
+	// many pixels of an active one (rt_select_active_dilated; rt_select_budget_dilated when adaptivePassCap > 0), so a pixel that missed a
+	// rare bright path goes on sampling while its neighbours do.  0: TickAdaptive is unchanged.  With adaptivePassCap == 0 a pixel that is
+	// listed again after a pause takes the Tick's frame like every listed pixel: its frames are distinct, not consecutive.  With several
+	// contexts (UseDevices) Tick throws: a context that holds one row shard has no statistics for its neighbours' rows.
+	int adaptiveDilate = 0;
 	// Variance-guided denoised preview of the adaptive frame (needs 'adaptive': the filter reads its statistics; 'denoise' clear): every
 	// adaptive Tick ends with rt_render_aovs (0.001f, a no-op on a current G-buffer), rt_denoise_variance and rt_resolve_denoised into
 	// screenPixels; 'accumulator' stays the raw download.  Without 'adaptive', Tick throws.  Off: Tick is unchanged.

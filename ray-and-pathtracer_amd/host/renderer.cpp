@@ -141,6 +141,7 @@ void Renderer::Tick(float /*deltaTime*/)
 	if (adaptive) {
 		if (denoise) throw std::runtime_error("Renderer::Tick: adaptive with denoise: rt_denoise divides the whole frame by one iteration count");
 		if (qlearning) throw std::runtime_error("Renderer::Tick: adaptive with the Q-learning sampler: the rewards of a pixel subset are not defined");
+		if (adaptiveDilate > 0 && ctxs.size() > 1) throw std::runtime_error("Renderer::Tick: adaptiveDilate with several contexts: a context that holds one row shard has no statistics for its neighbours' rows");
 		if (!scene.raytracer) { TickAdaptive(); return; }
 	} else {
 		if (denoiseVariance) throw std::runtime_error("Renderer::Tick: denoiseVariance without adaptive: rt_denoise_variance needs the per-pixel statistics adaptive sampling keeps");
@@ -204,7 +205,7 @@ void Renderer::Tick(float /*deltaTime*/)
 
 // Tick in path mode with 'adaptive' set: the iteration bookkeeping of Tick, whole frames until every pixel has min_samples samples, then
 // one frame of the pixels that are still noisy; every pixel is shown divided by its own count.  With adaptivePassCap > 0 every Tick is a
-// budgeted pass instead (rt_select_budget + rt_render_budget).
+// budgeted pass instead (rt_select_budget + rt_render_budget).  With adaptiveDilate > 0 (one context only) the selections are the dilated ones.
 // Several contexts: context k renders, selects and samples the rows k, k + n, ... only (rt_render_rows, rt_select_active_rows /
 // rt_select_budget_rows: the predicate is per pixel and a sample a function of (seed, pixel, frame), so the shards' lists are the
 // one-context list cut by rows and the frame is the one-context frame bit for bit) and pushes what it wrote to context 0: whole rows with
@@ -288,7 +289,8 @@ void Renderer::TickAdaptive()
 		// a budgeted pass: every active pixel's own number of samples as one batch (no whole-frame phase: a pixel below min_samples is active)
 		uint32_t taken = 0;
 		int capUsed = 0;
-		check(ctx, rt_select_budget(ctx, &bp, &activePixels, &taken, &capUsed));
+		if (adaptiveDilate > 0) check(ctx, rt_select_budget_dilated(ctx, &bp, adaptiveDilate, &activePixels, &taken, &capUsed));
+		else check(ctx, rt_select_budget(ctx, &bp, &activePixels, &taken, &capUsed));
 		check(ctx, rt_render_budget(ctx, frameBase, seedBase, 4));
 		passSamples = (int)taken;
 		wholeFrames = adaptiveParams.min_samples; // (switching the cap off mid-run goes on with selections: the counts are uneven)
@@ -296,7 +298,8 @@ void Renderer::TickAdaptive()
 		check(ctx, rt_render(ctx, RT_MODE_PATH, frame, 1, seedBase, 0, height, 4));
 		wholeFrames++, activePixels = width * height, passSamples = activePixels;
 	} else {
-		check(ctx, rt_select_active(ctx, &adaptiveParams, &activePixels));
+		if (adaptiveDilate > 0) check(ctx, rt_select_active_dilated(ctx, &adaptiveParams, adaptiveDilate, &activePixels));
+		else check(ctx, rt_select_active(ctx, &adaptiveParams, &activePixels));
 		check(ctx, rt_render_active(ctx, frame, 1, seedBase, 4));
 		passSamples = activePixels;
 	}

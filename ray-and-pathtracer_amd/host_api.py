@@ -33,7 +33,8 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_render_active", "rt_resolve_adaptive", "rt_denoise_variance",
               "rt_select_budget", "rt_download_budgets", "rt_render_budget",
               "rt_history_capture", "rt_reproject", "rt_download_aov_positions",
-              "rt_select_active_rows", "rt_select_budget_rows", "rt_gather_stats_rows", "rt_gather_active"]
+              "rt_select_active_rows", "rt_select_budget_rows", "rt_gather_stats_rows", "rt_gather_active",
+              "rt_select_active_dilated", "rt_select_budget_dilated"]
 
 RT_E_ARG, RT_E_STATE = -2, -5
 RT_E_UNSUPPORTED = -4
@@ -229,6 +230,8 @@ def rt_lib():
         L.rt_select_budget_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_gather_stats_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.rt_gather_active.argtypes = [C.c_void_p, C.c_void_p]
+        L.rt_select_active_dilated.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.rt_select_budget_dilated.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _rt = L
     return _rt
 
@@ -519,6 +522,10 @@ class HostRenderer:
         """rapt::Renderer::adaptivePassCap / adaptiveMaxPassSamples: adaptive Ticks are budgeted passes (pass_cap 0: one frame per Tick, as ever)"""
         self.L.rth_renderer_set_adaptive_budget(self.h, int(pass_cap), C.c_uint32(int(max_pass_samples)))
 
+    def set_adaptive_dilate(self, radius):
+        """rapt::Renderer::adaptiveDilate: the adaptive Ticks' selections also list the pixels within 'radius' of an active one (0: as ever)"""
+        self.L.rth_renderer_set_adaptive_dilate(self.h, int(radius))
+
     def pass_samples(self):
         """rapt::Renderer::passSamples: the samples the last adaptive Tick took"""
         return int(self.L.rth_renderer_pass_samples(self.h))
@@ -733,6 +740,21 @@ class HostRenderer:
         n, total, cap = C.c_int(-1), C.c_uint32(0), C.c_int(-1)
         self._rt(self.rt.rt_select_budget_rows(self.ctx, C.byref(p) if p is not None else None, row_first, row_stride, row_count,
                                                C.byref(n), C.byref(total), C.byref(cap)))
+        return n.value, total.value, cap.value
+
+    # ---- dilated adaptive selection (include/rt_amd.h rt_select_active_dilated, rt_select_budget_dilated) ----
+    def select_active_dilated(self, radius, params=None):
+        """rt_select_active_dilated: select_active plus the eligible pixels within 'radius' of an active one: the number of pixels listed"""
+        p = adaptive_params(params)
+        n = C.c_int(-1)
+        self._rt(self.rt.rt_select_active_dilated(self.ctx, C.byref(p) if p is not None else None, int(radius), C.byref(n)))
+        return n.value
+
+    def select_budget_dilated(self, radius, params=None):
+        """rt_select_budget_dilated: that list with select_budget's plan (1 sample where dilation alone lists): (pixels, samples, cap used)"""
+        p = budget_params(params)
+        n, total, cap = C.c_int(-1), C.c_uint32(0), C.c_int(-1)
+        self._rt(self.rt.rt_select_budget_dilated(self.ctx, C.byref(p) if p is not None else None, int(radius), C.byref(n), C.byref(total), C.byref(cap)))
         return n.value, total.value, cap.value
 
     def _rt_src(self, src, rc):
