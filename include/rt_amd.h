@@ -30,7 +30,7 @@ typedef enum {
 	RT_E_HIP = -3,         /* HIP runtime error */
 	RT_E_UNSUPPORTED = -4, /* scene feature outside the device path (see rt_upload_scene) */
 	RT_E_STATE = -5,       /* call order (e.g. render before upload) */
-	RT_E_OVERFLOW = -6     /* traversal stack deeper than 130 = tlas.cpp:67 stack[64] + instance sentinel + bvh.cpp:608 stack[64], too many pending Whitted branches, or (Q-learning sampler) more than 2^19 rewards for one (cell, direction) within one batch of frames of a render call (reported by that call) */
+	RT_E_OVERFLOW = -6     /* traversal stack deeper than 130 = tlas.cpp:67 stack[64] + instance sentinel + bvh.cpp:608 stack[64], too many pending Whitted branches, a full call-frame stack in the general Trace / Sample kernels (see rt_set_scene_raytracer), or (Q-learning sampler) more than 2^19 rewards for one (cell, direction) within one batch of frames of a render call (reported by that call) */
 } rt_status;
 
 /* ---- scene records -------------------------------------------------------------------------
@@ -236,13 +236,20 @@ int rt_sky_color_batch(rt_ctx* ctx, int n, const float* D, float* rgb_out);
 /* Camera::GetPrimaryRay(x, y) + Scene::FindNearest(t_min) for every pixel ("primary rays only") */
 int rt_primary_hits(rt_ctx* ctx, float t_min, int32_t* obj_idx_out, float* t_out);
 /* Renderer::Trace / Renderer::Sample on caller-supplied rays: rgb_out[n*3].  Stream i starts at
- * InitSeed(seed_base + i). */
+ * InitSeed(seed_base + i).  Any depth is accepted; the one-lane-per-call-tree kernels hold at most 12 (Trace) / 6 (Sample) nested call
+ * frames and answer a deeper nesting with RT_E_OVERFLOW: see rt_set_scene_raytracer. */
 int rt_trace_batch(rt_ctx* ctx, int mode, int n, const float* O, const float* D, int depth, uint32_t seed_base, float* rgb_out);
 /* scene.raytracer as the caller's Scene holds it, for rt_trace_batch*: -1 (default) the flag follows the function called -- Trace with the
  * flag set, Sample with it clear, as Renderer::Tick calls them (renderer.cpp:268-283); 0 / 1: the flag's value.  Trace with the flag clear
  * (Russian roulette, sampled light positions, an indirect child: renderer.cpp:33-43, 107-121) and Sample with it set (:143-153) are what the
  * reference's Renderer::Trace / Sample compute when called that way; the device evaluates them one lane per call tree (slow path,
- * correctness only; not with the Q-learning sampler on: RT_E_UNSUPPORTED).  rt_render ignores the flag (it is Tick's loop). */
+ * correctness only; not with the Q-learning sampler on: RT_E_UNSUPPORTED).  rt_render ignores the flag (it is Tick's loop).
+ * Frame limits of that slow path (it also serves Sample on a scene with a shiny diffuse material or one built with raytracer == false): a
+ * call tree may hold at most 12 nested call frames in Trace and 6 in Sample.  A frame is a shiny diffuse hit waiting for its mirror child
+ * (in Trace also a glass hit's reflection child waiting for the refraction child).  The limits bound the frames nested at one moment, not
+ * the depth argument as such: two facing shiny surfaces reach them at depth 12 (Trace) and 5 (Sample), a scene without such hits never
+ * does.  Past them the call returns RT_E_OVERFLOW, rt_last_error names the call-frame stack and the limit, rgb_out is left unwritten and
+ * the context stays usable: start at a lower depth. */
 int rt_set_scene_raytracer(rt_ctx* ctx, int flag);
 /* The same with Trace / Sample's third argument: energy[3] instead of float3(1) */
 int rt_trace_batch_energy(rt_ctx* ctx, int mode, int n, const float* O, const float* D, int depth, uint32_t seed_base, const float* energy, float* rgb_out);

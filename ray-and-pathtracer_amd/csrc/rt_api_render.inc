@@ -517,7 +517,7 @@ static int run_general(rt_ctx* c, const RenderParams& R, bool whitted)
 {
 	if (whitted) hipLaunchKernelGGL(k_trace_general, dim3(c->gridBlocks), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, R, c->spill, c->flags + 1);
 	else hipLaunchKernelGGL(k_sample_general, dim3(c->gridBlocks), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, R, c->spill, c->flags + 1);
-	return check_overflow(c);
+	return check_overflow(c, whitted ? FAM_TRACE_GENERAL : FAM_SAMPLE_GENERAL);
 }
 // The batch R describes, on the pipeline that serves it; 'depth' is the depth its samples start at (Whitted: R.maxDepth).  Sets
 // R.finishInline: whether the samples were finished where they ended (an entry or slot each) or by k_finish.

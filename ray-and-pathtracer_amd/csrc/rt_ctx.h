@@ -290,16 +290,19 @@ static int fail(rt_ctx* c, int code, const char* fmt, ...)
 // ---- the status word ---------------------------------------------------------------------------
 // Every traversal launch leaves at most one word of trouble: counts[3] of the round pipelines' queues, flags[1] of the Whitted, general and
 // query kernels.  This is the one place that knows its values; 'family' names the kernels in the debug-check message.
-//   1 traversal stack   2 pending Whitted branches (the general kernels: their call-frame stack, reported as a stack like the query side
-//   always did)   3 a level queue is full (run_levels repeats the frame as one launch before it gets here)   199 unknown link   100+ debug check
-enum StatusFamily { FAM_WAVEFRONT = 0, FAM_WHITTED, FAM_QUERY };
+//   1 traversal stack   2 pending Whitted branches; from a general kernel (run_general): its call-frame stack is full (a query kernel never raises 2)
+//   3 a level queue is full (run_levels repeats the frame as one launch before it gets here)   199 unknown link   100+ debug check
+enum StatusFamily { FAM_WAVEFRONT = 0, FAM_WHITTED, FAM_QUERY, FAM_TRACE_GENERAL, FAM_SAMPLE_GENERAL };
 static int decode_status(rt_ctx* c, int f, StatusFamily family)
 {
-	static const char* const name[] = { "a wavefront kernel", "the Whitted kernel", "a query kernel" };
+	static const char* const name[] = { "a wavefront kernel", "the Whitted kernel", "a query kernel", "the general Trace kernel", "the general Sample kernel" };
 	if (f == 0) return RT_OK;
 	if (f == 199) return fail(c, RT_E_STATE, "a traversal launch met a link no step understands (corrupt tree?) and dropped rays");
 	if (f >= 100) return fail(c, RT_E_STATE, "debug check %d failed in %s (RT_DEBUG_CHECKS build)", f - 100, name[family]);
 	if (f == 3) return fail(c, RT_E_OVERFLOW, "a Whitted level queue overflowed");
+	if (f == 2 && (family == FAM_TRACE_GENERAL || family == FAM_SAMPLE_GENERAL))
+		return fail(c, RT_E_OVERFLOW, "the call-frame stack of %s is full: more than %d nested call frames in one call tree (shiny diffuse or glass hits inside one another); start at a lower depth",
+			name[family], family == FAM_TRACE_GENERAL ? RT_TRACE_FRAMES : RT_SAMPLE_FRAMES);
 	if (f == 2 && family != FAM_QUERY) return fail(c, RT_E_OVERFLOW, "more than %d pending Whitted branches in one pixel", RT_PEND_CAP);
 	return fail(c, RT_E_OVERFLOW, "traversal stack deeper than %d entries", RT_STACK_MAX);
 }
@@ -312,13 +315,13 @@ static int read_flags(rt_ctx* c, int& f)
 	return RT_OK;
 }
 // the general and query kernels' launches: did one of them report trouble?
-static int check_overflow(rt_ctx* c)
+static int check_overflow(rt_ctx* c, StatusFamily family = FAM_QUERY)
 {
 	int f = 0;
 	const int rc = read_flags(c, f);
 	if (rc != RT_OK) return rc;
 	if (f != 0) (void)hipMemset(c->flags, 0, 2 * sizeof(int));
-	return decode_status(c, f, FAM_QUERY);
+	return decode_status(c, f, family);
 }
 
 static int tuning(const rt_ctx* c) { return c->counting == RT_COUNT_EXECUTED ? RT_TUNE_CULL_COUNTED : 0; } // the traversal kernels' one launch-time flag (the thresholds are constants: rt_scene_dev.h)

@@ -894,6 +894,10 @@ __global__ void __launch_bounds__(RT_BLOCK) k_finish(DScene S, DCamera C, Render
 // In both cases random draws interleave with occlusion queries in depth-first order, so one lane runs
 // one whole sample: recursion becomes a stack of suspended light loops, radiance is carried forward as
 // weights exactly as in the wavefront kernels.  Slow path by design (divergent, scratch-heavy).
+// The call-frame stacks of the two general kernels: frames nested at one moment in one call tree, not the depth argument as such (a tree
+// without shiny diffuse hits or glass nests nothing at any depth).  A push past the limit is dropped and raises status 2 (rt_ctx.h).
+#define RT_SAMPLE_FRAMES 6 // k_sample_general: the suspended light loops of shiny diffuse hits, one per level of nested mirror children
+#define RT_TRACE_FRAMES 12 // k_trace_general: the same, plus a glass hit's reflection child while its refraction child runs
 struct Suspended { // a DIFFUSE hit whose light loop is waiting for a shiny branch to return
 	f3 P, N, rayD, W, E;
 	int mat, nextLight, depth;
@@ -922,7 +926,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_sample_general(DScene S, DCamera C
 		}
 		f3 W(1.0f), E(1.0f), Lsum(0.0f);
 		if (R.customO) E = f3(R.customE[0], R.customE[1], R.customE[2]);
-		Suspended stack[6];
+		Suspended stack[RT_SAMPLE_FRAMES];
 		int sp = 0;
 		bool resume = false;
 		Suspended cur;
@@ -1004,7 +1008,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_sample_general(DScene S, DCamera C
 					// directLightning += shinieness * col * Sample(mirror ray, depth - 1, energy): run it now
 					// (its draws come before the next light's), keep the rest of this loop for later
 					cur.nextLight = i + 1;
-					if (sp < 6) stack[sp++] = cur; else *overflow = 2;
+					if (sp < RT_SAMPLE_FRAMES) stack[sp++] = cur; else *overflow = 2;
 					O = cur.P, D = reflect(cur.rayD, cur.N), E = cur.E, depth = cur.depth - 1;
 					W = cur.W * (((m.shinieness * col) * RT_INVPI) * albedo);
 					branched = true;
@@ -1033,7 +1037,6 @@ struct TraceFrame {
 	f3 P, N, rayD, W, E, sdir; // kind 0: a child Trace(P, rayD) still to be called with weight W and energy E; kind 1: a suspended light loop
 	int mat, nextLight, depth, kind;
 };
-#define RT_TRACE_FRAMES 12
 __global__ void __launch_bounds__(RT_BLOCK) k_trace_general(DScene S, DCamera C, RenderParams R, uint* spill, int* overflow)
 {
 	__shared__ uint ldsStack[RT_STACK_LDS * RT_BLOCK];
