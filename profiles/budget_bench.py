@@ -1,10 +1,11 @@
 """Budgeted adaptive passes, timed on config 3's scene (pretty_tlas) at 1920x1080 (the selection at 3840x2160 too).
-  python3 profiles/budget_bench.py --parent <checkout of the parent commit, built> [--rounds N] [--json out.json]   (GPU box, repository root)
+  python3 profiles/budget_bench.py --parent <checkout of the parent commit, built> [--parent-budget] [--rounds N] [--json out.json]   (GPU box, repository root)
 Every measurement runs in a child process of its own (two builds of the library cannot share a process), parent and this commit
 alternated round by round in one session; host times bracketed by rt_synchronize, after a warm-up call of the same shape.
   overhead   one pass over the FULL list with every budget forced to 16 (from rt_clear with min_samples = 16 = pass_cap: rt_render_budget
              alone is timed, its selection beside it) against whole16 (rt_render of 16 frames, statistics off) and full_list16
              (rt_render_active of 16 frames, every pixel listed) of the parent commit AND of this one, and whole16 with statistics on
+             (--parent-budget: the parent commit has the budgeted calls too, and its selection and pass are timed as well)
   loops      from rt_clear until nothing is active under the same rt_adaptive_params:
                (a) rt_select_active + rt_render_active(frame, 1), as TickAdaptive does (min_samples whole frames first)
                (b) rt_select_budget + rt_render_budget at pass_cap 8, 64, 512
@@ -187,6 +188,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--root", default=os.path.dirname(HERE), help="the checkout whose library is measured")
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit (the overhead part's baseline)")
+    ap.add_argument("--parent-budget", action="store_true", help="the parent commit has the budgeted calls: time them on its build too")
     ap.add_argument("--part", default=None, choices=["overhead", "loops", "select"], help="(a child's work)")
     ap.add_argument("--baseline", action="store_true", help="(child) only the calls the parent commit has")
     ap.add_argument("--child-timeout", type=int, default=300)
@@ -198,7 +200,7 @@ def main():
         raise SystemExit("--parent: a built checkout of the parent commit")
     over = dict(parent=[], this=[])
     for rnd in range(a.rounds):  # alternated: parent, this, parent, this, ...
-        over["parent"].append(run_child(a.parent, "overhead", a, baseline=True))
+        over["parent"].append(run_child(a.parent, "overhead", a, baseline=not a.parent_budget))
         over["this"].append(run_child(a.root, "overhead", a))
 
     def merged(runs):

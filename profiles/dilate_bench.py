@@ -1,5 +1,5 @@
 """Dilated adaptive selection, timed on config 3's scene (pretty_tlas) at 1920x1080 on the statistics of 16 whole frames.
-  python3 profiles/dilate_bench.py --parent <checkout of the parent commit, built> [--rounds N] [--json out.json]   (GPU box, repository root)
+  python3 profiles/dilate_bench.py --parent <checkout of the parent commit, built> [--parent-dilated] [--rounds N] [--json out.json]   (GPU box, repository root)
 Every measurement runs in a child process of its own (two builds of the library cannot share a process), parent and this commit
 alternated round by round in one session.  Per call, after two warm-up calls of the same shape, medians of --reps (7) calls:
   event_ms   HIP events on the context's stream (rt_set_profiling: the call's entry of rt_profile.query) -- rt_select_active and
@@ -8,6 +8,7 @@ alternated round by round in one session.  Per call, after two warm-up calls of 
   wall_ms    host time of the call between two rt_synchronize: launches, the read-back of the count and its synchronisation included
   rt_select_active, rt_select_budget (pass_cap 64): parent build and this build
   rt_select_active_dilated at radius 0, 1, 4, 16; rt_select_budget_dilated at radius 1, 4: this build, same statistics, same process
+    (--parent-dilated: the parent commit has these calls too, and they are timed on its build as well)
 The yardstick: per pixel the undilated selection reads 12 B of statistics twice (count, scatter), the dilated one once, plus bitmasks of
 width * height / 8 bytes that stay in the L2; bytes / event time is printed as GB/s beside the device's HBM rate.
 The result is stamped with rt_build_info of both libraries."""
@@ -91,6 +92,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--root", default=os.path.dirname(HERE), help="the checkout whose library is measured")
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit")
+    ap.add_argument("--parent-dilated", action="store_true", help="the parent commit has the dilated calls: time them on its build too")
     ap.add_argument("--child", action="store_true", help="(a child's work)")
     ap.add_argument("--baseline", action="store_true", help="(child) only the calls the parent commit has")
     ap.add_argument("--child-timeout", type=int, default=240)
@@ -102,7 +104,7 @@ def main():
         raise SystemExit("--parent: a built checkout of the parent commit")
     runs = dict(parent=[], this=[])
     for rnd in range(a.rounds):  # alternated: parent, this, parent, this, ...
-        runs["parent"].append(run_child(a.parent, a, True))
+        runs["parent"].append(run_child(a.parent, a, not a.parent_dilated))
         runs["this"].append(run_child(a.root, a, False))
 
     def merged(rs):

@@ -12,6 +12,8 @@
 // The launches walk a ROW SET (RowMap: rows rowFirst + k * rowStride, k < rowCount -- the share of the frame a context renders when the
 // rows are interleaved over several contexts, rt_select_active_rows): lane i owns the i-th pixel of the set in ascending pixel order, so
 // a shard reads only its own rows' statistics and its list ascends.  The whole frame is the set (0, 1, height), where i is the pixel.
+// What count and scatter do with a wave's ballot (block_total_of, scatter_listed) is shared with the dilated selection of rt_dilate.h,
+// whose lanes are decided by a bit of a mask instead of the predicate.
 #pragma once
 #include "rt_kernels.h" // PixelStats, resolve_pixel
 
@@ -63,19 +65,27 @@ __device__ __forceinline__ bool pixel_active(uint count, float sumY, float sumYY
 	return pixel_noisy(count, sumY, sumYY, A, pixel_moments(count, sumY, sumYY, A));
 }
 
+typedef unsigned long long bits64; // a wave's ballot; a word of the bitmasks of rt_dilate.h
+
 // lanes of this wave below the caller that are set in 'mask'
-__device__ __forceinline__ uint lanes_below(unsigned long long mask)
+__device__ __forceinline__ uint lanes_below(bits64 mask)
 {
 	return __builtin_amdgcn_mbcnt_hi((uint)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint)mask, 0u));
 }
 
-__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_select_count(PixelStats St, AdaptiveArgs A, RowMap M, uint* blockTotal)
+// inclusive prefix sum over the wave
+__device__ __forceinline__ uint wave_inclusive(uint v, uint lane)
+{
+	for (int o = 1; o < 64; o <<= 1) { const uint t = __shfl_up(v, o); if ((int)lane >= o) v += t; }
+	return v;
+}
+
+// The two tails of the list form, shared by the row-set kernels below and the dilated ones of rt_dilate.h: 'mask' is the wave's ballot of
+// its listed lanes (or the word of the listed mask that holds the same bits).
+// count: blockTotal[this block] = the listed lanes of its waves
+__device__ __forceinline__ void block_total_of(bits64 mask, uint* blockTotal)
 {
 	__shared__ uint waveTotal[RT_SELECT_BLOCK / 64];
-	const int i = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
-	const int p = i < M.nPixels ? row_map_pixel(M, i) : 0;
-	const bool on = i < M.nPixels && pixel_active(St.count[p], St.sumY[p], St.sumYY[p], A);
-	const unsigned long long mask = __ballot(on);
 	if ((threadIdx.x & 63) == 0) waveTotal[threadIdx.x >> 6] = (uint)__popcll(mask);
 	__syncthreads();
 	if (threadIdx.x == 0) {
@@ -83,6 +93,27 @@ __global__ void __launch_bounds__(RT_SELECT_BLOCK) k_select_count(PixelStats St,
 		for (int w = 0; w < RT_SELECT_BLOCK / 64; w++) sum += waveTotal[w];
 		blockTotal[blockIdx.x] = sum;
 	}
+}
+// scatter: list[block base + waves before + rank inside the wave] = pixel, for the lanes whose bit is set.  at < the grand total <= the
+// lanes of the launch: the count pass made the totals from the same bits.
+__device__ __forceinline__ void scatter_listed(bits64 mask, uint pixel, const uint* blockBase, uint* list)
+{
+	__shared__ uint waveTotal[RT_SELECT_BLOCK / 64];
+	const uint wave = threadIdx.x >> 6;
+	if ((threadIdx.x & 63) == 0) waveTotal[wave] = (uint)__popcll(mask);
+	__syncthreads();
+	if (!((mask >> (threadIdx.x & 63)) & 1ull)) return;
+	uint at = blockBase[blockIdx.x] + lanes_below(mask);
+	for (uint w = 0; w < wave; w++) at += waveTotal[w];
+	list[at] = pixel;
+}
+
+__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_select_count(PixelStats St, AdaptiveArgs A, RowMap M, uint* blockTotal)
+{
+	const int i = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
+	const int p = i < M.nPixels ? row_map_pixel(M, i) : 0;
+	const bool on = i < M.nPixels && pixel_active(St.count[p], St.sumY[p], St.sumYY[p], A);
+	block_total_of(__ballot(on), blockTotal);
 }
 
 // one block: blockTotal[0 .. nBlocks) -> its exclusive prefix sums, *nActive = the total.  A lane owns a run of consecutive entries.
@@ -94,8 +125,7 @@ __global__ void __launch_bounds__(RT_SELECT_SCAN_BLOCK) k_select_scan(uint* bloc
 	uint mine = 0;
 	for (int i = first; i < last; i++) mine += blockTotal[i];
 	const uint lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	uint incl = mine; // inclusive prefix sum over the wave
-	for (int o = 1; o < 64; o <<= 1) { const uint t = __shfl_up(incl, o); if ((int)lane >= o) incl += t; }
+	const uint incl = wave_inclusive(mine, lane);
 	if (lane == 63) waveSum[wave] = incl;
 	__syncthreads();
 	uint base = 0, total = 0;
@@ -105,20 +135,13 @@ __global__ void __launch_bounds__(RT_SELECT_SCAN_BLOCK) k_select_scan(uint* bloc
 	if (threadIdx.x == 0) *nActive = (int)total;
 }
 
+// the predicate again: the three launches evaluate it on the same statistics
 __global__ void __launch_bounds__(RT_SELECT_BLOCK) k_select_scatter(PixelStats St, AdaptiveArgs A, RowMap M, const uint* blockBase, uint* list)
 {
-	__shared__ uint waveTotal[RT_SELECT_BLOCK / 64];
 	const int i = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
 	const int p = i < M.nPixels ? row_map_pixel(M, i) : 0;
 	const bool on = i < M.nPixels && pixel_active(St.count[p], St.sumY[p], St.sumYY[p], A);
-	const unsigned long long mask = __ballot(on);
-	const uint wave = threadIdx.x >> 6;
-	if ((threadIdx.x & 63) == 0) waveTotal[wave] = (uint)__popcll(mask);
-	__syncthreads();
-	if (!on) return;
-	uint at = blockBase[blockIdx.x] + lanes_below(mask);
-	for (uint w = 0; w < wave; w++) at += waveTotal[w];
-	list[at] = (uint)p; // at < the grand total <= M.nPixels: the three launches evaluate one predicate on the same statistics
+	scatter_listed(__ballot(on), (uint)p, blockBase, list);
 }
 
 // rt_resolve with the pixel's own sample count as the divisor; a pixel without samples is black

@@ -191,7 +191,6 @@ int rt_bind_accumulator(rt_ctx* c, void* p)
 #include "rt_api_denoise.inc"
 #include "rt_api_adaptive.inc"
 #include "rt_api_budget.inc"
-#include "rt_api_dilate.inc"
 #include "rt_api_reproject.inc"
 
 // ---- measurement ------------------------------------------------------------------------------

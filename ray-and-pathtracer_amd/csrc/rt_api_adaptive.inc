@@ -1,6 +1,7 @@
-// Adaptive sampling: rt_stats_enable, rt_download_stats, rt_select_active, rt_select_active_rows, rt_set_active_pixels, rt_download_active,
-// rt_render_active, rt_resolve_adaptive.  Included by rt_api.hip.  The statistics are kept by k_accumulate<true> (rt_kernels.h; launched by render_batches
-// of rt_api_render.inc while they are on), the selection and the per-count resolve are the kernels of rt_adaptive.h.
+// Adaptive sampling: rt_stats_enable, rt_download_stats, rt_select_active, rt_select_active_rows, rt_select_active_dilated, rt_set_active_pixels,
+// rt_download_active, rt_render_active, rt_resolve_adaptive.  Included by rt_api.hip.  The statistics are kept by k_accumulate<true> (rt_kernels.h;
+// launched by render_batches of rt_api_render.inc while they are on), the selection and the per-count resolve are the kernels of rt_adaptive.h,
+// the dilated selection's those of rt_dilate.h.
 int rt_stats_enable(rt_ctx* c, int on)
 {
 	if (!c) return RT_E_ARG;
@@ -54,42 +55,105 @@ static int ensure_active_list(rt_ctx* c)
 	return RT_OK;
 }
 
-// the row set of rt_select_active_rows / rt_select_budget_rows as the kernels take it (row_set_ok: rt_gather_rows' rule for what lies in the frame)
-static bool row_map_of(const rt_ctx* c, int row_first, int row_stride, int row_count, RowMap& M)
-{
-	if (!row_set_ok(c, row_first, row_stride, row_count)) return false;
-	M.rowFirst = row_first, M.rowStride = row_stride, M.width = c->width, M.nPixels = row_count * c->width;
-	return true;
-}
+// ---- the selection: one list skeleton here, one plan skeleton in rt_api_budget.inc, six entry points that say what is walked -------
+// What a selection walks: a row set (rt_adaptive.h RowMap; the whole frame is the rows (0, 1, height)), or the whole frame through the
+// dilated masks of rt_dilate.h at 'radius' (whole frame only: a context that holds one row shard has no statistics for its neighbours'
+// rows).  The entry points fill it with their arguments as they came; select_over_ok checks them.
+struct SelectOver {
+	bool dilated;
+	int rowFirst, rowStride, rowCount; // !dilated
+	int radius;                        // dilated
+	bool planEntry; // select_plan brackets the whole call, read-backs included, as one entry of rt_profile.query.  Only rt_select_budget_dilated
+	                // does: rt_select_budget and rt_select_budget_rows have no entry at all (profiles/dilate_bench.py relies on both).
+};
+static SelectOver over_rows(int row_first, int row_stride, int row_count) { return SelectOver{ false, row_first, row_stride, row_count, 0, false }; }
+static SelectOver over_dilated(int radius, bool plan_entry) { return SelectOver{ true, 0, 0, 0, radius, plan_entry }; }
 
-// rt_select_active (what = its name, the rows (0, 1, height)) and rt_select_active_rows
-static int select_active_rows(rt_ctx* c, const char* what, const rt_adaptive_params* params, int row_first, int row_stride, int row_count, int* n_active_out)
+// the rules of rt_adaptive_params, for every selection
+static int adaptive_params_ok(rt_ctx* c, const char* what, const rt_adaptive_params& P)
 {
-	const rt_adaptive_params P = params ? *params : rt_adaptive_params RT_ADAPTIVE_DEFAULTS;
 	if (P.min_samples < 2 || P.max_samples < P.min_samples) return fail(c, RT_E_ARG, "%s: min_samples %d (>= 2), max_samples %d (>= min_samples)", what, P.min_samples, P.max_samples);
 	if (!(P.threshold >= 0.0f) || !(P.floor > 0.0f)) return fail(c, RT_E_ARG, "%s: threshold must be >= 0 and floor > 0 (neither NaN)", what);
-	if (!c || !n_active_out) return fail(c, RT_E_ARG, "%s: null argument", what);
-	RowMap M;
-	if (!row_map_of(c, row_first, row_stride, row_count, M)) return fail(c, RT_E_ARG, "%s: rows %d + k*%d (k < %d) outside 0..%d", what, row_first, row_stride, row_count, c->height);
-	if (!c->stats.count) return fail(c, RT_E_STATE, "%s: statistics are off (rt_stats_enable)", what);
-	HIPCHK(c, hipSetDevice(c->device));
-	int rc = ensure_active_list(c);
-	if (rc != RT_OK) return rc;
+	return RT_OK;
+}
+// the radius, or the row set (row_set_ok: rt_gather_rows' rule for what lies in the frame); M: the lanes of the launches as the kernels take them
+static int select_over_ok(rt_ctx* c, const char* what, const SelectOver& over, RowMap& M)
+{
+	if (over.dilated) {
+		if (over.radius < 0 || over.radius > RT_DILATE_MAX_RADIUS) return fail(c, RT_E_ARG, "%s: radius %d (0..%d)", what, over.radius, RT_DILATE_MAX_RADIUS);
+		M.rowFirst = 0, M.rowStride = 1, M.width = c->width, M.nPixels = c->width * c->height;
+		return RT_OK;
+	}
+	if (!row_set_ok(c, over.rowFirst, over.rowStride, over.rowCount))
+		return fail(c, RT_E_ARG, "%s: rows %d + k*%d (k < %d) outside 0..%d", what, over.rowFirst, over.rowStride, over.rowCount, c->height);
+	M.rowFirst = over.rowFirst, M.rowStride = over.rowStride, M.width = c->width, M.nPixels = over.rowCount * c->width;
+	return RT_OK;
+}
+static AdaptiveArgs adaptive_args(const rt_adaptive_params& P)
+{
 	AdaptiveArgs A;
 	A.minSamples = P.min_samples, A.maxSamples = P.max_samples, A.threshold = P.threshold, A.floor = P.floor;
-	const int n = M.nPixels, blocks = (n + RT_SELECT_BLOCK - 1) / RT_SELECT_BLOCK;
+	return A;
+}
+static int select_blocks(const RowMap& M) { return (M.nPixels + RT_SELECT_BLOCK - 1) / RT_SELECT_BLOCK; }
+
+// the three mask launches: c->dilate.listed and, in c->selectTotals, the listed pixels of every block
+static void launch_dilate_masks(rt_ctx* c, const AdaptiveArgs& A, int radius, const RowMap& M)
+{
+	const DilateMasks& D = c->dilate;
+	const int n = M.nPixels, blocks = select_blocks(M);
+	hipLaunchKernelGGL(k_dilate_mask, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, n, D.raw, D.eligible);
+	hipLaunchKernelGGL(k_dilate_rows, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, D.raw, n, c->width, radius, D.rows);
+	hipLaunchKernelGGL(k_dilate_cols, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, D, n, c->width, c->height, radius, c->selectTotals);
+}
+// the list alone, from the prefix sums of the listed pixels in c->selectTotals (dilated: and the listed mask)
+static void launch_list_scatter(rt_ctx* c, const SelectOver& over, const AdaptiveArgs& A, const RowMap& M)
+{
+	const int blocks = select_blocks(M);
+	if (over.dilated) hipLaunchKernelGGL(k_dilate_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->dilate.listed, M.nPixels, c->selectTotals, c->activeList);
+	else hipLaunchKernelGGL(k_select_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, M, c->selectTotals, c->activeList);
+}
+// The totals come home, in stream order behind what is queued: the selected count (c->activeCount) and, for a plan, the 64-bit total of its
+// budgets (c->planTotal).  Pinned words 8 and 10..11 (the round pipelines use 0..4, rt_reproject 9), then the only synchronisation of
+// a list call, of a plan call the one of this cap.
+static int read_selected(rt_ctx* c, int& got, unsigned long long* total)
+{
+	HIPCHK(c, hipMemcpyAsync(c->hostCounts + 8, c->activeCount, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+	if (total) HIPCHK(c, hipMemcpyAsync(c->hostCounts + 10, c->planTotal, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	got = c->hostCounts[8];
+	if (total) memcpy(total, c->hostCounts + 10, sizeof(*total));
+	return RT_OK;
+}
+
+// rt_select_active, rt_select_active_rows, rt_select_active_dilated (what = the caller's name)
+static int select_list(rt_ctx* c, const char* what, const rt_adaptive_params* params, const SelectOver& over, int* n_active_out)
+{
+	const rt_adaptive_params P = params ? *params : rt_adaptive_params RT_ADAPTIVE_DEFAULTS;
+	int rc = adaptive_params_ok(c, what, P);
+	if (rc != RT_OK) return rc;
+	if (!c || !n_active_out) return fail(c, RT_E_ARG, "%s: null argument", what);
+	RowMap M;
+	rc = select_over_ok(c, what, over, M);
+	if (rc != RT_OK) return rc;
+	if (!c->stats.count) return fail(c, RT_E_STATE, "%s: statistics are off (rt_stats_enable)", what);
+	HIPCHK(c, hipSetDevice(c->device));
+	rc = ensure_active_list(c);
+	if (rc != RT_OK) return rc;
+	const AdaptiveArgs A = adaptive_args(P);
+	const int n = M.nPixels, blocks = select_blocks(M);
 	c->nActive = -1; // no list until the count has come home
 	drop_plan(c);
-	prof_begin(c, K_QUERY); // (with rt_set_profiling on: the three launches are one entry of rt_profile.query)
-	hipLaunchKernelGGL(k_select_count, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, M, c->selectTotals);
+	prof_begin(c, K_QUERY); // (with rt_set_profiling on: the launches, three or five, are one entry of rt_profile.query)
+	if (over.dilated) launch_dilate_masks(c, A, over.radius, M);
+	else hipLaunchKernelGGL(k_select_count, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, M, c->selectTotals);
 	hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(RT_SELECT_SCAN_BLOCK), 0, c->stream, c->selectTotals, blocks, c->activeCount);
-	hipLaunchKernelGGL(k_select_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, M, c->selectTotals, c->activeList);
+	launch_list_scatter(c, over, A, M);
 	prof_end(c);
 	HIPCHK(c, hipGetLastError());
-	// the only synchronisation of the call: the selected count (pinned; the round pipelines use words 0..4)
-	HIPCHK(c, hipMemcpyAsync(c->hostCounts + 8, c->activeCount, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	const int got = c->hostCounts[8];
+	int got = 0;
+	rc = read_selected(c, got, nullptr);
+	if (rc != RT_OK) return rc;
 	if (got < 0 || got > n) return fail(c, RT_E_STATE, "%s: %d pixels selected of %d", what, got, n);
 	c->nActive = got;
 	*n_active_out = got;
@@ -98,12 +162,17 @@ static int select_active_rows(rt_ctx* c, const char* what, const rt_adaptive_par
 
 int rt_select_active(rt_ctx* c, const rt_adaptive_params* params, int* n_active_out)
 {
-	return select_active_rows(c, "rt_select_active", params, 0, 1, c ? c->height : 1, n_active_out);
+	return select_list(c, "rt_select_active", params, over_rows(0, 1, c ? c->height : 1), n_active_out);
 }
 
 int rt_select_active_rows(rt_ctx* c, const rt_adaptive_params* params, int row_first, int row_stride, int row_count, int* n_active_out)
 {
-	return select_active_rows(c, "rt_select_active_rows", params, row_first, row_stride, row_count, n_active_out);
+	return select_list(c, "rt_select_active_rows", params, over_rows(row_first, row_stride, row_count), n_active_out);
+}
+
+int rt_select_active_dilated(rt_ctx* c, const rt_adaptive_params* params, int radius, int* n_active_out)
+{
+	return select_list(c, "rt_select_active_dilated", params, over_dilated(radius, false), n_active_out);
 }
 
 int rt_set_active_pixels(rt_ctx* c, const uint32_t* pixels, int n)

@@ -1,5 +1,6 @@
-// Budgeted adaptive passes: rt_select_budget, rt_select_budget_rows, rt_download_budgets, rt_render_budget.  Included by rt_api.hip after rt_api_adaptive.inc
-// (the list's storage and ensure_active_list are its).  The kernels are rt_budget.h's; the batch itself runs on whichever round pipeline
+// Budgeted adaptive passes: rt_select_budget, rt_select_budget_rows, rt_select_budget_dilated, rt_download_budgets, rt_render_budget.  Included by
+// rt_api.hip after rt_api_adaptive.inc (the list's storage, ensure_active_list, what a selection walks and its shared steps are its).  The kernels
+// are rt_budget.h's, over the dilated masks rt_dilate.h's; the batch itself runs on whichever round pipeline
 // trace_samples (rt_api_render.inc) picks for that many samples -- a plan only changes which (pixel, frame) a sample id names.
 // The plan is dropped (drop_plan, rt_ctx.h) by whatever moves the counts or the list: a path-mode render_batches, stats_clear,
 // rt_reproject, rt_select_active, rt_set_active_pixels.
@@ -35,58 +36,59 @@ static int ensure_records(rt_ctx* c, size_t count)
 
 #define RT_PASS_SAMPLES_MAX 0x7FFFFFFFull // sample ids are ints on the round pipelines
 
-// rt_select_budget (what = its name, the rows (0, 1, height)) and rt_select_budget_rows
-static int select_budget_rows(rt_ctx* c, const char* what, const rt_budget_params* params, int row_first, int row_stride, int row_count, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out)
+// rt_select_budget, rt_select_budget_rows, rt_select_budget_dilated (what = the caller's name): select_list's list (rt_api_adaptive.inc)
+// and, per entry, the plan
+static int select_plan(rt_ctx* c, const char* what, const rt_budget_params* params, const SelectOver& over, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out)
 {
 	const rt_budget_params B = params ? *params : rt_budget_params RT_BUDGET_DEFAULTS;
-	const rt_adaptive_params& P = B.select;
-	if (P.min_samples < 2 || P.max_samples < P.min_samples) return fail(c, RT_E_ARG, "%s: min_samples %d (>= 2), max_samples %d (>= min_samples)", what, P.min_samples, P.max_samples);
-	if (!(P.threshold >= 0.0f) || !(P.floor > 0.0f)) return fail(c, RT_E_ARG, "%s: threshold must be >= 0 and floor > 0 (neither NaN)", what);
+	int rc = adaptive_params_ok(c, what, B.select);
+	if (rc != RT_OK) return rc;
 	if (B.pass_cap < 1 || B.pass_cap > 1024) return fail(c, RT_E_ARG, "%s: pass_cap %d (1..1024)", what, B.pass_cap);
 	if (!c || !n_active_out || !n_samples_out || !cap_used_out) return fail(c, RT_E_ARG, "%s: null argument", what);
 	RowMap M;
-	if (!row_map_of(c, row_first, row_stride, row_count, M)) return fail(c, RT_E_ARG, "%s: rows %d + k*%d (k < %d) outside 0..%d", what, row_first, row_stride, row_count, c->height);
+	rc = select_over_ok(c, what, over, M);
+	if (rc != RT_OK) return rc;
 	if (!c->stats.count) return fail(c, RT_E_STATE, "%s: statistics are off (rt_stats_enable)", what);
 	HIPCHK(c, hipSetDevice(c->device));
-	int rc = ensure_active_list(c);
+	rc = ensure_active_list(c);
 	if (rc == RT_OK) rc = ensure_plan(c);
 	if (rc != RT_OK) return rc;
-	AdaptiveArgs A;
-	A.minSamples = P.min_samples, A.maxSamples = P.max_samples, A.threshold = P.threshold, A.floor = P.floor;
-	const int n = M.nPixels, blocks = (n + RT_SELECT_BLOCK - 1) / RT_SELECT_BLOCK;
+	const AdaptiveArgs A = adaptive_args(B.select);
+	const int n = M.nPixels, blocks = select_blocks(M);
 	unsigned long long limit = B.max_pass_samples ? (unsigned long long)B.max_pass_samples : ((unsigned long long)c->knobs.sampleGiB << 30) / sizeof(float4);
 	if (limit > RT_PASS_SAMPLES_MAX) limit = RT_PASS_SAMPLES_MAX;
 	c->nActive = -1; // no list until the count has come home
 	drop_plan(c);
+	struct Entry { rt_ctx* c; ~Entry() { if (c) prof_end(c); } } entry{ over.planEntry ? c : nullptr }; // (over.planEntry: every way out ends the entry)
+	if (over.planEntry) prof_begin(c, K_QUERY);
+	if (over.dilated) launch_dilate_masks(c, A, over.radius, M); // once: the masks do not depend on the cap
 	// the fit rule: the largest cap = pass_cap >> k whose total fits; the list does not depend on the cap
 	int cap = B.pass_cap, got = 0;
 	unsigned long long total = 0;
 	for (;; cap >>= 1) {
-		hipLaunchKernelGGL(k_budget_count, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, cap, M, c->selectTotals, c->budgetTotals);
+		if (over.dilated) hipLaunchKernelGGL(k_dilate_budget_count, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->dilate, c->stats, A, cap, n, c->selectTotals, c->budgetTotals);
+		else hipLaunchKernelGGL(k_budget_count, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, cap, M, c->selectTotals, c->budgetTotals);
 		hipLaunchKernelGGL(k_budget_scan, dim3(1), dim3(RT_SELECT_SCAN_BLOCK), 0, c->stream, c->selectTotals, c->budgetTotals, blocks, c->activeCount, c->planTotal);
 		HIPCHK(c, hipGetLastError());
-		// the call's only synchronisation, once per cap tried (pinned; words 8 and 10..11: the round pipelines use 0..4, rt_reproject 9)
-		HIPCHK(c, hipMemcpyAsync(c->hostCounts + 8, c->activeCount, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(c, hipMemcpyAsync(c->hostCounts + 10, c->planTotal, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(c, hipStreamSynchronize(c->stream));
-		got = c->hostCounts[8];
-		memcpy(&total, c->hostCounts + 10, sizeof(total));
+		rc = read_selected(c, got, &total); // the call's only synchronisation, once per cap tried
+		if (rc != RT_OK) return rc;
 		if (got < 0 || got > n || total < (unsigned long long)got || total > (unsigned long long)got * (unsigned)cap)
 			return fail(c, RT_E_STATE, "%s: %d pixels of %d selected, %llu samples at cap %d", what, got, n, total, cap);
 		if (total <= limit || cap == 1) break;
 	}
 	*n_active_out = got;
 	if (total > limit) {
-		// not even one sample per active pixel fits: the list alone, for rt_render_active (selectTotals holds the pixels' prefix sums)
-		hipLaunchKernelGGL(k_select_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, M, c->selectTotals, c->activeList);
+		// not even one sample per listed pixel fits: the list alone, for rt_render_active (selectTotals holds the pixels' prefix sums)
+		launch_list_scatter(c, over, A, M);
 		HIPCHK(c, hipGetLastError());
 		c->nActive = got;
-		return fail(c, RT_E_UNSUPPORTED, "%s: %d active pixels do not fit a pass of %llu samples", what, got, limit);
+		return fail(c, RT_E_UNSUPPORTED, "%s: %d %s pixels do not fit a pass of %llu samples", what, got, over.dilated ? "listed" : "active", limit);
 	}
 	if (got > 0) {
 		rc = ensure_records(c, (size_t)total);
 		if (rc != RT_OK) return rc;
-		hipLaunchKernelGGL(k_budget_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, cap, M, c->selectTotals, c->budgetTotals, c->activeList, c->plan);
+		if (over.dilated) hipLaunchKernelGGL(k_dilate_budget_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->dilate, c->stats, A, cap, n, c->selectTotals, c->budgetTotals, c->activeList, c->plan);
+		else hipLaunchKernelGGL(k_budget_scatter, dim3(blocks), dim3(RT_SELECT_BLOCK), 0, c->stream, c->stats, A, cap, M, c->selectTotals, c->budgetTotals, c->activeList, c->plan);
 		HIPCHK(c, hipGetLastError());
 	}
 	c->nActive = got, c->planSamples = (long long)total;
@@ -96,12 +98,17 @@ static int select_budget_rows(rt_ctx* c, const char* what, const rt_budget_param
 
 int rt_select_budget(rt_ctx* c, const rt_budget_params* params, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out)
 {
-	return select_budget_rows(c, "rt_select_budget", params, 0, 1, c ? c->height : 1, n_active_out, n_samples_out, cap_used_out);
+	return select_plan(c, "rt_select_budget", params, over_rows(0, 1, c ? c->height : 1), n_active_out, n_samples_out, cap_used_out);
 }
 
 int rt_select_budget_rows(rt_ctx* c, const rt_budget_params* params, int row_first, int row_stride, int row_count, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out)
 {
-	return select_budget_rows(c, "rt_select_budget_rows", params, row_first, row_stride, row_count, n_active_out, n_samples_out, cap_used_out);
+	return select_plan(c, "rt_select_budget_rows", params, over_rows(row_first, row_stride, row_count), n_active_out, n_samples_out, cap_used_out);
+}
+
+int rt_select_budget_dilated(rt_ctx* c, const rt_budget_params* params, int radius, int* n_active_out, uint32_t* n_samples_out, int* cap_used_out)
+{
+	return select_plan(c, "rt_select_budget_dilated", params, over_dilated(radius, true), n_active_out, n_samples_out, cap_used_out);
 }
 
 int rt_download_budgets(rt_ctx* c, uint32_t* out, int cap, int* n_out)

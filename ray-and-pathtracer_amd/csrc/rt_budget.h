@@ -13,6 +13,8 @@
 //                     records TOGETHER: lanes stride over the wave's range of the pool and find their entry in the wave's prefix sums
 //                     (one lane per entry would serialise the wave behind its noisiest pixel: up to 1024 records)
 // The count runs once per cap tried (the fit rule: cap = pass_cap >> k), the scatter once, after the total has been read back and fits.
+// Count and scatter are written once, as budget_count_body / budget_scatter_body over a lane source; the kernels name the source
+// (here the row set, in rt_dilate.h the listed mask of the dilated selection).
 #pragma once
 #include "rt_adaptive.h"
 
@@ -44,21 +46,31 @@ __device__ __forceinline__ uint pixel_budget(uint count, float sumY, float sumYY
 	return (uint)b;
 }
 
-// inclusive prefix sum over the wave
-__device__ __forceinline__ uint wave_inclusive(uint v, uint lane)
-{
-	for (int o = 1; o < 64; o <<= 1) { const uint t = __shfl_up(v, o); if ((int)lane >= o) v += t; }
-	return v;
-}
+// What decides a lane of the count and the scatter below: a source has one method, lane(i) -> the pixel lane i stands for, its count
+// at selection time and its budget (0: not listed; pixel and count are then not used).  The row-set source walks rt_adaptive.h's RowMap;
+// rt_dilate.h has the one that walks the listed mask.
+struct BudgetLane { uint pixel, count, budget; };
+struct RowSetSource {
+	PixelStats St;
+	AdaptiveArgs A;
+	int cap;
+	RowMap M;
+	__device__ __forceinline__ BudgetLane lane(int i) const
+	{
+		if (i >= M.nPixels) return BudgetLane{ 0u, 0u, 0u };
+		const int p = row_map_pixel(M, i);
+		const uint count = St.count[p];
+		return BudgetLane{ (uint)p, count, pixel_budget(count, St.sumY[p], St.sumYY[p], A, cap) };
+	}
+};
 
-__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_budget_count(PixelStats St, AdaptiveArgs A, int cap, RowMap M, uint* blockPixels, uint* blockBudget)
+// a block of RT_SELECT_BLOCK lanes: its listed pixels and the sum of their budgets
+template <class Source> __device__ __forceinline__ void budget_count_body(const Source& S, uint* blockPixels, uint* blockBudget)
 {
 	__shared__ uint wavePixels[RT_SELECT_BLOCK / 64], waveBudget[RT_SELECT_BLOCK / 64];
-	const int i = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
-	const int p = i < M.nPixels ? row_map_pixel(M, i) : 0;
-	const uint b = i < M.nPixels ? pixel_budget(St.count[p], St.sumY[p], St.sumYY[p], A, cap) : 0u;
+	const uint b = S.lane(blockIdx.x * RT_SELECT_BLOCK + threadIdx.x).budget;
 	const uint lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const unsigned long long mask = __ballot(b != 0);
+	const bits64 mask = __ballot(b != 0);
 	const uint incl = wave_inclusive(b, lane);
 	if (lane == 63) wavePixels[wave] = (uint)__popcll(mask), waveBudget[wave] = incl;
 	__syncthreads();
@@ -67,6 +79,11 @@ __global__ void __launch_bounds__(RT_SELECT_BLOCK) k_budget_count(PixelStats St,
 		for (int w = 0; w < RT_SELECT_BLOCK / 64; w++) pixels += wavePixels[w], budget += waveBudget[w];
 		blockPixels[blockIdx.x] = pixels, blockBudget[blockIdx.x] = budget;
 	}
+}
+
+__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_budget_count(PixelStats St, AdaptiveArgs A, int cap, RowMap M, uint* blockPixels, uint* blockBudget)
+{
+	budget_count_body(RowSetSource{ St, A, cap, M }, blockPixels, blockBudget);
 }
 
 // one block: both arrays -> their exclusive prefix sums; *nActive and *nSamples the totals.  The budgets are summed in 64 bits (a 4K frame
@@ -108,24 +125,23 @@ __global__ void __launch_bounds__(RT_SELECT_SCAN_BLOCK) k_budget_scan(uint* bloc
 }
 
 // Runs only after the host has seen that the total of the budgets fits the pool (nSamples records).  Entries: at < the total of the
-// pixels <= M.nPixels; records: below the total of the budgets -- the count and this kernel evaluate one function on the same statistics.
-__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_budget_scatter(PixelStats St, AdaptiveArgs A, int cap, RowMap M, const uint* pixelBase, const uint* budgetBase, uint* list, BudgetPlan B)
+// listed pixels <= the lanes of the launch; records: below the total of the budgets -- the count and this body evaluate one source on the
+// same statistics.
+template <class Source> __device__ __forceinline__ void budget_scatter_body(const Source& S, const uint* pixelBase, const uint* budgetBase, uint* list, BudgetPlan B)
 {
 	__shared__ uint wavePixels[RT_SELECT_BLOCK / 64], waveBudget[RT_SELECT_BLOCK / 64];
-	const int i = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
-	const int p = i < M.nPixels ? row_map_pixel(M, i) : 0; // the mapped pixel: what the list and the records name
-	const uint count = i < M.nPixels ? St.count[p] : 0u;
-	const uint b = i < M.nPixels ? pixel_budget(count, St.sumY[p], St.sumYY[p], A, cap) : 0u;
+	const BudgetLane L = S.lane(blockIdx.x * RT_SELECT_BLOCK + threadIdx.x); // L.pixel: what the list and the records name
+	const uint b = L.budget;
 	const uint lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const unsigned long long mask = __ballot(b != 0);
-	const uint incl = wave_inclusive(b, lane); // non-decreasing over the lanes: an inactive lane adds 0
+	const bits64 mask = __ballot(b != 0);
+	const uint incl = wave_inclusive(b, lane); // non-decreasing over the lanes: an unlisted lane adds 0
 	if (lane == 63) wavePixels[wave] = (uint)__popcll(mask), waveBudget[wave] = incl;
 	__syncthreads();
 	uint at = pixelBase[blockIdx.x], waveOffset = budgetBase[blockIdx.x];
 	for (uint w = 0; w < wave; w++) at += wavePixels[w], waveOffset += waveBudget[w];
 	if (b != 0) {
 		at += lanes_below(mask);
-		list[at] = (uint)p, B.budget[at] = b, B.first[at] = count, B.offset[at] = waveOffset + incl - b;
+		list[at] = L.pixel, B.budget[at] = b, B.first[at] = L.count, B.offset[at] = waveOffset + incl - b;
 	}
 	// the wave's records: record j of the wave belongs to the first lane whose inclusive sum is past j
 	const uint waveSamples = waveBudget[wave];
@@ -137,9 +153,14 @@ __global__ void __launch_bounds__(RT_SELECT_BLOCK) k_budget_scatter(PixelStats S
 			if (probe <= j) owner += step;
 		}
 		const int src = (int)min(owner, 63u); // (j >= waveSamples: no owner, nothing written)
-		const uint ownerPixel = __shfl((uint)p, src), ownerCount = __shfl(count, src), ownerStart = __shfl(incl - b, src);
+		const uint ownerPixel = __shfl(L.pixel, src), ownerCount = __shfl(L.count, src), ownerStart = __shfl(incl - b, src);
 		if (j < waveSamples) B.records[waveOffset + j] = make_uint2(ownerPixel, ownerCount + (j - ownerStart));
 	}
+}
+
+__global__ void __launch_bounds__(RT_SELECT_BLOCK) k_budget_scatter(PixelStats St, AdaptiveArgs A, int cap, RowMap M, const uint* pixelBase, const uint* budgetBase, uint* list, BudgetPlan B)
+{
+	budget_scatter_body(RowSetSource{ St, A, cap, M }, pixelBase, budgetBase, list, B);
 }
 
 // k_accumulate<true> (rt_kernels.h) with lane = list entry: the entry's b samples, adjacent in the pool, in frame order

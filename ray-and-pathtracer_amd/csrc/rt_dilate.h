@@ -11,19 +11,18 @@
 //                     of at most 2 r + 1 <= 33 bits of the linear index, in at most two words; clipping the run to the pixel's own row is
 //                     all the row clip there is, whatever the width is to 64 (several rows in a word, a row across words)
 //   k_dilate_cols     vertical: listed = raw || (eligible && OR of single bits of 'rows' at p + dy * width, rows y + dy inside the frame);
-//                     stores the listed mask and the block's total -- k_select_count's part in the compaction
+//                     stores the listed mask and the block's total -- k_select_count's part in the compaction, by its block_total_of
 //   k_select_scan     rt_adaptive.h's own, unchanged
-//   k_dilate_scatter  k_select_scatter on the listed mask: a bit per lane instead of the predicate
+//   k_dilate_scatter  k_select_scatter on the listed mask: a bit per lane instead of the predicate, into the same scatter_listed
 // The vertical OR costs up to 33 bit reads, so it runs once and its result is kept as a fourth mask: the scatter, and the budget form's
 // count (once per cap tried) and scatter, read one word per wave instead of walking the column again.
 // The budget form (rt_select_budget_dilated) makes rt_budget.h's plan over the listed mask: a raw-active pixel gets pixel_budget, a pixel
-// listed by dilation alone gets 1; only listed pixels' statistics are read (their own).  The scan is k_budget_scan, unchanged.
+// listed by dilation alone gets 1; only listed pixels' statistics are read (their own).  Its count and scatter are rt_budget.h's bodies
+// over DilatedSource; the scan is k_budget_scan, unchanged.
 #pragma once
 #include "rt_budget.h"
 
 namespace rtd {
-
-typedef unsigned long long bits64;
 
 struct DilateMasks {
 	bits64* raw;      // rt_select_active's predicate
@@ -67,7 +66,6 @@ __global__ void __launch_bounds__(RT_SELECT_BLOCK) k_dilate_rows(const bits64* r
 
 __global__ void __launch_bounds__(RT_SELECT_BLOCK) k_dilate_cols(DilateMasks D, int nPixels, int width, int height, int radius, uint* blockTotal)
 {
-	__shared__ uint waveTotal[RT_SELECT_BLOCK / 64];
 	const int i = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
 	bool on = false;
 	if (i < nPixels) {
@@ -79,93 +77,41 @@ __global__ void __launch_bounds__(RT_SELECT_BLOCK) k_dilate_cols(DilateMasks D, 
 		}
 	}
 	const bits64 bits = __ballot(on);
-	if ((threadIdx.x & 63) == 0) {
-		if (i < nPixels) D.listed[i >> 6] = bits;
-		waveTotal[threadIdx.x >> 6] = (uint)__popcll(bits);
-	}
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		uint sum = 0;
-		for (int w = 0; w < RT_SELECT_BLOCK / 64; w++) sum += waveTotal[w];
-		blockTotal[blockIdx.x] = sum;
-	}
+	if ((threadIdx.x & 63) == 0 && i < nPixels) D.listed[i >> 6] = bits;
+	block_total_of(bits, blockTotal);
 }
 
+// k_dilate_cols counted the bits of this mask
 __global__ void __launch_bounds__(RT_SELECT_BLOCK) k_dilate_scatter(const bits64* listed, int nPixels, const uint* blockBase, uint* list)
 {
-	__shared__ uint waveTotal[RT_SELECT_BLOCK / 64];
 	const int i = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
-	const bits64 mask = i < nPixels ? listed[i >> 6] : 0ull; // the wave's word (a wave past the frame has none)
-	const uint wave = threadIdx.x >> 6;
-	if ((threadIdx.x & 63) == 0) waveTotal[wave] = (uint)__popcll(mask);
-	__syncthreads();
-	if (!((mask >> (threadIdx.x & 63)) & 1ull)) return;
-	uint at = blockBase[blockIdx.x] + lanes_below(mask);
-	for (uint w = 0; w < wave; w++) at += waveTotal[w];
-	list[at] = (uint)i; // at < the grand total <= nPixels: k_dilate_cols counted the bits of this mask
+	scatter_listed(i < nPixels ? listed[i >> 6] : 0ull, (uint)i, blockBase, list); // the wave's word (a wave past the frame has none)
 }
 
-// a lane's budget under the listed mask: rt_select_budget's on a raw-active pixel, 1 on a pixel listed by dilation alone, 0 unlisted.
-// 'count' is read for listed pixels only (its first frame).
-__device__ __forceinline__ uint dilated_budget(const DilateMasks& D, const PixelStats& St, const AdaptiveArgs& A, int cap, int i, int nPixels, uint& count)
-{
-	count = 0;
-	if (i >= nPixels || !mask_bit(D.listed, i)) return 0u;
-	count = St.count[i];
-	if (!mask_bit(D.raw, i)) return 1u;
-	return pixel_budget(count, St.sumY[i], St.sumYY[i], A, cap); // >= 1: the raw mask is pixel_active of these statistics
-}
+// rt_budget.h's source over the listed mask, lane i = pixel i: rt_select_budget's budget on a raw-active pixel, 1 on a pixel listed by
+// dilation alone, 0 unlisted.  Only listed pixels' statistics are read.
+struct DilatedSource {
+	DilateMasks D;
+	PixelStats St;
+	AdaptiveArgs A;
+	int cap, nPixels;
+	__device__ __forceinline__ BudgetLane lane(int i) const
+	{
+		if (i >= nPixels || !mask_bit(D.listed, i)) return BudgetLane{ (uint)i, 0u, 0u };
+		const uint count = St.count[i];
+		if (!mask_bit(D.raw, i)) return BudgetLane{ (uint)i, count, 1u };
+		return BudgetLane{ (uint)i, count, pixel_budget(count, St.sumY[i], St.sumYY[i], A, cap) }; // >= 1: the raw mask is pixel_active of these statistics
+	}
+};
 
 __global__ void __launch_bounds__(RT_SELECT_BLOCK) k_dilate_budget_count(DilateMasks D, PixelStats St, AdaptiveArgs A, int cap, int nPixels, uint* blockPixels, uint* blockBudget)
 {
-	__shared__ uint wavePixels[RT_SELECT_BLOCK / 64], waveBudget[RT_SELECT_BLOCK / 64];
-	const int i = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
-	uint count;
-	const uint b = dilated_budget(D, St, A, cap, i, nPixels, count);
-	const uint lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const bits64 mask = __ballot(b != 0);
-	const uint incl = wave_inclusive(b, lane);
-	if (lane == 63) wavePixels[wave] = (uint)__popcll(mask), waveBudget[wave] = incl;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		uint pixels = 0, budget = 0; // a block's budgets: at most RT_SELECT_BLOCK * 1024
-		for (int w = 0; w < RT_SELECT_BLOCK / 64; w++) pixels += wavePixels[w], budget += waveBudget[w];
-		blockPixels[blockIdx.x] = pixels, blockBudget[blockIdx.x] = budget;
-	}
+	budget_count_body(DilatedSource{ D, St, A, cap, nPixels }, blockPixels, blockBudget);
 }
 
-// k_budget_scatter over the listed mask.  Runs only after the host has seen that the total of the budgets fits the pool; entries and
-// records stay below the totals the count pass made from the same masks and statistics.
 __global__ void __launch_bounds__(RT_SELECT_BLOCK) k_dilate_budget_scatter(DilateMasks D, PixelStats St, AdaptiveArgs A, int cap, int nPixels, const uint* pixelBase, const uint* budgetBase, uint* list, BudgetPlan B)
 {
-	__shared__ uint wavePixels[RT_SELECT_BLOCK / 64], waveBudget[RT_SELECT_BLOCK / 64];
-	const int i = blockIdx.x * RT_SELECT_BLOCK + threadIdx.x;
-	uint count;
-	const uint b = dilated_budget(D, St, A, cap, i, nPixels, count);
-	const uint lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const bits64 mask = __ballot(b != 0);
-	const uint incl = wave_inclusive(b, lane); // non-decreasing over the lanes: an unlisted lane adds 0
-	if (lane == 63) wavePixels[wave] = (uint)__popcll(mask), waveBudget[wave] = incl;
-	__syncthreads();
-	uint at = pixelBase[blockIdx.x], waveOffset = budgetBase[blockIdx.x];
-	for (uint w = 0; w < wave; w++) at += wavePixels[w], waveOffset += waveBudget[w];
-	if (b != 0) {
-		at += lanes_below(mask);
-		list[at] = (uint)i, B.budget[at] = b, B.first[at] = count, B.offset[at] = waveOffset + incl - b;
-	}
-	// the wave's records, expanded together as in k_budget_scatter: record j belongs to the first lane whose inclusive sum is past j
-	const uint waveSamples = waveBudget[wave];
-	for (uint j0 = 0; j0 < waveSamples; j0 += 64) { // (wave-uniform trip count: every lane takes part in the shuffles)
-		const uint j = j0 + lane;
-		uint owner = 0;
-		for (uint step = 32; step; step >>= 1) {
-			const uint probe = __shfl(incl, (int)(owner + step - 1));
-			if (probe <= j) owner += step;
-		}
-		const int src = (int)min(owner, 63u); // (j >= waveSamples: no owner, nothing written)
-		const uint ownerPixel = __shfl((uint)i, src), ownerCount = __shfl(count, src), ownerStart = __shfl(incl - b, src);
-		if (j < waveSamples) B.records[waveOffset + j] = make_uint2(ownerPixel, ownerCount + (j - ownerStart));
-	}
+	budget_scatter_body(DilatedSource{ D, St, A, cap, nPixels }, pixelBase, budgetBase, list, B);
 }
 
 } // namespace rtd
