@@ -6,9 +6,10 @@
 //   g++ -std=c++17 -O2 examples/render_scene.cpp -Iray-and-pathtracer_amd/host \
 //       -Lray-and-pathtracer_amd/host -lrapt_host -Lray-and-pathtracer_amd/csrc -lrt_amd \
 //       -Wl,-rpath,$PWD/ray-and-pathtracer_amd/host -Wl,-rpath,$PWD/ray-and-pathtracer_amd/csrc -o render_scene
-//   ./render_scene scene.rapt out.ppm 640 360 path 16 [all | d0,d1,...]
+//   ./render_scene scene.rapt out.ppm 640 360 path 16 [all | d0,d1,...] [--filter reference|point|box|tent]
 // The optional last argument spreads every Tick over several GPUs (one rt_ctx and one host thread per device,
-// rows interleaved, rt_gather_rows into device d0): "all" = every visible device.
+// rows interleaved, rt_gather_rows into device d0): "all" = every visible device.  --filter (anywhere after the frame count) sets
+// Renderer::pixelFilter: the sub-pixel camera samples of path mode (rt_set_pixel_filter; default: the reference's truncated jitter).
 #include "rapt.h"
 #include <cstdio>
 #include <cstdlib>
@@ -20,7 +21,18 @@ using namespace rapt;
 
 int main(int argc, char** argv)
 {
-	if (argc < 7) { fprintf(stderr, "usage: %s scene.rapt out.ppm width height whitted|path frames [all | d0,d1,...]\n", argv[0]); return 2; }
+	if (argc < 7) { fprintf(stderr, "usage: %s scene.rapt out.ppm width height whitted|path frames [all | d0,d1,...] [--filter reference|point|box|tent]\n", argv[0]); return 2; }
+	int filter = RT_FILTER_REFERENCE;
+	for (int a = 7; a < argc; a++) {
+		if (strcmp(argv[a], "--filter") != 0) continue;
+		static const char* const names[4] = { "reference", "point", "box", "tent" };
+		int k = -1;
+		for (int i = 0; i < 4 && a + 1 < argc; i++) if (strcmp(argv[a + 1], names[i]) == 0) k = i;
+		if (k < 0) { fprintf(stderr, "--filter reference|point|box|tent\n"); return 2; }
+		filter = k;
+		for (int b = a; b + 2 < argc; b++) argv[b] = argv[b + 2]; // the positional arguments close up
+		argc -= 2, a--;
+	}
 	const int w = atoi(argv[3]), h = atoi(argv[4]), frames = atoi(argv[6]);
 	const bool path = strcmp(argv[5], "path") == 0;
 	try {
@@ -33,6 +45,7 @@ int main(int argc, char** argv)
 				app.UseDevices(devs);
 			}
 		}
+		app.pixelFilter = filter;
 		app.Init();                          // allocates the accumulator on the GPU(s)
 		app.scene.LoadFile(argv[1]);         // meshes, materials, lights, BVH / TLAS (host builders)
 		if (path) app.scene.toogleRaytracer(); // key 'P' in the reference: path tracing, lights sampled

@@ -162,6 +162,37 @@ int rt_render(rt_ctx* ctx, int mode, uint32_t frame0, int nframes, uint32_t seed
 /* Same for the rows row_first + k*row_stride, k < row_count: the row-interleaved pixel shard used
  * when the frame is split over several GPUs (rank r of n renders row_first = r, row_stride = n). */
 int rt_render_rows(rt_ctx* ctx, int mode, uint32_t frame0, int nframes, uint32_t seed_base, int row_first, int row_stride, int row_count, int max_depth);
+/* ---- pixel filter: sub-pixel camera samples in path mode ------------------------------------------------------------------
+ * The reference's Tick draws a jitter and GetPrimaryRay(const int, const int) truncates it: every path sample of pixel (x, y) looks through
+ * the corner of one of the integer pixels [x - 1, x] x [y - 1, y], and a converged frame is a 2 x 2 box blur of a point-sampled image.
+ * RT_FILTER_REFERENCE (the default of a context) is that, bit for bit.  The other kinds apply to RT_MODE_PATH camera samples -- rt_render,
+ * rt_render_rows, rt_render_active, rt_render_budget -- and change nothing else: Whitted mode and rt_trace_batch* ignore the filter.
+ * Definition for sample (pixel p = y * width + x, frame f, seed_base); all arithmetic f32, IEEE divide and square root, no contraction:
+ *   s  = seed_base + p + f * width * height                       (uint32, wrapping)
+ *   the path's random stream starts at StreamSeed(s) = InitSeed(s), or 0x9E3779B9 where that is 0, with NO draw consumed: the stream
+ *   rt_trace_batch gives ray s - seed_base (reference mode starts the path two draws in: they were its jitter);
+ *   js = StreamSeed(~s); u1 = RandomFloat(js); u2 = RandomFloat(js)  (a stream of its own: the offset is not tied to the first bounce)
+ *   dx = o(u1), dy = o(u2) with  POINT: o(u) = 0 (no draw is made)
+ *                                BOX:   o(u) = u - 0.5f
+ *                                TENT:  o(u) = u < 0.5f ? sqrtf(2 * u) - 1 : 1 - sqrtf(2 - 2 * u)       (radius 1 pixel)
+ *   (RandomFloat can return 1.0f: the offsets lie in the closed intervals [-0.5, 0.5] and [-1, 1])
+ *   fx = (float)x + dx; fy = (float)y + dy
+ *   the ray is Camera::GetPrimaryRay's on u = fx * (1.0f / width), v = fy * (1.0f / height): P = topLeft + u * (topRight - topLeft) +
+ *   v * (bottomLeft - topLeft), D = normalize(P - camPos); integral fx, fy give GetPrimaryRay(x, y)'s bits.
+ * The filter is centred on the ray rt_render_aovs traces for the pixel, not on x + 0.5.  A sample is accumulated into its own pixel (filter
+ * importance sampling, no splatting), so it stays a function of (seed_base, pixel, frame, kind): lists, budget plans, row shards, the
+ * statistics, rt_reproject and both denoisers compose with it as they do with the reference's samples.
+ * A fisheye camera: POINT is GetPrimaryRay(x, y) itself; BOX / TENT make the render calls return RT_E_UNSUPPORTED (nothing pins them).
+ * With the Q-learning sampler on and a kind other than REFERENCE set, the render calls return RT_E_UNSUPPORTED (its learn_mask is defined
+ * on the post-jitter state).  rt_set_pixel_filter does not clear the accumulator and does not make the G-buffer stale; the primary-hit table
+ * (RT_PRIMARY_TABLE) serves reference-mode batches only: with a filter kind every camera ray is traced.  RT_E_ARG: an unknown kind.
+ * rt_sample_rays: the camera rays of one frame's path samples under the context's kind (REFERENCE included), rows [y0, y1): O_out, D_out
+ *   3 floats per pixel, row-major; one launch, a lane per pixel, counted as a query in rt_get_profile.  Synchronous.  RT_E_UNSUPPORTED:
+ *   BOX / TENT under a fisheye camera. */
+enum { RT_FILTER_REFERENCE = 0, RT_FILTER_POINT = 1, RT_FILTER_BOX = 2, RT_FILTER_TENT = 3 };
+int rt_set_pixel_filter(rt_ctx* ctx, int kind);
+int rt_get_pixel_filter(const rt_ctx* ctx);
+int rt_sample_rays(rt_ctx* ctx, uint32_t frame, uint32_t seed_base, int y0, int y1, float* O_out, float* D_out);
 /* memset of the accumulator (renderer.cpp:9, :274) */
 int rt_clear(rt_ctx* ctx);
 /* rows [y0, y1) of the float4 accumulator -> host (Renderer::accumulator, renderer.h:98) */
@@ -255,8 +286,9 @@ int rt_set_scene_raytracer(rt_ctx* ctx, int flag);
 int rt_trace_batch_energy(rt_ctx* ctx, int mode, int n, const float* O, const float* D, int depth, uint32_t seed_base, const float* energy, float* rgb_out);
 
 /* ---- G-buffer and denoised preview ------------------------------------------------------------------
- * rt_render_aovs: the G-buffer of the frame -- per pixel, Camera::GetPrimaryRay(x, y) + Scene::FindNearest(t_min) (the first hit of every
- *   path sample of the pixel: Tick's jitter is truncated by GetPrimaryRay's int parameters) as the rt_hit record rt_intersect_batch gives,
+ * rt_render_aovs: the G-buffer of the frame -- per pixel, Camera::GetPrimaryRay(x, y) + Scene::FindNearest(t_min) (in reference mode ONE of
+ *   the up to four integer-pixel rays the pixel's path samples take: Tick's jitter, truncated by GetPrimaryRay's int parameters, lands on
+ *   pixels [x - 1, x] x [y - 1, y]; with a pixel filter set, rt_set_pixel_filter, the ray the pixel's samples are centred on) as the rt_hit record rt_intersect_batch gives,
  *   an albedo (diffuse: col * albedo, metal / glass: col, a light: the light's col, a miss: 0) and the world position O + D * t (f32).
  *   t_min: 0.001f is what Sample uses (renderer.cpp:133), 1e-6f what Trace uses.  The buffers belong to the context (allocated on first
  *   use); the launch counts as a query in rt_get_profile.  The G-buffer goes stale with rt_upload_scene, rt_set_time and an rt_set_camera

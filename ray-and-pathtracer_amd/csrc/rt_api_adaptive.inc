@@ -217,7 +217,7 @@ int rt_render_active(rt_ctx* c, uint32_t frame0, int nframes, uint32_t seed_base
 	if (c->Qt.on) return fail(c, RT_E_UNSUPPORTED, "rt_render_active: not with the Q-learning sampler on");
 	if (c->nActive == 0) return RT_OK;
 	HIPCHK(c, hipSetDevice(c->device));
-	return render_batches(c, RT_MODE_PATH, frame0, nframes, seed_base, 0, 1, (size_t)c->nActive, c->activeList, max_depth);
+	return render_batches(c, RT_MODE_PATH, frame0, nframes, seed_base, 0, 1, (size_t)c->nActive, c->activeList, max_depth, "rt_render_active");
 }
 
 int rt_resolve_adaptive(rt_ctx* c, int y0, int y1, uint32_t* rgb8_out)

@@ -385,7 +385,9 @@ static int primary_table_for(rt_ctx* c, const RenderParams& R, hipStream_t st, b
 {
 	rt_ctx::DenseState& d = c->dense;
 	*use = false;
-	if (!c->knobs.primaryTable || R.customO) return RT_OK;
+	// (a filter kind: the samples of a pixel take distinct rays, which no table of the frame's integer-pixel rays holds; such a batch does
+	// not count towards a rebuild either)
+	if (!c->knobs.primaryTable || R.customO || R.filter != RT_FILTER_REFERENCE) return RT_OK;
 	if (d.tableGen == c->sceneGen) { *use = true; return RT_OK; }
 	const size_t records = (size_t)(c->width + 2) * (size_t)(c->height + 2);
 	if (d.tablePendingGen != c->sceneGen) d.tablePendingGen = c->sceneGen, d.tablePending = 0;
@@ -558,12 +560,25 @@ static int stats_clear(rt_ctx* c)
 	return RT_OK;
 }
 
+// rt_set_pixel_filter's rules for a path-mode render call (include/rt_amd.h); fn: the entry point the caller came through
+static int filter_check(rt_ctx* c, const char* fn)
+{
+	if (c->pixelFilter == RT_FILTER_REFERENCE) return RT_OK;
+	if (c->Qt.on) return fail(c, RT_E_UNSUPPORTED, "%s: a pixel filter with the Q-learning sampler on (its learn_mask is defined on the post-jitter state)", fn);
+	if (c->C.fisheye && c->pixelFilter != RT_FILTER_POINT) return fail(c, RT_E_UNSUPPORTED, "%s: RT_FILTER_BOX / RT_FILTER_TENT under a fisheye camera", fn);
+	return RT_OK;
+}
+
 // Frames [frame0, frame0 + nframes) of one tile of pixels -- tilePixels of them: the rows row_first + k * row_stride of rt_render_rows, or
 // the entries of pixelList (rt_render_active) -- in batches of frames: the finished samples of a batch live in a [frame][tile pixel]
 // buffer (<= 4 GiB), which k_accumulate adds to the accumulator (and, with rt_stats_enable, to the pixels' statistics) in frame order.
-static int render_batches(rt_ctx* c, int mode, uint32_t frame0, int nframes, uint32_t seed_base, int row_first, int row_stride, size_t tilePixels, const uint* pixelList, int max_depth)
+static int render_batches(rt_ctx* c, int mode, uint32_t frame0, int nframes, uint32_t seed_base, int row_first, int row_stride, size_t tilePixels, const uint* pixelList, int max_depth, const char* fn)
 {
-	if (mode == RT_MODE_PATH) drop_plan(c); // the batch moves the counts a budget plan was made from
+	if (mode == RT_MODE_PATH) {
+		const int rc = filter_check(c, fn);
+		if (rc != RT_OK) return rc;
+		drop_plan(c); // the batch moves the counts a budget plan was made from
+	}
 	const size_t sampleGiB = (size_t)c->knobs.sampleGiB;
 	int batchFrames = (int)((sampleGiB << 30) / (tilePixels * sizeof(float4)));
 	if (batchFrames < 1) batchFrames = 1;
@@ -582,6 +597,7 @@ static int render_batches(rt_ctx* c, int mode, uint32_t frame0, int nframes, uin
 		R.mode = mode, R.frame0 = frame0 + (uint)f, R.nSamples = (uint)total, R.tilePixels = (uint)tilePixels, R.samples = c->samples;
 		R.seedBase = seed_base, R.rowFirst = row_first, R.rowStride = row_stride, R.maxDepth = max_depth, R.accum = c->accum;
 		R.pixelList = pixelList;
+		R.filter = mode == RT_MODE_PATH ? c->pixelFilter : RT_FILTER_REFERENCE;
 		R.deferGamma = mode == RT_MODE_PATH ? c->knobs.deferGamma : 0;
 		R.sceneRt = -1; // (rt_render is Tick's loop: the flag is what the mode says)
 		if (mode == RT_MODE_PATH && c->Qt.on && !c->pathUnsupported && !stream_eligible(c, mode, total))
@@ -610,7 +626,7 @@ int rt_render_rows(rt_ctx* c, int mode, uint32_t frame0, int nframes, uint32_t s
 			HIPCHK(c, hipMemsetAsync(c->accum + (size_t)(row_first + k * row_stride) * c->width, 0, (size_t)c->width * sizeof(float4), c->stream));
 		return RT_OK;
 	}
-	return render_batches(c, mode, frame0, nframes, seed_base, row_first, row_stride, (size_t)c->width * row_count, nullptr, max_depth);
+	return render_batches(c, mode, frame0, nframes, seed_base, row_first, row_stride, (size_t)c->width * row_count, nullptr, max_depth, "rt_render / rt_render_rows");
 }
 
 int rt_render(rt_ctx* c, int mode, uint32_t frame0, int nframes, uint32_t seed_base, int y0, int y1, int max_depth)
@@ -670,3 +686,37 @@ int rt_trace_batch_energy(rt_ctx* c, int mode, int n, const float* O, const floa
 	return rc;
 }
 
+// ---- pixel filter (include/rt_amd.h) ------------------------------------------------------------------
+int rt_set_pixel_filter(rt_ctx* c, int kind)
+{
+	if (!c || kind < RT_FILTER_REFERENCE || kind > RT_FILTER_TENT) return fail(c, RT_E_ARG, "rt_set_pixel_filter: kind %d", kind);
+	c->pixelFilter = kind; // neither the accumulator nor the G-buffer depends on it
+	return RT_OK;
+}
+int rt_get_pixel_filter(const rt_ctx* c) { return c ? c->pixelFilter : RT_E_ARG; }
+
+int rt_sample_rays(rt_ctx* c, uint32_t frame, uint32_t seed_base, int y0, int y1, float* O_out, float* D_out)
+{
+	if (!c || !O_out || !D_out) return fail(c, RT_E_ARG, "rt_sample_rays: null argument");
+	if (y0 < 0 || y1 > c->height || y0 >= y1) return fail(c, RT_E_ARG, "rt_sample_rays: rows [%d,%d) outside 0..%d", y0, y1, c->height);
+	if (c->C.fisheye && c->pixelFilter > RT_FILTER_POINT) return fail(c, RT_E_UNSUPPORTED, "rt_sample_rays: RT_FILTER_BOX / RT_FILTER_TENT under a fisheye camera");
+	HIPCHK(c, hipSetDevice(c->device));
+	const size_t n = (size_t)c->width * (size_t)(y1 - y0);
+	float *dO = nullptr, *dD = nullptr;
+	std::vector<void*> tmp;
+	struct Guard { rt_ctx* c; std::vector<void*>& v; ~Guard() { (void)hipStreamSynchronize(c->stream); free_pool(v); } } guard{ c, tmp }; // every return path frees
+	HIPCHK(c, dalloc(tmp, &dO, 3 * n));
+	HIPCHK(c, dalloc(tmp, &dD, 3 * n));
+	RenderParams R;
+	memset(&R, 0, sizeof(R));
+	R.mode = RT_MODE_PATH, R.frame0 = frame, R.nSamples = (uint)n, R.tilePixels = (uint)n, R.seedBase = seed_base, R.rowFirst = y0, R.rowStride = 1;
+	R.sceneRt = -1, R.filter = c->pixelFilter;
+	prof_begin(c, K_QUERY);
+	hipLaunchKernelGGL(k_sample_rays, dim3((unsigned)((n + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, c->stream, c->C, R, dO, dD);
+	prof_end(c);
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipMemcpyAsync(O_out, dO, 12 * n, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpyAsync(D_out, dD, 12 * n, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	return RT_OK;
+}

@@ -13,6 +13,7 @@
 //   rt_api_adaptive.inc rt_stats_*, rt_select_active, the active-pixel list, rt_render_active, rt_resolve_adaptive
 //   rt_api_reproject.inc rt_history_capture, rt_reproject, rt_download_aov_positions
 #pragma once
+#include "../../include/rt_amd.h" // first: the kernels read its enums (RT_FILTER_*)
 #include "rt_kernels.h"
 #include "rt_stream.h"
 #include "rt_mega.h"
@@ -24,7 +25,6 @@
 #include "rt_denoise_var.h"
 #include "rt_reproject.h"
 #include "rt_gather.h"
-#include "../../include/rt_amd.h"
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -128,6 +128,7 @@ struct rt_ctx {
 	// camera
 	DCamera C{};
 	bool cameraSet = false;
+	int pixelFilter = RT_FILTER_REFERENCE; // rt_set_pixel_filter: the kind of the path-mode camera samples (RenderParams::filter of their batches)
 	// accumulator
 	float4* accum = nullptr;
 	bool accumOwned = true;

@@ -74,6 +74,8 @@ struct RenderParams {
 	int sceneRt;       // rt_trace_batch with rt_set_scene_raytracer: scene.raytracer as the caller's Scene holds it, when it is NOT what the
 	                   // function called implies (Trace with the flag clear, Sample with it set: renderer.cpp:33-43, 107-121, 143-153) -- the
 	                   // general kernels below; -1: the flag follows the function, as Tick calls it
+	int filter;        // rt_set_pixel_filter: RT_FILTER_* of a path-mode camera sample; read by camera_sample() alone.  (Here: the four bytes
+	                   // were padding in front of the pointers below, so the record's size and every other field's place are the parent's.)
 	const uint* pixelList; // rt_render_active: tile pixel lp is pixel pixelList[lp] (tilePixels = the list's length); nullptr: the row mapping
 	const uint2* plan;     // rt_render_budget (rt_budget.h): sample sid is { pixel, frame - frame0 } = plan[sid]; nullptr: frame-major over the tile
 };
@@ -112,12 +114,25 @@ __device__ __forceinline__ f3 cam_rotate_x(const f3& p, const f3& center, float 
 	res = cam_rotate_y(res, f3(0.f), yAngle);
 	return res + center;
 }
-__device__ __forceinline__ void primary_ray(const DCamera& C, int x, int y, f3& O, f3& D)
+// The pinhole ray through the point (fx, fy) of the pixel grid: u = fx * (1.0f / W), v = fy * (1.0f / H).  primary_ray's pinhole case is
+// this function on ((float)x, (float)y), so integral fx, fy give its bits by construction (rt_set_pixel_filter's BOX / TENT samples are
+// the other callers).
+__device__ __forceinline__ void primary_ray_f(const DCamera& C, float fx, float fy, f3& O, f3& D)
 {
 	const f3 camPos(C.camPos[0], C.camPos[1], C.camPos[2]), TL(C.topLeft[0], C.topLeft[1], C.topLeft[2]);
 	const f3 TR(C.topRight[0], C.topRight[1], C.topRight[2]), BL(C.bottomLeft[0], C.bottomLeft[1], C.bottomLeft[2]);
 	O = camPos;
+	const float u = fx * (1.0f / C.width);
+	const float v = fy * (1.0f / C.height);
+	const f3 P = TL + u * (TR - TL) + v * (BL - TL);
+	D = normalize(P - camPos);
+}
+__device__ __forceinline__ void primary_ray(const DCamera& C, int x, int y, f3& O, f3& D)
+{
 	if (C.fisheye) {
+		const f3 camPos(C.camPos[0], C.camPos[1], C.camPos[2]), TL(C.topLeft[0], C.topLeft[1], C.topLeft[2]);
+		const f3 TR(C.topRight[0], C.topRight[1], C.topRight[2]), BL(C.bottomLeft[0], C.bottomLeft[1], C.bottomLeft[2]);
+		O = camPos;
 		const float aspect = (float)C.width / (float)C.height;
 		f3 screenCenter = TL + .5f * (TR - TL) + .5f * (BL - TL);
 		const float u = (float)(x - C.width / 2) * (aspect * C.viewAngle / C.width);
@@ -126,10 +141,7 @@ __device__ __forceinline__ void primary_ray(const DCamera& C, int x, int y, f3& 
 		D = normalize(newRay);
 		return;
 	}
-	const float u = (float)x * (1.0f / C.width);
-	const float v = (float)y * (1.0f / C.height);
-	const f3 P = TL + u * (TR - TL) + v * (BL - TL);
-	D = normalize(P - camPos);
+	primary_ray_f(C, (float)x, (float)y, O, D);
 }
 
 // ---- lights (template/scene.h:121-137, 152-165) -----------------------------------------------
@@ -395,20 +407,45 @@ __device__ __forceinline__ void sample_pixel_frame(const DCamera& C, const Rende
 	frame = R.frame0 + sid / R.tilePixels;
 	tile_pixel(C, R, lp, x, y);
 }
+// The offset of a filtered camera sample from its pixel's ray, from one uniform draw of [0, 1] (RandomFloat can return 1.0f: the
+// intervals are closed): POINT 0, BOX u - 0.5, TENT (radius 1) the inverse of the tent's distribution function.
+__device__ __forceinline__ float filter_offset(int kind, float u)
+{
+	if (kind == RT_FILTER_BOX) return u - 0.5f;
+	if (kind == RT_FILTER_TENT) return u < 0.5f ? sqrtf(2 * u) - 1 : 1 - sqrtf(2 - 2 * u);
+	return 0.0f;
+}
+// The ONE place that reads R.filter: camera sample (x, y, frame) of a path batch -> the state its path's random stream starts in and its
+// ray.  REFERENCE (renderer.cpp:263-278): the stream's first two draws are the jitter, truncated by primary_ray's int parameters.
+// A filter kind (include/rt_amd.h rt_set_pixel_filter): the path's stream starts at StreamSeed(s) with nothing drawn, the jitter has
+// the stream StreamSeed(~s) of its own, and the ray goes through (x + dx, y + dy).  R.filter is the same for every lane of a launch.
+__device__ __forceinline__ void camera_sample(const DCamera& C, const RenderParams& R, int x, int y, uint frame, f3& O, f3& D, uint& seed)
+{
+	const uint s = R.seedBase + (uint)(y * C.width + x) + frame * (uint)(C.width * C.height);
+	seed = StreamSeed(s);
+	int px = x, py = y;
+	if (R.filter == RT_FILTER_REFERENCE) {
+		float newX = x + (RandomFloat(seed) * 2 - 1);
+		float newY = y + (RandomFloat(seed) * 2 - 1);
+		px = (int)newX, py = (int)newY; // jitter truncated by the int parameters (renderer.cpp:276-278)
+	} else if (R.filter != RT_FILTER_POINT && !C.fisheye) { // (a fisheye camera has whole pixels only: the host refuses BOX / TENT there)
+		uint js = StreamSeed(~s);
+		const float u1 = RandomFloat(js), u2 = RandomFloat(js);
+		primary_ray_f(C, (float)x + filter_offset(R.filter, u1), (float)y + filter_offset(R.filter, u2), O, D);
+		return;
+	}
+	primary_ray(C, px, py, O, D); // ONE call for the reference's pixel and POINT's: the fisheye body is compiled once per caller
+}
 // camera sample 'sid' of the pool (renderer.cpp:263-278): its seed, jitter and primary ray; deterministic in (R, C, sid)
 __device__ __forceinline__ void sample_primary(const DCamera& C, const RenderParams& R, uint sid, f3& O, f3& D, uint& seed)
 {
 	int x, y;
 	uint frame;
 	sample_pixel_frame(C, R, sid, x, y, frame);
-	const int pixel = y * C.width + x;
-	seed = StreamSeed(R.seedBase + (uint)pixel + frame * (uint)(C.width * C.height));
-	if (R.mode == 0) primary_ray(C, x, y, O, D);
-	else {
-		float newX = x + (RandomFloat(seed) * 2 - 1);
-		float newY = y + (RandomFloat(seed) * 2 - 1);
-		primary_ray(C, (int)newX, (int)newY, O, D); // jitter truncated by the int parameters (renderer.cpp:276-278)
-	}
+	if (R.mode == 0) {
+		seed = StreamSeed(R.seedBase + (uint)(y * C.width + x) + frame * (uint)(C.width * C.height));
+		primary_ray(C, x, y, O, D);
+	} else camera_sample(C, R, x, y, frame, O, D, seed);
 }
 // The pixel whose ray a path-mode camera sample gets: sample_primary up to its primary_ray call, on the same operands (seed: after
 // the two draws).  RandomFloat is uint * 2^-32 rounded to float: 0 gives 0 and 2^32 - 1 rounds to 1.0f, so the jitter r * 2 - 1 lies in
@@ -497,6 +534,18 @@ __global__ void __launch_bounds__(RT_BLOCK) k_generate(DScene S, DCamera C, Rend
 	start_sample(S, C, R, P, slot, R.sampleFirst + (uint)slot, 0, !R.finishInline);
 	P.status[slot] = ST_ACTIVE;
 	if (slot == 0) Q.counts[7] = P.nSlots, Q.counts[1] = 0;
+}
+
+// rt_sample_rays: the camera ray of sample sid of a one-frame path batch over rows, as every pipeline's generate builds it; a lane per pixel
+__global__ void __launch_bounds__(RT_BLOCK) k_sample_rays(DCamera C, RenderParams R, float* outO, float* outD)
+{
+	const uint sid = blockIdx.x * blockDim.x + threadIdx.x;
+	if (sid >= R.nSamples) return;
+	f3 O, D;
+	uint seed;
+	sample_primary(C, R, sid, O, D, seed);
+	outO[3 * (size_t)sid] = O.x, outO[3 * (size_t)sid + 1] = O.y, outO[3 * (size_t)sid + 2] = O.z;
+	outD[3 * (size_t)sid] = D.x, outD[3 * (size_t)sid + 1] = D.y, outD[3 * (size_t)sid + 2] = D.z;
 }
 
 // round bookkeeping between kernels: reset the work heads and the queue counts
@@ -918,10 +967,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_sample_general(DScene S, DCamera C
 			int x, y;
 			uint frame;
 			sample_pixel_frame(C, R, sid, x, y, frame);
-			seed = StreamSeed(R.seedBase + (uint)(y * C.width + x) + frame * (uint)(C.width * C.height));
-			float newX = x + (RandomFloat(seed) * 2 - 1);
-			float newY = y + (RandomFloat(seed) * 2 - 1);
-			primary_ray(C, (int)newX, (int)newY, O, D);
+			camera_sample(C, R, x, y, frame, O, D, seed);
 			depth = 4;
 		}
 		f3 W(1.0f), E(1.0f), Lsum(0.0f);

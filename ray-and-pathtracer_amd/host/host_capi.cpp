@@ -284,6 +284,16 @@ void rth_renderer_set_adaptive_budget(void* h, int passCap, unsigned maxPassSamp
 	Renderer* r = ((RthRenderer*)h)->r;
 	r->adaptivePassCap = passCap, r->adaptiveMaxPassSamples = maxPassSamples;
 }
+// Renderer::pixelFilter, sent to every context at once (the C ABI's render calls of a test see it without a Tick)
+int rth_renderer_set_pixel_filter(void* h, int kind)
+{
+	RthRenderer* r = (RthRenderer*)h;
+	const int before = r->r->pixelFilter;
+	r->r->pixelFilter = kind;
+	try { r->r->SyncPixelFilter(); } catch (const std::exception& e) { r->r->pixelFilter = before; r->err = e.what(); return -1; }
+	return 0;
+}
+int rth_renderer_pixel_filter(void* h) { return ((RthRenderer*)h)->r->pixelFilter; }
 void rth_renderer_set_adaptive_dilate(void* h, int radius) { ((RthRenderer*)h)->r->adaptiveDilate = radius; }
 int rth_renderer_pass_samples(void* h) { return ((RthRenderer*)h)->r->passSamples; }
 int rth_renderer_carried_pixels(void* h) { return ((RthRenderer*)h)->r->carriedPixels; }

@@ -372,8 +372,17 @@ public:
 	bool qlearning = false;
 	int qgrid = 0;
 	uint32_t qlearnMask = 0;          // rt_qlearn_params::learn_mask for the next EnableQLearning (0: every sample pays rewards)
+	// Pixel filter of the path-mode camera samples (rt_set_pixel_filter: RT_FILTER_REFERENCE, the default, is the reference's truncated
+	// jitter; POINT / BOX / TENT are sub-pixel samples centred on the G-buffer's ray).  Tick sends it to every context with the camera.  A
+	// change of kind between two path Ticks is treated like a camera change without a reprojection carry: the Tick clears (the accumulator
+	// would mix two estimators), and under 'adaptive' min_samples whole frames follow.  With BOX / TENT under a fisheye camera, or a kind
+	// other than REFERENCE with the Q-learning sampler, the path Tick throws (RT_E_UNSUPPORTED).
+	int pixelFilter = RT_FILTER_REFERENCE;
+	void SyncPixelFilter();           // pixelFilter -> every context, now (Tick does it anyway)
 	// Denoised preview (path mode only): Tick refreshes the G-buffer when something changed (rt_render_aovs, 0.001f as Sample), filters the
 	// mean with rt_denoise and shows rt_resolve_denoised in screenPixels; 'accumulator' stays the raw download.  Off: Tick is unchanged.
+	// (The G-buffer's ray of a pixel is GetPrimaryRay(x, y): in reference mode one of the up to four integer-pixel rays its samples take,
+	// with a pixelFilter the centre of their footprint.)
 	bool denoise = false;
 	rt_denoise_params denoiseParams = RT_DENOISE_DEFAULTS;
 	// Adaptive sampling (path mode only): Tick keeps per-pixel statistics (rt_stats_enable), renders whole frames until every
@@ -443,6 +452,7 @@ private:
 	bool adaptiveOn = false;          // the context's statistics were enabled by TickAdaptive
 	int wholeFrames = 0;              // whole frames rendered since the accumulator was last cleared
 	uint32_t frameBase = 0;           // 'frame' at the last clear or reprojection carry: rt_render_budget's frame_base
+	int sampledFilter = RT_FILTER_REFERENCE; // pixelFilter of the last path Tick: the kind the accumulator's samples were taken with
 	rt_camera syncedCam{};            // the record of the last SyncCamera
 	bool lastTickAdaptive = false;    // the last Tick was TickAdaptive: the accumulator holds its samples, taken under sampledCam
 	rt_camera sampledCam{};           // ... and of the last adaptive Tick: the camera the accumulator's samples were taken with

@@ -132,6 +132,11 @@ void Renderer::SyncCamera()
 	syncedCam = c;
 }
 
+void Renderer::SyncPixelFilter()
+{
+	for (rt_ctx* k : ctxs) check(k, rt_set_pixel_filter(k, pixelFilter));
+}
+
 // renderer.cpp:240-305 without the animation, input and printf parts.  As in the reference, 'it' is read before a
 // camera change resets the iteration number (:247 vs :253-255): the frame on which the camera changed is resolved
 // with the stale count and does not advance it (:293-294).
@@ -154,7 +159,10 @@ void Renderer::Tick(float /*deltaTime*/)
 	lastTickAdaptive = false;
 	scene.totIterationNumber++;
 	const int it = scene.GetIterationNumber();
-	const bool camChanged = camera.GetChange();
+	SyncPixelFilter();
+	// (a path Tick under another filter kind than the last one's: like a camera change)
+	const bool camChanged = camera.GetChange() || (!scene.raytracer && pixelFilter != sampledFilter);
+	if (!scene.raytracer) sampledFilter = pixelFilter;
 	if (camChanged && !scene.raytracer) {
 		scene.SetIterationNumber(1);
 		for (rt_ctx* k : ctxs) check(k, rt_clear(k)); // accumulator[...] = float3(0) for every pixel (:273-275)
@@ -216,10 +224,13 @@ void Renderer::TickAdaptive()
 	scene.totIterationNumber++;
 	const int it = scene.GetIterationNumber();
 	const int n = (int)ctxs.size();
-	bool reset = camera.GetChange();
+	const bool filterChanged = pixelFilter != sampledFilter; // like a camera change, without a carry: the carried samples would be the old kind's
+	SyncPixelFilter();
+	sampledFilter = pixelFilter;
+	bool reset = camera.GetChange() || filterChanged;
 	// a camera move with 'reproject' set (statistics already on, pinhole before and after): the samples follow their surface points
 	// (only straight after an adaptive Tick: a Whitted Tick in between has overwritten the accumulator under cameras of its own)
-	const bool carry = reset && reproject && adaptiveOn && lastTickAdaptive && !sampledCam.fisheye && !camera.fishEye;
+	const bool carry = reset && !filterChanged && reproject && adaptiveOn && lastTickAdaptive && !sampledCam.fisheye && !camera.fishEye;
 	if (!adaptiveOn) {
 		for (rt_ctx* k : ctxs) check(k, rt_stats_enable(k, 1));
 		adaptiveOn = true, reset = true; // the counts start now, so the accumulator does too

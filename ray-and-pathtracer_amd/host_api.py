@@ -34,9 +34,12 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_select_budget", "rt_download_budgets", "rt_render_budget",
               "rt_history_capture", "rt_reproject", "rt_download_aov_positions",
               "rt_select_active_rows", "rt_select_budget_rows", "rt_gather_stats_rows", "rt_gather_active",
-              "rt_select_active_dilated", "rt_select_budget_dilated"]
+              "rt_select_active_dilated", "rt_select_budget_dilated",
+              "rt_set_pixel_filter", "rt_get_pixel_filter", "rt_sample_rays"]
 
 RT_E_ARG, RT_E_STATE = -2, -5
+# include/rt_amd.h rt_set_pixel_filter
+RT_FILTER_REFERENCE, RT_FILTER_POINT, RT_FILTER_BOX, RT_FILTER_TENT = 0, 1, 2, 3
 RT_E_UNSUPPORTED = -4
 # include/rt_amd.h RT_ADAPTIVE_DEFAULTS (a starting point, not tuned)
 ADAPTIVE_DEFAULTS = dict(min_samples=16, max_samples=1024, threshold=0.05, floor=1e-3)
@@ -232,6 +235,9 @@ def rt_lib():
         L.rt_gather_active.argtypes = [C.c_void_p, C.c_void_p]
         L.rt_select_active_dilated.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.rt_select_budget_dilated.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_set_pixel_filter.argtypes = [C.c_void_p, C.c_int]
+        L.rt_get_pixel_filter.argtypes = [C.c_void_p]
+        L.rt_sample_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _rt = L
     return _rt
 
@@ -502,6 +508,22 @@ class HostRenderer:
     def tick_pixels(self):
         p = C.cast(self.L.rth_renderer_pixels(self.h), C.POINTER(C.c_uint32))
         return np.ctypeslib.as_array(p, shape=(self.hgt, self.w)).copy()
+
+    def set_pixel_filter(self, kind):
+        """rapt::Renderer::pixelFilter (RT_FILTER_*), sent to every context at once: the sub-pixel camera samples of path mode"""
+        self._chk(self.L.rth_renderer_set_pixel_filter(self.h, int(kind)))
+
+    def pixel_filter(self):
+        """rt_get_pixel_filter of context 0"""
+        return int(self.rt.rt_get_pixel_filter(self.ctx))
+
+    def sample_rays(self, frame, seed_base=0x12345678, y0=0, y1=None):
+        """rt_sample_rays: the camera rays (O, D), each (rows * width, 3), of frame 'frame' of the path samples under the context's filter"""
+        y1 = self.hgt if y1 is None else y1
+        O = np.zeros(((y1 - y0) * self.w, 3), dtype=np.float32)
+        D = np.zeros(((y1 - y0) * self.w, 3), dtype=np.float32)
+        self._rt(self.rt.rt_sample_rays(self.ctx, C.c_uint32(frame & 0xFFFFFFFF), C.c_uint32(seed_base & 0xFFFFFFFF), y0, y1, _p(O), _p(D)))
+        return O, D
 
     def set_denoise(self, on, params=None):
         """rapt::Renderer::denoise / denoiseParams: Tick shows the denoised mean in path mode (params: dict, see denoise_params)"""
