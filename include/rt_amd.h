@@ -275,6 +275,8 @@ int rt_trace_batch(rt_ctx* ctx, int mode, int n, const float* O, const float* D,
  * (Russian roulette, sampled light positions, an indirect child: renderer.cpp:33-43, 107-121) and Sample with it set (:143-153) are what the
  * reference's Renderer::Trace / Sample compute when called that way; the device evaluates them one lane per call tree (slow path,
  * correctness only; not with the Q-learning sampler on: RT_E_UNSUPPORTED).  rt_render ignores the flag (it is Tick's loop).
+ * Both general kernels (k_trace_general, k_sample_general) run one lane per call tree: ray i's whole recursion is one lane's loop, so a wave
+ * holds 64 unrelated trees and lasts as long as its longest, and the cost of a call grows with n and the depth, not with a frame's size.
  * Frame limits of that slow path (it also serves Sample on a scene with a shiny diffuse material or one built with raytracer == false): a
  * call tree may hold at most 12 nested call frames in Trace and 6 in Sample.  A frame is a shiny diffuse hit waiting for its mirror child
  * (in Trace also a glass hit's reflection child waiting for the refraction child).  The limits bound the frames nested at one moment, not

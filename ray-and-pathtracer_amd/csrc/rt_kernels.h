@@ -21,6 +21,7 @@
 // the segment order is the reference's depth-first order.
 #pragma once
 #include "rt_scene_dev.h"
+#include "rt_shade.h"
 
 namespace rtd {
 
@@ -144,39 +145,6 @@ __device__ __forceinline__ void primary_ray(const DCamera& C, int x, int y, f3& 
 	primary_ray_f(C, (float)x, (float)y, O, D);
 }
 
-// ---- lights (template/scene.h:121-137, 152-165) -----------------------------------------------
-__device__ __forceinline__ f3 light_intensity(const DLight& L, const f3& p, const f3& n, const f3& from)
-{
-	const f3 col(L.col[0], L.col[1], L.col[2]);
-	if (L.kind == 0) {
-		float dis = length(from - p);
-		f3 dir = from - p;
-		float cos_ang = dot(normalize(n), normalize(dir));
-		float relStr = 1 / (dis * RT_PI) * L.strength;
-		// isZero(float3) compares each component '< 1e-4' in double (template/precomp.h:885)
-		if (dis <= L.radius && ((double)cos_ang < 1e-4)) return L.strength * col;
-		return relStr * col;
-	}
-	if (L.kind == 1) {
-		const f3 pos(L.pos[0], L.pos[1], L.pos[2]), normal(L.normal[0], L.normal[1], L.normal[2]);
-		f3 dir = p - pos;
-		float sTheta = length(cross(dir, normal)) / length(dir) * length(normal);
-		if (dot(dir, normal) < 0) return f3(0.0f);
-		float dis = length(dir);
-		float str = L.sinAngle - sTheta > 0 ? x_asinf(L.sinAngle) - x_asinf(sTheta) : 0;
-		return f3(1 / dis * str * L.strength);
-	}
-	return f3(1.0f);
-}
-__device__ __forceinline__ f3 light_position(const DLight& L, bool raytracer, uint& seed)
-{
-	const f3 pos(L.pos[0], L.pos[1], L.pos[2]);
-	if (L.kind != 0 || raytracer) return pos;
-	float newRad = L.radius * sqrtf(RandomFloat(seed));
-	float theta = RandomFloat(seed) * 2 * RT_PI;
-	return f3(pos.x + newRad * x_cosf(theta), pos.y + newRad * x_sinf(theta), pos.z);
-}
-
 // Scene::GetSkyColor (template/scene.h:1312-1327): the texel the direction D looks at (null without a sky texture)
 __device__ __forceinline__ const unsigned char* sky_texel(const DScene& S, const f3& D)
 {
@@ -234,19 +202,6 @@ __global__ void k_gamma_lut(float* lut)
 	const int b = (int)threadIdx.x;
 	const f3 c = f3((float)b, (float)b, (float)b) / 255;
 	lut[b] = g_exactGamma ? x_powf(c.x * 1, RT_GAMMA) : gamma_powf(c.x * 1);
-}
-
-// diffuse::scatter (template/scene.h:605-620): att out, energy in/out
-__device__ __forceinline__ f3 diffuse_scatter(const DMaterial& m, const f3& rayD, const f3& lightDir, const f3& lightIntensity, const f3& normal, f3& energy)
-{
-	const f3 albedo(m.albedo[0], m.albedo[1], m.albedo[2]);
-	f3 reflectionDirection = reflect(-lightDir, normal);
-	f3 specularColor = x_powf(libm_fmaxf(0.0f, -dot(reflectionDirection, rayD)), (float)m.N) * lightIntensity;
-	f3 att = albedo * lightIntensity * m.diffu + specularColor * m.specu;
-	f3 retention = f3(1.0f) - albedo;
-	f3 newEnergy = energy - retention;
-	energy = newEnergy.x > 0 ? newEnergy : f3(0.0f);
-	return att;
 }
 
 // Per-wave ranges: wave w of the grid owns the contiguous slots [w*R, (w+1)*R), R a multiple of 64.
@@ -656,45 +611,26 @@ __global__ void __launch_bounds__(RT_BLOCK, RT_SHADE_WAVES) k_shade(DScene S, DC
 			// Trace(depth <= 0) = 0 (renderer.cpp:23), Sample(depth < 0) = 0.05 (:129)
 			const bool childTraces = path ? (nDepth >= 0) : (nDepth > 0);
 
-			if (id.x == -1) {
-				Lsum = Lsum + W * sky_color(S, D); // renderer.cpp:26 / :134
-			} else if (id.x >= 11 && id.x < 11 + S.nLights) {
-				Lsum = Lsum + W * light_intensity(S.lights[id.x - 11], I, normal, I); // :27-28 / :135-137
+			f3 term;
+			if (terminal_radiance(S, id.x, I, normal, D, term)) {
+				Lsum = Lsum + W * term; // renderer.cpp:26-28 / :134-137
 			} else {
 				const DMaterial m = S.mats[id.y];
 				const f3 col(m.col[0], m.col[1], m.col[2]);
 				if (m.type == 3) { // GLASS, renderer.cpp:45-80 / :198-233
-					const float kr = glass_fresnel(normalize(D), normalize(normal), m.ir);
-					const bool outside = dot(D, normal) < 0;
-					const f3 bias = 0.0001f * normal;
-					const f3 norm = outside ? normal : -normal;
-					const float r = !outside ? m.ir : (1 / m.ir);
-					if (outside) {
-						E.x *= x_expf(m.absorption[0] * -t);
-						E.y *= x_expf(m.absorption[1] * -t);
-						E.z *= x_expf(m.absorption[2] * -t);
-					}
+					const GlassHit g = glass_hit(m, D, normal, t, E);
 					bool takeRefr, takeRefl;
 					if (path) {
-						const bool refr = kr < RandomFloat(seed);
+						const bool refr = g.kr < RandomFloat(seed);
 						takeRefr = refr, takeRefl = !refr;
 					} else {
-						takeRefr = kr < 1, takeRefl = true;
+						takeRefr = g.kr < 1, takeRefl = true;
 					}
 					f3 refrO(0.0f), refrD(0.0f), refrW(0.0f), reflO(0.0f), reflD(0.0f), reflW(0.0f);
-					if (takeRefr) {
-						refrD = normalize(glass_refract(D, norm, r));
-						refrO = outside ? I - bias : I + bias;
-						const f3 tempCol = col * E;
-						refrW = W * (tempCol * (1 - kr));
-					}
-					if (takeRefl) {
-						reflD = normalize(reflect(D, norm));
-						reflO = outside ? I + bias : I - bias;
-						reflW = W * (col * kr);
-					}
+					if (takeRefr) glass_refracted(g, m, I, D, W, E, refrO, refrD, refrW);
+					if (takeRefl) glass_reflected(g, m, I, D, W, reflO, reflD, reflW);
 					if (!childTraces) {
-						if (path) Lsum = Lsum + (takeRefr ? refrW : reflW) * f3(0.05f);
+						if (path) Lsum = Lsum + untraced_child(takeRefr ? refrW : reflW);
 					} else if (takeRefr) {
 						if (takeRefl) push_pending(P, slot, reflO, reflD, reflW, E, nDepth, &Q.counts[3]); // refraction first, reflection resumes later
 						nO = refrO, nD = refrD, nW = refrW, segmentEnds = false;
@@ -702,10 +638,9 @@ __global__ void __launch_bounds__(RT_BLOCK, RT_SHADE_WAVES) k_shade(DScene S, DC
 						nO = reflO, nD = reflD, nW = reflW, segmentEnds = false;
 					}
 				} else if (m.type == 2) { // METAL, renderer.cpp:81-86 / :192-197, metal::scatter template/scene.h:630-635
-					nO = I + normal * 0.001f, nD = reflect(D, normal);
-					nW = path ? W * col : W * (col * E);
+					metal_bounce(path, col, I, D, normal, W, E, nO, nD, nW);
 					if (childTraces) segmentEnds = false;
-					else if (path) Lsum = Lsum + nW * f3(0.05f);
+					else if (path) Lsum = Lsum + untraced_child(nW);
 				} else { // DIFFUSE, renderer.cpp:87-122 / :156-191
 					for (int i = 0; i < S.nLights; i++) {
 						const f3 pickedPos = light_position(S.lights[i], !path, seed);
@@ -714,12 +649,10 @@ __global__ void __launch_bounds__(RT_BLOCK, RT_SHADE_WAVES) k_shade(DScene S, DC
 					wantShadow = S.nLights > 0;
 					if (path) {
 						const f3 albedo(m.albedo[0], m.albedo[1], m.albedo[2]);
-						const f3 rayToHemi = RandomInHemisphere(seed, normal);
-						const f3 cos_i(dot(rayToHemi, normal));
-						nO = I, nD = rayToHemi;
-						nW = W * ((2 * (col * cos_i)) * albedo); // child coefficient of (direct*INVPI + 2*indirect) * albedo
+						nO = I;
+						hemisphere_bounce(seed, normal, col, albedo, W, nD, nW);
 						if (childTraces) segmentEnds = false;
-						else Lsum = Lsum + nW * f3(0.05f);
+						else Lsum = Lsum + untraced_child(nW);
 					}
 				}
 			}
@@ -764,10 +697,7 @@ struct ConnectPolicy {
 		RT_CHECK(slot >= 0 && slot < P.nSlots && li >= 0 && li < nLights, 11, flag);
 		const f3 I = xyz(ld_stream(P.hitP + slot)); // O + t * D, as shade computed it
 		const f3 pickedPos = xyz(ld_stream(P.sh + ((size_t)li * P.nSlots + slot)));
-		f3 lightRayDirection = pickedPos - I;
-		const float len2 = dot(lightRayDirection, lightRayDirection);
-		lightRayDirection = normalize(lightRayDirection);
-		O = I + lightRayDirection * 1e-4f, D = lightRayDirection, tmax = sqrtf(len2);
+		shadow_ray(I, pickedPos, O, D, tmax);
 		return true;
 	}
 	__device__ __forceinline__ void store(int work, bool occluded) const
@@ -847,12 +777,12 @@ __global__ void RT_LIGHT_BOUNDS k_light(DScene S, RenderParams R, PathState P, Q
 				if (occluded) continue;
 				if (path) att = diffuse_scatter(m, D, lightRayDirection, light_intensity(S.lights[i], I, normal, pickedPos), normal, E);
 				if (!path && m.shinieness != 0 && depth - 1 > 0) // renderer.cpp:101-102: a mirror branch per visible light
-					push_pending(P, slot, I, reflect(D, normal), W * ((m.shinieness * col) * E), E, depth - 1, &Q.counts[3]);
-				direct = direct + (1 - m.shinieness) * col * att * E;
+					push_pending(P, slot, I, reflect(D, normal), W * mirror_weight(m, col, E), E, depth - 1, &Q.counts[3]);
+				direct = direct + direct_term(m, col, att, E);
 			}
 			if (path) {
 				const f3 albedo(m.albedo[0], m.albedo[1], m.albedo[2]);
-				Lsum = Lsum + W * ((direct * RT_INVPI) * albedo); // direct part of (direct*INVPI + 2*indirect) * albedo
+				Lsum = Lsum + W * path_direct(direct, albedo);
 			} else {
 				Lsum = Lsum + W * direct;
 			}
@@ -979,7 +909,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_sample_general(DScene S, DCamera C
 		while (true) {
 			if (!resume) {
 				// ---- Sample(ray, depth, energy) from its first line ----
-				if (depth < 0) { Lsum = Lsum + W * f3(0.05f); }
+				if (depth < 0) { Lsum = Lsum + untraced_child(W); }
 				else {
 					HitRef hit;
 					find_nearest_one(S, O, D, 1e34f, 0.001f, hit, st);
@@ -987,40 +917,23 @@ __global__ void __launch_bounds__(RT_BLOCK) k_sample_general(DScene S, DCamera C
 					f3 normal;
 					resolve_hit(S, hit, O, D, objIdx, matId, normal);
 					const f3 I = O + hit.t * D;
-					if (objIdx == -1) Lsum = Lsum + W * sky_color(S, D);
-					else if (objIdx >= 11 && objIdx < 11 + S.nLights) Lsum = Lsum + W * light_intensity(S.lights[objIdx - 11], I, normal, I);
+					f3 term;
+					if (terminal_radiance(S, objIdx, I, normal, D, term)) Lsum = Lsum + W * term;
 					else {
 						const DMaterial m = S.mats[matId];
 						const f3 col(m.col[0], m.col[1], m.col[2]);
-						bool survives = true;
-						if (R.sceneRt == 1) { // Sample with scene.raytracer set (renderer.cpp:143-153): Russian roulette on the largest colour component
-							const double p = col.x > col.y && col.x > col.z ? col.x : col.y > col.z ? col.y : col.z;
-							if (depth < 5 || !p) survives = (double)RandomFloat(seed) < p; // (the survivor's f = f * (1 / p) is never read)
-						}
-						if (!survives) {
-							// return totCol (= 0): nothing is added
+						// Sample with scene.raytracer set (renderer.cpp:143-153) plays Russian roulette; the loser returns totCol (= 0): nothing is added
+						if (R.sceneRt == 1 && !roulette_survives(col, depth, seed)) {
 						} else
 						if (m.type == 2) {
-							O = I + normal * 0.001f, D = reflect(D, normal), W = W * col, depth--;
+							metal_bounce(true, col, I, D, normal, W, E, O, D, W);
+							depth--;
 							continue;
 						} else
 						if (m.type == 3) {
-							const float kr = glass_fresnel(normalize(D), normalize(normal), m.ir);
-							const bool outside = dot(D, normal) < 0;
-							const f3 bias = 0.0001f * normal, norm = outside ? normal : -normal;
-							const float r = !outside ? m.ir : (1 / m.ir);
-							if (outside) {
-								E.x *= x_expf(m.absorption[0] * -hit.t);
-								E.y *= x_expf(m.absorption[1] * -hit.t);
-								E.z *= x_expf(m.absorption[2] * -hit.t);
-							}
-							if (kr < RandomFloat(seed)) {
-								const f3 nd = normalize(glass_refract(D, norm, r));
-								O = outside ? I - bias : I + bias, D = nd, W = W * ((col * E) * (1 - kr));
-							} else {
-								const f3 nd = normalize(reflect(D, norm));
-								O = outside ? I + bias : I - bias, D = nd, W = W * (col * kr);
-							}
+							const GlassHit g = glass_hit(m, D, normal, hit.t, E);
+							if (g.kr < RandomFloat(seed)) glass_refracted(g, m, I, D, W, E, O, D, W);
+							else glass_reflected(g, m, I, D, W, O, D, W);
 							depth--;
 							continue;
 						} else {
@@ -1043,30 +956,28 @@ __global__ void __launch_bounds__(RT_BLOCK) k_sample_general(DScene S, DCamera C
 			bool branched = false;
 			for (int i = cur.nextLight; i < S.nLights; i++) {
 				const f3 pickedPos = light_position(S.lights[i], R.sceneRt == 1, seed); // (a light follows scene.raytracer: its position itself when the flag is set, template/scene.h:133)
-				f3 L = pickedPos - cur.P;
-				const float len2 = dot(L, L);
-				L = normalize(L);
-				if (is_occluded_one(S, cur.P + L * 1e-4f, L, sqrtf(len2), st)) continue;
+				f3 sO, L;
+				float tmax;
+				shadow_ray(cur.P, pickedPos, sO, L, tmax);
+				if (is_occluded_one(S, sO, L, tmax, st)) continue;
 				const f3 att = diffuse_scatter(m, cur.rayD, L, light_intensity(S.lights[i], cur.P, cur.N, pickedPos), cur.N, cur.E);
 				if (!m.raytracer) (void)RandomInHemisphere(seed, cur.N); // diffuse::scatter's own draw (template/scene.h:612-614)
-				Lsum = Lsum + cur.W * ((((1 - m.shinieness) * col * att * cur.E) * RT_INVPI) * albedo);
+				Lsum = Lsum + cur.W * path_direct(direct_term(m, col, att, cur.E), albedo);
 				if (m.shinieness != 0) {
 					// directLightning += shinieness * col * Sample(mirror ray, depth - 1, energy): run it now
 					// (its draws come before the next light's), keep the rest of this loop for later
 					cur.nextLight = i + 1;
 					if (sp < RT_SAMPLE_FRAMES) stack[sp++] = cur; else *overflow = 2;
 					O = cur.P, D = reflect(cur.rayD, cur.N), E = cur.E, depth = cur.depth - 1;
-					W = cur.W * (((m.shinieness * col) * RT_INVPI) * albedo);
+					W = cur.W * path_direct(m.shinieness * col, albedo); // (the mirror child's coefficient carries no energy factor, :172-173)
 					branched = true;
 					break;
 				}
 			}
 			if (branched) continue;
 			// indirect term: one hemisphere sample (renderer.cpp:181-186)
-			const f3 rayToHemi = RandomInHemisphere(seed, cur.N);
-			const f3 cos_i(dot(rayToHemi, cur.N));
-			O = cur.P, D = rayToHemi, E = cur.E, depth = cur.depth - 1;
-			W = cur.W * ((2 * (col * cos_i)) * albedo);
+			hemisphere_bounce(seed, cur.N, col, albedo, cur.W, D, W);
+			O = cur.P, E = cur.E, depth = cur.depth - 1;
 		}
 		if (R.customOut) R.customOut[sid] = mk4(Lsum, 0.0f);
 		else store_sample(R, sid, Lsum);
@@ -1107,33 +1018,24 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_general(DScene S, DCamera C,
 					f3 normal;
 					resolve_hit(S, hit, O, D, objIdx, matId, normal);
 					const f3 I = O + hit.t * D;
-					if (objIdx == -1) Lsum = Lsum + W * sky_color(S, D);
-					else if (objIdx >= 11 && objIdx < 11 + S.nLights) Lsum = Lsum + W * light_intensity(S.lights[objIdx - 11], I, normal, I);
+					f3 term;
+					if (terminal_radiance(S, objIdx, I, normal, D, term)) Lsum = Lsum + W * term;
 					else {
 						const DMaterial m = S.mats[matId];
 						const f3 col(m.col[0], m.col[1], m.col[2]);
-						const double p = col.x > col.y && col.x > col.z ? col.x : col.y > col.z ? col.y : col.z; // :34
-						bool survives = true;
-						if (depth < 5 || !p) survives = (double)RandomFloat(seed) < p; // :35-40
+						const bool survives = roulette_survives(col, depth, seed); // :34-40
 						if (survives && m.type == 3) { // GLASS :45-80: the refraction child first, the reflection child after it
-							const float kr = glass_fresnel(normalize(D), normalize(normal), m.ir);
-							const bool outside = dot(D, normal) < 0;
-							const f3 bias = 0.0001f * normal, norm = outside ? normal : -normal;
-							const float r = !outside ? m.ir : (1 / m.ir);
-							if (outside) {
-								E.x *= x_expf(m.absorption[0] * -hit.t);
-								E.y *= x_expf(m.absorption[1] * -hit.t);
-								E.z *= x_expf(m.absorption[2] * -hit.t);
-							}
-							const f3 reflD = normalize(reflect(D, norm)), reflO = outside ? I + bias : I - bias, reflW = W * (col * kr);
-							if (kr < 1) {
+							const GlassHit g = glass_hit(m, D, normal, hit.t, E);
+							f3 reflO, reflD, reflW;
+							glass_reflected(g, m, I, D, W, reflO, reflD, reflW);
+							if (g.kr < 1) {
 								if (sp < RT_TRACE_FRAMES) { TraceFrame& f = stack[sp++]; f.kind = 0, f.P = reflO, f.rayD = reflD, f.W = reflW, f.E = E, f.depth = depth - 1; } else *overflow = 2;
-								const f3 refrD = normalize(glass_refract(D, norm, r));
-								O = outside ? I - bias : I + bias, D = refrD, W = W * ((col * E) * (1 - kr));
+								glass_refracted(g, m, I, D, W, E, O, D, W);
 							} else O = reflO, D = reflD, W = reflW;
 							depth--, returned = false;
 						} else if (survives && m.type == 2) { // METAL :81-86
-							O = I + normal * 0.001f, D = reflect(D, normal), W = W * (col * E), depth--, returned = false;
+							metal_bounce(false, col, I, D, normal, W, E, O, D, W);
+							depth--, returned = false;
 						} else if (survives) { // DIFFUSE :87-122
 							cur.kind = 1, cur.P = I, cur.N = normal, cur.rayD = D, cur.W = W, cur.E = E, cur.sdir = f3(0.0f), cur.mat = matId, cur.nextLight = 0, cur.depth = depth;
 							resume = true, returned = false;
@@ -1155,18 +1057,18 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_general(DScene S, DCamera C,
 			bool branched = false;
 			for (int i = cur.nextLight; i < S.nLights; i++) {
 				const f3 pickedPos = light_position(S.lights[i], false, seed); // the flag is clear: a sampled position
-				f3 L = pickedPos - cur.P;
-				const float len2 = dot(L, L);
-				L = normalize(L);
+				f3 sO, L;
+				float tmax;
+				shadow_ray(cur.P, pickedPos, sO, L, tmax);
 				const f3 att = diffuse_scatter(m, cur.rayD, L, light_intensity(S.lights[i], cur.P, cur.N, pickedPos), cur.N, cur.E); // before the occlusion test (:97-98)
 				if (!m.raytracer) cur.sdir = RandomInHemisphere(seed, cur.N); // diffuse::scatter's own draw: scatteredDir (template/scene.h:612-614)
-				if (is_occluded_one(S, cur.P + L * 1e-4f, L, sqrtf(len2), st)) continue;
-				Lsum = Lsum + cur.W * ((((1 - m.shinieness) * col * att) * cur.E) * RT_INVPI); // (totCol = totCol * INVPI at :119 scales the whole loop's sum)
+				if (is_occluded_one(S, sO, L, tmax, st)) continue;
+				Lsum = Lsum + cur.W * (direct_term(m, col, att, cur.E) * RT_INVPI); // (totCol = totCol * INVPI at :119 scales the whole loop's sum)
 				if (m.shinieness != 0) {
 					cur.nextLight = i + 1;
 					if (sp < RT_TRACE_FRAMES) stack[sp++] = cur; else *overflow = 2;
 					O = cur.P, D = reflect(cur.rayD, cur.N), E = cur.E, depth = cur.depth - 1;
-					W = cur.W * ((((m.shinieness * col)) * cur.E) * RT_INVPI);
+					W = cur.W * (mirror_weight(m, col, cur.E) * RT_INVPI);
 					branched = true;
 					break;
 				}

@@ -95,6 +95,26 @@ __global__ void __launch_bounds__(RT_MEGA_ORDER_BLOCK) k_mega_order(const uint* 
 	}
 }
 
+// The shadow ray of light i for the diffuse hit a lane keeps in M (renderer.cpp:93-99), for both policies below; false: no light left.
+// ew: what the policy keeps in E.w (the single launch its pending branches, the level launch 0).  (Fifteen operands: a lane's whole
+// light-loop state; it is the one function both policies held word for word.)
+__device__ __forceinline__ bool light_step(const DScene& S, const MegaState& M, int gl, int i, const f3& I, const f3& normal, const f3& rayD, const DMaterial& m,
+                                           f3& E, int ew, const f3& direct, f3& O, f3& D, float& tmax, bool& nextAny)
+{
+	if (i >= S.nLights) return false;
+	uint unusedSeed = 0;
+	const f3 pickedPos = light_position(S.lights[i], true, unusedSeed);
+	shadow_ray(I, pickedPos, O, D, tmax);
+	// scatter first: the energy changes even when the light turns out to be occluded (renderer.cpp:95-96)
+	const f3 att = diffuse_scatter(m, rayD, D, light_intensity(S.lights[i], I, normal, pickedPos), normal, E);
+	M.E[gl] = mk4(E, __int_as_float(ew));
+	M.hN[gl] = mk4(normal, __int_as_float(i));
+	M.hA[gl] = mk4(att, 0.0f);
+	M.hS[gl] = mk4(direct, 0.0f);
+	nextAny = true;
+	return true;
+}
+
 struct WhittedMegaPolicy {
 	static constexpr bool kAdvance = true;
 	static constexpr int kRefill = 32;
@@ -160,25 +180,6 @@ struct WhittedMegaPolicy {
 		e[0] = mk4(O, __int_as_float(depth)), e[1] = mk4(D, 0.0f), e[2] = mk4(W, 0.0f), e[3] = mk4(E, 0.0f);
 		np++;
 	}
-	// the shadow ray of light i for the diffuse hit kept in M (renderer.cpp:93-99; as ConnectPolicy::load); false: no light left
-	__device__ __forceinline__ bool light_step(int i, const f3& I, const f3& normal, const f3& rayD, const DMaterial& m, f3& E, int np, const f3& direct,
-	                                           f3& O, f3& D, float& tmax, bool& nextAny) const
-	{
-		if (i >= S.nLights) return false;
-		uint unusedSeed = 0;
-		const f3 pickedPos = light_position(S.lights[i], true, unusedSeed);
-		f3 dir = pickedPos - I;
-		const float len2 = dot(dir, dir);
-		dir = normalize(dir);
-		// scatter first: the energy changes even when the light turns out to be occluded (renderer.cpp:95-96)
-		const f3 att = diffuse_scatter(m, rayD, dir, light_intensity(S.lights[i], I, normal, pickedPos), normal, E);
-		M.E[gl] = mk4(E, __int_as_float(np));
-		M.hN[gl] = mk4(normal, __int_as_float(i));
-		M.hA[gl] = mk4(att, 0.0f);
-		M.hS[gl] = mk4(direct, 0.0f);
-		O = I + dir * 1e-4f, D = dir, tmax = sqrtf(len2), nextAny = true;
-		return true;
-	}
 	__device__ __forceinline__ bool advance_once(int work, bool wasAny, const HitRef& res, f3& O, f3& D, float& tmax, HitRef& head, bool& nextAny) const
 	{
 		const float4 w4 = M.W[gl], e4 = M.E[gl], l4 = M.L[gl];
@@ -198,33 +199,17 @@ struct WhittedMegaPolicy {
 			const int nDepth = depth - 1;
 			const bool childTraces = nDepth > 0; // Trace(depth <= 0) = 0 (renderer.cpp:23)
 			f3 nO(0.0f), nD(0.0f), nW(0.0f);
-			if (objIdx == -1) Lsum = Lsum + W * sky_color(S, rayD);
-			else if (objIdx >= 11 && objIdx < 11 + S.nLights) Lsum = Lsum + W * light_intensity(S.lights[objIdx - 11], I, normal, I);
+			f3 term;
+			if (terminal_radiance(S, objIdx, I, normal, rayD, term)) Lsum = Lsum + W * term;
 			else {
 				const DMaterial m = S.mats[matId];
 				const f3 col(m.col[0], m.col[1], m.col[2]);
 				if (m.type == 3) { // GLASS, renderer.cpp:45-80: refraction now, reflection waits
-					const float kr = glass_fresnel(normalize(rayD), normalize(normal), m.ir);
-					const bool outside = dot(rayD, normal) < 0;
-					const f3 bias = 0.0001f * normal;
-					const f3 norm = outside ? normal : -normal;
-					const float r = !outside ? m.ir : (1 / m.ir);
-					if (outside) {
-						E.x *= x_expf(m.absorption[0] * -t);
-						E.y *= x_expf(m.absorption[1] * -t);
-						E.z *= x_expf(m.absorption[2] * -t);
-					}
-					const bool takeRefr = kr < 1;
-					f3 refrO(0.0f), refrD(0.0f), refrW(0.0f);
-					if (takeRefr) {
-						refrD = normalize(glass_refract(rayD, norm, r));
-						refrO = outside ? I - bias : I + bias;
-						const f3 tempCol = col * E;
-						refrW = W * (tempCol * (1 - kr));
-					}
-					const f3 reflD = normalize(reflect(rayD, norm));
-					const f3 reflO = outside ? I + bias : I - bias;
-					const f3 reflW = W * (col * kr);
+					const GlassHit g = glass_hit(m, rayD, normal, t, E);
+					const bool takeRefr = g.kr < 1;
+					f3 refrO(0.0f), refrD(0.0f), refrW(0.0f), reflO, reflD, reflW;
+					if (takeRefr) glass_refracted(g, m, I, rayD, W, E, refrO, refrD, refrW);
+					glass_reflected(g, m, I, rayD, W, reflO, reflD, reflW);
 					if (childTraces) {
 						if (takeRefr) {
 							push(np, reflO, reflD, reflW, E, nDepth);
@@ -233,13 +218,12 @@ struct WhittedMegaPolicy {
 						segmentEnds = false;
 					}
 				} else if (m.type == 2) { // METAL, renderer.cpp:81-86
-					nO = I + normal * 0.001f, nD = reflect(rayD, normal);
-					nW = W * (col * E);
+					metal_bounce(false, col, I, rayD, normal, W, E, nO, nD, nW);
 					if (childTraces) segmentEnds = false;
 				} else if (S.nLights > 0) { // DIFFUSE, renderer.cpp:87-122: the light loop, one shadow query at a time
 					M.hI[gl] = mk4(I, __int_as_float(matId));
 					M.L[gl] = mk4(Lsum, l4.w);
-					if (light_step(0, I, normal, rayD, m, E, np, f3(0.0f), O, D, tmax, nextAny)) return true;
+					if (light_step(S, M, gl, 0, I, normal, rayD, m, E, np, f3(0.0f), O, D, tmax, nextAny)) return true;
 				}
 			}
 			if (!segmentEnds) {
@@ -260,10 +244,10 @@ struct WhittedMegaPolicy {
 			const f3 col(m.col[0], m.col[1], m.col[2]);
 			if (res.kind != 1) { // visible
 				if (m.shinieness != 0 && depth - 1 > 0) // renderer.cpp:101-102: a mirror branch per visible light
-					push(np, I, reflect(rayD, normal), W * ((m.shinieness * col) * E), E, depth - 1);
-				direct = direct + (1 - m.shinieness) * col * att * E;
+					push(np, I, reflect(rayD, normal), W * mirror_weight(m, col, E), E, depth - 1);
+				direct = direct + direct_term(m, col, att, E);
 			}
-			if (light_step(i + 1, I, normal, rayD, m, E, np, direct, O, D, tmax, nextAny)) return true;
+			if (light_step(S, M, gl, i + 1, I, normal, rayD, m, E, np, direct, O, D, tmax, nextAny)) return true;
 			Lsum = Lsum + W * direct;
 		}
 		// ---- the segment is over: the most recent pending branch, or the pixel is done (k_finish) ----
@@ -418,24 +402,6 @@ struct WhittedLevelPolicy {
 			sg[2] = mk4(ch.W, __uint_as_float((uint)ck)), sg[3] = mk4(ch.E, __uint_as_float((uint)(ck >> 32)));
 		}
 	}
-	// the shadow ray of light i for the diffuse hit kept in M (renderer.cpp:93-99); false: no light left
-	__device__ __forceinline__ bool light_step(int i, const f3& I, const f3& normal, const f3& rayD, const DMaterial& m, f3& E, const f3& direct,
-	                                           f3& O, f3& D, float& tmax, bool& nextAny) const
-	{
-		if (i >= S.nLights) return false;
-		uint unusedSeed = 0;
-		const f3 pickedPos = light_position(S.lights[i], true, unusedSeed);
-		f3 dir = pickedPos - I;
-		const float len2 = dot(dir, dir);
-		dir = normalize(dir);
-		const f3 att = diffuse_scatter(m, rayD, dir, light_intensity(S.lights[i], I, normal, pickedPos), normal, E); // before the query: E changes either way (:95-96)
-		M.E[gl] = mk4(E, 0.0f);
-		M.hN[gl] = mk4(normal, __int_as_float(i));
-		M.hA[gl] = mk4(att, 0.0f);
-		M.hS[gl] = mk4(direct, 0.0f);
-		O = I + dir * 1e-4f, D = dir, tmax = sqrtf(len2), nextAny = true;
-		return true;
-	}
 	__device__ __forceinline__ bool advance(int work, bool wasAny, const HitRef& res, f3& O, f3& D, float& tmax, HitRef& head, bool& nextAny) const
 	{
 		if (advance_once(work, wasAny, res, O, D, tmax, head, nextAny)) return true;
@@ -467,44 +433,31 @@ struct WhittedLevelPolicy {
 			const f3 I = rayO + t * rayD;
 			const int nDepth = depth - 1;
 			const bool childTraces = nDepth > 0; // Trace(depth <= 0) = 0 (renderer.cpp:23)
+			// (the two terminal terms stay written out here: through terminal_radiance the two log_term calls become one behind a merged
+			// value, and this kernel, which sits at its 128-register bound, then spills 224 bytes instead of 176)
 			if (objIdx == -1) log_term(work, key, sid, W * sky_color(S, rayD));
 			else if (objIdx >= 11 && objIdx < 11 + S.nLights) log_term(work, key, sid, W * light_intensity(S.lights[objIdx - 11], I, normal, I));
 			else {
 				const DMaterial m = S.mats[matId];
 				const f3 col(m.col[0], m.col[1], m.col[2]);
 				if (m.type == 3) { // GLASS, renderer.cpp:45-80
-					const float kr = glass_fresnel(normalize(rayD), normalize(normal), m.ir);
-					const bool outside = dot(rayD, normal) < 0;
-					const f3 bias = 0.0001f * normal;
-					const f3 norm = outside ? normal : -normal;
-					const float r = !outside ? m.ir : (1 / m.ir);
-					if (outside) {
-						E.x *= x_expf(m.absorption[0] * -t);
-						E.y *= x_expf(m.absorption[1] * -t);
-						E.z *= x_expf(m.absorption[2] * -t);
-					}
+					const GlassHit g = glass_hit(m, rayD, normal, t, E);
 					if (childTraces) {
-						if (kr < 1) {
+						if (g.kr < 1) {
 							a.want = true, a.digit = 1, a.depth = nDepth, a.E = E;
-							a.D = normalize(glass_refract(rayD, norm, r));
-							a.O = outside ? I - bias : I + bias;
-							const f3 tempCol = col * E;
-							a.W = W * (tempCol * (1 - kr));
+							glass_refracted(g, m, I, rayD, W, E, a.O, a.D, a.W);
 						}
 						b.want = true, b.digit = 2, b.depth = nDepth, b.E = E;
-						b.D = normalize(reflect(rayD, norm));
-						b.O = outside ? I + bias : I - bias;
-						b.W = W * (col * kr);
+						glass_reflected(g, m, I, rayD, W, b.O, b.D, b.W);
 					}
 				} else if (m.type == 2) { // METAL, renderer.cpp:81-86
 					if (childTraces) {
 						a.want = true, a.digit = 1, a.depth = nDepth, a.E = E;
-						a.O = I + normal * 0.001f, a.D = reflect(rayD, normal);
-						a.W = W * (col * E);
+						metal_bounce(false, col, I, rayD, normal, W, E, a.O, a.D, a.W);
 					}
 				} else if (S.nLights > 0) { // DIFFUSE, renderer.cpp:87-122
 					M.hI[gl] = mk4(I, __int_as_float(matId));
-					go = light_step(0, I, normal, rayD, m, E, f3(0.0f), O, D, tmax, nextAny);
+					go = light_step(S, M, gl, 0, I, normal, rayD, m, E, 0, f3(0.0f), O, D, tmax, nextAny);
 				}
 			}
 		} else {
@@ -519,11 +472,11 @@ struct WhittedLevelPolicy {
 				if (m.shinieness != 0 && depth - 1 > 0) { // renderer.cpp:101-102: a mirror branch per visible light
 					a.want = true, a.digit = (uint)(1 + (S.nLights - 1 - i)), a.depth = depth - 1, a.E = E;
 					a.O = I, a.D = reflect(rayD, normal);
-					a.W = W * ((m.shinieness * col) * E);
+					a.W = W * mirror_weight(m, col, E);
 				}
-				direct = direct + (1 - m.shinieness) * col * att * E;
+				direct = direct + direct_term(m, col, att, E);
 			}
-			go = light_step(i + 1, I, normal, rayD, m, E, direct, O, D, tmax, nextAny);
+			go = light_step(S, M, gl, i + 1, I, normal, rayD, m, E, 0, direct, O, D, tmax, nextAny);
 			if (!go) log_term(work, key, sid, W * direct);
 		}
 		append(a, b, key, sid);

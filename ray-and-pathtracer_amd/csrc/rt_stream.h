@@ -539,14 +539,10 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 			const bool learner = (keyWord & RT_Q_LEARNER) != 0;
 			const uint prevKey = learner ? (keyWord & ~RT_Q_LEARNER) : 0u;
 
-			if (id.x == -1) {
-				const f3 sky = sky_color(S, D);
-				Lsum = Lsum + W * sky; // renderer.cpp:134
-				if (QL && prevKey) qOld |= q_reward(Qt, prevKey, q_lum(sky));
-			} else if (id.x >= 11 && id.x < 11 + S.nLights) {
-				const f3 li = light_intensity(S.lights[id.x - 11], I, normal, I);
-				Lsum = Lsum + W * li; // :135-137
-				if (QL && prevKey) qOld |= q_reward(Qt, prevKey, q_lum(li));
+			f3 term;
+			if (terminal_radiance(S, id.x, I, normal, D, term)) {
+				Lsum = Lsum + W * term; // renderer.cpp:134-137
+				if (QL && prevKey) qOld |= q_reward(Qt, prevKey, q_lum(term));
 			} else {
 				const DMaterial m = S.mats[id.y];
 				const f3 col(m.col[0], m.col[1], m.col[2]);
@@ -556,37 +552,15 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 					qOld |= q_reward(Qt, prevKey, q_expected(Qt, q_cell(Qt, I), normal, dif ? q_lum(col * albedoQ) : q_lum(col), dif));
 				}
 				if (m.type == 3) { // GLASS, renderer.cpp:198-233
-					const float kr = glass_fresnel(normalize(D), normalize(normal), m.ir);
-					const bool outside = dot(D, normal) < 0;
-					const f3 bias = 0.0001f * normal;
-					const f3 norm = outside ? normal : -normal;
-					const float r = !outside ? m.ir : (1 / m.ir);
-					if (outside) {
-						// exp(+-0) is exactly 1 and x * 1 is x: a glass without absorption (every glass of the reference's scenes
-						// but one) skips three double-precision exp calls; NaN / inf exponents still take them
-						const float ax = m.absorption[0] * -t, ay = m.absorption[1] * -t, az = m.absorption[2] * -t;
-						if (ax != 0) E.x *= x_expf(ax);
-						if (ay != 0) E.y *= x_expf(ay);
-						if (az != 0) E.z *= x_expf(az);
-					}
-					const bool refr = kr < RandomFloat(seed);
-					if (refr) {
-						nD = normalize(glass_refract(D, norm, r));
-						nO = outside ? I - bias : I + bias;
-						const f3 tempCol = col * E;
-						nW = W * (tempCol * (1 - kr));
-					} else {
-						nD = normalize(reflect(D, norm));
-						nO = outside ? I + bias : I - bias;
-						nW = W * (col * kr);
-					}
+					const GlassHit g = glass_hit(m, D, normal, t, E);
+					if (g.kr < RandomFloat(seed)) glass_refracted(g, m, I, D, W, E, nO, nD, nW);
+					else glass_reflected(g, m, I, D, W, nO, nD, nW);
 					if (childTraces) segmentEnds = false;
-					else Lsum = Lsum + nW * f3(0.05f);
-				} else if (m.type == 2) { // METAL, renderer.cpp:192-197, metal::scatter template/scene.h:630-635
-					nO = I + normal * 0.001f, nD = reflect(D, normal);
-					nW = W * col;
+					else Lsum = Lsum + untraced_child(nW);
+				} else if (m.type == 2) { // METAL, renderer.cpp:192-197
+					metal_bounce(true, col, I, D, normal, W, E, nO, nD, nW);
 					if (childTraces) segmentEnds = false;
-					else Lsum = Lsum + nW * f3(0.05f);
+					else Lsum = Lsum + untraced_child(nW);
 				} else { // DIFFUSE, renderer.cpp:156-191
 					wantShadow = S.nLights > 0;
 					shadowSeed = seed; // light draws the light positions again from here
@@ -612,13 +586,11 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 							if (learner) qOld |= q_reward(Qt, 1u + (uint)cell * RT_Q_PATCHES + (uint)patch, 0.0f);
 						}
 					} else {
-						const f3 rayToHemi = RandomInHemisphere(seed, normal);
-						const f3 cos_i(dot(rayToHemi, normal));
-						nO = I, nD = rayToHemi;
-						nW = W * ((2 * (col * cos_i)) * albedo); // child coefficient of (direct*INVPI + 2*indirect) * albedo
+						nO = I;
+						hemisphere_bounce(seed, normal, col, albedo, W, nD, nW);
 					}
 					if (childTraces) segmentEnds = false;
-					else Lsum = Lsum + nW * f3(0.05f);
+					else Lsum = Lsum + untraced_child(nW);
 				}
 			}
 			// the class byte promised exactly these outputs
@@ -661,10 +633,7 @@ struct StreamConnectPolicy {
 		RT_CHECK(s >= 0 && s < T.cap && li >= 0 && li < RT_MAX_LIGHTS, 23, flag);
 		const f3 I = xyz(ld_stream(T.shI + s));
 		const f3 pickedPos = xyz(ld_stream(T.shP + ((size_t)li * (size_t)T.cap + (size_t)s)));
-		f3 lightRayDirection = pickedPos - I;
-		const float len2 = dot(lightRayDirection, lightRayDirection);
-		lightRayDirection = normalize(lightRayDirection);
-		O = I + lightRayDirection * 1e-4f, D = lightRayDirection, tmax = sqrtf(len2);
+		shadow_ray(I, pickedPos, O, D, tmax);
 		return true;
 	}
 	__device__ __forceinline__ void store(int work, bool occluded) const
@@ -753,10 +722,10 @@ __global__ void RT_LIGHT_BOUNDS k_light_s(DScene S0, RenderParams R, StreamState
 			const f3 lightRayDirection = normalize(pickedPos - I);
 			if (T.vis[(size_t)i * cap + (size_t)s] != 0) continue;
 			const f3 att = diffuse_scatter(m, D, lightRayDirection, light_intensity(S.lights[i], I, normal, pickedPos), normal, E);
-			direct = direct + (1 - m.shinieness) * col * att * E;
+			direct = direct + direct_term(m, col, att, E);
 		}
 		const f3 albedo(m.albedo[0], m.albedo[1], m.albedo[2]);
-		Lsum = Lsum + W * ((direct * RT_INVPI) * albedo); // direct part of (direct*INVPI + 2*indirect) * albedo
+		Lsum = Lsum + W * path_direct(direct, albedo);
 		if (last) store_sample(R, __float_as_uint(l4.w), Lsum);
 		else {
 			if (E.x != e4.x || E.y != e4.y || E.z != e4.z) T.E[pout][cp] = mk4(E, e4.w);

@@ -243,13 +243,13 @@ def tlas_test2(b, rt=True, mesh="lowBigB"):
     return dict(name="tlas_test2", tlas=True)
 
 
-def mixed_small(b, rt=True, split=BINNEDSAH):
+def mixed_small(b, rt=True, split=BINNEDSAH, absorption=(0.1, 0.2, 0.05)):
     """Small all-materials scene for fast parity tests: glass + metal + diffuse meshes and
-    spheres, two area lights, floor; exercises every shading branch."""
+    spheres, two area lights, floor; exercises every shading branch.  absorption: the glass material's."""
     b.sky(assets.synthetic_sky(64, 32, seed=4))
     b.area_light(11, (1.0, 4.0, 1.0), 10.0, WHITE, 1.0, (0, -1, 0))
     b.area_light(12, (-1.0, 3.0, 0.5), 5.0, WHITE, 0.5, (0, -1, 0))
-    gl = b.glass(1.5, BABYBLUE, (0.1, 0.2, 0.05), rt=rt)
+    gl = b.glass(1.5, BABYBLUE, absorption, rt=rt)
     me = b.metal(0.7, GOLD, rt=rt)
     df = b.diffuse(0.8, GREEN, 0.6, 0.4, 10, rt=rt)
     fl = b.diffuse(0.8, WHITE, 0.0, 1.0, 4, rt=rt)

@@ -1364,6 +1364,58 @@ def test_whitted_single_launch_equals_rounds(name, kw, w, h, scenes, oracle_api,
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
+def test_glass_absorption_with_zero_components(scenes, oracle_api, host_api, monkeypatch):
+    """glass_hit (csrc/rt_shade.h) calls exp only for the absorption components whose exponent is not +-0: exp(+-0) is exactly 1.  Every
+    pipeline shades a glass hit through it, so every pipeline renders a glass with absorption (0.3, 0.0, -0.0) -- one component that
+    absorbs, a +0 and a -0 -- and is held to the oracle, which calls exp three times: the Whitted frame by rounds (RT_MEGA=0), as one
+    launch (RT_MEGA=1) and by default, the path frames on the slot wavefront (RT_STREAM=0) and by default, the two general kernels
+    through rt_trace_batch with the scene's flag cleared.  The frames of one mode are bit-equal to each other.  The test is not empty:
+    the oracle's own frames change when the absorption is (0, 0, 0), so rays do enter the glass from outside."""
+    w, h, absorption = 48, 32, (0.3, 0.0, -0.0)
+
+    def oracle_frame(ab, whitted, frames):
+        o = oracle_api.OracleScene()
+        scenes.mixed_small(o, absorption=ab)
+        orr = oracle_api.OracleRenderer(o, w, h)
+        o.set_raytracer(whitted)
+        orr.clear()
+        orr.render(0, frames, nthreads=0)
+        return orr.accumulator().copy()
+    for whitted, frames in ((True, 1), (False, 3)):
+        assert not np.array_equal(oracle_frame(absorption, whitted, frames).view(np.uint32), oracle_frame((0, 0, 0), whitted, frames).view(np.uint32))
+    for mode, frames, var, values in (("whitted", 1, "RT_MEGA", ("0", "1", None)), ("path", 3, "RT_STREAM", ("0", None))):
+        out = []
+        for v in values:
+            monkeypatch.delenv(var, raising=False)
+            if v is not None:
+                monkeypatch.setenv(var, v)
+            o, orr, r, d = make_pair(scenes.mixed_small, oracle_api, host_api, w, h, absorption=absorption)
+            if v is None:
+                check_frames(orr, r, mode, frames, host_api)  # the default pipeline against the oracle
+            r.clear()
+            r.render(host_api.RT_MODE_WHITTED if mode == "whitted" else host_api.RT_MODE_PATH, 0, frames)
+            out.append(r.accumulator().copy())
+            r.close()
+        for a in out[1:]:
+            assert np.array_equal(out[0].view(np.uint32), a.view(np.uint32)), mode
+    # k_trace_general and k_sample_general: materials built while the flag is clear, and the flag cleared (as test_trace_and_sample_with_the_other_flag)
+    o, orr, r, d = make_pair(scenes.mixed_small, oracle_api, host_api, w, h, rt=False, absorption=absorption)
+    O, D = orr.primary_rays()
+    O, D = O[::5].copy(), D[::5].copy()
+    e = (0.9, 0.8, 0.7)
+    o.set_raytracer(False)
+    r.scene.set_raytracer(False)
+    r.set_scene_raytracer(0)
+    for mode in (host_api.RT_MODE_WHITTED, host_api.RT_MODE_PATH):
+        for depth in (1, 4):
+            ref = orr.trace_rays(mode, O, D, depth, e, seed_base=4242)
+            got = r.trace_batch(mode, O, D, depth=depth, seed_base=4242, energy=e)
+            err, cls_ok = rel_err(got, ref)
+            assert cls_ok and err.max() <= RADIANCE_TOL, (mode, depth, err.max())
+            assert np.abs(ref[np.isfinite(ref)]).sum() > 0
+    r.close()
+
+
 @pytest.mark.parametrize("name,kw,w,h", [("mixed_small", {}, 200, 83), ("pretty_tlas", {"n_instances": 4}, 192, 108)])
 def test_whitted_longest_first_order(name, kw, w, h, scenes, oracle_api, host_api, monkeypatch):
     """The single-launch Whitted frame (RT_MEGA_LEVELS=0) deals its pixels out by what they cost in the launch before
