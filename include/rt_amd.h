@@ -15,6 +15,7 @@
  */
 #ifndef RT_AMD_H
 #define RT_AMD_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -145,6 +146,22 @@ int rt_set_camera(rt_ctx* ctx, const rt_camera* cam);
  * bottom-up (bvh::Refit, bvh.cpp:556-594), all on the GPU.  Non-TLAS scenes only (the reference's
  * animOn is false under useTLAS, template/scene.h:1389).  t = 0 restores the uploaded geometry. */
 int rt_set_time(rt_ctx* ctx, float t);
+/* The traversal layout rt_upload_scene copies to the device, built on the host and handed to the caller: no device, no context.  For tests
+ * and tools that want to look at what upload makes of a description (csrc/rt_layout.h describes the records).
+ * rt_layout_build: wide (-1 / 0 / 1), wide8 and tlas_lds are the values of RT_WIDE, RT_WIDE8 and RT_TLAS_LDS a context would have read.
+ *   NULL on failure: rt_last_error(NULL) then holds the message, and the status is the one rt_upload_scene returns for that description.
+ * rt_layout_array: *data / *bytes of array 'which' (owned by the layout, valid until rt_layout_free; an array that was not built has 0 bytes):
+ *   PAIRS, PRIMS, WIDE, LEAFBOX, REACH, BRUTE f32; WIDE8, REFIT_ORDER, ROOT_LINK, ROOT_WIDE, ROOT_WIDE8 (the last three per BLAS) u32;
+ *   REFIT_LEVEL_START i32; INST 128-byte, LIGHTS 56-byte and MATS 64-byte device records; REACH and BRUTE end with 16 spare words.
+ *   SCALARS: 14 32-bit words in this order: rootLink, tlasBase, tlasPairs, nInst, reachOriginMax (the f32's bits), tlasLds, stackRows,
+ *   nBruteSph, nBrutePla, wideOK, wide8OK, pathUnsupported, animSlots, refitLevels.  RT_E_ARG: a null pointer, an unknown array. */
+typedef struct rt_layout rt_layout;
+enum { RT_LAYOUT_PAIRS = 0, RT_LAYOUT_PRIMS, RT_LAYOUT_WIDE, RT_LAYOUT_WIDE8, RT_LAYOUT_LEAFBOX, RT_LAYOUT_REACH, RT_LAYOUT_BRUTE, RT_LAYOUT_INST,
+       RT_LAYOUT_LIGHTS, RT_LAYOUT_MATS, RT_LAYOUT_REFIT_ORDER, RT_LAYOUT_REFIT_LEVEL_START, RT_LAYOUT_ROOT_LINK, RT_LAYOUT_ROOT_WIDE,
+       RT_LAYOUT_ROOT_WIDE8, RT_LAYOUT_SCALARS };
+rt_layout* rt_layout_build(const rt_scene_desc* desc, int wide, int wide8, int tlas_lds);
+int rt_layout_array(const rt_layout* layout, int which, const void** data, size_t* bytes);
+void rt_layout_free(rt_layout* layout);
 
 /* ---- the pixel loop ---------------------------------------------------------------------------- */
 /* Replaces the pixel loop of Renderer::Tick (renderer.cpp:259-285) for frames

@@ -1,8 +1,9 @@
 // librt_amd.so: implementation of the C ABI in include/rt_amd.h for gfx950.
 // This file: context, camera, accumulator access, counters and timers, build / tuning info; the other units of the library
-// (scene upload, device builders, the render loops, gather, batch queries, the Q-learning sampler, the output stage's helpers, the denoisers, adaptive sampling, budgeted passes, reprojection) are the rt_api_*.inc files
+// (scene upload, whose host-only layout builder is rt_layout.h, device builders, the render loops, gather, batch queries, the Q-learning sampler, the output stage's helpers, the denoisers, adaptive sampling, budgeted passes, reprojection) are the rt_api_*.inc files
 // included below -- one translation unit, see rt_ctx.h.
 #include "rt_ctx.h"
+#include "rt_layout.h"
 
 extern "C" {
 

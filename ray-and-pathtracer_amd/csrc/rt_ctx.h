@@ -2,7 +2,8 @@
 // HIP-event kernel timers, the measurement builds' probes.  rt_api.hip is ONE translation unit on purpose -- the kernels live in headers and the
 // hot ones' code generation is pinned to this compilation (bench.py kernel_hash) -- cut into units by what they do:
 //   rt_api.hip          context, camera, accumulator access, counters / timers, build + tuning info
-//   rt_api_upload.inc   rt_upload_scene
+//   rt_layout.h         the scene layout as a value: build_layout, host arithmetic only (no hip* call, no rt_ctx)
+//   rt_api_upload.inc   rt_upload_scene: build_layout's arrays copied to the device; rt_layout_*
 //   rt_api_build.inc    device builders, refit
 //   rt_api_render.inc   rt_render*, rt_trace_batch*: round loops and batches
 //   rt_api_gather.inc   rt_gather_*
@@ -287,6 +288,15 @@ static int fail(rt_ctx* c, int code, const char* fmt, ...)
 	return code;
 }
 #define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(c, RT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
+
+// v, copied into a new array of the scene pool with 'slack' spare elements behind it: kernels may read whole vectors past the end
+template <typename T>
+static int scene_array(rt_ctx* c, T** p, const std::vector<T>& v, size_t slack = 0)
+{
+	HIPCHK(c, dalloc(c->sceneAllocs, p, v.size() + slack));
+	if (!v.empty()) HIPCHK(c, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+	return RT_OK;
+}
 
 // ---- the status word ---------------------------------------------------------------------------
 // Every traversal launch leaves at most one word of trouble: counts[3] of the round pipelines' queues, flags[1] of the Whitted, general and

@@ -1,62 +1,7 @@
 // HBM-resident scene layout and the traversal device functions (the hot loops).
 //
-// Layout (built by rt_upload_scene from the reference-shaped arrays of include/rt_amd.h):
-//   pairs[]  one 64-byte record per sibling pair of BLAS nodes (the reference allocates children
-//            in adjacent slots, bvh.cpp:318-319, so one inner-node visit reads exactly one record):
-//              float4 {minA.xyz, linkA} {maxA.xyz, -} {minB.xyz, linkB} {maxB.xyz, -}
-//            link = LEAF_BIT | first primitive slot   (leaf)
-//                 = pair index of the children          (inner)
-//            A lane's fetch is one aligned half cache line; a component-wise SoA would touch
-//            eight lines for the same visit (gather access, not streaming).
-//   prims[]  one 64-byte record per leaf slot, in leaf order (primitiveIdx already applied):
-//              tri    {v0.xyz, N.x} {v1.xyz, N.y} {v2.xyz, N.z} {d, objIdx, mat, kind|last}
-//              sphere {pos.xyz, r2} {invr, r, -, -} {-}          {-, objIdx, mat, kind|last}
-//              plane  {N.xyz, d}    {-}            {-}          {-, objIdx, mat, kind|last}
-//            'last' marks the final slot of a leaf, so a leaf is named by its first slot alone and
-//            a stack entry is one dword.
-//            TLAS inner nodes (tlas.h:4-11) are stored in the same form (children boxes inside the
-//            parent's record, link = pair index or INST_BIT | instance), so one piece of code walks both
-//            levels; tlas::Intersect tests child (leftRight & 0xFFFF) first, which is slot A here.
-//   inst[]   128-byte records: invTransform rows 0-2, matTransform rows 0-2, root link.
-//   reach[]  one 48-byte record per TLAS pair, beside pairs[]: {minA.xyz, maxA.x}{maxA.yz, minB.xy}{minB.z, maxB.xyz}.
-//            The reference's instance bounds are the union of the BLAS's LOCAL box and its transformed
-//            box (bvhInstance.h:15-30 never resets 'bounds'), so TLAS boxes overlap nearly everywhere and
-//            a ray enters almost every instance only to fail the first BLAS test.  reach holds, per child,
-//            the world box of what the subtree can really contain: the corners of (BLAS root's two child
-//            boxes) under the exact inverse of invTransform, evaluated in double at upload, inflated by
-//            a margin m = a + b * reachOriginMax that covers the float rounding of the object-space ray
-//            (~500 ulps of the magnitudes involved, scaled by the transform's condition number) for every
-//            ray whose world origin has |O|_1 <= reachOriginMax (64 x the extent of the instanced geometry;
-//            rays from further away are not culled).  A child whose
-//            inflated reach box the ray misses cannot yield a hit and is dropped; the ORDER in which the
-//            remaining children are visited still comes from the reference's boxes, so the first-found
-//            rule for equal t is untouched and results are identical.  Counting launches either walk like
-//            the reference (no culling: the counters are the reference's tallies) or like the timed
-//            kernels (RT_TUNE_CULL_COUNTED: the counters are the work actually done).
-//   wide[]   4-wide nodes for occlusion queries (the reference's own 4-wide variant is bvh.cpp:335-512,
-//            :658-761).  One 128-byte record = one cache line: {min.x[4]}{min.y[4]}{min.z[4]}{max.x[4]}{max.y[4]}{max.z[4]}
-//            {link[4]}{source[4]}; built at upload by collapsing the reference's binary tree (a node's children are
-//            expanded, largest surface first, until there are four); a child entry carries the binary node's OWN box,
-//            an unused entry an inverted box.  Why this is exact for Scene::IsOccluded: the answer is "some primitive of
-//            some visited leaf occludes", a leaf is visited by the reference iff every binary ancestor's box passes
-//            the slab test, and for a ray that cannot produce a NaN slab product (ray_is_clean) a box that passes
-//            implies every box CONTAINING it passes (rounding is monotone: (b - O) * rD keeps the order of the b's), so
-//            with nested boxes -- checked at upload, parents are unions of their children after bvh::Refit -- the
-//            visited leaves are exactly those whose own box passes, whichever ancestors a walk tests on the way.  Order
-//            is free (a boolean).  Rays that are not clean, in world or in an instance's object space, are handed to the
-//            binary walk (leftover list).  Half as many dependent fetches per ray, and each fetch is one L1 line.
-//   wide8[]  8-wide nodes with QUANTISED child boxes, the re-thought form of the reference's QBVH, for occlusion
-//            queries.  One 128-byte record (96 used, six dwordx4): {origin.xyz, exponents} {qlo.x[8] qlo.y[8]} {qlo.z[8] qhi.x[8]}
-//            {qhi.y[8] qhi.z[8]} {link[0..3]} {link[4..7]}; a child's box is origin + q * 2^e per axis (one fma, the expression
-//            the builder checked), rounded OUTWARDS at upload so that it contains the binary node's box it stands for; built
-//            by collapsing the reference's binary tree (largest surface first, up to eight children).  Exactness: the argument
-//            of wide[] needs the boxes a walk tests on the way to a leaf only to CONTAIN the leaf's own box (for a clean ray a
-//            box that passes implies every box containing it passes), and the leaf's own, exact box to decide whether the leaf
-//            is visited.  So inner entries may be quantised as long as they contain, and a leaf entry names a leafBox[] record
-//            -- the reference's exact box + the first primitive slot -- that is tested (exact slab test) before any primitive:
-//            visited leaves are exactly those whose own box passes, as in bvh::BIsOccluded.  A third of the dependent fetches
-//            of the binary walk, half its load instructions per ray.
-// All of it is read-only and a few MB at most: every XCD's 4 MiB L2 ends up holding its own copy.
+// The layout itself -- pairs[], prims[], inst[], reach[], wide[], wide8[] / leafBox[] -- is described in rt_layout.h, next to the host code
+// that builds it (build_layout); the record constants and the D* structs the kernels read stay here.
 #pragma once
 #include "rt_dmath.h"
 
@@ -79,7 +24,7 @@ namespace rtd {
 //   [0, rows)            the top 'rows' entries of every lane's traversal stack, [entry][lane]
 //   [rows, rows + 6)     the world-space ray of a lane that is inside an instance, [component][lane]
 //   the rest             the block's copy of the TLAS (pairs, reach records, instance transforms), when it fits
-// rows = 14 without a TLAS copy; a copy takes rows away down to RT_STACK_ROWS_MIN (the bench scene's 8 instances: 12 rows; the 16 of config 5: 10;
+// rows = 14 without a TLAS copy; a copy takes rows away down to RT_STACK_ROWS_MIN (the bench scene's 8 instances: 12 rows; the 16 of config 5: 11;
 // measured there: 13 rows cost nothing, the copy takes 4 % off the frame set); a TLAS too large for that stays in global memory.
 #ifndef RT_LDS_WORDS
 #define RT_LDS_WORDS 5120 // 20 KB: eight blocks = 32 waves per CU of the 160 KB

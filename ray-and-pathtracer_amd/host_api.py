@@ -35,7 +35,8 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_history_capture", "rt_reproject", "rt_download_aov_positions",
               "rt_select_active_rows", "rt_select_budget_rows", "rt_gather_stats_rows", "rt_gather_active",
               "rt_select_active_dilated", "rt_select_budget_dilated",
-              "rt_set_pixel_filter", "rt_get_pixel_filter", "rt_sample_rays"]
+              "rt_set_pixel_filter", "rt_get_pixel_filter", "rt_sample_rays",
+              "rt_layout_build", "rt_layout_array", "rt_layout_free"]
 
 RT_E_ARG, RT_E_STATE = -2, -5
 # include/rt_amd.h rt_set_pixel_filter
@@ -238,6 +239,10 @@ def rt_lib():
         L.rt_set_pixel_filter.argtypes = [C.c_void_p, C.c_int]
         L.rt_get_pixel_filter.argtypes = [C.c_void_p]
         L.rt_sample_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.rt_layout_build.restype = C.c_void_p
+        L.rt_layout_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.rt_layout_array.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.rt_layout_free.argtypes = [C.c_void_p]
         _rt = L
     return _rt
 
@@ -904,6 +909,48 @@ class HostRenderer:
         p = RtProfile()
         self._rt(self.rt.rt_get_profile(self.ctx, C.byref(p), int(reset)))
         return {k: dict(launches=int(getattr(p, k).launches), ms=float(getattr(p, k).ms)) for k in ("generate", "extend", "shade", "connect", "query")}
+
+
+# include/rt_amd.h RT_LAYOUT_*: (name, dtype) in enum order; RT_LAYOUT_SCALARS' words in their documented order
+LAYOUT_ARRAYS = [("pairs", np.float32), ("prims", np.float32), ("wide", np.float32), ("wide8", np.uint32), ("leafBox", np.float32),
+                 ("reach", np.float32), ("brute", np.float32), ("inst", np.uint32), ("lights", np.uint32), ("mats", np.uint32),
+                 ("refitOrder", np.uint32), ("refitLevelStart", np.int32), ("rootLink", np.uint32), ("rootWide", np.uint32),
+                 ("rootWide8", np.uint32), ("scalars", np.int32)]
+LAYOUT_SCALARS = ["root", "tlasBase", "tlasPairs", "nInst", "reachOriginMax", "tlasLds", "stackRows", "nBruteSph", "nBrutePla",
+                  "wideOK", "wide8OK", "pathUnsupported", "animSlots", "refitLevels"]
+
+
+class LayoutError(RuntimeError):
+    """rt_layout_build refused the description: .message is the text rt_upload_scene would report for it"""
+
+    def __init__(self, message):
+        RuntimeError.__init__(self, message)
+        self.message = message
+
+
+def layout(desc, wide=-1, wide8=0, tlas_lds=1):
+    """rt_layout_build + rt_layout_array: the traversal layout rt_upload_scene would copy to the device for the rt_scene_desc 'desc'
+    (HostScene.describe()) under RT_WIDE / RT_WIDE8 / RT_TLAS_LDS = wide / wide8 / tlas_lds, as a dict of flat numpy arrays named as in
+    LAYOUT_ARRAYS (device records as uint32 words; rootLink, rootWide, rootWide8 per BLAS) plus every name of LAYOUT_SCALARS as a Python
+    number ('root' is the scalar the header calls rootLink: the scene's root link).  Needs no device."""
+    L = rt_lib()
+    h = L.rt_layout_build(desc, int(wide), int(wide8), int(tlas_lds))
+    if not h:
+        raise LayoutError(L.rt_last_error(None).decode())
+    try:
+        out = {}
+        for which, (name, dtype) in enumerate(LAYOUT_ARRAYS):
+            data, nbytes = C.c_void_p(), C.c_size_t()
+            if L.rt_layout_array(h, which, C.byref(data), C.byref(nbytes)) != 0:
+                raise RuntimeError(L.rt_last_error(None).decode())
+            out[name] = np.frombuffer(C.string_at(data, nbytes.value), dtype=dtype).copy() if nbytes.value else np.zeros(0, dtype)
+        for name, v in zip(LAYOUT_SCALARS, out["scalars"]):
+            out[name] = int(v)
+        out["root"], out["tlasBase"] = (int(v) for v in out["scalars"].view(np.uint32)[:2])
+        out["reachOriginMax"] = float(out["scalars"].view(np.float32)[4])
+        return out
+    finally:
+        L.rt_layout_free(h)
 
 
 def device_pci_bus_id(device):

@@ -872,6 +872,45 @@ def test_limits_are_reported(scenes, oracle_api, host_api):
     r.close()
 
 
+def test_failed_upload_leaves_no_scene(scenes, host_api):
+    """A refused rt_upload_scene leaves the context without a scene (the old one is freed), and a good upload after it renders the same bits."""
+    import ctypes as C
+    from test_layout_cpu import INSTANCE, RtSceneDesc
+    r = host_api.HostRenderer(16, 16)
+    scenes.tlas_test2(r.scene)
+    r.commit()
+    r.render(host_api.RT_MODE_PATH, 0, 1)
+    first = r.accumulator().view(np.uint32)
+    good = r.scene.describe()
+    bad = RtSceneDesc.from_buffer_copy(C.string_at(good, C.sizeof(RtSceneDesc)))
+    inst = np.frombuffer(C.string_at(bad.instances, bad.n_instances * INSTANCE.itemsize), dtype=INSTANCE).copy()
+    inst["blas"][bad.n_instances - 1] = bad.n_blas
+    bad.instances = inst.ctypes.data
+    assert r.rt.rt_upload_scene(r.ctx, C.byref(bad)) == host_api.RT_E_ARG
+    assert r.rt.rt_last_error(r.ctx).decode() == "rt_upload_scene: instance %d blas %d out of range" % (bad.n_instances - 1, bad.n_blas)
+    assert r.rt.rt_render(r.ctx, host_api.RT_MODE_PATH, 0, 1, 0x12345678, 0, 16, 4) == host_api.RT_E_STATE
+    assert r.rt.rt_last_error(r.ctx).decode() == "rt_render: no scene uploaded"
+    assert r.rt.rt_upload_scene(r.ctx, good) == 0
+    r.clear()
+    r.render(host_api.RT_MODE_PATH, 0, 1)
+    assert np.array_equal(r.accumulator().view(np.uint32), first)
+    r.close()
+
+
+def test_upload_refusals_carry_their_status(host_api):
+    """every refusal of test_layout_cpu.py's table, through rt_upload_scene itself: the status and the text; the context stays usable"""
+    import ctypes as C
+    from test_layout_cpu import ERRORS, tiny_desc
+    r = host_api.HostRenderer(16, 16)
+    for spoil, tlas, status, message in ERRORS:
+        desc, blas, alive = tiny_desc(host_api, tlas)
+        assert r.rt.rt_upload_scene(r.ctx, C.byref(desc)) == 0, spoil.__name__
+        spoil(desc, blas, alive)
+        assert r.rt.rt_upload_scene(r.ctx, C.byref(desc)) == status, spoil.__name__
+        assert r.rt.rt_last_error(r.ctx).decode() == message
+    r.close()
+
+
 def _many_lights(b, n=12):
     """a floor, a diffuse and a glass sphere, a metal mesh, n area lights on a ring (more than the 8 the device path stopped at before round 3)"""
     import math

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_c_abi_exports_every_declared_symbol(host_api):
     hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    declared = set(re.findall(r"^(?:int|void\*?|rt_ctx\*|const char\*)\s+\*?(rt_[a-z_]+)\s*\(", hdr, re.M))
+    declared = set(re.findall(r"^(?:int|void\*?|rt_ctx\*|rt_layout\*|const char\*)\s+\*?(rt_[a-z_]+)\s*\(", hdr, re.M))
     assert declared == set(host_api.RT_SYMBOLS), declared ^ set(host_api.RT_SYMBOLS)
     L = host_api.rt_lib()
     for sym in declared:
