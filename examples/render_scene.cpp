@@ -6,23 +6,33 @@
 //   g++ -std=c++17 -O2 examples/render_scene.cpp -Iray-and-pathtracer_amd/host \
 //       -Lray-and-pathtracer_amd/host -lrapt_host -Lray-and-pathtracer_amd/csrc -lrt_amd \
 //       -Wl,-rpath,$PWD/ray-and-pathtracer_amd/host -Wl,-rpath,$PWD/ray-and-pathtracer_amd/csrc -o render_scene
-//   ./render_scene scene.rapt out.ppm 640 360 path 16 [all | d0,d1,...] [--filter reference|point|box|tent]
+//   ./render_scene scene.rapt out.ppm 640 360 path 16 [all | d0,d1,...] [--filter reference|point|box|tent] [--spin DEG]
 // The optional last argument spreads every Tick over several GPUs (one rt_ctx and one host thread per device,
 // rows interleaved, rt_gather_rows into device d0): "all" = every visible device.  --filter (anywhere after the frame count) sets
 // Renderer::pixelFilter: the sub-pixel camera samples of path mode (rt_set_pixel_filter; default: the reference's truncated jitter).
+// --spin DEG (a TLAS scene): before the last frame instance 0 is turned by DEG degrees about y (bvhInstance::SetTransform) and sent on with
+// Scene::CommitInstances (rt_set_instances: no re-upload); that Tick clears, so the image is the moved scene's.
 #include "rapt.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <stdexcept>
 #include <vector>
 
 using namespace rapt;
 
 int main(int argc, char** argv)
 {
-	if (argc < 7) { fprintf(stderr, "usage: %s scene.rapt out.ppm width height whitted|path frames [all | d0,d1,...] [--filter reference|point|box|tent]\n", argv[0]); return 2; }
+	if (argc < 7) { fprintf(stderr, "usage: %s scene.rapt out.ppm width height whitted|path frames [all | d0,d1,...] [--filter reference|point|box|tent] [--spin DEG]\n", argv[0]); return 2; }
 	int filter = RT_FILTER_REFERENCE;
+	float spin = 0;
+	for (int a = 7; a + 1 < argc; a++) {
+		if (strcmp(argv[a], "--spin") != 0) continue;
+		spin = (float)atof(argv[a + 1]);
+		for (int b = a; b + 2 < argc; b++) argv[b] = argv[b + 2];
+		argc -= 2, a--;
+	}
 	for (int a = 7; a < argc; a++) {
 		if (strcmp(argv[a], "--filter") != 0) continue;
 		static const char* const names[4] = { "reference", "point", "box", "tent" };
@@ -50,7 +60,17 @@ int main(int argc, char** argv)
 		app.scene.LoadFile(argv[1]);         // meshes, materials, lights, BVH / TLAS (host builders)
 		if (path) app.scene.toogleRaytracer(); // key 'P' in the reference: path tracing, lights sampled
 		app.Commit();                        // flatten + rt_upload_scene on every context
-		for (int f = 0; f < (path ? frames : 1); f++) app.Tick(0.0f);
+		const int ticks = path ? frames : 1;
+		for (int f = 0; f < ticks; f++) {
+			if (spin != 0 && f == ticks - 1) {
+				if (!app.scene.useTLAS) throw std::runtime_error("--spin needs a scene with a TLAS");
+				mat4 M = app.scene.bvhList[0].matTransform * mat4::RotateY(spin * 3.14159265358979f / 180.0f);
+				app.scene.bvhList[0].SetTransform(M);
+				app.scene.CommitInstances();
+				app.camera.SetChange(true); // the accumulator holds the scene before the move: this Tick clears
+			}
+			app.Tick(0.0f);
+		}
 		FILE* out = fopen(argv[2], "wb");
 		if (!out) { perror(argv[2]); return 1; }
 		fprintf(out, "P6\n%d %d\n255\n", w, h);

@@ -517,7 +517,7 @@ int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_var_params* params);
  * rt_history_capture: copies the bound accumulator, the three statistics arrays, the three G-buffer arrays and the current camera record
  *   into history buffers of the context (allocated on first use, freed by rt_destroy): device to device on the context's stream, without
  *   synchronising.  RT_E_STATE: statistics off; the G-buffer missing or stale (rt_render_aovs first).  RT_E_UNSUPPORTED: the current
- *   camera is a fisheye.  A history stays valid until rt_upload_scene, rt_set_time or rt_stats_enable(ctx, 0); rt_clear and rt_set_camera
+ *   camera is a fisheye.  A history stays valid until rt_upload_scene, rt_set_time, rt_set_instances or rt_stats_enable(ctx, 0); rt_clear and rt_set_camera
  *   do not touch it.
  * rt_reproject: rewrites the accumulator and the statistics of EVERY pixel: carried from the history, or zeroed (a zero float4, count 0,
  *   sums 0).  On the context's stream; *n_carried_out (may be NULL) receives the number of carried pixels, and reading those 4 bytes back
@@ -549,7 +549,9 @@ int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_var_params* params);
  *   (metal, glass, shiny diffuse, a light seen directly) starts empty unless carry_view_dependent is set; a miss is never carried.
  *   params NULL: RT_REPROJECT_DEFAULTS.  RT_E_ARG (checked before the context): a tolerance that is negative or NaN, max_history < 0.
  *   RT_E_STATE: statistics off; no valid history; the current G-buffer missing or stale.  RT_E_UNSUPPORTED: the current camera is a
- *   fisheye.  With rt_set_profiling on, rt_history_capture's copies and k_reproject are each one launch of rt_profile.query. */
+ *   fisheye.  With rt_set_profiling on, rt_history_capture's copies and k_reproject are each one launch of rt_profile.query.
+ *   Object motion is not reprojected: rt_set_instances (like rt_set_time and rt_upload_scene) invalidates the history, and a carry is across a
+ *   camera move only. */
 typedef struct { float normal_tolerance, plane_tolerance; int32_t max_history; int32_t carry_view_dependent; } rt_reproject_params;
 #define RT_REPROJECT_DEFAULTS { 0.25f, 0.01f, 0, 0 }   /* a starting point, NOT tuned */
 int rt_history_capture(rt_ctx* ctx);
@@ -604,6 +606,52 @@ int rt_build_bvh_split(rt_ctx* ctx, int split_method, const rt_triangle* tris, u
  * device.  bounds6: per instance the world box its bvhInstance holds (min.xyz, max.xyz, template bvhInstance.cpp:37-44);
  * 1 <= n <= 256; nodes_out has room for 2 n + 1 nodes.  Same node order and boxes as the host builder. */
 int rt_build_tlas(rt_ctx* ctx, const float* bounds6, uint32_t n, rt_tlas_node* nodes_out, uint32_t* nodes_used_out);
+
+/* ---- moving instances without a re-upload -------------------------------------------------------------------
+ * A TLAS exists so that objects can move without rebuilding their trees.  rt_set_instances is bvhInstance::SetTransform
+ * (bvhInstance.cpp:37-44) for instances [first, first + count) followed by tlas::build (tlas.cpp:13-48) over ALL instances, on the device,
+ * into the loaded scene: no BLAS is laid out or copied again.  Afterwards the context holds, byte for byte, what rt_upload_scene would hold
+ * of the updated description (same BLASes, the new instance records, tlas_nodes = the rebuilt TLAS): the inst[] records, the TLAS pair
+ * records, the reach[] records and the scalars rootLink, tlasBase, tlasPairs, reachOriginMax, tlasLds, stackRows (rt_scene_array reads
+ * them back).  (The reference leaves tl->Build() commented out, template/scene.h:1245: moving instances is this library's own addition.)
+ *   Transforms: instances[k].transform / .inv_transform replace those of instance first + k.  instances[k].blas must equal the uploaded
+ *     instance's BLAS (RT_E_ARG otherwise): an instance cannot be re-pointed at another BLAS.
+ *   bounds6 != NULL: count * 6 floats (min.xyz, max.xyz), the world box the caller's bvhInstance holds after its SetTransform.  The
+ *     reference never resets 'bounds' (bvhInstance.h:15-30), so a caller that mirrors it sends a box that grows with every move: that is
+ *     the reference's behaviour, the host mirror's, and what rt_build_tlas takes.
+ *   bounds6 == NULL: the device computes the box of a FRESH instance -- bvhInstance(blas) followed by one SetTransform: the BLAS's local
+ *     box (bvh::bounds = node 0's box, bvh.cpp:48-49; kept per BLAS at upload) grown by the 8 corners TransformPosition(corner(i),
+ *     transform), i = 0..7, corner(i) taking max.x / max.y / max.z where bits 0 / 1 / 2 of i are set and min otherwise; f32 in
+ *     TransformPosition's operation order ((c0 * x + c1 * y) + c2 * z) + c3 * 1.0f, no contraction.  This box does NOT accumulate over
+ *     successive calls: it is what an animation wants, and the library's own choice.
+ *   The TLAS afterwards is tlas::build's over the boxes of all n instances.  An untouched instance keeps the box it last had; one never
+ *     set, the box of its leaf in the uploaded tlas_nodes (the first such leaf in node order; an instance without one must be part of the
+ *     first update).  Node numbering and boxes are exactly rt_build_tlas's on those boxes.  An uploaded TLAS of another shape (a hand-made
+ *     tree, another pair count) is replaced by it; the split of a traversal block's LDS is re-evaluated for the new pair count.
+ *   Ordering: queued on the context's stream behind what is there.  The nodes are built into scratch first; reading 4 bytes (nodes used)
+ *     back is the call's only synchronisation.  If the build finds no finite union area left (rt_build_tlas's failure: e.g. boxes whose
+ *     union areas all reach 1e30), the call returns RT_E_UNSUPPORTED and the scene is exactly as before; only after that check do the
+ *     copies and the kernel that rewrite the scene run.
+ *   Invalidation: everything rt_set_time invalidates -- the G-buffer is stale (rt_render_aovs), the primary-hit table is rebuilt by the
+ *     next dense batch, a captured history is invalid (rt_reproject: RT_E_STATE until a new rt_history_capture).  The accumulator, the
+ *     statistics and the active-pixel list are not touched: the caller clears, or reprojects across a CAMERA move only -- rt_reproject
+ *     does not follow object motion.  A call that fails invalidates nothing.
+ *   Errors.  RT_E_STATE: no scene loaded.  RT_E_UNSUPPORTED: the scene has no TLAS (rt_set_time stays RT_E_UNSUPPORTED under one).
+ *     RT_E_ARG, checked on the host before anything is queued, the scene unchanged: a null ctx or instances; count == 0; a range outside
+ *     the instances; a blas mismatch; a non-finite matrix entry; a bound that is non-finite or beyond 1e30 in magnitude (with bounds6 ==
+ *     NULL: a transform that could take the BLAS's box there); an untouched instance that has no box yet.
+ *   Q-learning, the wide walks (per BLAS: a transform does not change them), counters and profiling work as before; with rt_set_profiling
+ *     on, the call is one entry of rt_profile.query (its copies, kernels and the read-back).
+ * rt_download_tlas: the TLAS the context walks now, as rt_build_tlas returns it: nodes_out has room for 2 n + 1 nodes, *nodes_used_out
+ *   = 2 n after an rt_set_instances; before the first one, the uploaded tlas_nodes and their count (RT_E_UNSUPPORTED if they are more than
+ *   2 n + 1).  Synchronous.  RT_E_STATE: no scene; RT_E_UNSUPPORTED: no TLAS.
+ * rt_scene_array: what the context holds of the layout rt_layout_build describes, read back from the device: which in { RT_LAYOUT_PAIRS,
+ *   RT_LAYOUT_REACH, RT_LAYOUT_INST, RT_LAYOUT_SCALARS }, the element formats and the 14 scalars of rt_layout_array; any other array:
+ *   RT_E_UNSUPPORTED (the context does not keep its size).  *bytes_out receives the array's size; out == NULL asks for the size alone;
+ *   cap_bytes below it: RT_E_ARG.  Synchronous; for tests and tools.  RT_E_STATE: no scene. */
+int rt_set_instances(rt_ctx* ctx, uint32_t first, uint32_t count, const rt_instance* instances, const float* bounds6);
+int rt_download_tlas(rt_ctx* ctx, rt_tlas_node* nodes_out, uint32_t* nodes_used_out);
+int rt_scene_array(rt_ctx* ctx, int which, void* out, size_t cap_bytes, size_t* bytes_out);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Kernels tally rt_counters (slower; keep off when timing).

@@ -5,6 +5,58 @@
 // scene_array (rt_ctx.h): a vector copied into a new array of the scene pool
 #define SCENE_ARRAY(...) do { const int rc_ = scene_array(c, __VA_ARGS__); if (rc_ != RT_OK) return rc_; } while (0)
 
+// RT_LAYOUT_SCALARS (include/rt_amd.h): the 14 words, in their documented order
+static void layout_scalars(const SceneLayout& L, int32_t* out)
+{
+	int32_t originMaxBits;
+	memcpy(&originMaxBits, &L.reachOriginMax, 4);
+	const int32_t s[14] = { (int32_t)L.root, (int32_t)L.tlasBase, L.tlasPairs, L.nInst, originMaxBits, L.tlasLds, L.stackRows, L.nBruteSph, L.nBrutePla,
+	                        L.wideOK, L.wide8OK, L.pathUnsupported, L.animSlots, L.refitLevels };
+	memcpy(out, s, sizeof(s));
+}
+
+// What rt_set_instances (rt_api_instances.inc) needs of a TLAS scene, kept at upload: see rt_ctx.h InstanceState
+static int instances_keep(rt_ctx* c, const rt_scene_desc* d, const SceneLayout& L, DInstance* instDev, float* reachDev)
+{
+	rt_ctx::InstanceState& I = c->instances;
+	I = rt_ctx::InstanceState();
+	const uint n = d->n_instances;
+	I.inst = L.inst, I.instMut = instDev, I.reachMut = reachDev;
+	I.blasOf.resize(n), I.reach.resize(n), I.boundsKnown.assign(n, 0);
+	I.objBox.resize(d->n_blas), I.blasBox6.resize((size_t)6 * d->n_blas);
+	for (uint k = 0; k < d->n_blas; k++) {
+		I.objBox[k] = blas_object_box(d->blas[k]);
+		// bvh::bounds (bvh.cpp:48-49): an empty box grown by node 0's two corners
+		const rt_bvh_node& r = d->blas[k].nodes[0];
+		for (int a = 0; a < 3; a++) {
+			float lo = 1e30f, hi = -1e30f;
+			lo = lo < r.aabb_min[a] ? lo : r.aabb_min[a], hi = hi > r.aabb_min[a] ? hi : r.aabb_min[a];
+			lo = lo < r.aabb_max[a] ? lo : r.aabb_max[a], hi = hi > r.aabb_max[a] ? hi : r.aabb_max[a];
+			I.blasBox6[6 * k + a] = lo, I.blasBox6[6 * k + 3 + a] = hi;
+		}
+	}
+	for (uint i = 0; i < n; i++) I.blasOf[i] = d->instances[i].blas, I.reach[i] = instance_reach(I.objBox[d->instances[i].blas], d->instances[i].inv_transform);
+	// an untouched instance keeps the box of its leaf in the uploaded TLAS (the first one in node order)
+	std::vector<float> b6((size_t)6 * n, 0.0f);
+	I.uploaded.assign(d->tlas_nodes, d->tlas_nodes + d->tlas_nodes_used);
+	for (uint i = d->tlas_nodes_used; i-- > 0;) {
+		const rt_tlas_node& nd = d->tlas_nodes[i];
+		if (nd.left_right != 0 || nd.blas >= n || (i == 0 && d->tlas_nodes_used > 1)) continue;
+		memcpy(&b6[6 * nd.blas], nd.aabb_min, 12), memcpy(&b6[6 * nd.blas + 3], nd.aabb_max, 12);
+		I.boundsKnown[nd.blas] = 1;
+	}
+	SCENE_ARRAY(&I.bounds, b6);
+	SCENE_ARRAY(&I.blasBox, I.blasBox6);
+	SCENE_ARRAY(&I.blasOfDev, I.blasOf);
+	HIPCHK(c, dalloc(c->sceneAllocs, &I.tlasKeep, (size_t)2 * n + 1));
+	HIPCHK(c, dalloc(c->sceneAllocs, &I.boundsNew, (size_t)6 * n));
+	HIPCHK(c, dalloc(c->sceneAllocs, &I.nodesNew, (size_t)2 * n + 1));
+	HIPCHK(c, dalloc(c->sceneAllocs, &I.used, 1));
+	HIPCHK(c, dalloc(c->sceneAllocs, &I.reachIn, n));
+	HIPCHK(c, dalloc(c->sceneAllocs, &I.xform, (size_t)12 * n));
+	return RT_OK;
+}
+
 int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
 {
 	if (!c || !d) return fail(c, RT_E_ARG, "rt_upload_scene: null argument");
@@ -19,6 +71,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
 	c->mega.pick = {}; // another scene: the Whitted forms are timed again
 	free_pool(c->sceneAllocs);
 	c->sceneLoaded = false;
+	c->instances = rt_ctx::InstanceState();
 	LayoutKnobs knobs;
 	knobs.wide = c->knobs.wide, knobs.wide8 = c->knobs.wide8, knobs.tlasLds = c->knobs.tlasLds;
 	rc = build_layout(d, knobs, L, err);
@@ -29,7 +82,10 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
 	DScene S;
 	memset(&S, 0, sizeof(S));
 	float* dp = nullptr;
-	SCENE_ARRAY(&dp, L.pairs, 16);
+	// rt_set_instances rebuilds the TLAS as tlas::build's, n pair records for n instances (rt_instances.h): the tail of pairs[] and reach[]
+	// have room for them from the start
+	const size_t tlasRoom = d->use_tlas && (int)d->n_instances > L.tlasPairs ? (size_t)((int)d->n_instances - L.tlasPairs) : 0;
+	SCENE_ARRAY(&dp, L.pairs, 16 + tlasRoom * 16);
 	S.pairs = (const float4*)dp;
 	SCENE_ARRAY(&dp, L.prims, 16);
 	S.prims = (const float4*)dp;
@@ -66,8 +122,10 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
 		SCENE_ARRAY(&dp, L.brute);
 		S.brute = (const float4*)dp;
 		S.nBruteSph = L.nBruteSph, S.nBrutePla = L.nBrutePla;
-		SCENE_ARRAY(&dp, L.reach);
+		SCENE_ARRAY(&dp, L.reach, tlasRoom * 12);
 		S.reach = (const float4*)dp;
+		const int rc_ = instances_keep(c, d, L, di, dp);
+		if (rc_ != RT_OK) return rc_;
 		S.tlasBase = L.tlasBase, S.reachOriginMax = L.reachOriginMax, S.tlasPairs = L.tlasPairs, S.nInst = L.nInst, S.tlasLds = L.tlasLds;
 	}
 	DLight* dl = nullptr;
@@ -87,6 +145,8 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
 		S.sky = ds, S.skyW = d->sky_w, S.skyH = d->sky_h, S.skyN = d->sky_n;
 	}
 	c->S = S;
+	c->blasPairs = (uint)(L.pairs.size() / 16) - (uint)L.tlasPairs;
+	layout_scalars(L, c->layoutScalars);
 	c->blasRootWide8 = L.rootWide8;
 	c->blasRoot = L.rootLink, c->blasRootWide = L.wideOK ? L.rootWide : L.rootLink, c->nInstances = d->use_tlas ? (int)d->n_instances : 0;
 	c->sceneLoaded = true;
@@ -108,11 +168,7 @@ rt_layout* rt_layout_build(const rt_scene_desc* d, int wide, int wide8, int tlas
 	std::string err;
 	const int rc = build_layout(d, knobs, L, err);
 	if (rc != RT_OK) { fail(nullptr, rc, "%s", err.c_str()); delete o; return nullptr; }
-	int32_t originMaxBits;
-	memcpy(&originMaxBits, &L.reachOriginMax, 4);
-	const int32_t s[14] = { (int32_t)L.root, (int32_t)L.tlasBase, L.tlasPairs, L.nInst, originMaxBits, L.tlasLds, L.stackRows, L.nBruteSph, L.nBrutePla,
-	                        L.wideOK, L.wide8OK, L.pathUnsupported, L.animSlots, L.refitLevels };
-	memcpy(o->scalars, s, sizeof(s));
+	layout_scalars(L, o->scalars);
 	return o;
 }
 int rt_layout_array(const rt_layout* o, int which, const void** data, size_t* bytes)

@@ -5,6 +5,7 @@
 //   rt_layout.h         the scene layout as a value: build_layout, host arithmetic only (no hip* call, no rt_ctx)
 //   rt_api_upload.inc   rt_upload_scene: build_layout's arrays copied to the device; rt_layout_*
 //   rt_api_build.inc    device builders, refit
+//   rt_api_instances.inc rt_set_instances (kernels: rt_instances.h), rt_download_tlas, rt_scene_array
 //   rt_api_render.inc   rt_render*, rt_trace_batch*: round loops and batches
 //   rt_api_gather.inc   rt_gather_*
 //   rt_api_query.inc    batch queries
@@ -19,6 +20,8 @@
 #include "rt_stream.h"
 #include "rt_mega.h"
 #include "rt_build.h"
+#include "rt_instances.h"
+#include "rt_layout.h"
 #include "rt_denoise.h"
 #include "rt_adaptive.h"
 #include "rt_budget.h"
@@ -126,6 +129,26 @@ struct rt_ctx {
 	uint* refitOrder = nullptr; int* refitLevelStart = nullptr;
 	int refitLevels = 0, animSlots = 0;
 	std::vector<int> refitLevelHost; // levelStart[] on the host: which levels are wide enough for a launch of their own
+	// rt_set_instances (rt_api_instances.inc): the part of the layout an instance's transform decides, kept where the call can rewrite it.
+	// Host: a mirror of inst[], per instance its BLAS and its reach (rt_layout.h instance_reach), per BLAS its object box (f64) and its
+	// local box (f32, bvh::bounds), the uploaded TLAS until the first update replaces it, the RT_LAYOUT_SCALARS words.  Device (scene
+	// pool): every instance's world box and the TLAS nodes the context walks, the local boxes, and the scratch a call builds into.
+	struct InstanceState {
+		std::vector<DInstance> inst;
+		std::vector<int> blasOf;
+		std::vector<Reach> reach;
+		std::vector<ObjectBox> objBox;
+		std::vector<float> blasBox6;
+		std::vector<char> boundsKnown; // the instance had a leaf in the uploaded TLAS, or has been set since
+		std::vector<rt_tlas_node> uploaded;
+		bool built = false; // tlasKeep holds a tlas::build of the context's own
+		DInstance* instMut = nullptr; float* reachMut = nullptr;
+		float* bounds = nullptr; TlasNodeDev* tlasKeep = nullptr; float* blasBox = nullptr; int* blasOfDev = nullptr;
+		float* boundsNew = nullptr; TlasNodeDev* nodesNew = nullptr; int* used = nullptr; InstReach* reachIn = nullptr; float* xform = nullptr;
+	};
+	InstanceState instances;
+	uint blasPairs = 0;          // pair records in front of the TLAS's: pairs[] holds blasPairs + S.tlasPairs records
+	int32_t layoutScalars[14] = { 0 }; // RT_LAYOUT_SCALARS of the loaded scene (rt_scene_array)
 	// camera
 	DCamera C{};
 	bool cameraSet = false;

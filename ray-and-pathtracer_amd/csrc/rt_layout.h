@@ -453,74 +453,109 @@ static int pack_instances(const rt_scene_desc* d, SceneLayout& L, std::string& e
 }
 
 // ---- reach[]: per TLAS pair, the world boxes its children's geometry can occupy (see above) ----------------------
+// The per-instance part, in two steps that rt_set_instances (rt_api_instances.inc) repeats for a moved instance: the object box of a BLAS
+// (kept per BLAS with the context at upload), and the world box of that geometry under the instance's transform with its margins.
+struct Reach { double lo[3], hi[3], a, b; };
+static Reach reach_unbounded()
+{
+	const double big = 1e30;
+	Reach r;
+	for (int k = 0; k < 3; k++) r.lo[k] = -big, r.hi[k] = big;
+	r.a = 0, r.b = 0;
+	return r;
+}
+struct ObjectBox { double lo[3], hi[3]; bool bounded; }; // bounded == false: whatever the transform, the instance's reach is unbounded
+// object-space box of everything a ray can hit in this BLAS: triangles and spheres; a plane is
+// unbounded.  Triangle::Intersect rejects a triangle with N == 0 for every ray with finite D
+// (|dot(N, D)| < t_min), and one with a NaN in N for every ray (t is NaN and fails the final
+// range test) -- the two sentinel triangles a .tri mesh ends with (v0 = v1 = v2 = 999) are such.
+static ObjectBox blas_object_box(const rt_blas& b)
+{
+	const double big = 1e30;
+	ObjectBox ob;
+	for (int k = 0; k < 3; k++) ob.lo[k] = ob.hi[k] = 0;
+	ob.bounded = false;
+	if (b.n_prims == 0 || b.n_pla > 0) return ob;
+	double lo[3] = { big, big, big }, hi[3] = { -big, -big, -big };
+	bool finite = true;
+	for (uint j = 0; j < b.n_tri; j++) {
+		const rt_triangle& t = b.tris[j];
+		if ((t.N[0] == 0 && t.N[1] == 0 && t.N[2] == 0) || t.N[0] != t.N[0] || t.N[1] != t.N[1] || t.N[2] != t.N[2]) continue;
+		for (int k = 0; k < 3; k++) {
+			lo[k] = std::min(lo[k], (double)std::min(t.v0[k], std::min(t.v1[k], t.v2[k])));
+			hi[k] = std::max(hi[k], (double)std::max(t.v0[k], std::max(t.v1[k], t.v2[k])));
+			if (!(std::fabs(t.v0[k]) < 1e29f && std::fabs(t.v1[k]) < 1e29f && std::fabs(t.v2[k]) < 1e29f)) finite = false;
+		}
+	}
+	for (uint j = 0; j < b.n_sph; j++) {
+		const rt_sphere& q = b.spheres[j];
+		const double rr = std::max(std::fabs((double)q.r), std::sqrt(std::fabs((double)q.r2))); // r and r2 are separate inputs
+		for (int k = 0; k < 3; k++) {
+			lo[k] = std::min(lo[k], (double)q.pos[k] - rr), hi[k] = std::max(hi[k], (double)q.pos[k] + rr);
+			if (!(std::fabs(q.pos[k]) < 1e29f && rr < 1e29)) finite = false;
+		}
+	}
+	if (lo[0] > hi[0]) { for (int k = 0; k < 3; k++) lo[k] = hi[k] = 0; } // nothing hittable: an empty box at the origin
+	for (int k = 0; k < 3; k++) ob.lo[k] = lo[k], ob.hi[k] = hi[k];
+	ob.bounded = finite;
+	return ob;
+}
+// the world box of an object box under the exact inverse of inv_transform (rows 0-2: the float matrix the device applies), in double, and
+// the margins a, b of the float rounding of the object-space ray (see reach[] above); unbounded where that cannot be bounded
+static Reach instance_reach(const ObjectBox& ob, const float* m)
+{
+	const double big = 1e30, rel = 1.0 / 32768.0;
+	Reach r = reach_unbounded();
+	if (!ob.bounded) return r;
+	const double* lo = ob.lo;
+	const double* hi = ob.hi;
+	const double A[3][3] = { { m[0], m[1], m[2] }, { m[4], m[5], m[6] }, { m[8], m[9], m[10] } }, tv[3] = { m[3], m[7], m[11] };
+	const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
+	                   A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+	if (!(std::fabs(det) > 1e-30) || !std::isfinite(det)) return reach_unbounded();
+	double Ai[3][3];
+	for (int rI = 0; rI < 3; rI++)
+		for (int cI = 0; cI < 3; cI++) {
+			const int r1 = (cI + 1) % 3, r2 = (cI + 2) % 3, c1 = (rI + 1) % 3, c2 = (rI + 2) % 3;
+			Ai[rI][cI] = (A[r1][c1] * A[r2][c2] - A[r1][c2] * A[r2][c1]) / det;
+		}
+	double nA = 0, nAi = 0, lmax = 0, wmax = 0;
+	for (int rI = 0; rI < 3; rI++) {
+		nA = std::max(nA, std::fabs(A[rI][0]) + std::fabs(A[rI][1]) + std::fabs(A[rI][2]));
+		nAi = std::max(nAi, std::fabs(Ai[rI][0]) + std::fabs(Ai[rI][1]) + std::fabs(Ai[rI][2]));
+	}
+	for (int k = 0; k < 3; k++) r.lo[k] = big, r.hi[k] = -big, lmax = std::max(lmax, std::max(std::fabs(lo[k]), std::fabs(hi[k])) + std::fabs(tv[k]));
+	for (int corner = 0; corner < 8; corner++) {
+		const double l[3] = { (corner & 1 ? hi[0] : lo[0]) - tv[0], (corner & 2 ? hi[1] : lo[1]) - tv[1], (corner & 4 ? hi[2] : lo[2]) - tv[2] };
+		for (int k = 0; k < 3; k++) {
+			const double w = Ai[k][0] * l[0] + Ai[k][1] * l[1] + Ai[k][2] * l[2];
+			r.lo[k] = std::min(r.lo[k], w), r.hi[k] = std::max(r.hi[k], w);
+		}
+	}
+	for (int k = 0; k < 3; k++) wmax = std::max(wmax, std::max(std::fabs(r.lo[k]), std::fabs(r.hi[k])));
+	const double cond = std::max(1.0, nA * nAi);
+	r.a = rel * (cond * wmax + nAi * lmax) + 1e-20, r.b = rel * cond;
+	if (!(wmax < 1e29) || !std::isfinite(r.a) || !std::isfinite(r.b) || r.a > 1e29 || r.b > 1e10) return reach_unbounded();
+	return r;
+}
+// the boxes are stored inflated for every world origin with |O|_1 <= originMax: 64 x the extent of
+// the instanced geometry (camera and bounce rays start inside that; a ray from further away is
+// simply not culled)
+static double reach_origin_max(const Reach* instReach, size_t n)
+{
+	double extent = 1.0;
+	for (size_t i = 0; i < n; i++)
+		if (instReach[i].b > 0) for (int k = 0; k < 3; k++) extent = std::max(extent, std::max(std::fabs(instReach[i].lo[k]), std::fabs(instReach[i].hi[k])));
+	return 64.0 * 3.0 * extent;
+}
+
 static int pack_reach(const rt_scene_desc* d, SceneLayout& L, const std::vector<uint>& tlasSlots, std::string& err)
 {
-	struct Reach { double lo[3], hi[3], a, b; };
-	const double big = 1e30, rel = 1.0 / 32768.0;
-	auto unbounded = [&]() { Reach r; for (int k = 0; k < 3; k++) r.lo[k] = -big, r.hi[k] = big; r.a = 0, r.b = 0; return r; };
+	const double big = 1e30;
+	std::vector<ObjectBox> box(d->n_blas);
+	for (uint k = 0; k < d->n_blas; k++) box[k] = blas_object_box(d->blas[k]);
 	std::vector<Reach> instReach(d->n_instances);
-	for (uint i = 0; i < d->n_instances; i++) {
-		const rt_instance& in = d->instances[i];
-		const rt_blas& b = d->blas[in.blas];
-		Reach r = unbounded();
-		instReach[i] = r;
-		// object-space box of everything a ray can hit in this BLAS: triangles and spheres; a plane is
-		// unbounded.  Triangle::Intersect rejects a triangle with N == 0 for every ray with finite D
-		// (|dot(N, D)| < t_min), and one with a NaN in N for every ray (t is NaN and fails the final
-		// range test) -- the two sentinel triangles a .tri mesh ends with (v0 = v1 = v2 = 999) are such.
-		if (b.n_prims == 0 || b.n_pla > 0) continue;
-		double lo[3] = { big, big, big }, hi[3] = { -big, -big, -big };
-		bool finite = true;
-		for (uint j = 0; j < b.n_tri; j++) {
-			const rt_triangle& t = b.tris[j];
-			if ((t.N[0] == 0 && t.N[1] == 0 && t.N[2] == 0) || t.N[0] != t.N[0] || t.N[1] != t.N[1] || t.N[2] != t.N[2]) continue;
-			for (int k = 0; k < 3; k++) {
-				lo[k] = std::min(lo[k], (double)std::min(t.v0[k], std::min(t.v1[k], t.v2[k])));
-				hi[k] = std::max(hi[k], (double)std::max(t.v0[k], std::max(t.v1[k], t.v2[k])));
-				if (!(std::fabs(t.v0[k]) < 1e29f && std::fabs(t.v1[k]) < 1e29f && std::fabs(t.v2[k]) < 1e29f)) finite = false;
-			}
-		}
-		for (uint j = 0; j < b.n_sph; j++) {
-			const rt_sphere& q = b.spheres[j];
-			const double rr = std::max(std::fabs((double)q.r), std::sqrt(std::fabs((double)q.r2))); // r and r2 are separate inputs
-			for (int k = 0; k < 3; k++) {
-				lo[k] = std::min(lo[k], (double)q.pos[k] - rr), hi[k] = std::max(hi[k], (double)q.pos[k] + rr);
-				if (!(std::fabs(q.pos[k]) < 1e29f && rr < 1e29)) finite = false;
-			}
-		}
-		if (lo[0] > hi[0]) { for (int k = 0; k < 3; k++) lo[k] = hi[k] = 0; } // nothing hittable: an empty box at the origin
-		if (!finite) continue;
-		// exact inverse of the float matrix the device applies (rows 0-2 of invTransform), in double
-		const float* m = in.inv_transform;
-		const double A[3][3] = { { m[0], m[1], m[2] }, { m[4], m[5], m[6] }, { m[8], m[9], m[10] } }, tv[3] = { m[3], m[7], m[11] };
-		const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
-		                   A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
-		if (!(std::fabs(det) > 1e-30) || !std::isfinite(det)) continue;
-		double Ai[3][3];
-		for (int rI = 0; rI < 3; rI++)
-			for (int cI = 0; cI < 3; cI++) {
-				const int r1 = (cI + 1) % 3, r2 = (cI + 2) % 3, c1 = (rI + 1) % 3, c2 = (rI + 2) % 3;
-				Ai[rI][cI] = (A[r1][c1] * A[r2][c2] - A[r1][c2] * A[r2][c1]) / det;
-			}
-		double nA = 0, nAi = 0, lmax = 0, wmax = 0;
-		for (int rI = 0; rI < 3; rI++) {
-			nA = std::max(nA, std::fabs(A[rI][0]) + std::fabs(A[rI][1]) + std::fabs(A[rI][2]));
-			nAi = std::max(nAi, std::fabs(Ai[rI][0]) + std::fabs(Ai[rI][1]) + std::fabs(Ai[rI][2]));
-		}
-		for (int k = 0; k < 3; k++) r.lo[k] = big, r.hi[k] = -big, lmax = std::max(lmax, std::max(std::fabs(lo[k]), std::fabs(hi[k])) + std::fabs(tv[k]));
-		for (int corner = 0; corner < 8; corner++) {
-			const double l[3] = { (corner & 1 ? hi[0] : lo[0]) - tv[0], (corner & 2 ? hi[1] : lo[1]) - tv[1], (corner & 4 ? hi[2] : lo[2]) - tv[2] };
-			for (int k = 0; k < 3; k++) {
-				const double w = Ai[k][0] * l[0] + Ai[k][1] * l[1] + Ai[k][2] * l[2];
-				r.lo[k] = std::min(r.lo[k], w), r.hi[k] = std::max(r.hi[k], w);
-			}
-		}
-		for (int k = 0; k < 3; k++) wmax = std::max(wmax, std::max(std::fabs(r.lo[k]), std::fabs(r.hi[k])));
-		const double cond = std::max(1.0, nA * nAi);
-		r.a = rel * (cond * wmax + nAi * lmax) + 1e-20, r.b = rel * cond;
-		if (!(wmax < 1e29) || !std::isfinite(r.a) || !std::isfinite(r.b) || r.a > 1e29 || r.b > 1e10) continue;
-		instReach[i] = r;
-	}
+	for (uint i = 0; i < d->n_instances; i++) instReach[i] = instance_reach(box[d->instances[i].blas], d->instances[i].inv_transform);
 	const uint nT = d->tlas_nodes_used;
 	std::vector<Reach> nodeReach(nT);
 	std::vector<char> state(nT, 0); // 0 unseen, 1 open, 2 done
@@ -529,7 +564,7 @@ static int pack_reach(const rt_scene_desc* d, SceneLayout& L, const std::vector<
 	while (!walk.empty()) {
 		const uint i = walk.back();
 		const rt_tlas_node& nd = d->tlas_nodes[i];
-		if (nd.left_right == 0) { nodeReach[i] = nd.blas < d->n_instances ? instReach[nd.blas] : unbounded(); state[i] = 2; walk.pop_back(); continue; }
+		if (nd.left_right == 0) { nodeReach[i] = nd.blas < d->n_instances ? instReach[nd.blas] : reach_unbounded(); state[i] = 2; walk.pop_back(); continue; }
 		const uint ch[2] = { nd.left_right & 0xFFFFu, nd.left_right >> 16 };
 		if (state[i] == 0) {
 			state[i] = 1;
@@ -546,19 +581,13 @@ static int pack_reach(const rt_scene_desc* d, SceneLayout& L, const std::vector<
 		nodeReach[i] = r, state[i] = 2;
 		walk.pop_back();
 	}
-	// the boxes are stored inflated for every world origin with |O|_1 <= originMax: 64 x the extent of
-	// the instanced geometry (camera and bounce rays start inside that; a ray from further away is
-	// simply not culled)
-	double extent = 1.0;
-	for (uint i = 0; i < d->n_instances; i++)
-		if (instReach[i].b > 0) for (int k = 0; k < 3; k++) extent = std::max(extent, std::max(std::fabs(instReach[i].lo[k]), std::fabs(instReach[i].hi[k])));
-	const double originMax = 64.0 * 3.0 * extent;
+	const double originMax = reach_origin_max(instReach.data(), instReach.size());
 	L.reach.assign((size_t)tlasSlots.size() * 12 + 16, 0.0f);
 	for (size_t sI = 0; sI < tlasSlots.size(); sI++) {
 		const rt_tlas_node& nd = d->tlas_nodes[tlasSlots[sI]];
 		const uint ch[2] = { nd.left_right & 0xFFFFu, nd.left_right >> 16 };
 		for (int h = 0; h < 2; h++) {
-			const Reach& r = state[ch[h]] == 2 ? nodeReach[ch[h]] : unbounded();
+			const Reach r = state[ch[h]] == 2 ? nodeReach[ch[h]] : reach_unbounded();
 			float* rec = &L.reach[sI * 12 + 6 * h]; // {min.xyz, max.xyz} of child h
 			const double m = r.a + r.b * originMax;
 			// round outwards: the float box must contain the inflated double one

@@ -232,6 +232,7 @@ const char* rth_renderer_error(void* h) { return ((RthRenderer*)h)->err.c_str();
 void* rth_renderer_scene(void* h) { return &((RthRenderer*)h)->scene; }
 int rth_renderer_init(void* h) { RthRenderer* r = (RthRenderer*)h; GUARD(r, r->r->Init()); return 0; }
 void* rth_renderer_ctx(void* h) { return ((RthRenderer*)h)->r->ctx; }
+void* rth_renderer_ctx_at(void* h, int k) { Renderer* r = ((RthRenderer*)h)->r; return k >= 0 && (size_t)k < r->ctxs.size() ? r->ctxs[(size_t)k] : nullptr; } // UseDevices: context k
 int rth_renderer_commit(void* h) { RthRenderer* r = (RthRenderer*)h; GUARD(r, r->r->Commit()); return 0; }
 void rth_renderer_set_camera(void* h, const float* camPos, const float* TL, const float* TR, const float* BL, int fisheye, float viewAngle, float yAngle)
 {
@@ -313,6 +314,33 @@ int rth_scene_set_time(void* h, float t)
 {
 	RthScene* s = (RthScene*)h;
 	GUARD(s, s->sc->SetTime(t));
+	return 0;
+}
+// bvhInstance::SetTransform for instances [first, first + count) (T16: row-major mat4 each), then Scene::CommitInstances sends them on
+int rth_scene_set_transforms(void* h, int first, int count, const float* T16)
+{
+	RthScene* s = (RthScene*)h;
+	Scene& sc = *s->sc;
+	if (!sc.useTLAS || first < 0 || count < 0 || (uint)(first + count) > sc.bvhCount) { s->err = "rth_scene_set_transforms: instances out of range (or no TLAS)"; return -1; }
+	for (int k = 0; k < count; k++) {
+		mat4 M;
+		memcpy(M.cell, T16 + 16 * k, 64);
+		sc.bvhList[first + k].SetTransform(M);
+	}
+	return 0;
+}
+int rth_scene_commit_instances(void* h)
+{
+	RthScene* s = (RthScene*)h;
+	GUARD(s, s->sc->CommitInstances());
+	return 0;
+}
+// tlas::build on the host over the instances' current bounds (what CommitInstances makes the device do)
+int rth_scene_rebuild_tlas(void* h)
+{
+	RthScene* s = (RthScene*)h;
+	if (!s->sc->useTLAS || !s->sc->tl) { s->err = "rth_scene_rebuild_tlas: no TLAS"; return -1; }
+	GUARD(s, s->sc->tl->build());
 	return 0;
 }
 int rth_scene_find_nearest(void* h, const float* O, const float* D, float tmax, float t_min, float* t, int* obj, float* normal)

@@ -303,6 +303,12 @@ public:
 	// template/scene.h:1210: mesh wobble + bvh::Refit, executed on the device (rt_set_time); the
 	// reference runs it only when animOn (raytracer && defaultAnim && !useTLAS)
 	void SetTime(float t);
+	// Moving instances without a re-upload (rt_set_instances; the reference leaves tl->Build() commented out, template/scene.h:1245): call
+	// bvhList[i].SetTransform(M) for every instance that moved, then this.  It sends ALL instances' matrices and their 'bounds' -- which
+	// SetTransform grows and never resets, as the reference's -- to ctx and every context of CommitAlso, and refreshes tl->tlasNode /
+	// nodesUsed from rt_download_tlas, so that tl is the tree the device walks.  Throws without useTLAS (RT_E_UNSUPPORTED) and for what
+	// rt_set_instances refuses.  The accumulator is the caller's to clear (Renderer: camera.SetChange(true) before the next Tick).
+	void CommitInstances();
 	void FindNearest(Ray& ray, float t_min) const;   // template/scene.h:1248
 	bool IsOccluded(Ray& ray) const;                 // template/scene.h:1286
 	float3 GetSkyColor(Ray& ray) const;              // template/scene.h:1312, evaluated on the device (rt_sky_color_batch)

@@ -411,6 +411,27 @@ void Scene::SetTime(float t)
 	for (rt_ctx* o : alsoCtx) check(o, rt_set_time(o, t));
 }
 
+void Scene::CommitInstances()
+{
+	if (!ctx) throw std::runtime_error("Scene: Commit() has not been called");
+	if (!useTLAS || !tl) throw std::runtime_error("rt_amd: Scene::CommitInstances: the scene has no TLAS (RT_E_UNSUPPORTED)");
+	std::vector<rt_instance> in(bvhCount);
+	std::vector<float> b6((size_t)6 * bvhCount);
+	for (uint i = 0; i < bvhCount; i++) {
+		in[i].blas = bvhList[i].blas->blasIndex; // the order Describe() flattened them in (set by Commit)
+		memcpy(in[i].transform, bvhList[i].matTransform.cell, 64);
+		memcpy(in[i].inv_transform, bvhList[i].invTransform.cell, 64);
+		put3(&b6[6 * i], bvhList[i].bounds.bmin), put3(&b6[6 * i + 3], bvhList[i].bounds.bmax);
+		Transforms[i] = bvhList[i].matTransform;
+	}
+	check(ctx, rt_set_instances(ctx, 0, bvhCount, in.data(), b6.data()));
+	for (rt_ctx* o : alsoCtx) check(o, rt_set_instances(o, 0, bvhCount, in.data(), b6.data()));
+	static_assert(sizeof(TLASNode) == sizeof(rt_tlas_node), "TLASNode must match rt_tlas_node");
+	uint32_t used = 0;
+	check(ctx, rt_download_tlas(ctx, (rt_tlas_node*)tl->tlasNode, &used)); // tl has 2 n + 1 nodes of room (tlas::tlas)
+	tl->nodesUsed = used;
+}
+
 void Scene::FindNearestBatch(int n, const float* O, const float* D, const float* tmax, float t_min, rt_hit* out) const
 {
 	if (!ctx) throw std::runtime_error("Scene: Commit() has not been called");

@@ -36,7 +36,8 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_select_active_rows", "rt_select_budget_rows", "rt_gather_stats_rows", "rt_gather_active",
               "rt_select_active_dilated", "rt_select_budget_dilated",
               "rt_set_pixel_filter", "rt_get_pixel_filter", "rt_sample_rays",
-              "rt_layout_build", "rt_layout_array", "rt_layout_free"]
+              "rt_layout_build", "rt_layout_array", "rt_layout_free",
+              "rt_set_instances", "rt_download_tlas", "rt_scene_array"]
 
 RT_E_ARG, RT_E_STATE = -2, -5
 # include/rt_amd.h rt_set_pixel_filter
@@ -143,6 +144,8 @@ RT_TRIANGLE_DTYPE = np.dtype([("v0", np.float32, 3), ("v1", np.float32, 3), ("v2
 RT_SPHERE_DTYPE = np.dtype([("pos", np.float32, 3), ("r2", np.float32), ("invr", np.float32), ("r", np.float32), ("obj_idx", np.int32), ("material", np.int32)])
 RT_PLANE_DTYPE = np.dtype([("N", np.float32, 3), ("d", np.float32), ("obj_idx", np.int32), ("material", np.int32)])
 RT_BVH_NODE_DTYPE = np.dtype([("aabb_min", np.float32, 3), ("left_first", np.uint32), ("aabb_max", np.float32, 3), ("prim_count", np.uint32)])
+RT_INSTANCE_DTYPE = np.dtype([("blas", np.int32), ("transform", np.float32, 16), ("inv_transform", np.float32, 16)])
+RT_TLAS_NODE_DTYPE = np.dtype([("aabb_min", np.float32, 3), ("left_right", np.uint32), ("aabb_max", np.float32, 3), ("blas", np.uint32)])
 RT_HIT_DTYPE = np.dtype([("t", np.float32), ("obj_idx", np.int32), ("material", np.int32), ("normal", np.float32, 3)])
 
 
@@ -243,6 +246,9 @@ def rt_lib():
         L.rt_layout_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.rt_layout_array.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.rt_layout_free.argtypes = [C.c_void_p]
+        L.rt_set_instances.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.rt_download_tlas.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_scene_array.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         _rt = L
     return _rt
 
@@ -254,7 +260,7 @@ def host_lib():
         if not os.path.exists(HOST_SO):
             raise RuntimeError("librapt_host.so is not built (run __graft_entry__.build())")
         L = C.CDLL(HOST_SO)
-        for name in ["rth_scene_new", "rth_renderer_new", "rth_renderer_new_multi", "rth_renderer_scene", "rth_renderer_ctx", "rth_describe",
+        for name in ["rth_scene_new", "rth_renderer_new", "rth_renderer_new_multi", "rth_renderer_scene", "rth_renderer_ctx", "rth_renderer_ctx_at", "rth_describe",
                      "rth_renderer_accumulator", "rth_renderer_pixels", "rth_get_sky"]:
             getattr(L, name).restype = C.c_void_p
         L.rth_last_error.restype = C.c_char_p
@@ -367,6 +373,20 @@ class HostScene:
     def set_time(self, t):
         """Scene::SetTime (animation + refit on the device); needs a committed scene."""
         self._chk(self.L.rth_scene_set_time(self.h, C.c_float(t)))
+
+    def set_transforms(self, first, transforms):
+        """bvhInstance::SetTransform for instances first, first + 1, ... (row-major mat4 each); commit_instances() sends them to the device"""
+        T = np.ascontiguousarray(np.stack([np.asarray(t, dtype=np.float32).reshape(16) for t in transforms]))
+        self._chk(self.L.rth_scene_set_transforms(self.h, int(first), len(T), _p(T)))
+
+    def commit_instances(self):
+        """Scene::CommitInstances: every instance's matrices and (accumulating) bounds through rt_set_instances, to every committed context;
+        the scene's tlas is then the tree the device walks.  Needs a committed scene."""
+        self._chk(self.L.rth_scene_commit_instances(self.h))
+
+    def rebuild_tlas(self):
+        """tlas::build on the host over the instances' current bounds"""
+        self._chk(self.L.rth_scene_rebuild_tlas(self.h))
 
     # ---- dumps ----
     def n_meshes(self):
@@ -657,6 +677,43 @@ class HostRenderer:
         self._rt(self.rt.rt_build_bvh_split(self.ctx, int(split), _p(T) if len(T) else None, len(T), _p(S) if len(S) else None, len(S),
                                       _p(P) if len(P) else None, len(P), _p(nodes), _p(prim), C.byref(used)))
         return nodes[:used.value].view(np.uint32).reshape(-1, 8).copy(), prim[:n].copy()
+
+    # ---- moving instances (include/rt_amd.h rt_set_instances, rt_download_tlas, rt_scene_array) ----
+    def set_instances(self, first, instances, bounds6=None):
+        """rt_set_instances: instances is an RT_INSTANCE_DTYPE array (blas, transform, inv_transform) for instances first, first + 1, ...;
+        bounds6 (count, 6) their world boxes, or None: the device computes the box of a fresh instance.  Returns the rt_status (0: done)."""
+        ins = np.ascontiguousarray(instances, dtype=RT_INSTANCE_DTYPE).reshape(-1)
+        b = None if bounds6 is None else np.ascontiguousarray(bounds6, dtype=np.float32).reshape(-1, 6)
+        assert b is None or len(b) == len(ins)
+        return int(self.rt.rt_set_instances(self.ctx, int(first), len(ins), _p(ins) if len(ins) else None, None if b is None else _p(b)))
+
+    def download_tlas(self):
+        """rt_download_tlas: the TLAS the context walks, as (nodes_used, 8) uint32 like build_tlas"""
+        n = self.scene_array("scalars")[3]
+        nodes = np.zeros((2 * int(n) + 1, 8), dtype=np.uint32)
+        used = C.c_uint32(0)
+        self._rt(self.rt.rt_download_tlas(self.ctx, _p(nodes), C.byref(used)))
+        return nodes[:used.value].copy()
+
+    def ctx_at(self, k):
+        """context k of a renderer made with devices=[...] (context 0 is .ctx)"""
+        return C.c_void_p(self.L.rth_renderer_ctx_at(self.h, int(k)))
+
+    def scene_array(self, name, ctx=None):
+        """rt_scene_array: 'pairs', 'reach', 'inst' or 'scalars' as the context (ctx None: context 0) holds them, in layout()'s formats"""
+        ctx = self.ctx if ctx is None else ctx
+        which = [k for k, _ in LAYOUT_ARRAYS].index(name)
+        nbytes = C.c_size_t(0)
+        if self.rt.rt_scene_array(ctx, which, None, 0, C.byref(nbytes)) != 0:
+            raise RuntimeError("rt_scene_array: %s" % self.rt.rt_last_error(ctx).decode())
+        out = np.zeros(nbytes.value // 4, dtype=dict(LAYOUT_ARRAYS)[name])
+        if nbytes.value and self.rt.rt_scene_array(ctx, which, _p(out), nbytes.value, C.byref(nbytes)) != 0:
+            raise RuntimeError("rt_scene_array: %s" % self.rt.rt_last_error(ctx).decode())
+        return out
+
+    def upload_desc(self, desc):
+        """rt_upload_scene of a caller's rt_scene_desc (a ctypes pointer, e.g. another scene's describe()) into context 0"""
+        self._rt(self.rt.rt_upload_scene(self.ctx, desc))
 
     def primary_hits(self, t_min=1e-6):
         obj = np.zeros((self.hgt, self.w), dtype=np.int32)
