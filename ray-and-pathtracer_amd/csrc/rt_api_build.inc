@@ -114,6 +114,35 @@ int rt_build_bvh_split(rt_ctx* c, int split_method, const rt_triangle* tris, uin
 		stack.push_back({ tn.right, pair + 1 }); // popped after the whole left subtree
 		stack.push_back({ tn.left, pair });
 	}
+	// The device's boxes are hardware min / max in reduction order; the reference's are what its closing Refit (bvh.cpp:556-594) leaves:
+	// a leaf folds its primitives in primitiveIdx order, an inner node takes its children, both with the ternaries a < b ? a : b and
+	// a > b ? a : b.  The two agree in value; where the value is zero and both zeros occur among the candidates, the ternaries keep the
+	// sign of the last one and the hardware prefers -0 / +0.  Restore the reference's sign (children have larger numbers than their parent).
+	for (uint i = nodesUsed; i-- > rootAt;) {
+		if (i == 1 || (n_pla > 0 && i == 3)) continue;
+		rt_bvh_node& nd = nodes_out[i];
+		for (int k = 0; k < 3; k++) {
+			if (nd.aabb_min[k] != 0.0f && nd.aabb_max[k] != 0.0f) continue;
+			float lo = 1e30f, hi = -1e30f;
+			if (nd.prim_count > 0) {
+				for (uint j = 0; j < nd.prim_count; j++) {
+					const uint p = prim_idx_out[nd.left_first + j];
+					if (p < n_tri) {
+						const float v[3] = { tris[p].v0[k], tris[p].v1[k], tris[p].v2[k] };
+						for (int q = 0; q < 3; q++) lo = lo < v[q] ? lo : v[q], hi = hi > v[q] ? hi : v[q];
+					} else {
+						const rt_sphere& s = spheres[p - n_tri];
+						const float a = s.pos[k] - s.r, b = s.pos[k] + s.r;
+						lo = lo < a ? lo : a, hi = hi > b ? hi : b;
+					}
+				}
+			} else {
+				const rt_bvh_node &l = nodes_out[nd.left_first], &r = nodes_out[nd.left_first + 1];
+				lo = l.aabb_min[k] < r.aabb_min[k] ? l.aabb_min[k] : r.aabb_min[k], hi = l.aabb_max[k] > r.aabb_max[k] ? l.aabb_max[k] : r.aabb_max[k];
+			}
+			nd.aabb_min[k] = lo, nd.aabb_max[k] = hi;
+		}
+	}
 	if (n_pla > 0) { // Refit of the root (bvh.cpp:556-594): union of its two children
 		rt_bvh_node& r = nodes_out[0];
 		const rt_bvh_node &a = nodes_out[2], &b = nodes_out[3];

@@ -8,8 +8,9 @@
 //   * level by level instead of depth first: every open node of a level is subdivided by one block; the
 //     depth-first numbering (children pairs are allocated in the order Subdivide reaches their parents) is
 //     restored at the end from the tree's shape;
-//   * centroid bounds, bin counts and bin boxes are min / max / integer sums: any order gives the same bits
-//     (inputs are checked to be finite: NaN would make the reference's ternary min / max order dependent);
+//   * centroid bounds, bin counts and bin boxes are min / max / integer sums: any order gives the same value
+//     (inputs are checked to be finite: NaN would make the reference's ternary min / max order dependent; the
+//     sign of a zero bound is order dependent too, and rt_build_bvh_split restores the reference's on the host);
 //   * the 7-plane sweep and the '<' comparisons run on one lane in the reference's order;
 //   * the in-place partition loop (bvh.cpp:296-313) moves elements in a fixed pattern that has a closed
 //     form: with L = "centroid < splitPos", nL = #L, holes h_1 < h_2 < ... = positions below nL holding an R,

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from build_cases import same_tree as _same_tree, tlas_reference
 from conftest import random_rays, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -1778,15 +1779,6 @@ class _Recorder:
         return m
 
 
-def _same_tree(got, ref):
-    nodes, prim = got
-    assert len(nodes) == ref["nodes_used"]
-    assert np.array_equal(prim, ref["prim_idx"])
-    keep = np.ones(len(nodes), dtype=bool)
-    keep[1] = False  # node 1 is never allocated (Q4)
-    assert np.array_equal(nodes[keep], ref["nodes"][:ref["nodes_used"]][keep])
-
-
 @pytest.mark.parametrize("name,kw", [("mixed_small", {}), ("scene3", {"force_diffuse": False, "split": 0}), ("background", {}), ("tower", {}),
                                      ("mixed_small", {"split": 1}), ("mixed_small", {"split": 2}), ("mixed_small", {"split": 3}),
                                      ("scene3", {"force_diffuse": True, "split": 3}),  # BASELINE config 2's tree: full-sweep SAH
@@ -1840,48 +1832,14 @@ def test_device_tlas_build_equals_reference(name, kw, scenes, oracle_api, host_a
 
 
 def test_device_tlas_build_sizes(host_api):
-    """1, 2, 3, 100 and 256 instances with random boxes against a plain restatement of the clustering loop; > 256 is refused."""
+    """1, 2, 3, 100 and 256 instances with random boxes against a plain restatement of the clustering loop (tests/build_cases.py
+    tlas_reference, shared with tests/test_gpu_build.py); > 256 is refused."""
     r = host_api.HostRenderer(8, 8)
     rng = np.random.default_rng(12)
-    def reference(b6):
-        n = len(b6)
-        node = np.zeros((2 * n + 1, 8), np.uint32)
-        nf = node.view(np.float32)
-        idx = list(range(1, n + 1))
-        for i in range(n):
-            nf[1 + i, 0:3], nf[1 + i, 4:7] = b6[i, :3], b6[i, 3:]
-            node[1 + i, 7] = i
-        used = n + 1
-        live = n
-        def best(A):
-            ids = np.array(idx[:live])
-            e = np.maximum(nf[idx[A], 4:7][None], nf[ids, 4:7]) - np.minimum(nf[idx[A], 0:3][None], nf[ids, 0:3])  # float32 throughout
-            area = (e[:, 0] * e[:, 1] + e[:, 1] * e[:, 2]) + e[:, 2] * e[:, 0]
-            if A < live:
-                area[A] = np.inf
-            B = int(np.argmin(area))  # the first minimum, like the strict '<' of FindBestMatch
-            return B if area[B] < np.float32(1e30) else -1
-        A, B = 0, best(0) if n > 1 else 0
-        while live > 1:
-            Cc = best(B)
-            if A != Cc:
-                A, B = B, Cc
-                continue
-            ia, ib = idx[A], idx[B]
-            node[used, 3] = ia + (ib << 16)
-            nf[used, 0:3] = np.minimum(nf[ia, 0:3], nf[ib, 0:3])
-            nf[used, 4:7] = np.maximum(nf[ia, 4:7], nf[ib, 4:7])
-            idx[A] = used
-            used += 1
-            idx[B] = idx[live - 1]  # the list only shrinks logically: A may now sit past its end, as in the reference
-            live -= 1
-            B = best(A)
-        node[0] = node[idx[A]]
-        return node[:used]
     for n in (1, 2, 3, 100, 256):
         lo = rng.uniform(-20, 20, (n, 3)).astype(np.float32)
         b6 = np.concatenate([lo, lo + rng.uniform(0.1, 5, (n, 3)).astype(np.float32)], 1)
-        assert np.array_equal(r.build_tlas(b6), reference(b6)), n
+        assert np.array_equal(r.build_tlas(b6), tlas_reference(b6)), n
     with pytest.raises(RuntimeError):
         r.build_tlas(np.zeros((257, 6), np.float32))
     r.close()
