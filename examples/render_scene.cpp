@@ -6,12 +6,14 @@
 //   g++ -std=c++17 -O2 examples/render_scene.cpp -Iray-and-pathtracer_amd/host \
 //       -Lray-and-pathtracer_amd/host -lrapt_host -Lray-and-pathtracer_amd/csrc -lrt_amd \
 //       -Wl,-rpath,$PWD/ray-and-pathtracer_amd/host -Wl,-rpath,$PWD/ray-and-pathtracer_amd/csrc -o render_scene
-//   ./render_scene scene.rapt out.ppm 640 360 path 16 [all | d0,d1,...] [--filter reference|point|box|tent] [--spin DEG]
+//   ./render_scene scene.rapt out.ppm 640 360 path 16 [all | d0,d1,...] [--filter reference|point|box|tent] [--spin DEG [--carry]]
 // The optional last argument spreads every Tick over several GPUs (one rt_ctx and one host thread per device,
 // rows interleaved, rt_gather_rows into device d0): "all" = every visible device.  --filter (anywhere after the frame count) sets
 // Renderer::pixelFilter: the sub-pixel camera samples of path mode (rt_set_pixel_filter; default: the reference's truncated jitter).
 // --spin DEG (a TLAS scene): before the last frame instance 0 is turned by DEG degrees about y (bvhInstance::SetTransform) and sent on with
 // Scene::CommitInstances (rt_set_instances: no re-upload); that Tick clears, so the image is the moved scene's.
+// --carry (path mode with --spin only; refused otherwise): the Ticks are adaptive with Renderer::reproject set and the move goes through Renderer::CommitInstances,
+// so the last Tick keeps the samples of the frames before it where their surface points are still in view (rt_reproject_motion).
 #include "rapt.h"
 #include <cstdio>
 #include <cstdlib>
@@ -24,9 +26,16 @@ using namespace rapt;
 
 int main(int argc, char** argv)
 {
-	if (argc < 7) { fprintf(stderr, "usage: %s scene.rapt out.ppm width height whitted|path frames [all | d0,d1,...] [--filter reference|point|box|tent] [--spin DEG]\n", argv[0]); return 2; }
+	if (argc < 7) { fprintf(stderr, "usage: %s scene.rapt out.ppm width height whitted|path frames [all | d0,d1,...] [--filter reference|point|box|tent] [--spin DEG [--carry]]\n", argv[0]); return 2; }
 	int filter = RT_FILTER_REFERENCE;
 	float spin = 0;
+	bool carry = false;
+	for (int a = 7; a < argc; a++) {
+		if (strcmp(argv[a], "--carry") != 0) continue;
+		carry = true;
+		for (int b = a; b + 1 < argc; b++) argv[b] = argv[b + 1];
+		argc -= 1, a--;
+	}
 	for (int a = 7; a + 1 < argc; a++) {
 		if (strcmp(argv[a], "--spin") != 0) continue;
 		spin = (float)atof(argv[a + 1]);
@@ -45,6 +54,7 @@ int main(int argc, char** argv)
 	}
 	const int w = atoi(argv[3]), h = atoi(argv[4]), frames = atoi(argv[6]);
 	const bool path = strcmp(argv[5], "path") == 0;
+	if (carry && (spin == 0 || !path)) { fprintf(stderr, "--carry needs --spin DEG and path mode (it keeps the path samples across the spin)\n"); return 2; }
 	try {
 		Renderer app(w, h, 0);
 		if (argc > 7) {
@@ -56,6 +66,7 @@ int main(int argc, char** argv)
 			}
 		}
 		app.pixelFilter = filter;
+		if (carry) app.adaptive = app.reproject = true;
 		app.Init();                          // allocates the accumulator on the GPU(s)
 		app.scene.LoadFile(argv[1]);         // meshes, materials, lights, BVH / TLAS (host builders)
 		if (path) app.scene.toogleRaytracer(); // key 'P' in the reference: path tracing, lights sampled
@@ -66,8 +77,11 @@ int main(int argc, char** argv)
 				if (!app.scene.useTLAS) throw std::runtime_error("--spin needs a scene with a TLAS");
 				mat4 M = app.scene.bvhList[0].matTransform * mat4::RotateY(spin * 3.14159265358979f / 180.0f);
 				app.scene.bvhList[0].SetTransform(M);
-				app.scene.CommitInstances();
-				app.camera.SetChange(true); // the accumulator holds the scene before the move: this Tick clears
+				if (carry) app.CommitInstances(); // adaptive path Ticks: this Tick carries the samples across the move; otherwise it clears
+				else {
+					app.scene.CommitInstances();
+					app.camera.SetChange(true); // the accumulator holds the scene before the move: this Tick clears
+				}
 			}
 			app.Tick(0.0f);
 		}

@@ -507,18 +507,23 @@ typedef struct { int32_t iterations; float sigma_luminance, sigma_normal, sigma_
 #define RT_DENOISE_VAR_DEFAULTS { 5, 4.0f, 0.25f, 0.1f, 0.1f, 1e-4f }
 int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_var_params* params);
 
-/* ---- reprojection: carrying samples and statistics across a camera move ----------------------------------------
+/* ---- reprojection: carrying samples and statistics across a camera move and across instance motion ---------------
  * A camera move need not throw every sample away: the radiance a diffuse surface point sends does not depend on the view, so the pixel
  * that sees the point after the move may keep the samples of the pixel that saw it before.  Pinhole cameras only; nearest history pixel,
  * no interpolation; statistics (rt_stats_enable) required.  (This library's own addition.)  The caller's sequence:
  *   rt_render_aovs (old camera) - rt_history_capture - rt_set_camera - rt_render_aovs - rt_reproject - rt_select_active / rt_render_active
  * rt_download_aov_positions: rows [y0, y1) of the G-buffer's world positions, 3 floats per pixel: O + D * t as k_primary_aovs stored it
  *   (a restatement of rt_reproject must start from these bits, not from a product recomputed on the host).  Errors as rt_download_aovs.
- * rt_history_capture: copies the bound accumulator, the three statistics arrays, the three G-buffer arrays and the current camera record
- *   into history buffers of the context (allocated on first use, freed by rt_destroy): device to device on the context's stream, without
+ * rt_download_aov_instances: rows [y0, y1) of the G-buffer's instance indices, one int32 per pixel: the TLAS instance whose BLAS holds the
+ *   primitive the pixel's ray hit; -1 for a miss, a light, a brute-force sphere or plane, and every hit of a scene without a TLAS.  The
+ *   array is made by rt_render_aovs with the other three and goes stale with them.  Errors as rt_download_aov_positions.
+ * rt_history_capture: copies the bound accumulator, the three statistics arrays, the G-buffer arrays (the instance indices included), the
+ *   current camera record and, of a scene with a TLAS, every instance's transform and inv_transform (rows 0..2: 12 + 12 floats, as they
+ *   are at this moment) into history buffers of the context (allocated on first use, freed by rt_destroy): device to device on the context's stream, without
  *   synchronising.  RT_E_STATE: statistics off; the G-buffer missing or stale (rt_render_aovs first).  RT_E_UNSUPPORTED: the current
  *   camera is a fisheye.  A history stays valid until rt_upload_scene, rt_set_time, rt_set_instances or rt_stats_enable(ctx, 0); rt_clear and rt_set_camera
- *   do not touch it.
+ *   do not touch it.  Validity has two levels: rt_set_instances ends it for rt_reproject only -- for rt_reproject_motion the history stays
+ *   valid across any number of rt_set_instances calls (a failed one changes nothing for either).
  * rt_reproject: rewrites the accumulator and the statistics of EVERY pixel: carried from the history, or zeroed (a zero float4, count 0,
  *   sums 0).  On the context's stream; *n_carried_out (may be NULL) receives the number of carried pixels, and reading those 4 bytes back
  *   is the only synchronisation of the call.  The history is not modified (a second call gives the same result), the active-pixel list
@@ -550,13 +555,47 @@ int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_var_params* params);
  *   params NULL: RT_REPROJECT_DEFAULTS.  RT_E_ARG (checked before the context): a tolerance that is negative or NaN, max_history < 0.
  *   RT_E_STATE: statistics off; no valid history; the current G-buffer missing or stale.  RT_E_UNSUPPORTED: the current camera is a
  *   fisheye.  With rt_set_profiling on, rt_history_capture's copies and k_reproject are each one launch of rt_profile.query.
- *   Object motion is not reprojected: rt_set_instances (like rt_set_time and rt_upload_scene) invalidates the history, and a carry is across a
- *   camera move only. */
+ *   Object motion is not reprojected by this call: rt_set_instances (like rt_set_time and rt_upload_scene) invalidates the history for it,
+ *   and its carry is across a camera move only.  rt_reproject_motion is the call that follows instances.
+ * rt_reproject_motion: rt_reproject with the other half of a motion vector: a surface point of an instance that has moved since the capture
+ *   (rt_set_instances, any number of times) is taken back through the instance's own motion before it is projected into the history camera.
+ *   The caller's sequence:
+ *     rt_render_aovs - rt_history_capture - rt_set_instances [- rt_set_camera] - rt_render_aovs - rt_reproject_motion - rt_select_active / ...
+ *   Same parameters, defaults, outputs, stream ordering, single read-back, profiling entry (k_reproject_motion: one launch of
+ *   rt_profile.query), dropped budget plan and errors as rt_reproject, except that an instance move since the capture is no error:
+ *   RT_E_STATE only after rt_upload_scene, rt_set_time or rt_stats_enable(ctx, 0).  The definition is rt_reproject's with these changes (all
+ *   f32, no contraction; tests/reproject_motion_ref.py restates it).  For the current pixel p let k = inst_p, the G-buffer's instance index:
+ *     moved_k = k >= 0 && any of instance k's 24 words (transform rows 0..2, inv_transform rows 0..2) differs BITWISE from the capture's
+ *     !moved_k:  x_h = x_p;  n_h = n_p                     (no arithmetic: an unmoved point keeps its bits)
+ *      moved_k:  x_h = xform_pos(T'_k, xform_pos(invT_k, x_p))         invT_k: the CURRENT inv_transform, T'_k: the capture's transform
+ *                n_h = normalize(xform_vec(T'_k, xform_vec(invT_k, n_p)))
+ *     xform_pos(c, a) = (((c[0] * a.x + c[1] * a.y) + c[2] * a.z) + c[3] * 1.0f,
+ *                        ((c[4] * a.x + c[5] * a.y) + c[6] * a.z) + c[7] * 1.0f,
+ *                        ((c[8] * a.x + c[9] * a.y) + c[10] * a.z) + c[11] * 1.0f)          c: rows 0..2 of a row-major 4 x 4 matrix
+ *     xform_vec(c, a) = the same with c[3] * 0.0f, c[7] * 0.0f, c[11] * 0.0f as the last terms (a non-finite c[3] makes a NaN)
+ *     normalize(v)    = v * (1.0f / sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z))              (per component; IEEE sqrt and division)
+ *   Normals go through transform, not its inverse transpose: that is how a world normal is made from an instance's local one, so n_h is
+ *   the normal the capture would have stored.  Then, in rt_reproject's definition:
+ *     d = x_h - cam'                                      the projection starts from the point taken back
+ *     carried = eligible && the projection's conditions
+ *            && count'_q > 0 && obj'_q == obj_p && mat'_q == mat_p && inst'_q == inst_p
+ *            && dist2(n_h, n'_q) <= normal_tolerance * normal_tolerance
+ *            && fabsf(dot(n'_q, x_h - x'_q)) <= plane_tolerance * t_p         (t_p stays the scale: the unmoved case is rt_reproject's)
+ *   A NaN anywhere (a singular inverse) fails a comparison and the pixel starts empty.  Eligibility, the max_history rescale and the
+ *   zeroing of pixels that are not carried are unchanged.  Two consequences: with no instance moved since the capture (or every moved one
+ *   moved back to the same bits), and on any scene without a TLAS, the call leaves accumulator, statistics and *n_carried_out bit-equal
+ *   to rt_reproject's; and a second call gives the same result (the history is not modified).
+ *   What it does not do: it moves SAMPLES, not light.  Radiance on and around a moved object changes -- its shadow, what it reflects onto
+ *   its neighbours, its own lighting as it turns towards or away from the lights -- and the carried samples there are biased until new
+ *   ones outweigh them: max_history is the remedy (a small value lets new samples take over quickly).  Deforming meshes (rt_set_time) still
+ *   invalidate the history, and so does rt_upload_scene. */
 typedef struct { float normal_tolerance, plane_tolerance; int32_t max_history; int32_t carry_view_dependent; } rt_reproject_params;
 #define RT_REPROJECT_DEFAULTS { 0.25f, 0.01f, 0, 0 }   /* a starting point, NOT tuned */
 int rt_history_capture(rt_ctx* ctx);
 int rt_reproject(rt_ctx* ctx, const rt_reproject_params* params, int* n_carried_out);
+int rt_reproject_motion(rt_ctx* ctx, const rt_reproject_params* params, int* n_carried_out);
 int rt_download_aov_positions(rt_ctx* ctx, int y0, int y1, float* xyz_out);
+int rt_download_aov_instances(rt_ctx* ctx, int y0, int y1, int32_t* inst_out);
 
 /* ---- Q-learning guided sampling ("next" row N4) ------------------------------------------------------
  * The reference snapshot has no code for it: README.md:36-42 names Dahm & Keller 2017, "Learning Light Transport
@@ -633,9 +672,9 @@ int rt_build_tlas(rt_ctx* ctx, const float* bounds6, uint32_t n, rt_tlas_node* n
  *     union areas all reach 1e30), the call returns RT_E_UNSUPPORTED and the scene is exactly as before; only after that check do the
  *     copies and the kernel that rewrite the scene run.
  *   Invalidation: everything rt_set_time invalidates -- the G-buffer is stale (rt_render_aovs), the primary-hit table is rebuilt by the
- *     next dense batch, a captured history is invalid (rt_reproject: RT_E_STATE until a new rt_history_capture).  The accumulator, the
- *     statistics and the active-pixel list are not touched: the caller clears, or reprojects across a CAMERA move only -- rt_reproject
- *     does not follow object motion.  A call that fails invalidates nothing.
+ *     next dense batch, a captured history is invalid for rt_reproject (RT_E_STATE until a new rt_history_capture).  The accumulator, the
+ *     statistics and the active-pixel list are not touched: the caller clears, or carries the samples with rt_reproject_motion, which
+ *     follows the instances (rt_reproject itself does not follow object motion).  A call that fails invalidates nothing.
  *   Errors.  RT_E_STATE: no scene loaded.  RT_E_UNSUPPORTED: the scene has no TLAS (rt_set_time stays RT_E_UNSUPPORTED under one).
  *     RT_E_ARG, checked on the host before anything is queued, the scene unchanged: a null ctx or instances; count == 0; a range outside
  *     the instances; a blas mismatch; a non-finite matrix entry; a bound that is non-finite or beyond 1e30 in magnitude (with bounds6 ==

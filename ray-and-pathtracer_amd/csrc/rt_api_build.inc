@@ -188,7 +188,7 @@ int rt_set_time(rt_ctx* c, float t)
 {
 	if (!c) return RT_E_ARG;
 	c->sceneGen++; // the G-buffer (rt_render_aovs) is stale from here on
-	c->geomGen++;  // ... and so is a captured history (rt_history_capture)
+	c->geomGen++, c->shapeGen++;  // ... and so is a captured history (rt_history_capture)
 	if (!c->sceneLoaded) return fail(c, RT_E_STATE, "rt_set_time: no scene uploaded");
 	if (c->S.useTLAS) return fail(c, RT_E_UNSUPPORTED, "rt_set_time: the reference animates only without the TLAS (animOn, template/scene.h:1389)");
 	if (!c->primsOrig) return RT_OK; // nothing to animate

@@ -87,7 +87,7 @@ int rt_set_instances(rt_ctx* c, uint32_t first, uint32_t count, const rt_instanc
 	int32_t* s = c->layoutScalars; // rootLink, tlasBase, tlasPairs, nInst, reachOriginMax, tlasLds, stackRows: the first seven words
 	s[0] = (int32_t)L.root, s[1] = (int32_t)L.tlasBase, s[2] = L.tlasPairs, memcpy(&s[4], &L.reachOriginMax, 4), s[5] = L.tlasLds, s[6] = L.stackRows;
 	c->sceneGen++; // everything rt_set_time invalidates: the G-buffer and the primary-hit table ...
-	c->geomGen++;  // ... and a captured history
+	c->geomGen++;  // ... and a captured history, for rt_reproject; rt_reproject_motion follows the move (shapeGen stays)
 	return RT_OK;
 }
 

@@ -13,7 +13,7 @@
 //   rt_api_output.inc   the output stage's shared helpers: row ranges, row downloads, the resolve, the a-trous drivers' common part
 //   rt_api_denoise.inc  rt_render_aovs, rt_denoise, rt_denoise_variance and their downloads
 //   rt_api_adaptive.inc rt_stats_*, rt_select_active, the active-pixel list, rt_render_active, rt_resolve_adaptive
-//   rt_api_reproject.inc rt_history_capture, rt_reproject, rt_download_aov_positions
+//   rt_api_reproject.inc rt_history_capture, rt_reproject, rt_reproject_motion, rt_download_aov_positions, rt_download_aov_instances
 #pragma once
 #include "../../include/rt_amd.h" // first: the kernels read its enums (RT_FILTER_*)
 #include "rt_kernels.h"
@@ -260,6 +260,7 @@ struct rt_ctx {
 	int gridAovs = 0;
 	std::vector<void*> denoiseAllocs;
 	float4* aovNrm = nullptr; float4* aovPos = nullptr; float4* aovAlb = nullptr; // width * height each, allocated on first use
+	int* aovInst = nullptr; // the hit's TLAS instance per pixel (-1: none), allocated and current with the three above
 	float4* denoiseBuf[2] = { nullptr, nullptr }; // ping-pong of the filter's iterations
 	float4* denoised = nullptr; // the buffer holding the last rt_denoise result (null: none yet)
 	float4* samples = nullptr; // finished samples of the current batch, [frame][tile pixel]
@@ -285,16 +286,23 @@ struct rt_ctx {
 	// reprojection (rt_api_reproject.inc): copies of the accumulator, the statistics, the G-buffer and the camera record taken by
 	// rt_history_capture, which rt_reproject gathers from.  geomGen counts what changes the surfaces (rt_upload_scene, rt_set_time) and,
 	// unlike sceneGen, not the camera: the history is valid while hist.gen == geomGen (0: none; rt_stats_enable(ctx, 0) drops it).
+	// rt_reproject_motion follows instance moves, so it has a level of its own: shapeGen counts what geomGen counts EXCEPT rt_set_instances,
+	// and the history is valid for it while hist.gen != 0 && hist.shapeGen == shapeGen.  For that call the capture also keeps the G-buffer's
+	// instance indices and the instance records of its moment: xf on the device (a copy of inst[], what the kernel reads T' from), xfHost
+	// beside the host mirror InstanceState::inst (what decides, bitwise, which instances have moved).
 	struct History {
 		float4* acc; float4* nrm; float4* pos; float4* alb;
 		PixelStats stats;
 		int* nCarried; // rt_reproject's count of carried pixels
 		rt_camera cam;
 		unsigned long long gen;
+		int* inst; DInstance* xf; // width * height indices; RT_TLAS_MAX records
+		unsigned long long shapeGen;
 	};
 	History hist{};
+	std::vector<DInstance> histXfHost; // empty: the captured scene had no TLAS
 	std::vector<void*> historyAllocs;
-	unsigned long long geomGen = 1;
+	unsigned long long geomGen = 1, shapeGen = 1;
 };
 
 // whatever changes a pixel's count or the installed list takes the budget plan made from them along (rt_api_budget.inc)

@@ -1,16 +1,27 @@
-// Reprojection of the accumulator and the per-pixel statistics across a camera move (rt_reproject): every pixel of the new frame either
-// takes the samples of the history pixel that saw the same surface point, or starts empty.  Defined in include/rt_amd.h (rt_reproject)
-// and restated in numpy in tests/reproject_ref.py; the two follow each other operation by operation (f32, IEEE division, no contraction:
-// the library is built with -ffp-contract=off).
+// Reprojection of the accumulator and the per-pixel statistics across a camera move (rt_reproject) and across instance motion as well
+// (rt_reproject_motion): every pixel of the new frame either takes the samples of the history pixel that saw the same surface point, or
+// starts empty.  Defined in include/rt_amd.h (rt_reproject, rt_reproject_motion) and restated in numpy in tests/reproject_ref.py and
+// tests/reproject_motion_ref.py; they follow each other operation by operation (f32, IEEE division, no contraction: the library is built
+// with -ffp-contract=off).
 //   k_reproject  a backward gather, one lane per pixel of the NEW frame, 32 x 8 tiles like the a-trous filters: the new G-buffer's point is
 //                projected through the HISTORY camera's pinhole onto its nearest pixel q, and q is accepted when it saw the same object and
 //                material under the same normal and the point lies on q's tangent plane.  Neighbouring pixels land on neighbouring history
 //                pixels, so a tile's gathers share lines.  The history's count, position, normal and material (40 B) are read first, its
 //                accumulator and sums (24 B) only by a lane that passed; 28 B are written per pixel, carried or zero.  The carried pixels are
 //                counted by a ballot per wave and one atomic add per wave that carried any (no LDS).
+//   k_reproject_motion  the same gather with the other half of a motion vector in front: a pixel whose hit belongs to an instance that has
+//                moved since the capture takes its point and normal back to where the capture saw them -- through the instance's CURRENT
+//                inverse, then the CAPTURE's transform -- before the projection, and q must have seen the same instance.  Which instances
+//                moved is decided on the host (a bitwise compare of two mirrors) and travels as 256 bits of kernel arguments, so an unmoved
+//                pixel costs two more 4-byte loads (its index, the history's at q) and no arithmetic.  A moved one reads 24 floats: rows
+//                0..2 of two 128-byte instance records, as six 16-byte global loads.  A 32 x 8 tile nearly always sees one or two
+//                instances, so a wave's lanes ask for the same one or two records and the loads are served as broadcasts from one or two
+//                cache lines each; staging the table in LDS (24 KB for 256 records, a barrier, and occupancy) would cost every block more
+//                than those lines cost the few waves that need them.
 #pragma once
 #include "rt_denoise.h" // the tile, dist2
-#include "rt_kernels.h" // PixelStats, DMaterial
+#include "rt_kernels.h" // PixelStats, DMaterial, DInstance
+#include "rt_build.h"   // RT_TLAS_MAX
 #include "../../include/rt_amd.h" // RT_MAT_DIFFUSE
 
 namespace rtd {
@@ -28,20 +39,59 @@ struct ReprojectArgs {
 	int* nCarried;
 };
 
+// what k_reproject_motion reads beyond that
+struct ReprojectMotionArgs : ReprojectArgs {
+	const int* inst; const int* hInst;           // the hit's instance per pixel (-1: none): the current G-buffer's, the history's
+	const DInstance* cur; const DInstance* hXf;  // the instance records: the scene's (invT_k is read from here), the capture's (T'_k)
+	uint moved[RT_TLAS_MAX / 32];                // bit k: one of instance k's 24 words (T and invT, rows 0..2) differs from the capture's
+};
+
 __device__ __forceinline__ float rp_dot(const f3& a, const f3& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ f3 rp_cross(const f3& a, const f3& b) { return f3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 
-// include/rt_amd.h rt_reproject, line by line: the history pixel that pixel p (records np, xp, material mat) takes its samples from, or -1;
-// count is that pixel's sample count (read once: the first thing the gather needs and the last thing it copies)
-__device__ __forceinline__ int reproject_source(const ReprojectArgs& R, const float4& np, const float4& xp, int mat, uint& count)
+// bit k of the 256 (k < 0: not an instance's hit).  The words are kernel arguments, i.e. scalar registers: a select chain, not an indexed
+// array (which would be copied to scratch first)
+__device__ __forceinline__ bool instance_moved(const ReprojectMotionArgs& R, int k)
+{
+	if (k < 0) return false;
+	uint w = R.moved[0];
+#pragma unroll
+	for (int j = 1; j < RT_TLAS_MAX / 32; j++) w = (k >> 5) == j ? R.moved[j] : w;
+	return ((w >> (k & 31)) & 1u) != 0;
+}
+__device__ __forceinline__ void load_rows(const float* rec, float* out12) // rows 0..2 of a matrix of a DInstance: 48 bytes, 16-byte aligned
+{
+	const float4* r = (const float4*)rec;
+	const float4 a = r[0], b = r[1], c = r[2];
+	out12[0] = a.x, out12[1] = a.y, out12[2] = a.z, out12[3] = a.w, out12[4] = b.x, out12[5] = b.y, out12[6] = b.z, out12[7] = b.w;
+	out12[8] = c.x, out12[9] = c.y, out12[10] = c.z, out12[11] = c.w;
+}
+
+// include/rt_amd.h rt_reproject (MOTION: rt_reproject_motion), line by line: the history pixel that pixel p (records np, xp, material mat)
+// takes its samples from, or -1; count is that pixel's sample count (read once: the first thing the gather needs and the last thing it copies)
+template <bool MOTION, typename Args>
+__device__ __forceinline__ int reproject_source(const Args& R, int p, const float4& np, const float4& xp, int mat, uint& count)
 {
 	if (__float_as_int(xp.w) == -1) return -1;
 	if (!R.carryViewDependent) {
 		if (mat < 0 || mat >= R.nMats) return -1;
 		if (R.mats[mat].type != RT_MAT_DIFFUSE || !(R.mats[mat].shinieness == 0.0f)) return -1;
 	}
+	float4 nm = np, xm = xp; // the point and its normal as the capture saw them (w: t_p and the object, untouched)
+	int k = -1;
+	if constexpr (MOTION) {
+		k = R.inst[p];
+		if (instance_moved(R, k)) { // (k < nInst: a G-buffer's index names an instance of the scene both tables describe)
+			float invT[12], Tc[12];
+			load_rows(R.cur[k].invT, invT), load_rows(R.hXf[k].T, Tc);
+			const f3 x = xform_pos(Tc, xform_pos(invT, xyz(xp)));
+			const f3 n = normalize(xform_vec(Tc, xform_vec(invT, xyz(np))));
+			xm = mk4(x, xp.w), nm = mk4(n, np.w);
+		}
+	}
+	const float4 &nh = MOTION ? nm : np, &xh = MOTION ? xm : xp;
 	const f3 cam(R.cam[0], R.cam[1], R.cam[2]), TL(R.TL[0], R.TL[1], R.TL[2]), TR(R.TR[0], R.TR[1], R.TR[2]), BL(R.BL[0], R.BL[1], R.BL[2]);
-	const f3 A = TR - TL, B = BL - TL, N = rp_cross(A, B), E = TL - cam, x(xp.x, xp.y, xp.z), d = x - cam;
+	const f3 A = TR - TL, B = BL - TL, N = rp_cross(A, B), E = TL - cam, x(xh.x, xh.y, xh.z), d = x - cam;
 	const float lam = rp_dot(E, N) / rp_dot(d, N);
 	if (!isfinite(lam) || !(lam > 0.0f)) return -1;
 	const f3 Q(lam * d.x - E.x, lam * d.y - E.y, lam * d.z - E.z);
@@ -55,21 +105,26 @@ __device__ __forceinline__ int reproject_source(const ReprojectArgs& R, const fl
 	const float4 xq = R.hPos[q];
 	if (__float_as_int(xq.w) != __float_as_int(xp.w)) return -1;
 	if (__float_as_int(R.hAlb[q].w) != mat) return -1;
+	if constexpr (MOTION) {
+		if (R.hInst[q] != k) return -1;
+	}
 	const float4 nq = R.hNrm[q];
-	if (!(dist2(np, nq) <= R.normalTol2)) return -1;
-	const f3 off(xp.x - xq.x, xp.y - xq.y, xp.z - xq.z);
+	if (!(dist2(nh, nq) <= R.normalTol2)) return -1;
+	const f3 off(xh.x - xq.x, xh.y - xq.y, xh.z - xq.z);
 	if (!(fabsf(rp_dot(f3(nq.x, nq.y, nq.z), off)) <= R.planeTol * np.w)) return -1;
 	return q;
 }
 
-__global__ void __launch_bounds__(RT_DENOISE_TX * RT_DENOISE_TY) k_reproject(ReprojectArgs R)
+// one lane's pixel: the gather, the max_history rescale, the 28 bytes written, the ballot count
+template <bool MOTION, typename Args>
+__device__ __forceinline__ void reproject_pixel(const Args& R)
 {
 	const int x = blockIdx.x * RT_DENOISE_TX + threadIdx.x, y = blockIdx.y * RT_DENOISE_TY + threadIdx.y;
 	const bool inside = x < R.width && y < R.height; // (no lane leaves before the ballot)
 	const int p = y * R.width + x;
 	int q = -1;
 	uint count = 0;
-	if (inside) q = reproject_source(R, R.nrm[p], R.pos[p], __float_as_int(R.alb[p].w), count);
+	if (inside) q = reproject_source<MOTION>(R, p, R.nrm[p], R.pos[p], __float_as_int(R.alb[p].w), count);
 	if (inside) {
 		float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 		if (q < 0) count = 0;
@@ -90,5 +145,8 @@ __global__ void __launch_bounds__(RT_DENOISE_TX * RT_DENOISE_TY) k_reproject(Rep
 	const uint lane = (threadIdx.y * RT_DENOISE_TX + threadIdx.x) & 63u;
 	if (lane == 0 && carried != 0) atomicAdd(R.nCarried, (int)__popcll(carried));
 }
+
+__global__ void __launch_bounds__(RT_DENOISE_TX * RT_DENOISE_TY) k_reproject(ReprojectArgs R) { reproject_pixel<false>(R); }
+__global__ void __launch_bounds__(RT_DENOISE_TX * RT_DENOISE_TY) k_reproject_motion(ReprojectMotionArgs R) { reproject_pixel<true>(R); }
 
 } // namespace rtd

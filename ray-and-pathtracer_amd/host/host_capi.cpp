@@ -297,6 +297,13 @@ int rth_renderer_set_pixel_filter(void* h, int kind)
 int rth_renderer_pixel_filter(void* h) { return ((RthRenderer*)h)->r->pixelFilter; }
 void rth_renderer_set_adaptive_dilate(void* h, int radius) { ((RthRenderer*)h)->r->adaptiveDilate = radius; }
 int rth_renderer_pass_samples(void* h) { return ((RthRenderer*)h)->r->passSamples; }
+// Renderer::CommitInstances: the scene's instance transforms (rth_scene_set_transforms) sent on; the next adaptive Tick carries or clears
+int rth_renderer_commit_instances(void* h)
+{
+	RthRenderer* r = (RthRenderer*)h;
+	GUARD(r, r->r->CommitInstances());
+	return 0;
+}
 int rth_renderer_carried_pixels(void* h) { return ((RthRenderer*)h)->r->carriedPixels; }
 int rth_renderer_active_pixels(void* h) { return ((RthRenderer*)h)->r->activePixels; }
 const float* rth_renderer_accumulator(void* h) { return &((RthRenderer*)h)->r->accumulator[0].x; }

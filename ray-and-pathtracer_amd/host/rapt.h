@@ -439,6 +439,15 @@ public:
 	bool reproject = false;
 	rt_reproject_params reprojectParams = RT_REPROJECT_DEFAULTS;
 	int carriedPixels = 0;            // the pixels the last reprojecting Tick carried
+	// Scene::CommitInstances (after bvhInstance::SetTransform on scene.bvhList[...]) for a renderer that may keep its samples.  With
+	// 'reproject' and 'adaptive' set, in path mode, straight after an adaptive Tick and with pinhole cameras, it runs rt_render_aovs (a
+	// no-op on a current G-buffer) and rt_history_capture under the camera of the last Tick, then scene.CommitInstances(), and the next
+	// adaptive Tick carries the samples with rt_reproject_motion instead of clearing -- along the path of the camera carry above (the
+	// push-back to the other contexts of UseDevices included), whether the camera moved as well or not.  Otherwise it is
+	// scene.CommitInstances() followed by camera.SetChange(true): the next Tick clears, as callers of Scene::CommitInstances do by hand.
+	// A Commit() before that Tick (a new upload ends the captured history) makes it clear as well.  If scene.CommitInstances() throws, no
+	// carry is pending; context 0 then holds the camera of the last Tick until the next Tick syncs the renderer's camera, as every Tick does.
+	void CommitInstances();
 	float4* accumulator = nullptr; // host copy, refreshed by Tick
 	uint32_t* screenPixels = nullptr; // Surface::pixels analogue (template/precomp.h:134)
 	Scene scene;
@@ -462,6 +471,8 @@ private:
 	rt_camera syncedCam{};            // the record of the last SyncCamera
 	bool lastTickAdaptive = false;    // the last Tick was TickAdaptive: the accumulator holds its samples, taken under sampledCam
 	rt_camera sampledCam{};           // ... and of the last adaptive Tick: the camera the accumulator's samples were taken with
+	bool motionPending = false;       // CommitInstances captured a history and moved instances: the next adaptive Tick carries across it
+	bool clearPending = false;        // CommitInstances moved instances without a capture, or Commit() followed one: the next Tick clears, with no carry
 };
 
 } // namespace rapt

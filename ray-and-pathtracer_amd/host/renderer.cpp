@@ -117,6 +117,24 @@ void Renderer::Commit()
 	if (!ctx) Init();
 	scene.Commit(ctx);
 	for (size_t k = 1; k < ctxs.size(); k++) scene.CommitAlso(ctxs[k]);
+	if (motionPending) motionPending = false, clearPending = true, camera.SetChange(true); // the upload ended the history CommitInstances captured: the next Tick clears
+}
+
+// Scene::CommitInstances for a renderer that may keep its samples: see rapt.h
+void Renderer::CommitInstances()
+{
+	if (!ctx) Init();
+	const bool carry = reproject && adaptive && !scene.raytracer && adaptiveOn && lastTickAdaptive && !sampledCam.fisheye && !camera.fishEye;
+	if (carry && !motionPending) { // (a second move before the Tick: the history of the first capture still holds the samples' moment)
+		check(ctx, rt_set_camera(ctx, &sampledCam)); // the camera of the samples: already the context's unless a caller synced the new one early
+		check(ctx, rt_render_aovs(ctx, 0.001f));     // a no-op when the G-buffer is current
+		check(ctx, rt_history_capture(ctx));
+	}
+	// (if this throws after the capture, context 0 keeps the camera of the samples until the next Tick syncs the renderer's, as every Tick
+	// does; nothing is pending, so that Tick treats the frame as it would have without this call)
+	scene.CommitInstances();
+	if (carry) motionPending = true;
+	else clearPending = true, camera.SetChange(true); // the accumulator holds the scene before the move: the next Tick clears (no camera carry either)
 }
 
 void Renderer::SyncCamera()
@@ -157,6 +175,8 @@ void Renderer::Tick(float /*deltaTime*/)
 		}
 	}
 	lastTickAdaptive = false;
+	if (motionPending) motionPending = false, camera.SetChange(true); // the carry was for an adaptive Tick: this one clears (path) or redraws
+	clearPending = false; // (this Tick clears on the camera change that was set with it)
 	scene.totIterationNumber++;
 	const int it = scene.GetIterationNumber();
 	SyncPixelFilter();
@@ -227,22 +247,30 @@ void Renderer::TickAdaptive()
 	const bool filterChanged = pixelFilter != sampledFilter; // like a camera change, without a carry: the carried samples would be the old kind's
 	SyncPixelFilter();
 	sampledFilter = pixelFilter;
-	bool reset = camera.GetChange() || filterChanged;
+	const bool motion = motionPending; // CommitInstances captured the history and moved the instances: carry with rt_reproject_motion
+	motionPending = false;
+	const bool mustClear = clearPending; // the instances moved without a capture (or the scene was committed again): nothing to carry from
+	clearPending = false;
+	bool reset = camera.GetChange() || filterChanged || motion || mustClear;
 	// a camera move with 'reproject' set (statistics already on, pinhole before and after): the samples follow their surface points
-	// (only straight after an adaptive Tick: a Whitted Tick in between has overwritten the accumulator under cameras of its own)
-	const bool carry = reset && !filterChanged && reproject && adaptiveOn && lastTickAdaptive && !sampledCam.fisheye && !camera.fishEye;
+	// (only straight after an adaptive Tick: a Whitted Tick in between has overwritten the accumulator under cameras of its own);
+	// an instance move through Renderer::CommitInstances takes the same path, the camera moved as well or not
+	const bool carry = reset && !filterChanged && !mustClear && reproject && adaptiveOn && lastTickAdaptive && !sampledCam.fisheye && !camera.fishEye;
 	if (!adaptiveOn) {
 		for (rt_ctx* k : ctxs) check(k, rt_stats_enable(k, 1));
 		adaptiveOn = true, reset = true; // the counts start now, so the accumulator does too
 	}
 	if (carry) {
 		scene.SetIterationNumber(1);
-		check(ctx, rt_set_camera(ctx, &sampledCam)); // the camera of the samples: already the context's unless a caller synced the new one early
-		check(ctx, rt_render_aovs(ctx, 0.001f));     // a no-op when the G-buffer is current
-		check(ctx, rt_history_capture(ctx));
+		if (!motion) {
+			check(ctx, rt_set_camera(ctx, &sampledCam)); // the camera of the samples: already the context's unless a caller synced the new one early
+			check(ctx, rt_render_aovs(ctx, 0.001f));     // a no-op when the G-buffer is current
+			check(ctx, rt_history_capture(ctx));
+		}
 		SyncCamera();
 		check(ctx, rt_render_aovs(ctx, 0.001f));
-		check(ctx, rt_reproject(ctx, &reprojectParams, &carriedPixels));
+		if (motion) check(ctx, rt_reproject_motion(ctx, &reprojectParams, &carriedPixels));
+		else check(ctx, rt_reproject(ctx, &reprojectParams, &carriedPixels));
 		// every pixel of context 0 is rewritten: each context gets its own rows back before it selects over them
 		for (int k = 1; k < n; k++) {
 			const int count = (height - k + n - 1) / n;

@@ -32,7 +32,7 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_stats_enable", "rt_download_stats", "rt_select_active", "rt_set_active_pixels", "rt_download_active",
               "rt_render_active", "rt_resolve_adaptive", "rt_denoise_variance",
               "rt_select_budget", "rt_download_budgets", "rt_render_budget",
-              "rt_history_capture", "rt_reproject", "rt_download_aov_positions",
+              "rt_history_capture", "rt_reproject", "rt_download_aov_positions", "rt_reproject_motion", "rt_download_aov_instances",
               "rt_select_active_rows", "rt_select_budget_rows", "rt_gather_stats_rows", "rt_gather_active",
               "rt_select_active_dilated", "rt_select_budget_dilated",
               "rt_set_pixel_filter", "rt_get_pixel_filter", "rt_sample_rays",
@@ -233,6 +233,8 @@ def rt_lib():
         L.rt_history_capture.argtypes = [C.c_void_p]
         L.rt_reproject.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_download_aov_positions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.rt_reproject_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_download_aov_instances.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.rt_select_active_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.rt_select_budget_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_gather_stats_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
@@ -582,6 +584,11 @@ class HostRenderer:
         p = reproject_params(params)
         self.L.rth_renderer_set_reproject(self.h, int(bool(on)), C.byref(p) if p is not None else None)
 
+    def commit_instances(self):
+        """rapt::Renderer::CommitInstances: the scene's instance transforms (scene.set_transforms) sent on; with reproject and adaptive set
+        the next adaptive Tick carries the samples across the move (rt_reproject_motion), otherwise it clears"""
+        self._chk(self.L.rth_renderer_commit_instances(self.h))
+
     def carried_pixels(self):
         """rapt::Renderer::carriedPixels: the pixels the last reprojecting Tick carried"""
         return int(self.L.rth_renderer_carried_pixels(self.h))
@@ -864,8 +871,21 @@ class HostRenderer:
         self._rt(self.rt.rt_download_aov_positions(self.ctx, y0, y1, _p(out)))
         return out
 
+    def aov_instances(self, y0=0, y1=None):
+        """rows [y0, y1) of the G-buffer's instance indices (int32, -1: no instance), shaped (rows, width)"""
+        y1, out = self._rows(y0, y1, np.int32)
+        self._rt(self.rt.rt_download_aov_instances(self.ctx, y0, y1, _p(out)))
+        return out
+
     def history_capture(self):
         self._rt(self.rt.rt_history_capture(self.ctx))
+
+    def reproject_motion(self, params=None):
+        """rt_reproject_motion: rt_reproject that also follows the instances moved (rt_set_instances) since the capture"""
+        p = reproject_params(params)
+        n = C.c_int(-1)
+        self._rt(self.rt.rt_reproject_motion(self.ctx, C.byref(p) if p is not None else None, C.byref(n)))
+        return n.value
 
     def reproject(self, params=None):
         """rt_reproject (params: dict, see reproject_params; None: the library's defaults): the number of pixels carried"""

@@ -1,0 +1,170 @@
+"""What tests/test_gpu_reproject_motion.py and profiles/reproject_motion_bench.py share: the small TLAS scenes with diffuse instances over a
+diffuse floor, the instance moves, and the experiment that says what a carry across an instance move is worth.  Nothing here needs a device
+until a renderer is handed in."""
+import ctypes as C
+
+import numpy as np
+
+import instances_ref as ir
+
+F32 = np.float32
+
+
+def look_at(eye, target):
+    """a 16 : 9 pinhole at 'eye' with the screen 2 in front of it, centred on 'target', x to the right"""
+    eye, target = np.asarray(eye, np.float64), np.asarray(target, np.float64)
+    f = (target - eye) / np.linalg.norm(target - eye)
+    right = np.cross((0.0, 1.0, 0.0), f)
+    right /= np.linalg.norm(right)
+    up = np.cross(f, right)
+    c = eye + 2 * f
+    return np.array([eye, c - 16 / 9 * right + up, c + 16 / 9 * right + up, c - 16 / 9 * right - up], F32)
+
+
+CAMERA = look_at((0.0, 5.0, -1.5), (0.0, 1.0, 3.2))  # above the instances, looking down: they are seen against the floor they stand on
+SCALE70 = 6.0        # the 70 one- and two-triangle meshes are 0.4 wide: scaled up until one of them is some 1 % of a small frame
+COUNTS = (1, 3, 70)  # the TLAS root is the instance; a few; more than one wave's worth of records
+
+
+def build(scene, n):
+    """n instances of diffuse geometry, a diffuse floor plane and a sphere tested by brute force, one light.  1, 3: the lowBigB mesh
+    (instances_ref.mesh_scene); 70: one- and two-triangle meshes on a grid, scaled up so that they fill a small frame"""
+    if n <= 3:
+        return ir.mesh_scene(scene, ir.mesh_transforms(scene, 0.0)[:n])
+    return ir.triangles_scene(scene, ir.grid_transforms(scene, n, scale=SCALE70))
+
+
+def one_pixel_camera(n):
+    """a camera whose top left corner ray (the one ray of a 1 x 1 frame) meets instance 0"""
+    target = np.array((0.0, 2.45, 2.33) if n <= 3 else (-3.0, 0.2 + 0.13 * SCALE70, 2.0 + 0.017 * SCALE70))  # a point of its surface
+    cam = target + (0.0, 0.4, -5.0)
+    TL = cam + (target - cam) * 0.4
+    return np.array([cam, TL, TL + (1, 0, 0), TL + (0, -1, 0)], F32)
+
+
+def _mat(T):
+    return np.asarray(T, np.float64).reshape(4, 4)
+
+
+def translated(T, d):
+    M = _mat(T).copy()
+    M[:3, 3] += d
+    return M.astype(F32).reshape(16)
+
+
+def turned(T, rad):
+    """T with a turn about its own y axis in front of it"""
+    c, s = np.cos(rad), np.sin(rad)
+    R = np.array([[c, 0, s, 0], [0, 1, 0, 0], [-s, 0, c, 0], [0, 0, 0, 1]])
+    return (_mat(T) @ R).astype(F32).reshape(16)
+
+
+def records(host_api, blas, Ts):
+    """rt_instance records: the transforms with the host mirror's inverse (mat4::Inverted, as bvhInstance::SetTransform takes it)"""
+    L = host_api.host_lib()
+    rec = np.zeros(len(Ts), dtype=host_api.RT_INSTANCE_DTYPE)
+    for k, T in enumerate(Ts):
+        T = np.ascontiguousarray(T, dtype=F32).reshape(16)
+        inv = np.zeros(16, dtype=F32)
+        L.rth_mat4_inverse(T.ctypes.data_as(C.c_void_p), inv.ctypes.data_as(C.c_void_p))
+        rec[k] = (blas[k], T, inv)
+    return rec
+
+
+def motions(n, base):
+    """name -> the rt_set_instances calls (first, transforms) of a motion away from the transforms 'base'; None: back to base itself"""
+    last = n - 1
+    k0, rot = (0, last) if n <= 3 else (6, 6)  # (of the 70 on their grid, 6 stands in front, in the middle of the view)
+    d = (0.7, 0.0, 0.2)
+    return {
+        "translated": [(k0, [translated(base[k0], d)])],
+        "rotated": [(rot, [turned(base[rot], 0.8)])],
+        "all": [(0, [translated(turned(base[i], 0.05 * (1 + i % 3)), (0.2, 0.0, -0.05 * (i % 2))) for i in range(n)])],
+        "there_and_back": [(k0, [translated(base[k0], d)]), (k0, None)],
+        "two_calls": [(k0, [translated(base[k0], d)]), (last, [turned(translated(base[last], (-0.25, 0.0, 0.0)), -0.1)])],
+    }
+
+
+def tables(r):
+    """the instance records the context holds now (rt_scene_array: 32 words each, invT rows 0..2 then T rows 0..2) as the restatement's table"""
+    import reproject_motion_ref as rm
+    w = r.scene_array("inst").view(F32).reshape(-1, 32)
+    return rm.table(w[:, 12:24], w[:, 0:12]) if len(w) else None
+
+
+# ---- what the carry is worth ---------------------------------------------------------------------------------------------------------
+QUALITY = dict(width=64, height=40, history_frames=32, fresh_frames=4, reference_frames=256, reference_frame0=1000, move=(0.3, 0.0, 0.0),
+               light=(0.1, 3.0, 1.5), floor_y=-1.0, margin=0.5)  # quality_scene's light and floor; the margin: generous for the penumbra of its small light
+
+
+def quality_scene(b):
+    """scenes.scene3's diffuse mesh, floor, light and sky (the scene of the camera-move experiment, tests/test_reproject_cpu.py QUALITY) with
+    the mesh held as a BLAS under one instance: a diffuse object over a diffuse floor, seen by the default camera"""
+    import importlib
+    assets = importlib.import_module("ray-and-pathtracer_amd.assets")
+    b.sky(assets.synthetic_sky(seed=11))
+    green = b.diffuse(0.8, (0.0, 1.0, 0.0), 0.6, 0.4, 2)
+    floor = b.diffuse(0.8, (1.0, 0.0, 0.0), 0.6, 0.4, 2)
+    # a small light: with scene3's radius of 1 a bounce off the floor meets the light's disc every few dozen samples, such a sample is not
+    # finite (as a light seen directly is not), and no floor pixel would be left to compare after 256 of them
+    b.area_light(11, (0.1, 3, 1.5), 10.0, (1, 1, 1), 0.1, (0, -1, 0))
+    b.plane(0, floor, (0, 1, 0), 1)
+    m = b.mesh_obj(1, assets.obj_path("three"), green, (0, 0, 0), 1.0)
+    b.build_tlas(0, [(m, b.trs((0, 0, 2), 2.5, 0.0, 0.0, 0.0))])
+    return dict(name="quality_scene", tlas=True)
+
+
+def _mse(a, b, on):
+    d = (a - b)[on]
+    return float((d * d).mean()) if on.any() else float("nan")
+
+
+def quality(host_api, r):
+    """The experiment on a renderer that holds quality_scene under the default camera with statistics on: 32 samples per pixel, the object translated
+    by a few pixels, the samples carried (rt_reproject_motion) and 4 more added -- against clearing and taking the 4 alone, both measured on
+    the library's own 256-sample render of the moved scene.  The shadow zone is the box on the floor around the object's visible points and
+    their projections from the light's centre onto the floor, before and after the move, grown by 'margin'.  'safe' pixels are carried ones
+    on the moved object, or on the floor outside that zone; 'shadow' pixels are the carried floor pixels inside it, whose bias is
+    reported beside it."""
+    q = QUALITY
+    PATH = host_api.RT_MODE_PATH
+    base = r.scene.instance_dump(0)
+    r.clear()
+    r.render(PATH, 0, q["history_frames"])
+    r.render_aovs(0.001)
+    before = dict(pos=r.aov_positions(), inst=r.aov_instances())
+    r.history_capture()
+    assert r.set_instances(0, records(host_api, [base["blas"]], [translated(base["T"], q["move"])])) == 0
+    r.render_aovs(0.001)
+    a, pos, inst = r.aovs(), r.aov_positions(), r.aov_instances()
+    n = r.reproject_motion()
+    carried = r.stats()[0] > 0
+    f0 = q["history_frames"]
+    r.render(PATH, f0, q["fresh_frames"])
+    acc, cnt = r.accumulator()[..., :3].astype(np.float64), r.stats()[0]
+    mean_carried = acc / cnt[..., None]
+    r.clear()
+    r.render(PATH, f0, q["fresh_frames"])
+    mean_fresh = r.accumulator()[..., :3].astype(np.float64) / q["fresh_frames"]
+    r.clear()
+    r.render(PATH, q["reference_frame0"], q["reference_frames"])
+    ref = r.accumulator()[..., :3].astype(np.float64) / q["reference_frames"]
+    # the object's points and their shadows on the floor, before and after
+    P = np.concatenate([before["pos"][before["inst"] == 0], pos[inst == 0]]).astype(np.float64)
+    L = np.array(q["light"])
+    P = P[P[:, 1] < L[1] - 0.1]
+    S = L + (P - L) * ((L[1] - q["floor_y"]) / (L[1] - P[:, 1]))[:, None]
+    obj_xz = np.concatenate([P[:, [0, 2]], S[:, [0, 2]]])
+    lo, hi = obj_xz.min(0) - q["margin"], obj_xz.max(0) + q["margin"]
+    floor = (inst == -1) & (a["obj"] == 0)
+    near = floor & np.all((pos[..., [0, 2]] >= lo) & (pos[..., [0, 2]] <= hi), -1)
+    fin = np.isfinite(ref).all(-1) & np.isfinite(mean_fresh).all(-1) & np.isfinite(mean_carried).all(-1)
+    safe = carried & fin & ((inst == 0) | (floor & ~near))
+    shadow = carried & fin & near
+    out = dict(QUALITY, carried_pixels=int(n), moved_object_pixels_carried=int((carried & (inst == 0)).sum()), safe_pixels=int(safe.sum()), shadow_zone_pixels=int(shadow.sum()),
+               floor_pixels=int(floor.sum()), finite_pixels=int(fin.sum()),
+               mse_carried=_mse(mean_carried, ref, safe), mse_fresh=_mse(mean_fresh, ref, safe),
+               shadow_zone_mse_carried=_mse(mean_carried, ref, shadow), shadow_zone_mse_fresh=_mse(mean_fresh, ref, shadow))
+    out["mse_ratio"] = out["mse_carried"] / out["mse_fresh"]
+    out["shadow_zone_mse_ratio"] = out["shadow_zone_mse_carried"] / out["shadow_zone_mse_fresh"] if shadow.any() else None
+    return out
