@@ -587,8 +587,8 @@ int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_var_params* params);
  *   to rt_reproject's; and a second call gives the same result (the history is not modified).
  *   What it does not do: it moves SAMPLES, not light.  Radiance on and around a moved object changes -- its shadow, what it reflects onto
  *   its neighbours, its own lighting as it turns towards or away from the lights -- and the carried samples there are biased until new
- *   ones outweigh them: max_history is the remedy (a small value lets new samples take over quickly).  Deforming meshes (rt_set_time) still
- *   invalidate the history, and so does rt_upload_scene. */
+ *   ones outweigh them: max_history is the remedy (a small value lets new samples take over quickly).  Deforming meshes (rt_set_time,
+ *   rt_set_triangles) still invalidate the history, and so does rt_upload_scene. */
 typedef struct { float normal_tolerance, plane_tolerance; int32_t max_history; int32_t carry_view_dependent; } rt_reproject_params;
 #define RT_REPROJECT_DEFAULTS { 0.25f, 0.01f, 0, 0 }   /* a starting point, NOT tuned */
 int rt_history_capture(rt_ctx* ctx);
@@ -691,6 +691,42 @@ int rt_build_tlas(rt_ctx* ctx, const float* bounds6, uint32_t n, rt_tlas_node* n
 int rt_set_instances(rt_ctx* ctx, uint32_t first, uint32_t count, const rt_instance* instances, const float* bounds6);
 int rt_download_tlas(rt_ctx* ctx, rt_tlas_node* nodes_out, uint32_t* nodes_used_out);
 int rt_scene_array(rt_ctx* ctx, int which, void* out, size_t cap_bytes, size_t* bytes_out);
+
+/* ---- deforming a mesh without a re-upload ----------------------------------------------------------------------
+ * A skinned character, cloth or a morph target changes its vertices and keeps its topology.  rt_set_triangles replaces ALL triangles of BLAS
+ * 'blas' of the loaded scene and runs bvh::Refit (bvh.cpp:556-594) over that BLAS's tree on the device: the tree keeps its shape and its
+ * prim_idx order, no other BLAS is touched, nothing is laid out again.  It works with and without a TLAS (without one, blas 0 is the scene
+ * BVH; its spheres and planes keep their records).  Afterwards the context holds, byte for byte, what rt_upload_scene would hold of the
+ * updated description: the uploaded one with blas[blas].tris replaced, blas[blas].nodes after bvh::Refit over the new primitives and,
+ * under a TLAS, every instance of that BLAS under the box of a fresh instance with its current transform (rt_set_instances' bounds6 ==
+ * NULL rule, applied to the refitted node 0's box; every other instance keeps the box it last had) and tlas_nodes = tlas::build over all
+ * the boxes.  That covers the BLAS's primitive and pair records (rt_blas_array), inst[], the TLAS pair records, reach[] and scalars 0-8 and
+ * 11-13 (rt_scene_array).  wideOK / wide8OK and the wide arrays keep their upload-time shape: the 4-wide child boxes are brought up to date,
+ * the 8-wide quantised walk is switched off for the scene, as rt_set_time does.
+ *   tris[p] replaces primitive p as a whole record: v0, v1, v2, N, obj_idx, material.  N is the caller's own Triangle::update and is not
+ *     checked, as at upload.  n_tri must equal the uploaded n_tri: a partial update is not supported (the object box the reach[] records
+ *     rest on needs every triangle).  A later rt_set_time deforms from the new vertices.
+ *   Ordering: queued on the context's stream behind what is there.  Under a TLAS the 4-byte read-back of the TLAS build is the call's only
+ *     synchronisation; without one there is none.  (The first call on a scene, or one for a larger BLAS than any before, also allocates
+ *     its staging and undo arrays.)  tris is copied with one hipMemcpyAsync: ordinary (pageable) memory has been read when the call
+ *     returns; page-locked memory is read when the stream gets there, so without a TLAS it stays the caller's to keep unchanged until
+ *     rt_synchronize or any later call that synchronises.
+ *   Failure is atomic.  RT_E_ARG, checked on the host before anything is queued: a null pointer; blas >= n_blas; n_tri different from the
+ *     uploaded count; a vertex coordinate that is non-finite or beyond 1e29 in magnitude; a transform of an instance of the BLAS that could
+ *     take the new box beyond 1e30; an instance of another BLAS that has no box yet (rt_set_instances' rule).  RT_E_STATE: no scene.
+ *     RT_E_UNSUPPORTED: the TLAS build finds no finite union area (rt_build_tlas's failure); the call returns this after its read-back, and
+ *     the records it had rewritten are copied back on the device: the scene is byte-equal to what it was.  (Also RT_E_UNSUPPORTED: the
+ *     uploaded nodes of the BLAS were not a tree.)
+ *   Invalidation is rt_set_time's: the G-buffer goes stale, the primary-hit table is rebuilt by the next dense batch, a captured history
+ *     becomes invalid for rt_reproject AND rt_reproject_motion (a deformed surface has no rigid motion to take back).  Accumulator,
+ *     statistics and lists are untouched; a failed call invalidates nothing.  With rt_set_profiling on, the call is one entry of
+ *     rt_profile.query.
+ * rt_blas_array: the context's records of one BLAS, read back from the device: which in { RT_LAYOUT_PAIRS, RT_LAYOUT_PRIMS }, in
+ *   rt_layout_array's formats, so that the result equals the BLAS's slice of rt_layout_build's arrays (nodes_used / 2 pair records and
+ *   n_prims primitive records per BLAS, in BLAS order).  out == NULL asks for the size alone.  RT_E_ARG: a short buffer, a bad BLAS;
+ *   RT_E_UNSUPPORTED: any other array; RT_E_STATE: no scene.  Synchronous; for tests and tools. */
+int rt_set_triangles(rt_ctx* ctx, uint32_t blas, const rt_triangle* tris, uint32_t n_tri);
+int rt_blas_array(rt_ctx* ctx, uint32_t blas, int which, void* out, size_t cap_bytes, size_t* bytes_out);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Kernels tally rt_counters (slower; keep off when timing).

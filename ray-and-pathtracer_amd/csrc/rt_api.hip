@@ -154,6 +154,7 @@ int rt_set_camera(rt_ctx* c, const rt_camera* cam)
 #include "rt_api_upload.inc"
 #include "rt_api_build.inc"
 #include "rt_api_instances.inc"
+#include "rt_api_triangles.inc"
 #include "rt_api_render.inc"
 #include "rt_api_output.inc"
 

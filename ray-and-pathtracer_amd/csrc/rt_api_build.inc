@@ -184,6 +184,28 @@ int rt_build_tlas(rt_ctx* c, const float* bounds6, uint32_t n, rt_tlas_node* nod
 	return RT_OK;
 }
 
+// bvh::Refit over one tree, queued on the context's stream: order lists its pair records by level (level l: order[level[l] .. level[l + 1])),
+// levelDev is level[] on the device.  Bottom up: a level with more records than one workgroup covers in two passes gets a launch of its
+// own across the chip; the narrow levels above the last such level share one workgroup with barriers between them.  rt_set_time and
+// rt_set_triangles (rt_api_triangles.inc) refit under this one plan.
+static void refit_launch(rt_ctx* c, const uint* order, const int* levelDev, const int* level, int nLevels)
+{
+	if (nLevels <= 0) return;
+	int top = nLevels; // levels [0, top) are left for the single-workgroup kernel
+	for (int l = nLevels - 1; l >= 0; l--) {
+		const int count = level[l + 1] - level[l];
+		if (count < 2048) continue;
+		// everything deeper than l must be done first: the narrow levels between two wide ones go with the next wide launch's predecessor
+		for (int m = top - 1; m > l; m--) {
+			const int cm = level[m + 1] - level[m];
+			if (cm > 0) hipLaunchKernelGGL(k_refit_level, dim3((cm + 255) / 256), dim3(256), 0, c->stream, c->pairsMut, c->primsMut, order, level[m], cm);
+		}
+		hipLaunchKernelGGL(k_refit_level, dim3((count + 255) / 256), dim3(256), 0, c->stream, c->pairsMut, c->primsMut, order, level[l], count);
+		top = l;
+	}
+	if (top > 0) hipLaunchKernelGGL(k_refit, dim3(1), dim3(1024), 0, c->stream, c->pairsMut, c->primsMut, order, levelDev, top);
+}
+
 int rt_set_time(rt_ctx* c, float t)
 {
 	if (!c) return RT_E_ARG;
@@ -198,23 +220,7 @@ int rt_set_time(rt_ctx* c, float t)
 	const float r = fmodf(t, 2 * RT_PI);
 	const float a = (float)sin((double)r) * 0.5f;
 	hipLaunchKernelGGL(k_animate, dim3((c->animSlots + 255) / 256), dim3(256), 0, c->stream, c->primsOrig, c->primsMut, c->animSlots, a);
-	if (c->refitLevels > 0) {
-		// bottom up: a level with more records than one workgroup covers in two passes gets a launch of its own across the
-		// chip; the narrow levels above the last such level share one workgroup with barriers between them
-		int top = c->refitLevels; // levels [0, top) are left for the single-workgroup kernel
-		for (int l = c->refitLevels - 1; l >= 0; l--) {
-			const int count = c->refitLevelHost[l + 1] - c->refitLevelHost[l];
-			if (count < 2048) continue;
-			// everything deeper than l must be done first: the narrow levels between two wide ones go with the next wide launch's predecessor
-			for (int m = top - 1; m > l; m--) {
-				const int cm = c->refitLevelHost[m + 1] - c->refitLevelHost[m];
-				if (cm > 0) hipLaunchKernelGGL(k_refit_level, dim3((cm + 255) / 256), dim3(256), 0, c->stream, c->pairsMut, c->primsMut, c->refitOrder, c->refitLevelHost[m], cm);
-			}
-			hipLaunchKernelGGL(k_refit_level, dim3((count + 255) / 256), dim3(256), 0, c->stream, c->pairsMut, c->primsMut, c->refitOrder, c->refitLevelHost[l], count);
-			top = l;
-		}
-		if (top > 0) hipLaunchKernelGGL(k_refit, dim3(1), dim3(1024), 0, c->stream, c->pairsMut, c->primsMut, c->refitOrder, c->refitLevelStart, top);
-	}
+	refit_launch(c, c->refitOrder, c->refitLevelStart, c->refitLevelHost.data(), c->refitLevels);
 	if (c->S.wide && c->wideNodes > 0) hipLaunchKernelGGL(k_wide_sync, dim3((c->wideNodes * 4 + 255) / 256), dim3(256), 0, c->stream, c->wideMut, c->pairsMut, c->wideNodes);
 	HIPCHK(c, hipGetLastError());
 	return RT_OK;

@@ -3,6 +3,53 @@
 // Included by rt_api.hip (one translation unit).
 static_assert(sizeof(InstReach) == sizeof(Reach) && sizeof(Reach) == 64, "the reach record the host uploads is pack_reach's");
 
+// The tail rt_set_instances and rt_set_triangles (rt_api_triangles.inc) share: from every instance's new box in I.boundsNew to the TLAS in the
+// traversal layout.  tlas::build into scratch and the call's one synchronisation (did it succeed?); then, and only then, the commit: the
+// caller's own (commit: its mirrors and copies), the reach records, k_pack_tlas, the scalars.  A build that fails runs undo (whatever the
+// caller has queued into the scene so far is taken back), closes the profile entry and returns RT_E_UNSUPPORTED.
+//   reach   instance_reach of every instance after the change; swapped into the context on success
+static int tlas_tail(rt_ctx* c, const char* who, std::vector<Reach>& reach, const std::function<int()>& commit, const std::function<int()>& undo)
+{
+	rt_ctx::InstanceState& I = c->instances;
+	const uint32_t n = (uint32_t)c->nInstances;
+	const double originMax = reach_origin_max(reach.data(), reach.size());
+	// the scalars that follow from n alone (rt_instances.h, fact 1)
+	SceneLayout L;
+	L.tlasPairs = n >= 2 ? (int)n : 0, L.nInst = (int)n;
+	L.tlasBase = n >= 2 ? c->blasPairs : 0, L.root = n >= 2 ? c->blasPairs : (RT_INST_BIT | 0u);
+	L.reachOriginMax = (float)originMax;
+	LayoutKnobs knobs;
+	knobs.tlasLds = c->knobs.tlasLds;
+	split_lds(L, knobs);
+	// ---- the TLAS over the new boxes, into scratch ----
+	HIPCHK(c, hipMemsetAsync(I.nodesNew, 0, ((size_t)2 * n + 1) * sizeof(TlasNodeDev), c->stream));
+	hipLaunchKernelGGL(k_build_tlas, dim3(1), dim3(64), 0, c->stream, I.boundsNew, (int)n, I.nodesNew, I.used);
+	// the call's one synchronisation: did the build succeed?
+	HIPCHK(c, hipMemcpyAsync(c->hostCounts + 8, I.used, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	HIPCHK(c, hipGetLastError());
+	if (c->hostCounts[8] != (int)(2 * n)) {
+		const int rcUndo = undo();
+		prof_end(c);
+		if (rcUndo != RT_OK) return rcUndo;
+		return fail(c, RT_E_UNSUPPORTED, "%s: no finite union area left (degenerate instance bounds); the scene is unchanged", who);
+	}
+	// ---- commit (whatever an earlier call queued from the mirrors has been consumed: the stream was just drained) ----
+	{ const int rc = commit(); if (rc != RT_OK) return rc; }
+	I.reach.swap(reach);
+	HIPCHK(c, hipMemcpyAsync(I.reachIn, I.reach.data(), (size_t)n * sizeof(Reach), hipMemcpyHostToDevice, c->stream));
+	hipLaunchKernelGGL(k_pack_tlas, dim3(1), dim3(RT_TLAS_MAX), 0, c->stream, I.nodesNew, (int)n, I.reachIn, originMax, L.tlasBase,
+	                   c->pairsMut + 4 * (size_t)L.tlasBase, I.reachMut, I.tlasKeep, I.boundsNew, I.bounds);
+	prof_end(c);
+	HIPCHK(c, hipGetLastError());
+	I.built = true;
+	c->S.rootLink = L.root, c->S.tlasBase = L.tlasBase, c->S.tlasPairs = L.tlasPairs, c->S.reachOriginMax = L.reachOriginMax;
+	c->S.tlasLds = L.tlasLds, c->S.stackRows = L.stackRows;
+	int32_t* s = c->layoutScalars; // rootLink, tlasBase, tlasPairs, nInst, reachOriginMax, tlasLds, stackRows: the first seven words
+	s[0] = (int32_t)L.root, s[1] = (int32_t)L.tlasBase, s[2] = L.tlasPairs, memcpy(&s[4], &L.reachOriginMax, 4), s[5] = L.tlasLds, s[6] = L.stackRows;
+	return RT_OK;
+}
+
 int rt_set_instances(rt_ctx* c, uint32_t first, uint32_t count, const rt_instance* instances, const float* bounds6)
 {
 	if (!c || !instances) return fail(c, RT_E_ARG, "rt_set_instances: null argument");
@@ -42,50 +89,24 @@ int rt_set_instances(rt_ctx* c, uint32_t first, uint32_t count, const rt_instanc
 		memcpy(&xform[(size_t)12 * k], instances[k].transform, 48);
 		reach[first + k] = instance_reach(I.objBox[instances[k].blas], instances[k].inv_transform);
 	}
-	const double originMax = reach_origin_max(reach.data(), reach.size());
-	// the scalars that follow from n alone (rt_instances.h, fact 1)
-	SceneLayout L;
-	L.tlasPairs = n >= 2 ? (int)n : 0, L.nInst = (int)n;
-	L.tlasBase = n >= 2 ? c->blasPairs : 0, L.root = n >= 2 ? c->blasPairs : (RT_INST_BIT | 0u);
-	L.reachOriginMax = (float)originMax;
-	LayoutKnobs knobs;
-	knobs.tlasLds = c->knobs.tlasLds;
-	split_lds(L, knobs);
-
 	HIPCHK(c, hipSetDevice(c->device));
 	prof_begin(c, K_QUERY);
-	// ---- the new boxes and the TLAS over them, into scratch ----
+	// ---- the new boxes, into scratch ----
 	HIPCHK(c, hipMemcpyAsync(I.boundsNew, I.bounds, (size_t)24 * n, hipMemcpyDeviceToDevice, c->stream));
 	if (bounds6) HIPCHK(c, hipMemcpyAsync(I.boundsNew + (size_t)6 * first, bounds6, (size_t)24 * count, hipMemcpyHostToDevice, c->stream));
 	else {
 		HIPCHK(c, hipMemcpyAsync(I.xform, xform.data(), xform.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-		hipLaunchKernelGGL(k_instance_bounds, dim3(1), dim3(RT_TLAS_MAX), 0, c->stream, I.xform, I.blasOfDev + first, I.blasBox, (int)count, I.boundsNew + (size_t)6 * first);
+		hipLaunchKernelGGL(k_instance_bounds, dim3(1), dim3(RT_TLAS_MAX), 0, c->stream, I.xform, I.blasOfDev + first, I.blasBox, (int)count, I.boundsNew + (size_t)6 * first, (const int*)nullptr);
 	}
-	HIPCHK(c, hipMemsetAsync(I.nodesNew, 0, ((size_t)2 * n + 1) * sizeof(TlasNodeDev), c->stream));
-	hipLaunchKernelGGL(k_build_tlas, dim3(1), dim3(64), 0, c->stream, I.boundsNew, (int)n, I.nodesNew, I.used);
-	// the call's one synchronisation: did the build succeed?
-	HIPCHK(c, hipMemcpyAsync(c->hostCounts + 8, I.used, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	HIPCHK(c, hipGetLastError());
-	if (c->hostCounts[8] != (int)(2 * n)) {
-		prof_end(c);
-		return fail(c, RT_E_UNSUPPORTED, "rt_set_instances: no finite union area left (degenerate instance bounds); the scene is unchanged");
-	}
-	// ---- commit (whatever an earlier call queued from the mirrors has been consumed: the stream was just drained) ----
-	std::copy(inst.begin(), inst.end(), I.inst.begin() + first);
-	I.reach.swap(reach);
-	for (uint32_t k = 0; k < count; k++) I.boundsKnown[first + k] = 1;
-	HIPCHK(c, hipMemcpyAsync(I.instMut + first, &I.inst[first], (size_t)count * sizeof(DInstance), hipMemcpyHostToDevice, c->stream));
-	HIPCHK(c, hipMemcpyAsync(I.reachIn, I.reach.data(), (size_t)n * sizeof(Reach), hipMemcpyHostToDevice, c->stream));
-	hipLaunchKernelGGL(k_pack_tlas, dim3(1), dim3(RT_TLAS_MAX), 0, c->stream, I.nodesNew, (int)n, I.reachIn, originMax, L.tlasBase,
-	                   c->pairsMut + 4 * (size_t)L.tlasBase, I.reachMut, I.tlasKeep, I.boundsNew, I.bounds);
-	prof_end(c);
-	HIPCHK(c, hipGetLastError());
-	I.built = true;
-	c->S.rootLink = L.root, c->S.tlasBase = L.tlasBase, c->S.tlasPairs = L.tlasPairs, c->S.reachOriginMax = L.reachOriginMax;
-	c->S.tlasLds = L.tlasLds, c->S.stackRows = L.stackRows;
-	int32_t* s = c->layoutScalars; // rootLink, tlasBase, tlasPairs, nInst, reachOriginMax, tlasLds, stackRows: the first seven words
-	s[0] = (int32_t)L.root, s[1] = (int32_t)L.tlasBase, s[2] = L.tlasPairs, memcpy(&s[4], &L.reachOriginMax, 4), s[5] = L.tlasLds, s[6] = L.stackRows;
+	const int rc = tlas_tail(c, "rt_set_instances", reach,
+		[&]() -> int {
+			std::copy(inst.begin(), inst.end(), I.inst.begin() + first);
+			for (uint32_t k = 0; k < count; k++) I.boundsKnown[first + k] = 1;
+			HIPCHK(c, hipMemcpyAsync(I.instMut + first, &I.inst[first], (size_t)count * sizeof(DInstance), hipMemcpyHostToDevice, c->stream));
+			return RT_OK;
+		},
+		[]() -> int { return RT_OK; }); // nothing of the scene has been touched yet
+	if (rc != RT_OK) return rc;
 	c->sceneGen++; // everything rt_set_time invalidates: the G-buffer and the primary-hit table ...
 	c->geomGen++;  // ... and a captured history, for rt_reproject; rt_reproject_motion follows the move (shapeGen stays)
 	return RT_OK;

@@ -54,6 +54,38 @@ static int instances_keep(rt_ctx* c, const rt_scene_desc* d, const SceneLayout& 
 	HIPCHK(c, dalloc(c->sceneAllocs, &I.used, 1));
 	HIPCHK(c, dalloc(c->sceneAllocs, &I.reachIn, n));
 	HIPCHK(c, dalloc(c->sceneAllocs, &I.xform, (size_t)12 * n));
+	HIPCHK(c, dalloc(c->sceneAllocs, &I.which, n));
+	HIPCHK(c, dalloc(c->sceneAllocs, &I.boxUndo, 6));
+	return RT_OK;
+}
+
+// What rt_set_triangles (rt_api_triangles.inc) needs of every BLAS, kept at upload: see rt_ctx.h BlasKeep.  The ranges are pack_blas's
+// (nodes_used / 2 pair records and n_prims slots per BLAS, in BLAS order).
+static int triangles_keep(rt_ctx* c, const rt_scene_desc* d, const SceneLayout& L)
+{
+	c->blasKeep.assign(d->n_blas, rt_ctx::BlasKeep());
+	c->slotOf = nullptr, c->refitOrderAll = nullptr, c->refitLevelAll = nullptr;
+	c->triStage = nullptr, c->triStageCap = 0, c->undoPairs = nullptr, c->undoPrims = nullptr, c->undoPairCap = 0, c->undoPrimCap = 0;
+	std::vector<uint> slotOf, order;
+	std::vector<int> levelAll;
+	uint pairOff = 0, primOff = 0;
+	for (uint k = 0; k < d->n_blas; k++) {
+		const rt_blas& b = d->blas[k];
+		rt_ctx::BlasKeep& K = c->blasKeep[k];
+		K.pairFirst = pairOff, K.pairCount = b.nodes_used / 2, K.slotFirst = primOff, K.slotCount = b.n_prims, K.nTri = b.n_tri;
+		slotOf.resize((size_t)primOff + b.n_prims, 0xFFFFFFFFu);
+		for (uint j = 0; j < b.n_prims; j++) slotOf[(size_t)primOff + b.prim_idx[j]] = primOff + j; // prim_idx[j] < n_prims: pack_blas checked
+		if (k == 0 && !d->use_tlas && L.animSlots > 0) { // the scene BVH's order is pack_refit's own (pairOff 0): not walked a second time
+			order = L.refitOrder, K.level = L.refitLevelStart;
+			K.refittable = order.size() <= (size_t)K.pairCount;
+		} else K.refittable = blas_refit_order(b, pairOff, order, K.level);
+		K.levelFirst = levelAll.size();
+		levelAll.insert(levelAll.end(), K.level.begin(), K.level.end());
+		pairOff += K.pairCount, primOff += K.slotCount;
+	}
+	SCENE_ARRAY(&c->slotOf, slotOf);
+	SCENE_ARRAY(&c->refitOrderAll, order, 1);
+	SCENE_ARRAY(&c->refitLevelAll, levelAll);
 	return RT_OK;
 }
 
@@ -104,6 +136,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
 		S.wide8 = (const uint4*)dw, S.leafBox = (const float4*)dp, S.rootWide8 = L.rootWide8[0];
 	}
 	c->pairsMut = (float4*)S.pairs, c->primsMut = (float4*)S.prims;
+	{ const int rc_ = triangles_keep(c, d, L); if (rc_ != RT_OK) return rc_; }
 	c->primsOrig = nullptr, c->refitLevels = L.refitLevels, c->animSlots = L.animSlots;
 	if (L.animSlots > 0) {
 		// rt_set_time support: a copy of the uploaded leaf records, and the refit order

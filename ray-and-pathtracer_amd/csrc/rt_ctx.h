@@ -6,6 +6,7 @@
 //   rt_api_upload.inc   rt_upload_scene: build_layout's arrays copied to the device; rt_layout_*
 //   rt_api_build.inc    device builders, refit
 //   rt_api_instances.inc rt_set_instances (kernels: rt_instances.h), rt_download_tlas, rt_scene_array
+//   rt_api_triangles.inc rt_set_triangles (kernels: rt_triangles.h), rt_blas_array
 //   rt_api_render.inc   rt_render*, rt_trace_batch*: round loops and batches
 //   rt_api_gather.inc   rt_gather_*
 //   rt_api_query.inc    batch queries
@@ -21,6 +22,7 @@
 #include "rt_mega.h"
 #include "rt_build.h"
 #include "rt_instances.h"
+#include "rt_triangles.h"
 #include "rt_layout.h"
 #include "rt_denoise.h"
 #include "rt_adaptive.h"
@@ -34,6 +36,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -145,8 +148,25 @@ struct rt_ctx {
 		DInstance* instMut = nullptr; float* reachMut = nullptr;
 		float* bounds = nullptr; TlasNodeDev* tlasKeep = nullptr; float* blasBox = nullptr; int* blasOfDev = nullptr;
 		float* boundsNew = nullptr; TlasNodeDev* nodesNew = nullptr; int* used = nullptr; InstReach* reachIn = nullptr; float* xform = nullptr;
+		int* which = nullptr; float* boxUndo = nullptr; // rt_set_triangles: the instances of the deformed BLAS (n ints), the BLAS's local box before the call
 	};
 	InstanceState instances;
+	// rt_set_triangles (rt_api_triangles.inc): what upload keeps per BLAS -- its pair records and leaf slots as ranges of pairs[] / prims[],
+	// the slot of each of its primitives (slotOf: the inverse of prim_idx, absolute slots, all BLASes concatenated in primitive order) and
+	// its refit order by level (rt_layout.h blas_refit_order: absolute pair indices in refitOrderAll, the level boundaries in
+	// refitLevelAll on the device and in BlasKeep::level on the host, both as indices into refitOrderAll).  The staging array of a call's
+	// triangles and the undo copies of the two record ranges are allocated by the first call that needs them and grown on demand.
+	struct BlasKeep {
+		uint pairFirst = 0, pairCount = 0, slotFirst = 0, slotCount = 0, nTri = 0;
+		size_t levelFirst = 0;  // this BLAS's first entry of refitLevelAll
+		std::vector<int> level; // its level boundaries (levels + 1 entries)
+		bool refittable = true; // false: its tree is not one (a node is its own ancestor)
+	};
+	std::vector<BlasKeep> blasKeep;
+	uint* slotOf = nullptr; uint* refitOrderAll = nullptr; int* refitLevelAll = nullptr;
+	float* triStage = nullptr; size_t triStageCap = 0;        // triangles
+	float4* undoPairs = nullptr; float4* undoPrims = nullptr; // records
+	size_t undoPairCap = 0, undoPrimCap = 0;
 	uint blasPairs = 0;          // pair records in front of the TLAS's: pairs[] holds blasPairs + S.tlasPairs records
 	int32_t layoutScalars[14] = { 0 }; // RT_LAYOUT_SCALARS of the loaded scene (rt_scene_array)
 	// camera
@@ -326,6 +346,16 @@ static int scene_array(rt_ctx* c, T** p, const std::vector<T>& v, size_t slack =
 {
 	HIPCHK(c, dalloc(c->sceneAllocs, p, v.size() + slack));
 	if (!v.empty()) HIPCHK(c, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+	return RT_OK;
+}
+
+// room for 'count' elements in a scene-pool array that only grows (the old one stays in the pool until the next upload)
+template <typename T>
+static int grow_scene_array(rt_ctx* c, T** p, size_t& cap, size_t count)
+{
+	if (cap >= count) return RT_OK;
+	HIPCHK(c, dalloc(c->sceneAllocs, p, count));
+	cap = count;
 	return RT_OK;
 }
 

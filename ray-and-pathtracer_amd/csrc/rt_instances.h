@@ -40,12 +40,15 @@ __device__ __forceinline__ float next_up(float x)
 
 // bounds6 == NULL: the world box of a FRESH instance -- bvhInstance(blas) followed by one SetTransform (bvhInstance.cpp:37-44): the BLAS's
 // local box (bvh::bounds, bvh.cpp:48-49) grown by its 8 corners under TransformPosition, corner i taking max.x / max.y / max.z with bits
-// 0 / 1 / 2.  A lane per changed instance; xform: 12 floats (rows 0-2 of the transform) per changed instance, blasOf: its BLAS.
-__global__ void __launch_bounds__(RT_TLAS_MAX) k_instance_bounds(const float* xform, const int* blasOf, const float* blasBox6, int count, float* bounds6Out)
+// 0 / 1 / 2.  A lane per changed instance; xform: 12 floats (rows 0-2 of the transform) per changed instance, in the order of the change.
+// Changed instance k is instance which[k] (which == nullptr: instance k, a contiguous run whose first instance blasOf and bounds6Out point
+// at; rt_set_triangles names the instances of one BLAS, which need not be contiguous); blasOf: its BLAS.
+__global__ void __launch_bounds__(RT_TLAS_MAX) k_instance_bounds(const float* xform, const int* blasOf, const float* blasBox6, int count, float* bounds6Out, const int* which)
 {
 	const int k = (int)threadIdx.x;
 	if (k >= count) return;
-	const float* bb = blasBox6 + 6 * blasOf[k];
+	const int at = which ? which[k] : k;
+	const float* bb = blasBox6 + 6 * blasOf[at];
 	const f3 lo(bb[0], bb[1], bb[2]), hi(bb[3], bb[4], bb[5]);
 	float mn[3] = { lo.x, lo.y, lo.z }, mx[3] = { hi.x, hi.y, hi.z };
 	for (int i = 0; i < 8; i++) {
@@ -54,7 +57,7 @@ __global__ void __launch_bounds__(RT_TLAS_MAX) k_instance_bounds(const float* xf
 		mn[0] = t_fminf(mn[0], p.x), mn[1] = t_fminf(mn[1], p.y), mn[2] = t_fminf(mn[2], p.z);
 		mx[0] = t_fmaxf(mx[0], p.x), mx[1] = t_fmaxf(mx[1], p.y), mx[2] = t_fmaxf(mx[2], p.z);
 	}
-	for (int a = 0; a < 3; a++) bounds6Out[6 * k + a] = mn[a], bounds6Out[6 * k + 3 + a] = mx[a];
+	for (int a = 0; a < 3; a++) bounds6Out[6 * at + a] = mn[a], bounds6Out[6 * at + 3 + a] = mx[a];
 }
 
 // The commit: pair records, reach records, the context's TLAS and bounds copies, from the scratch nodes of a build that succeeded.

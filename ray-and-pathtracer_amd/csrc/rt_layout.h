@@ -602,24 +602,34 @@ static int pack_reach(const rt_scene_desc* d, SceneLayout& L, const std::vector<
 
 // ---- refit order -------------------------------------------------------------------------------------------
 // rt_set_time support: the pair records of the scene BVH grouped by depth (children are deeper than their parents) for the bottom-up refit
-static void pack_refit(const rt_scene_desc* d, SceneLayout& L)
+// The order of one BLAS, appended to 'order': its pair records as ABSOLUTE indices (pairOff: the BLAS's first record in pairs[]), level by
+// level from the root's; levelStart receives one entry per level boundary, as indices into 'order' (its first entry is order's size on
+// entry).  A tree whose root is a leaf has no pair record and no level.  rt_set_triangles (rt_api_triangles.inc) keeps this per BLAS.
+// false: more records than the BLAS has (a node that is its own ancestor); the order is then cut short and of no use.
+static bool blas_refit_order(const rt_blas& b, uint pairOff, std::vector<uint>& order, std::vector<int>& levelStart)
 {
-	const rt_blas& b = d->blas[0];
-	std::vector<uint>& order = L.refitOrder;
-	std::vector<int>& levelStart = L.refitLevelStart;
-	levelStart.assign(1, 0);
-	std::vector<uint> level;
-	if (b.nodes[0].prim_count == 0) level.push_back(b.nodes[0].left_first / 2);
+	const size_t cap = order.size() + b.nodes_used / 2;
+	levelStart.assign(1, (int)order.size());
+	std::vector<uint> level; // pair records relative to the BLAS
+	if (b.n_prims > 0 && b.nodes[0].prim_count == 0) level.push_back(b.nodes[0].left_first / 2);
 	while (!level.empty()) {
 		std::vector<uint> next;
 		for (uint pr : level) {
-			order.push_back(pr);
+			order.push_back(pairOff + pr);
 			for (int sI = 0; sI < 2; sI++) { const rt_bvh_node& nd = b.nodes[2 * pr + sI]; if (nd.prim_count == 0) next.push_back(nd.left_first / 2); }
 		}
 		levelStart.push_back((int)order.size());
+		if (order.size() > cap) return false;
 		level.swap(next);
 	}
-	L.refitLevels = (int)levelStart.size() - 1;
+	return true;
+}
+static void pack_refit(const rt_scene_desc* d, SceneLayout& L)
+{
+	const rt_blas& b = d->blas[0];
+	L.refitOrder.clear();
+	blas_refit_order(b, 0, L.refitOrder, L.refitLevelStart);
+	L.refitLevels = (int)L.refitLevelStart.size() - 1;
 	L.animSlots = (int)b.n_prims;
 }
 

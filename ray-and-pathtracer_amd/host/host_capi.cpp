@@ -342,6 +342,38 @@ int rth_scene_commit_instances(void* h)
 	GUARD(s, s->sc->CommitInstances());
 	return 0;
 }
+// The triangles of mesh 'mesh' rewritten from n * 9 vertex floats (n must be the mesh's triangle count): vertices and Triangles as
+// Mesh(raw) makes them, objIdx and material kept.  Scene::CommitTriangles sends them on.
+int rth_mesh_set_vertices(void* h, int mesh, const float* v9, int n)
+{
+	RthScene* s = (RthScene*)h;
+	if (rth_mesh_count(h, mesh) != n) { s->err = "rth_mesh_set_vertices: the mesh does not have that many triangles"; return -1; }
+	Mesh& m = s->sc->meshes[mesh];
+	for (int i = 0; i < n; i++) {
+		const float* p = v9 + 9 * i;
+		m.tri[i] = Triangle(m.tri[i].objIdx, m.tri[i].mat, f3(p), f3(p + 3), f3(p + 6));
+		if (m.vertices.size() == (size_t)3 * n && m.faces.size() == (size_t)n)
+			m.vertices[m.faces[i].x - 1] = f3(p), m.vertices[m.faces[i].y - 1] = f3(p + 3), m.vertices[m.faces[i].z - 1] = f3(p + 6);
+	}
+	return 0;
+}
+// bvh::Refit of BLAS 'blas' on the host alone (no device): what the CPU tests compare their restatement with
+int rth_bvh_refit(void* h, int blas)
+{
+	RthScene* s = (RthScene*)h;
+	if (blas >= 0 ? (!s->sc->useTLAS || blas >= rth_blas_count(h)) : !s->sc->b) { s->err = "rth_bvh_refit: no such BLAS"; return -1; }
+	GUARD(s, const_cast<bvh*>(pick(*s->sc, blas))->Refit());
+	return 0;
+}
+// Scene::CommitTriangles of BLAS 'blas' (the order Scene::Describe flattens them in; < 0: the scene BVH)
+int rth_scene_commit_triangles(void* h, int blas)
+{
+	RthScene* s = (RthScene*)h;
+	if (blas >= 0 && (!s->sc->useTLAS || blas >= rth_blas_count(h))) { s->err = "rth_scene_commit_triangles: no such BLAS"; return -1; }
+	if (blas < 0 && !s->sc->b) { s->err = "rth_scene_commit_triangles: no scene BVH"; return -1; }
+	GUARD(s, s->sc->CommitTriangles(const_cast<bvh*>(pick(*s->sc, blas))));
+	return 0;
+}
 // tlas::build on the host over the instances' current bounds (what CommitInstances makes the device do)
 int rth_scene_rebuild_tlas(void* h)
 {

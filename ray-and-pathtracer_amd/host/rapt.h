@@ -309,6 +309,12 @@ public:
 	// nodesUsed from rt_download_tlas, so that tl is the tree the device walks.  Throws without useTLAS (RT_E_UNSUPPORTED) and for what
 	// rt_set_instances refuses.  The accumulator is the caller's to clear (Renderer: camera.SetChange(true) before the next Tick).
 	void CommitInstances();
+	// Deforming a mesh without a re-upload (rt_set_triangles): call it after rewriting the triangles of the mesh(es) under 'bv' (same
+	// count; Triangle::update or new Triangles).  It runs the host bvh::Refit() and refreshes bv->bounds, sends all of bv's triangles to
+	// ctx and every context of CommitAlso, and -- the library's choice, stated as in CommitInstances' counterpart rt_set_instances with
+	// bounds6 == NULL -- RESETS the 'bounds' of bv's instances to the box of a fresh instance under their current transform (they do not
+	// accumulate across a deformation); then tl is refreshed from rt_download_tlas.  Throws for what rt_set_triangles refuses.
+	void CommitTriangles(bvh* bv);
 	void FindNearest(Ray& ray, float t_min) const;   // template/scene.h:1248
 	bool IsOccluded(Ray& ray) const;                 // template/scene.h:1286
 	float3 GetSkyColor(Ray& ray) const;              // template/scene.h:1312, evaluated on the device (rt_sky_color_batch)

@@ -432,6 +432,38 @@ void Scene::CommitInstances()
 	tl->nodesUsed = used;
 }
 
+void Scene::CommitTriangles(bvh* bv)
+{
+	if (!ctx) throw std::runtime_error("Scene: Commit() has not been called");
+	if (!bv || bv->owner != this || bv->blasIndex < 0) throw std::runtime_error("rt_amd: Scene::CommitTriangles: not a bvh of the committed scene");
+	bv->Refit();
+	bv->bounds = aabb(); // bvh::bounds (bvh.cpp:48-49), from the refitted root
+	bv->bounds.grow(bv->bvhNode[bv->rootNodeIdx].aabbMin);
+	bv->bounds.grow(bv->bvhNode[bv->rootNodeIdx].aabbMax);
+	std::vector<rt_triangle> T;
+	auto flatten = [&](const Triangle& t) {
+		rt_triangle r;
+		put3(r.v0, t.v0), put3(r.v1, t.v1), put3(r.v2, t.v2), put3(r.N, t.N);
+		r.obj_idx = t.objIdx, r.material = materialIndex(t.mat);
+		T.push_back(r);
+	};
+	if (bv->scene) { for (auto& m : bv->scene->meshes) for (auto& t : m.tri) flatten(t); }
+	else for (auto& t : bv->mesh->tri) flatten(t);
+	check(ctx, rt_set_triangles(ctx, (uint32_t)bv->blasIndex, T.data(), (uint32_t)T.size()));
+	for (rt_ctx* o : alsoCtx) check(o, rt_set_triangles(o, (uint32_t)bv->blasIndex, T.data(), (uint32_t)T.size()));
+	if (!useTLAS || !tl) return;
+	// the library's choice, as rt_set_instances' bounds6 == NULL: the instances of a deformed mesh get the box of a fresh instance
+	for (uint i = 0; i < bvhCount; i++) {
+		if (bvhList[i].blas != bv) continue;
+		bvhList[i].bounds = bv->bounds;
+		mat4 M = bvhList[i].matTransform;
+		bvhList[i].SetTransform(M);
+	}
+	uint32_t used = 0;
+	check(ctx, rt_download_tlas(ctx, (rt_tlas_node*)tl->tlasNode, &used));
+	tl->nodesUsed = used;
+}
+
 void Scene::FindNearestBatch(int n, const float* O, const float* D, const float* tmax, float t_min, rt_hit* out) const
 {
 	if (!ctx) throw std::runtime_error("Scene: Commit() has not been called");

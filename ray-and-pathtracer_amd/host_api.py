@@ -37,7 +37,8 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_select_active_dilated", "rt_select_budget_dilated",
               "rt_set_pixel_filter", "rt_get_pixel_filter", "rt_sample_rays",
               "rt_layout_build", "rt_layout_array", "rt_layout_free",
-              "rt_set_instances", "rt_download_tlas", "rt_scene_array"]
+              "rt_set_instances", "rt_download_tlas", "rt_scene_array",
+              "rt_set_triangles", "rt_blas_array"]
 
 RT_E_ARG, RT_E_STATE = -2, -5
 # include/rt_amd.h rt_set_pixel_filter
@@ -251,6 +252,8 @@ def rt_lib():
         L.rt_set_instances.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.rt_download_tlas.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_scene_array.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rt_set_triangles.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.rt_blas_array.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         _rt = L
     return _rt
 
@@ -385,6 +388,22 @@ class HostScene:
         """Scene::CommitInstances: every instance's matrices and (accumulating) bounds through rt_set_instances, to every committed context;
         the scene's tlas is then the tree the device walks.  Needs a committed scene."""
         self._chk(self.L.rth_scene_commit_instances(self.h))
+
+    def set_mesh_vertices(self, mesh, v9):
+        """the triangles of mesh 'mesh' rewritten from (n, 9) vertices (n: its triangle count), as mesh_raw makes them; objIdx and material
+        stay.  commit_triangles() sends them to the device"""
+        v9 = np.ascontiguousarray(v9, dtype=np.float32).reshape(-1, 9)
+        self._chk(self.L.rth_mesh_set_vertices(self.h, int(mesh), _p(v9), len(v9)))
+
+    def refit(self, blas=-1):
+        """bvh::Refit of BLAS 'blas' (-1: the scene BVH) on the host alone: bvh_dump() then shows the refitted boxes"""
+        self._chk(self.L.rth_bvh_refit(self.h, int(blas)))
+
+    def commit_triangles(self, blas=-1):
+        """Scene::CommitTriangles of BLAS 'blas' (describe()'s order; -1: the scene BVH of a scene without a TLAS): the host bvh::Refit,
+        rt_set_triangles to every committed context, the BLAS's instances under the box of a fresh instance, the scene's tlas refreshed
+        from the device.  Needs a committed scene."""
+        self._chk(self.L.rth_scene_commit_triangles(self.h, int(blas)))
 
     def rebuild_tlas(self):
         """tlas::build on the host over the instances' current bounds"""
@@ -701,6 +720,25 @@ class HostRenderer:
         used = C.c_uint32(0)
         self._rt(self.rt.rt_download_tlas(self.ctx, _p(nodes), C.byref(used)))
         return nodes[:used.value].copy()
+
+    # ---- deforming meshes (include/rt_amd.h rt_set_triangles, rt_blas_array) ----
+    def set_triangles(self, blas, tris, ctx=None):
+        """rt_set_triangles: tris is an RT_TRIANGLE_DTYPE array holding ALL triangles of BLAS 'blas' (v0, v1, v2, N, obj_idx, material).
+        Returns the rt_status (0: done)."""
+        t = np.ascontiguousarray(tris, dtype=RT_TRIANGLE_DTYPE).reshape(-1)
+        return int(self.rt.rt_set_triangles(self.ctx if ctx is None else ctx, int(blas), _p(t) if len(t) else None, len(t)))
+
+    def blas_array(self, blas, name, ctx=None):
+        """rt_blas_array: 'pairs' or 'prims' of BLAS 'blas' as the context (ctx None: context 0) holds them: the BLAS's slice of layout()'s"""
+        ctx = self.ctx if ctx is None else ctx
+        which = [k for k, _ in LAYOUT_ARRAYS].index(name)
+        nbytes = C.c_size_t(0)
+        if self.rt.rt_blas_array(ctx, int(blas), which, None, 0, C.byref(nbytes)) != 0:
+            raise RuntimeError("rt_blas_array: %s" % self.rt.rt_last_error(ctx).decode())
+        out = np.zeros(nbytes.value // 4, dtype=dict(LAYOUT_ARRAYS)[name])
+        if nbytes.value and self.rt.rt_blas_array(ctx, int(blas), which, _p(out), nbytes.value, C.byref(nbytes)) != 0:
+            raise RuntimeError("rt_blas_array: %s" % self.rt.rt_last_error(ctx).decode())
+        return out
 
     def ctx_at(self, k):
         """context k of a renderer made with devices=[...] (context 0 is .ctx)"""
