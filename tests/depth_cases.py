@@ -11,7 +11,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_gpu_adaptive import _shiny as shiny  # noqa: E402  (the scene tests/test_gpu_adaptive.py renders under this name; nothing runs on import)
+from budget_shapes import shiny  # noqa: E402  (the scene tests/test_gpu_adaptive.py renders under this name)
 
 W, H = 48, 32                 # the caller rays: the primary rays of the scene's own camera at this size
 ENERGY = (0.9, 0.8, 0.7)
@@ -59,7 +59,6 @@ def scene_fn(scenes, name):
 PATH_SCENES = ("mixed_small", "pretty_tlas")
 PATH_DEPTHS = (-1, 0, 1, 2, 3, 4, 5, 6, 7)
 PATH_ENVS = [{}, {"RT_FUSE": "0"}, {"RT_FUSE": "1"}, {"RT_FUSE": "2"}, {"RT_DECIDE": "0"}, {"RT_STREAM": "0"}, {"RT_STREAM": "0", "RT_SLOTS": "777"}]
-PATH_KNOBS = ("RT_FUSE", "RT_DECIDE", "RT_STREAM", "RT_SLOTS")
 PREFIX_DEPTHS, PREFIX_SIZES = (0, 6), (1, 65)
 
 # ---- part B: the general kernels ------------------------------------------------------------------------------------------------------
@@ -82,7 +81,6 @@ ONE_RAY, ONE_DEPTH, ONE_SEED = 900, 5, 0x12345678  # rapt::Renderer::Trace / Sam
 
 # ---- part C: Whitted ----------------------------------------------------------------------------------------------------------------------
 WHITTED_ENVS = [{}, {"RT_MEGA": "0"}, {"RT_MEGA_LEVELS": "1"}]
-WHITTED_KNOBS = ("RT_MEGA", "RT_MEGA_LEVELS", "RT_MEGA_LPT", "RT_LEVEL_CAP")
 # scene -> (frame width, frame height, depths); 'shiny_rt' stops at 3: deeper shiny trees against the 12 pending branches a pixel may
 # hold have not been measured
 WHITTED_CASES = {"mixed_small": (97, 61, (1, 2, 3, 5, 7)), "pretty_tlas": (120, 67, (1, 2, 3, 5, 7)), "shiny_rt": (97, 61, (1, 2, 3))}

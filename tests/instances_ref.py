@@ -1,5 +1,5 @@
 """Restatements for rt_set_instances (include/rt_amd.h), in NumPy: the box of a fresh instance, tlas::build, the numbering its nodes always
-have, and the small scenes the CPU and GPU tests of the call share.  Nothing here loads the library under test."""
+have, and the small scenes the CPU and GPU tests of the call share.  Nothing here loads the library under test; records() takes the host mirror from its caller."""
 import numpy as np
 
 f32 = np.float32
@@ -163,3 +163,24 @@ def mesh_transforms(scene, turn):
     """three placements like tlas_test2's, each turned by 'turn' more"""
     return [scene.trs((0, 0, 3), 4, 0.0, f32(1.5707964 + turn), 0.0), scene.trs((f32(2 + 0.3 * turn), 0, 3), 4, 0.0, f32(3.1415927 - turn), 0.0),
             scene.trs((f32(-2.3), f32(0.2 * turn), 3), 4, 0.0, f32(1.5707964 + 2 * turn), 0.0)]
+
+
+def records(host_api, blas, Ts):
+    """rt_instance records: the transforms with the host mirror's inverse (mat4::Inverted, as SetTransform takes it)"""
+    import ctypes as C
+    L = host_api.host_lib()
+    rec = np.zeros(len(Ts), dtype=host_api.RT_INSTANCE_DTYPE)
+    for k, T in enumerate(Ts):
+        T = np.ascontiguousarray(T, dtype=f32).reshape(16)
+        inv = np.zeros(16, dtype=f32)
+        L.rth_mat4_inverse(T.ctypes.data_as(C.c_void_p), inv.ctypes.data_as(C.c_void_p))
+        rec[k] = (blas[k], T, inv)
+    return rec
+
+
+def mat_mul(A, B):
+    """rapt::operator*(mat4, mat4): ((a0 b0 + a1 b4) + a2 b8) + a3 b12 per entry, every operation rounded to f32"""
+    A, B = np.asarray(A, dtype=f32).reshape(4, 4), np.asarray(B, dtype=f32).reshape(4, 4)
+    s = A[:, 0:1] * B[0:1, :] + A[:, 1:2] * B[1:2, :]
+    s = s + A[:, 2:3] * B[2:3, :]
+    return (s + A[:, 3:4] * B[3:4, :]).astype(f32).reshape(16)

@@ -1,8 +1,6 @@
 """What tests/test_gpu_reproject_motion.py and profiles/reproject_motion_bench.py share: the small TLAS scenes with diffuse instances over a
 diffuse floor, the instance moves, and the experiment that says what a carry across an instance move is worth.  Nothing here needs a device
 until a renderer is handed in."""
-import ctypes as C
-
 import numpy as np
 
 import instances_ref as ir
@@ -59,16 +57,7 @@ def turned(T, rad):
     return (_mat(T) @ R).astype(F32).reshape(16)
 
 
-def records(host_api, blas, Ts):
-    """rt_instance records: the transforms with the host mirror's inverse (mat4::Inverted, as bvhInstance::SetTransform takes it)"""
-    L = host_api.host_lib()
-    rec = np.zeros(len(Ts), dtype=host_api.RT_INSTANCE_DTYPE)
-    for k, T in enumerate(Ts):
-        T = np.ascontiguousarray(T, dtype=F32).reshape(16)
-        inv = np.zeros(16, dtype=F32)
-        L.rth_mat4_inverse(T.ctypes.data_as(C.c_void_p), inv.ctypes.data_as(C.c_void_p))
-        rec[k] = (blas[k], T, inv)
-    return rec
+records = ir.records  # rt_instance records of transforms, with the host mirror's inverse
 
 
 def motions(n, base):

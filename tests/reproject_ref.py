@@ -171,3 +171,48 @@ class MaterialRecorder:
         n = max(self._mats) + 1 if self._mats else 0
         assert sorted(self._mats) == list(range(n)), "material indices are not 0 .. n - 1"
         return np.array([self._mats[i][0] for i in range(n)], np.int32), np.array([self._mats[i][1] for i in range(n)], F32)
+
+
+# ---- what tests/test_gpu_reproject.py and tests/test_gpu_reproject_motion.py share: the moves, the parameter sets and the histories --------
+ADAPTIVE = dict(min_samples=4, max_samples=64, threshold=0.05, floor=1e-3)
+MOVES = dict(none=(0.0, 0.0, 0.0), small=(0.05, 0.0, 0.0), large=(0.2, 0.05, 0.1), behind=(0.0, 0.0, -20.0))  # behind: the new camera sees ground that lies behind the old one
+PARAMS = dict(defaults={}, view_dependent=dict(carry_view_dependent=1), capped=dict(max_history=8), exact=dict(normal_tolerance=0.0, plane_tolerance=0.0))
+
+
+def moved(camera, move):
+    return (np.asarray(camera, F32) + np.array(move, F32)).astype(F32)
+
+
+def list_mask(w, h, seed=5):
+    """about 60 % of the pixels, never pixel 0 unless it is the only one, always the last"""
+    on = np.random.default_rng(seed).random(w * h) < 0.6
+    on[0] = False
+    on[w * h - 1] = True
+    return on
+
+
+def make_history(r, host_api, kind, w, h):
+    """samples for a capture, on a renderer with statistics on: 12 whole frames ('uniform'), an adaptive loop with uneven counts
+    ('adaptive'), or 5 frames on list_mask's pixels alone ('list')"""
+    PATH = host_api.RT_MODE_PATH
+    r.clear()
+    if kind == "uniform":
+        r.render(PATH, 0, 12)
+    elif kind == "adaptive":
+        r.render(PATH, 0, ADAPTIVE["min_samples"])
+        for f in range(ADAPTIVE["min_samples"], ADAPTIVE["min_samples"] + 6):
+            r.select_active(ADAPTIVE)
+            r.render_active(f, 1)
+    else:
+        r.set_active(np.flatnonzero(list_mask(w, h)).astype(np.uint32))
+        r.render_active(0, 5)
+
+
+def materials(r):
+    """(type, shinieness) of the materials the renderer's scene uploads (rt_material: 16 words, type at 0, shinieness at 10)"""
+    import ctypes as C
+    from test_layout_cpu import RtSceneDesc
+    d = RtSceneDesc.from_address(r.scene.describe().value)
+    n = int(d.n_materials)
+    words = np.ctypeslib.as_array(C.cast(d.materials, C.POINTER(C.c_uint32)), shape=(n, 16)).copy()
+    return words[:, 0].view(np.int32).copy(), words[:, 10].view(F32).copy()

@@ -53,8 +53,6 @@ ROULETTE = ("trace_g", "sample_g")
 # is below every batch: slots are refilled as samples finish, and k_finish stores the finished ones.
 SLOT_BUDGET = 24
 OWN_ENVS = [{"RT_SHADE_LDS": "0"}, {"RT_SHADE_LDS": "0", "RT_STREAM": "0"}, {"RT_STREAM": "0", "RT_SLOTS": str(SLOT_BUDGET)}]
-PATH_KNOBS = ("RT_FUSE", "RT_DECIDE", "RT_STREAM", "RT_SLOTS", "RT_SHADE_LDS")
-WHITTED_KNOBS = ("RT_MEGA", "RT_MEGA_LEVELS", "RT_MEGA_LPT", "RT_LEVEL_CAP", "RT_SHADE_LDS")
 
 
 def sky_pixels():

@@ -11,56 +11,19 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import adaptive_ref as ar  # noqa: E402
+import budget_shapes as tc  # noqa: E402
+import support as sp  # noqa: E402
 from test_adaptive_cpu import QUALITY  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("RT_PRIMARY_TABLE", "RT_PRIMARY_TABLE_MIN", "RT_FUSE", "RT_STREAM", "RT_MIXED_MAX", "RT_DECIDE", "RT_DEFER_GAMMA", "RT_EXACT_GAMMA")
 # the equivalent-path switches the GPU tier renders path frames under (a context reads them when it is created)
 SWITCHES = [{}, {"RT_PRIMARY_TABLE_MIN": "0"}, {"RT_PRIMARY_TABLE": "0"}, {"RT_STREAM": "0"}, {"RT_FUSE": "0"}, {"RT_FUSE": "1"}, {"RT_FUSE": "2"}]
 W, H = 96, 64
 
 
-def _shiny(b):
-    """a shiny diffuse floor: path mode runs k_sample_general (random draws interleave with the shadow queries)"""
-    from conftest import pkg
-    assets = pkg("assets")
-    b.sky(assets.synthetic_sky(64, 32, seed=4))
-    b.area_light(11, (1.0, 4.0, 1.0), 10.0, (1, 1, 1), 1.0, (0, -1, 0))
-    gl = b.glass(1.5, (0.6, 0.6, 1.0), (0.1, 0.2, 0.05), rt=False)
-    df = b.diffuse(0.8, (0, 1, 0), 0.6, 0.4, 10, rt=False)
-    fl = b.diffuse(0.8, (1, 1, 1), 0.3, 0.7, 4, shininess=0.25, rt=False)
-    b.mesh_obj(1, assets.obj_path("ico"), df, (-0.9, 0.6, 0.6), 0.5)
-    b.sphere(1, gl, (0.2, 0.35, 0.2), 0.35)
-    b.plane(0, fl, (0, 1, 0), 0)
-    b.build(0)
-    return dict(name="shiny", tlas=False)
-
-
-def _scene_fn(scenes, name):
-    return _shiny if name == "shiny" else getattr(scenes, name)
-
-
 def _renderer(host_api, scenes, monkeypatch, name, env=None, w=W, h=H):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
-    r = host_api.HostRenderer(w, h)
-    d = _scene_fn(scenes, name)(r.scene)
-    r.commit()
-    if d and "camera" in d:
-        c = d["camera"]
-        r.set_camera(c["cam_pos"], c["top_left"], c["top_right"], c["bottom_left"])
-    return r
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
+    return sp.renderer(host_api, monkeypatch, tc.scene_fn(scenes, name), w, h, env, path_ticks=False)
 
 
 def _seeded_list(w, h, seed=5):
@@ -101,8 +64,8 @@ def test_statistics_are_exact_and_have_no_side_effect(name, scenes, host_api, mo
             f += n
         cnt, sy, syy = r.stats()
         assert np.all(cnt == K)
-        assert _same(sy, sy_ref) and _same(syy, syy_ref), split
-        assert _same(r.accumulator(), acc_off), split
+        assert sp.same(sy, sy_ref) and sp.same(syy, syy_ref), split
+        assert sp.same(r.accumulator(), acc_off), split
         # a directly viewed light sums to +inf where the accumulator does
         lit = np.isposinf(acc_off[..., :3]).all(-1)
         assert np.all(np.isposinf(sy[lit])) and np.all(np.isposinf(syy[lit]))
@@ -116,12 +79,12 @@ def test_statistics_are_exact_and_have_no_side_effect(name, scenes, host_api, mo
     assert np.all(r.stats()[0] == 2)
     r.clear()
     cnt, sy, syy = r.stats()
-    assert not cnt.any() and not _bits(sy).any() and not _bits(syy).any()
+    assert not cnt.any() and not sp.bits(sy).any() and not sp.bits(syy).any()
     r.close()
 
 
 # ---- 2. rt_render_active ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("env", SWITCHES, ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()) or "default")
+@pytest.mark.parametrize("env", SWITCHES, ids=sp.env_id)
 @pytest.mark.parametrize("name", ["mixed_small", "tlas_test2", "shiny"])
 def test_render_active_equals_render_where_listed(name, env, scenes, host_api, monkeypatch):
     r = _renderer(host_api, scenes, monkeypatch, name, env)
@@ -143,14 +106,14 @@ def test_render_active_equals_render_where_listed(name, env, scenes, host_api, m
     A = state()
     r.clear()
     r.render(PATH, 0, 4)
-    assert all(_same(x, y) for x, y in zip(state(), four))
+    assert all(sp.same(x, y) for x, y in zip(state(), four))
     r.set_active(lst)
     got, n = r.active()
     assert n == len(lst) and np.array_equal(got, lst)
     r.render_active(4, 4)
     B = state()
     for b, a, f in zip(B, A, four):
-        assert _same(b[on], a[on]) and _same(b[~on], f[~on])
+        assert sp.same(b[on], a[on]) and sp.same(b[~on], f[~on])
     assert np.all(B[1][on] == 8) and np.all(B[1][~on] == 4)
     # the list survives rt_clear; every pixel listed: the whole-frame render
     r.clear()
@@ -158,7 +121,7 @@ def test_render_active_equals_render_where_listed(name, env, scenes, host_api, m
     r.render(PATH, 0, 4)
     r.set_active(np.arange(W * H, dtype=np.uint32))
     r.render_active(4, 4)
-    assert all(_same(x, y) for x, y in zip(state(), A))
+    assert all(sp.same(x, y) for x, y in zip(state(), A))
     # one pixel
     p = 31 * W + 17
     r.clear()
@@ -168,12 +131,12 @@ def test_render_active_equals_render_where_listed(name, env, scenes, host_api, m
     one = np.zeros((H, W), bool)
     one[31, 17] = True
     for b, a, f in zip(state(), A, four):
-        assert _same(b[one], a[one]) and _same(b[~one], f[~one])
+        assert sp.same(b[one], a[one]) and sp.same(b[~one], f[~one])
     # an empty list: OK, nothing touched
     before = state()
     r.set_active([])
     r.render_active(8, 4)
-    assert r.active()[1] == 0 and all(_same(x, y) for x, y in zip(state(), before))
+    assert r.active()[1] == 0 and all(sp.same(x, y) for x, y in zip(state(), before))
     # with statistics off: the region-of-interest render
     r.stats_enable(False)
     r.clear()
@@ -181,7 +144,7 @@ def test_render_active_equals_render_where_listed(name, env, scenes, host_api, m
     r.set_active(lst)
     r.render_active(4, 4)
     acc = r.accumulator()
-    assert _same(acc[on], A[0][on]) and _same(acc[~on], four[0][~on])
+    assert sp.same(acc[on], A[0][on]) and sp.same(acc[~on], four[0][~on])
     r.close()
 
 
@@ -316,7 +279,7 @@ def test_tick_adaptive_equals_the_loop_by_hand(scenes, host_api, monkeypatch):
         assert r.active_pixels() == n, t
         active.append(n)
         rendered += n
-        assert _same(r.tick_accumulator(), hand.accumulator()), t
+        assert sp.same(r.tick_accumulator(), hand.accumulator()), t
         assert np.array_equal(r.stats()[0], hand.stats()[0]), t
         assert np.array_equal(r.tick_pixels(), hand.resolve_adaptive()), t
     tail = active[P["min_samples"]:]

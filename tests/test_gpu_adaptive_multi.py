@@ -22,11 +22,10 @@ import adaptive_ref as ar  # noqa: E402
 import adaptive_shapes as sh  # noqa: E402
 import budget_ref as br  # noqa: E402
 import budget_shapes as tc  # noqa: E402
+import support as sp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("RT_PRIMARY_TABLE", "RT_PRIMARY_TABLE_MIN", "RT_FUSE", "RT_STREAM", "RT_MIXED_MAX", "RT_DECIDE", "RT_DEFER_GAMMA", "RT_EXACT_GAMMA",
-         "RT_SLOTS", "RT_WIDE", "RT_WIDE8", "RT_SAMPLE_GIB")
 F32 = np.float32
 SEED = 0x12345678
 # (width, height) -> the splits run at that size: what each is here for is the table of tests/test_adaptive_rows_cpu.py
@@ -34,32 +33,7 @@ SPLITS = {(97, 41): (2, 3), (257, 3): (2,), (64, 5): (4,), (1, 7): (3,), (641, 4
 
 
 def _renderer(host_api, scenes, monkeypatch, name, w, h, devices=None, **kw):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    r = host_api.HostRenderer(w, h, devices=devices)
-    d = tc.scene_fn(scenes, name)(r.scene, **kw)
-    r.scene.set_raytracer(False)  # Tick renders path frames
-    r.commit()
-    if d and "camera" in d:
-        c = d["camera"]
-        r.set_camera(c["cam_pos"], c["top_left"], c["top_right"], c["bottom_left"])
-    return r
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
-def _state(r):
-    return (r.accumulator(),) + tuple(r.stats())
-
-
-def _same_state(a, b):
-    return all(_same(x, y) for x, y in zip(a, b))
+    return sp.renderer(host_api, monkeypatch, lambda b: tc.scene_fn(scenes, name)(b, **kw), w, h, devices=devices)
 
 
 def _shard(h, r, n):
@@ -72,45 +46,12 @@ def _shard_pixels(w, h, r, n):
 
 
 def _uneven(r, host_api, w, h):
-    """tests/budget_shapes.py uneven_moments on the device: counts 4 and 7 (one count where the seeded list is the frame), sample k is frame k"""
-    r.stats_enable(True)
-    r.clear()
-    r.render(host_api.RT_MODE_PATH, 0, tc.UNEVEN_WHOLE)
-    r.set_active(sh.seeded_list(w, h, seed=tc.UNEVEN_SEED))
-    r.render_active(tc.UNEVEN_WHOLE, tc.UNEVEN_MORE)
-    return r.stats()
-
-
-# frames 0, 1, ... of mixed_small at a size, one at a time by a context of its own: snapshot n is the state after n frames (the method of
-# tests/test_gpu_budget.py _snapshots / _equals_snapshot_of_its_count, re-stated)
-_SNAPSHOTS = {}
+    """counts 4 and 7 (one count where the seeded list is the frame)"""
+    return sp.uneven(r, host_api, sh.seeded_list(w, h, seed=tc.UNEVEN_SEED))
 
 
 def _snapshots(host_api, scenes, monkeypatch, w, h, upto):
-    have = _SNAPSHOTS.get((w, h), [])
-    if len(have) <= upto:
-        r = _renderer(host_api, scenes, monkeypatch, "mixed_small", w, h)
-        r.stats_enable(True)
-        r.clear()
-        have = [_state(r)]
-        for n in range(upto):
-            r.render(host_api.RT_MODE_PATH, n, 1)
-            have.append(_state(r))
-        r.close()
-        _SNAPSHOTS[(w, h)] = have
-    return have
-
-
-def _equals_snapshot_of_its_count(state, snaps, on):
-    """every pixel of the mask with count n holds snapshot n's accumulator and sums"""
-    acc, cnt, sy, syy = state
-    for n in np.unique(cnt[on]):
-        m = on & (cnt == n)
-        a, c, y, yy = snaps[int(n)]
-        assert np.all(c[m] == n)
-        if not (_same(acc[m], a[m]) and _same(sy[m], y[m]) and _same(syy[m], yy[m])):
-            return "pixels with count %d differ from %d frames rendered one at a time" % (n, n)
-    return None
+    return sp.snapshots(host_api, monkeypatch, "mixed_small", scenes.mixed_small, w, h, upto)
 
 
 # ---- 1. shard selection --------------------------------------------------------------------------------------------------------------------
@@ -178,21 +119,21 @@ def test_shard_budgets_equal_the_restatement(n, scenes, host_api, monkeypatch):
     # a pass on every shard's plan in turn: listed pixels hold whole frames of their count, nothing else is written
     snaps = _snapshots(host_api, scenes, monkeypatch, w, h, tc.UNEVEN_WHOLE + tc.UNEVEN_MORE + 7)
     everything = np.ones((h, w), bool)
-    assert _equals_snapshot_of_its_count(_state(r), snaps, everything) is None  # the starting state is frames 0 .. count - 1 already
+    assert sp.differs_from_snapshot_of_its_count(sp.state(r), snaps, everything) is None  # the starting state is frames 0 .. count - 1 already
     for k in range(n):
-        before = _state(r)
+        before = sp.state(r)
         pix, b, used = _check_shard_plan(r, before[1:], w, h, k, n, tc.SELECT, 7)
         assert len(pix) > 0
         r.render_budget(0, SEED, 4)
-        after = _state(r)
+        after = sp.state(r)
         on = np.zeros(w * h, bool)
         on[pix] = True
         on = on.reshape(h, w)
         want = before[1].reshape(-1).copy()
         want[pix] += b
         assert np.array_equal(after[1].reshape(-1), want), k
-        assert all(_same(x[~on], y[~on]) for x, y in zip(after, before)), "the pass of rank %d wrote an unlisted pixel" % k
-        assert _equals_snapshot_of_its_count(after, snaps, everything) is None, k
+        assert all(sp.same(x[~on], y[~on]) for x, y in zip(after, before)), "the pass of rank %d wrote an unlisted pixel" % k
+        assert sp.differs_from_snapshot_of_its_count(after, snaps, everything) is None, k
     out = [C.c_int(-7), C.c_uint32(7), C.c_int(-7)]
     p = host_api.budget_params(dict(select=tc.SELECT, pass_cap=7))
     assert r.rt.rt_select_budget_rows(r.ctx, C.byref(p), 0, 1, h + 1, *(C.byref(o) for o in out)) == host_api.RT_E_ARG
@@ -221,7 +162,7 @@ def pair(scenes, host_api, monkeypatch):
 def test_gather_stats_rows(pair, scenes, host_api, monkeypatch):
     a, b = pair
     PATH = host_api.RT_MODE_PATH
-    want = _state(a)
+    want = sp.state(a)
     assert np.all(want[1] == 1)
     for n in (2, 3):
         for k in range(n):
@@ -229,20 +170,20 @@ def test_gather_stats_rows(pair, scenes, host_api, monkeypatch):
             b.clear()
             b.render_rows(PATH, 0, 3, first, stride, count)
             a.gather_stats_rows(b, first, stride, count)
-            src = _state(b)
+            src = sp.state(b)
             rows = np.arange(k, GH, n)
             assert np.all(src[1][rows] == 3)
             for x, y in zip(want, src):
                 x[rows] = y[rows]
-            assert _same_state(_state(a), want), (n, k)
+            assert sp.same_state(sp.state(a), want), (n, k)
     # the other direction, on another shard: the way reprojected rows get back to their owner
     first, stride, count = _shard(GH, 3, 4)
-    before = _state(b)
+    before = sp.state(b)
     b.gather_stats_rows(a, first, stride, count)
     rows = np.arange(3, GH, 4)
     for x, y in zip(before, want):
         x[rows] = y[rows]
-    assert _same_state(_state(b), before) and _same_state(_state(a), want)
+    assert sp.same_state(sp.state(b), before) and sp.same_state(sp.state(a), want)
     # errors: reported on the source
     rt, E_ARG, E_STATE = a.rt, host_api.RT_E_ARG, host_api.RT_E_STATE
     assert rt.rt_gather_stats_rows(a.ctx, a.ctx, 0, 1, GH) == 0  # dst == src
@@ -256,9 +197,9 @@ def test_gather_stats_rows(pair, scenes, host_api, monkeypatch):
     b.stats_enable(False)
     assert rt.rt_gather_stats_rows(a.ctx, b.ctx, 0, 1, GH) == E_STATE and b"source" in rt.rt_last_error(b.ctx)
     assert rt.rt_gather_stats_rows(b.ctx, a.ctx, 0, 1, GH) == E_STATE and b"destination" in rt.rt_last_error(a.ctx)
-    assert _same_state(_state(a), want)
+    assert sp.same_state(sp.state(a), want)
     assert rt.rt_gather_rows(a.ctx, b.ctx, 0, 1, GH) == 0  # the accumulator alone needs no statistics, as ever
-    assert _same(a.accumulator(), b.accumulator()) and all(_same(x, y) for x, y in zip(a.stats(), want[1:]))
+    assert sp.same(a.accumulator(), b.accumulator()) and all(sp.same(x, y) for x, y in zip(a.stats(), want[1:]))
 
 
 def _lists(w, h):
@@ -276,7 +217,7 @@ def test_gather_active(pair, scenes, host_api, monkeypatch):
     a, b = pair
     w, h = GW, GH
     assert w % 5 == 1
-    want = _state(a)
+    want = sp.state(a)
     frame = 0
     for name, lst in _lists(w, h):
         assert sh.acceptable(lst, w * h) and len(lst) == len(np.unique(lst)), name
@@ -284,14 +225,14 @@ def test_gather_active(pair, scenes, host_api, monkeypatch):
         b.render_active(frame, 2)
         frame += 2
         a.gather_active(b)
-        src = _state(b)
+        src = sp.state(b)
         on = np.zeros(w * h, bool)
         on[lst] = True
         on = on.reshape(h, w)
         assert np.all(src[1][on] >= 2)
         for x, y in zip(want, src):
             x[on] = y[on]
-        assert _same_state(_state(a), want), name  # B's bits at the listed pixels, A's own everywhere else
+        assert sp.same_state(sp.state(a), want), name  # B's bits at the listed pixels, A's own everywhere else
     # after a budgeted pass on a shard: the plan is consumed, the list still serves
     first, stride, count = _shard(h, 1, 2)
     sel = dict(min_samples=8, max_samples=16, threshold=0.05, floor=1e-3)
@@ -303,19 +244,19 @@ def test_gather_active(pair, scenes, host_api, monkeypatch):
     assert b.rt.rt_download_budgets(b.ctx, out.ctypes.data_as(C.c_void_p), w * h, C.byref(k)) == host_api.RT_E_STATE
     assert np.array_equal(b.active()[0], lst)
     a.gather_active(b)
-    src = _state(b)
+    src = sp.state(b)
     on = np.zeros(w * h, bool)
     on[lst] = True
     on = on.reshape(h, w)
     for x, y in zip(want, src):
         x[on] = y[on]
-    assert _same_state(_state(a), want)
+    assert sp.same_state(sp.state(a), want)
     # an empty list: RT_OK, nothing written; dst == src: RT_OK
     b.set_active(np.zeros(0, np.uint32))
     a.gather_active(b)
     a.set_active(np.array([5], np.uint32))
     a.gather_active(a)
-    assert _same_state(_state(a), want)
+    assert sp.same_state(sp.state(a), want)
     # no list on the source, statistics off on either side
     rt, E_STATE = a.rt, host_api.RT_E_STATE
     fresh = host_api.HostRenderer(w, h)
@@ -326,7 +267,7 @@ def test_gather_active(pair, scenes, host_api, monkeypatch):
     b.stats_enable(False)
     assert rt.rt_gather_active(a.ctx, b.ctx) == E_STATE and b"source" in rt.rt_last_error(b.ctx)
     assert rt.rt_gather_active(b.ctx, a.ctx) == E_STATE and b"destination" in rt.rt_last_error(a.ctx)
-    assert _same_state(_state(a), want)
+    assert sp.same_state(sp.state(a), want)
 
 
 # ---- 5. Renderer::Tick ---------------------------------------------------------------------------------------------------------------------
@@ -388,5 +329,5 @@ def test_adaptive_ticks_over_several_contexts_equal_one_context(devices, scenes,
         many = _run_ticks(host_api, scenes, monkeypatch, case, devices)
         for t, (x, y) in enumerate(zip(one, many)):
             for k in range(5):  # the accumulator, count, sum_y, sum_yy of context 0, the pixels
-                assert _same(x[k], y[k]), (case, t, k)
+                assert sp.same(x[k], y[k]), (case, t, k)
             assert x[5:] == y[5:], (case, t, x[5:], y[5:])  # activePixels, passSamples, carriedPixels, the iteration number

@@ -17,43 +17,15 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import adaptive_ref as ar  # noqa: E402
 import adaptive_shapes as sh  # noqa: E402
+import support as sp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-# a context reads its knobs when it is created: the ones this file sets, cleared first
-KNOBS = ("RT_PRIMARY_TABLE", "RT_PRIMARY_TABLE_MIN", "RT_FUSE", "RT_STREAM", "RT_MIXED_MAX", "RT_DECIDE", "RT_DEFER_GAMMA", "RT_EXACT_GAMMA",
-         "RT_SLOTS", "RT_WIDE", "RT_WIDE8")
 INF = float("inf")
 
 
 def _renderer(host_api, scenes, monkeypatch, name, env=None, w=97, h=41):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
-    r = host_api.HostRenderer(w, h)
-    d = getattr(scenes, name)(r.scene)
-    r.commit()
-    if d and "camera" in d:
-        c = d["camera"]
-        r.set_camera(c["cam_pos"], c["top_left"], c["top_right"], c["bottom_left"])
-    return r
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
-def _state(r):
-    return (r.accumulator(),) + r.stats()
-
-
-def _env_id(e):
-    return ",".join("%s=%s" % kv for kv in e.items()) or "default"
+    return sp.renderer(host_api, monkeypatch, getattr(scenes, name), w, h, env, path_ticks=False)
 
 
 # ---- 1. crafted masks through the compaction ---------------------------------------------------------------------------------------
@@ -104,9 +76,9 @@ def test_selection_of_crafted_masks(size, scenes, host_api, monkeypatch):
         if not (again_n == k and np.array_equal(again, want)):
             bad.append("%s: a second selection gives %d pixels, or another list" % (name, again_n))
         if name == "none":
-            before = _state(r)
+            before = sp.state(r)
             r.render_active(2, 1)  # nothing selected: nothing rendered
-            if not (r.active()[1] == 0 and all(_same(x, y) for x, y in zip(_state(r), before))):
+            if not (r.active()[1] == 0 and all(sp.same(x, y) for x, y in zip(sp.state(r), before))):
                 bad.append("none: rt_render_active over an empty selection touched the frame")
     r.close()
     assert not bad, "\n".join(bad)
@@ -221,9 +193,9 @@ def _whole_frames(host_api, scenes, monkeypatch, name, w, h, frame0, nframes):
         r.stats_enable(True)
         r.clear()
         r.render(host_api.RT_MODE_PATH, 0, WARM)
-        warm = _state(r)
+        warm = sp.state(r)
         r.render(host_api.RT_MODE_PATH, frame0, nframes)
-        _reference[key] = (warm, _state(r))
+        _reference[key] = (warm, sp.state(r))
         r.close()
         for a in warm + _reference[key][1]:
             a.setflags(write=False)
@@ -238,17 +210,17 @@ def _check_listed(host_api, scenes, monkeypatch, name, env, w, h, lst, frame0=WA
     r.stats_enable(True)
     r.clear()
     r.render(host_api.RT_MODE_PATH, 0, WARM)
-    assert all(_same(x, y) for x, y in zip(_state(r), warm)), "the whole frames under the list differ under %s" % (env,)
+    assert all(sp.same(x, y) for x, y in zip(sp.state(r), warm)), "the whole frames under the list differ under %s" % (env,)
     r.set_active(lst)
     r.render_active(frame0, nframes)
-    got = _state(r)
+    got = sp.state(r)
     r.close()
     on = np.zeros(w * h, bool)
     on[lst] = True
     on = on.reshape(h, w)
     for what, g, f, b in zip(("accumulator", "count", "sum_y", "sum_yy"), got, full, warm):
-        assert _same(g[on], f[on]), "%s of the listed pixels" % what
-        assert _same(g[~on], b[~on]), "%s of a pixel that is not listed" % what
+        assert sp.same(g[on], f[on]), "%s of the listed pixels" % what
+        assert sp.same(g[~on], b[~on]), "%s of a pixel that is not listed" % what
     assert np.all(got[1][on] == WARM + nframes) and np.all(got[1][~on] == WARM)
 
 
@@ -277,7 +249,7 @@ def test_render_active_with_fewer_slots_and_in_batches(name, size, slots, nframe
     _check_listed(host_api, scenes, monkeypatch, name, {"RT_SLOTS": slots}, w, h, lst, nframes=nframes)
 
 
-@pytest.mark.parametrize("env", [{"RT_WIDE": "1"}, {"RT_WIDE8": "1"}, {"RT_WIDE": "1", "RT_STREAM": "0"}], ids=_env_id)
+@pytest.mark.parametrize("env", [{"RT_WIDE": "1"}, {"RT_WIDE8": "1"}, {"RT_WIDE": "1", "RT_STREAM": "0"}], ids=sp.env_id)
 @pytest.mark.parametrize("size", SHAPES, ids=lambda s: "%dx%d" % s)
 @pytest.mark.parametrize("name", ["mixed_small", "tlas_test2"])
 def test_render_active_with_the_wide_walks(name, size, env, scenes, host_api, monkeypatch):
@@ -286,7 +258,7 @@ def test_render_active_with_the_wide_walks(name, size, env, scenes, host_api, mo
 
 
 @pytest.mark.parametrize("length,env", [(k, {}) for k in (1, 63, 64, 65, 255, 256, 257, 1025)] + [(k, {"RT_STREAM": "0"}) for k in (63, 65, 257)],
-                         ids=lambda v: _env_id(v) if isinstance(v, dict) else str(v))
+                         ids=lambda v: sp.env_id(v) if isinstance(v, dict) else str(v))
 @pytest.mark.parametrize("size", SHAPES, ids=lambda s: "%dx%d" % s)
 def test_render_active_list_lengths(size, length, env, scenes, host_api, monkeypatch):
     """the first 'length' entries of the seeded list: the wave and block edges of k_accumulate<true>'s grid over the list"""
@@ -362,8 +334,8 @@ def test_tick_adaptive_equals_the_loop_by_hand_at_a_ragged_size(scenes, host_api
         assert r.active_pixels() == k, t
         active.append(k)
         rendered += k
-        assert _same(r.tick_accumulator(), hand.accumulator()), t
-        assert all(_same(x, y) for x, y in zip(r.stats(), hand.stats())), t
+        assert sp.same(r.tick_accumulator(), hand.accumulator()), t
+        assert all(sp.same(x, y) for x, y in zip(r.stats(), hand.stats())), t
         assert np.array_equal(r.tick_pixels(), hand.resolve_adaptive()), t
     tail = active[P["min_samples"]:]
     assert all(b <= a for a, b in zip(tail, tail[1:])), active  # a static camera: pixels only ever leave the active set

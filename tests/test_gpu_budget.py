@@ -21,83 +21,21 @@ import adaptive_ref as ar  # noqa: E402
 import adaptive_shapes as sh  # noqa: E402
 import budget_ref as br  # noqa: E402
 import budget_shapes as tc  # noqa: E402
+import support as sp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("RT_PRIMARY_TABLE", "RT_PRIMARY_TABLE_MIN", "RT_FUSE", "RT_STREAM", "RT_MIXED_MAX", "RT_DECIDE", "RT_DEFER_GAMMA", "RT_EXACT_GAMMA",
-         "RT_SLOTS", "RT_WIDE", "RT_WIDE8", "RT_SAMPLE_GIB")
 INF = float("inf")
 F32 = np.float32
 SEED = 0x12345678
 
 
 def _renderer(host_api, scenes, monkeypatch, name, env=None, w=97, h=41):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
-    r = host_api.HostRenderer(w, h)
-    d = tc.scene_fn(scenes, name)(r.scene)
-    r.scene.set_raytracer(False)  # Tick renders path frames
-    r.commit()
-    if d and "camera" in d:
-        c = d["camera"]
-        r.set_camera(c["cam_pos"], c["top_left"], c["top_right"], c["bottom_left"])
-    return r
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
-def _state(r):
-    return (r.accumulator(),) + tuple(r.stats())
-
-
-def _same_state(a, b):
-    return all(_same(x, y) for x, y in zip(a, b))
-
-
-def _env_id(e):
-    return ",".join("%s=%s" % kv for kv in e.items()) or "default"
-
-
-# frames F, F + 1, ... of a scene at a size, rendered one at a time by a context of its own: snapshot n is the state after n frames
-# (0: after rt_clear).  Rendered once per (scene, size, F) and shared; the equivalent-path knobs do not change a bit of it
-# (tests/test_gpu_parity.py, tests/test_gpu_adaptive.py), so the default pipeline renders them for every variant.
-_SNAPSHOTS = {}
+    return sp.renderer(host_api, monkeypatch, tc.scene_fn(scenes, name), w, h, env)
 
 
 def _snapshots(host_api, scenes, monkeypatch, name, w, h, F, upto):
-    key = (name, w, h, F)
-    have = _SNAPSHOTS.get(key, [])
-    if len(have) <= upto:
-        r = _renderer(host_api, scenes, monkeypatch, name, w=w, h=h)
-        r.stats_enable(True)
-        r.clear()
-        have = [_state(r)]
-        for n in range(upto):
-            r.render(host_api.RT_MODE_PATH, (F + n) & 0xFFFFFFFF, 1)
-            have.append(_state(r))
-        r.close()
-        _SNAPSHOTS[key] = have
-    return have
-
-
-def _equals_snapshot_of_its_count(state, snaps):
-    """every pixel with count n holds snapshot n's accumulator and sums"""
-    acc, cnt, sy, syy = state
-    for n in np.unique(cnt):
-        on = cnt == n
-        a, c, y, yy = snaps[int(n)]
-        assert np.all(c[on] == n)
-        if not (_same(acc[on], a[on]) and _same(sy[on], y[on]) and _same(syy[on], yy[on])):
-            return "pixels with count %d differ from %d frames rendered one at a time" % (n, n)
-    return None
+    return sp.snapshots(host_api, monkeypatch, name, tc.scene_fn(scenes, name), w, h, upto, first=F)
 
 
 def _select(r, sel, cap, mps=0):
@@ -119,13 +57,8 @@ def _check_plan(r, stats, sel, cap, mps=0):
 
 
 def _uneven(r, host_api, w, h):
-    """tests/budget_shapes.py uneven_moments on the device: counts 4 and 7, every pixel's sample k is frame k"""
-    r.stats_enable(True)
-    r.clear()
-    r.render(host_api.RT_MODE_PATH, 0, tc.UNEVEN_WHOLE)
-    r.set_active(sh.seeded_list(w, h, seed=tc.UNEVEN_SEED))
-    r.render_active(tc.UNEVEN_WHOLE, tc.UNEVEN_MORE)
-    stats = r.stats()
+    """counts 4 and 7"""
+    stats = sp.uneven(r, host_api, sh.seeded_list(w, h, seed=tc.UNEVEN_SEED))
     assert set(np.unique(stats[0])) == {tc.UNEVEN_WHOLE, tc.UNEVEN_WHOLE + tc.UNEVEN_MORE}
     return stats
 
@@ -210,22 +143,22 @@ def test_selection_at_the_compaction_edges(size, scenes, host_api, monkeypatch):
     assert len(lst) == n and total == 7 * n
     nothing = dict(min_samples=2, max_samples=1024, threshold=INF, floor=1e-3)
     assert _check_plan(r, stats, nothing, 7)[2] == 0
-    before = _state(r)
+    before = sp.state(r)
     r.render_budget(0)  # an empty plan: RT_OK, nothing touched
-    assert _same_state(_state(r), before)
+    assert sp.same_state(sp.state(r), before)
     if size in RENDERED_SHAPES:
         snaps = _snapshots(host_api, scenes, monkeypatch, "mixed_small", w, h, 0, 12)
-        assert _equals_snapshot_of_its_count(before, snaps) is None  # the starting state is frames 0 .. count - 1 already
+        assert sp.differs_from_snapshot_of_its_count(before, snaps) is None  # the starting state is frames 0 .. count - 1 already
         lst, b, total, used = _check_plan(r, stats, SHAPE_SELECT, 7)
         r.render_budget(0)
-        after = _state(r)
+        after = sp.state(r)
         want = stats[0].reshape(-1).copy()
         want[lst] += b
         assert np.array_equal(after[1].reshape(-1), want)
-        assert _equals_snapshot_of_its_count(after, snaps) is None
+        assert sp.differs_from_snapshot_of_its_count(after, snaps) is None
         lst, b, total, used = _check_plan(r, r.stats(), everything, 7)  # every pixel, first frames 3 .. 11 by now
         r.render_budget(0)
-        assert _equals_snapshot_of_its_count(_state(r), snaps) is None
+        assert sp.differs_from_snapshot_of_its_count(sp.state(r), snaps) is None
     r.close()
 
 
@@ -237,19 +170,19 @@ def _count_decides(host_api, scenes, monkeypatch, name, w, h, F, env=None, diffe
     r.stats_enable(True)
     r.clear()
     for k in range(tc.LOOP_PASSES):
-        before = _state(r)
+        before = sp.state(r)
         lst, b, total, used = _check_plan(r, before[1:], P, cap)
         assert used == cap and len(lst) > 0
         r.render_budget(F, SEED, 4)
-        after = _state(r)
+        after = sp.state(r)
         on = np.zeros(w * h, bool)
         on[lst] = True
         on = on.reshape(h, w)
         want = before[1].reshape(-1).copy()
         want[lst] += b
         assert np.array_equal(after[1].reshape(-1), want), k
-        assert all(_same(x[~on], y[~on]) for x, y in zip(after, before)), "pass %d wrote an unlisted pixel" % k
-        assert _equals_snapshot_of_its_count(after, snaps) is None, k
+        assert all(sp.same(x[~on], y[~on]) for x, y in zip(after, before)), "pass %d wrote an unlisted pixel" % k
+        assert sp.differs_from_snapshot_of_its_count(after, snaps) is None, k
         if k == 0:
             assert len(lst) == w * h and np.all(b == min(P["min_samples"], cap))
         else:
@@ -274,7 +207,7 @@ PIPELINES = [{"RT_STREAM": "0"}, {"RT_SLOTS": "777"}, {"RT_PRIMARY_TABLE": "0"},
              {"RT_DEFER_GAMMA": "0"}, {"RT_WIDE": "1"}]
 
 
-@pytest.mark.parametrize("env", PIPELINES, ids=_env_id)
+@pytest.mark.parametrize("env", PIPELINES, ids=sp.env_id)
 def test_count_decides_on_every_pipeline(env, scenes, host_api, monkeypatch):
     """RT_SLOTS=777: the first pass has 15,908 samples for 777 slots (the slot wavefront hands slots on)."""
     _count_decides(host_api, scenes, monkeypatch, "mixed_small", 97, 41, 100, env=env)
@@ -297,12 +230,12 @@ def test_a_pass_at_cap_1_is_render_active(name, scenes, host_api, monkeypatch):
     lst, b, total, used = _check_plan(r, r.stats(), sel, 1)
     assert 0 < len(lst) < w * h and total == len(lst) and np.all(b == 1)
     r.render_budget(F)
-    new = _state(r)
+    new = sp.state(r)
     r.clear()
     r.render(PATH, F, k)
     r.set_active(lst)
     r.render_active(F + k, 1)
-    assert _same_state(_state(r), new)
+    assert sp.same_state(sp.state(r), new)
     r.close()
 
 
@@ -387,8 +320,8 @@ def test_plan_state_and_errors(scenes, host_api, monkeypatch):
     # an empty selection: a plan of no samples -- RT_OK without a launch, nothing touched, consumed like any other
     assert sel(dict(min_samples=2, threshold=INF)) == 0 and (n.value, total.value, cap.value) == (0, 0, 7)
     assert r.budgets()[1] == 0
-    state = _state(r)
-    assert render() == 0 and _same_state(_state(r), state) and render() == STATE
+    state = sp.state(r)
+    assert render() == 0 and sp.same_state(sp.state(r), state) and render() == STATE
     # statistics switched off under a plan
     assert sel() == 0
     r.stats_enable(False)
@@ -430,7 +363,7 @@ def test_tick_with_a_pass_cap_equals_the_loop_by_hand(scenes, host_api, monkeypa
         if t == 0:
             assert n == w * h and total == min(P["min_samples"], cap) * w * h  # no whole-frame phase: every pixel is below min_samples
         taken.append(total)
-        assert _same(r.tick_accumulator(), hand.accumulator()) and _same_state(_state(r), _state(hand)), t
+        assert sp.same(r.tick_accumulator(), hand.accumulator()) and sp.same_state(sp.state(r), sp.state(hand)), t
         assert np.array_equal(r.tick_pixels(), hand.resolve_adaptive()), t
     assert 0 < taken[1] < taken[0] and len(np.unique(r.stats()[0])) > 3
     r.close()
@@ -457,7 +390,7 @@ def test_tick_with_pass_cap_0_is_the_adaptive_tick_of_before(scenes, host_api, m
             n = hand.select_active(P)
             hand.render_active(t, 1)
         assert r.active_pixels() == r.pass_samples() == n, t
-        assert _same(r.tick_accumulator(), hand.accumulator()) and _same_state(_state(r), _state(hand)), t
+        assert sp.same(r.tick_accumulator(), hand.accumulator()) and sp.same_state(sp.state(r), sp.state(hand)), t
         assert np.array_equal(r.tick_pixels(), hand.resolve_adaptive()), t
     r.close()
     hand.close()

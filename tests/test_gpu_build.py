@@ -9,6 +9,7 @@ import pytest
 
 import build_cases as bc
 import instances_ref as ir
+import support as sp
 from conftest import random_rays
 
 pytestmark = pytest.mark.gpu
@@ -129,8 +130,7 @@ def test_refit_boxes_equal_oracle(name, wide, scenes, host_api, refit_refs, monk
     """After rt_set_time(t) pair record p holds the boxes of the oracle's nodes 2 p and 2 p + 1 after its SetTime(t) + Refit, for every pair
     of the tree; at t = 0 they are the uploaded ones again.  The queries at every t give the oracle's hits and flags: with RT_WIDE=1 through
     the 4-wide nodes k_wide_sync rewrote (the occlusion walk of clean rays) and the binary pairs, with RT_WIDE=0 through the pairs alone."""
-    monkeypatch.setenv("RT_WIDE", wide)
-    monkeypatch.setenv("RT_WIDE8", "0")
+    sp.clean_env(monkeypatch, {"RT_WIDE": wide, "RT_WIDE8": "0"})
     ref = refit_refs(name)
     used = ref["uploaded"]["nodes_used"]
     r = host_api.HostRenderer(16, 8)

@@ -14,6 +14,7 @@ from conftest import rel_err
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import denoise_ref as dr  # noqa: E402
 import denoise_var_ref as dv  # noqa: E402
+import support as sp  # noqa: E402
 from test_adaptive_cpu import QUALITY  # noqa: E402
 from test_denoise_var_cpu import quality_ratio  # noqa: E402
 from test_gpu_denoise import make  # noqa: E402
@@ -26,10 +27,6 @@ ALL_INF = dict(sigma_luminance=INF, sigma_normal=INF, sigma_position=INF, sigma_
 PARAMS = [dict(iterations=1), dict(iterations=5), dict(ALL_INF, iterations=5),
           dict(iterations=3, sigma_luminance=1.5, sigma_normal=INF, sigma_position=0.05, sigma_albedo=1.0, epsilon=1e-2)]
 ADAPT = dict(min_samples=4, max_samples=64, threshold=0.05, floor=1e-3)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def kernel_vs_ref(orr, r, params, label=""):
@@ -170,13 +167,13 @@ def test_no_side_effects(scenes, oracle_api, host_api):
     r.denoise_variance()
     r.resolve_denoised()
     after = state(r)
-    assert all(np.array_equal(_bits(a), _bits(b)) for a, b in zip(before, after))
+    assert all(sp.same(a, b) for a, b in zip(before, after))
     r.select_active(ADAPT)
     r.render_active(20, 2)
     r2 = start()
     r2.select_active(ADAPT)
     r2.render_active(20, 2)
-    assert all(np.array_equal(_bits(a), _bits(b)) for a, b in zip(state(r), state(r2)))
+    assert all(sp.same(a, b) for a, b in zip(state(r), state(r2)))
     r.close(), r2.close()
 
 
@@ -240,8 +237,8 @@ def test_rt_denoise_afterwards_is_its_own(scenes, oracle_api, host_api):
         assert (var[..., 3] > 0).any()
         r.denoise(4)
         again = r.denoised()
-        assert np.all(again[..., 3] == 0) and np.array_equal(_bits(again), _bits(plain))
-        assert not np.array_equal(_bits(again[..., :3]), _bits(var[..., :3]))
+        assert np.all(again[..., 3] == 0) and sp.same(again, plain)
+        assert not sp.same(again[..., :3], var[..., :3])
     r.close()
 
 
@@ -265,7 +262,7 @@ def test_tick_adaptive_denoised(scenes, host_api):
     for t in range(8):
         r.tick()
         px = r.tick_pixels()
-        assert np.array_equal(_bits(r.tick_accumulator()), _bits(r.accumulator()))  # the raw accumulator
+        assert sp.same(r.tick_accumulator(), r.accumulator())  # the raw accumulator
         r.denoise_variance(P)  # directly, on the same state
         assert np.array_equal(px, r.resolve_denoised()), t
         assert not np.array_equal(px, r.resolve_adaptive())
@@ -309,7 +306,7 @@ def test_tick_with_both_flags_off_is_the_plain_tick(scenes, host_api):
         for k in range(K):
             r.tick()
             hand.render(host_api.RT_MODE_PATH, k, 1)
-            assert np.array_equal(_bits(r.tick_accumulator()), _bits(hand.accumulator())), k
+            assert sp.same(r.tick_accumulator(), hand.accumulator()), k
         its = [it for it in range(1, K + 2) if np.array_equal(r.tick_pixels(), hand.resolve(it))]
         assert len(its) == 1, its  # rt_resolve of the same sums with Tick's frame count, and nothing else
         r.close()
@@ -334,7 +331,7 @@ def test_tick_adaptive_with_the_flag_off_is_the_adaptive_tick(scenes, host_api):
             else:
                 hand.select_active(ADAPT)
                 hand.render_active(k, 1)
-            assert np.array_equal(_bits(r.tick_accumulator()), _bits(hand.accumulator())), k
+            assert sp.same(r.tick_accumulator(), hand.accumulator()), k
             assert np.array_equal(r.tick_pixels(), hand.resolve_adaptive()), k
         r.close(), hand.close()
 

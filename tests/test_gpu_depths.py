@@ -17,22 +17,11 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import depth_cases as dc  # noqa: E402
+import support as sp  # noqa: E402
 from conftest import rel_err  # noqa: E402
 from test_gpu_parity import RADIANCE_TOL, make_pair  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _env(monkeypatch, knobs, env):
-    """a context reads its switches when it is created (csrc/rt_ctx.h Knobs)"""
-    for k in knobs:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
 
 
 def _pair(scenes, oracle_api, host_api, name, w=dc.W, h=dc.H):
@@ -50,15 +39,11 @@ def _hold(got, ref, what):
     assert np.abs(ref[fin]).sum() > 0, what
 
 
-def _env_id(env):
-    return ",".join("%s=%s" % kv for kv in env.items()) or "default"
-
-
 # ---- A: path mode on the round pipelines ----------------------------------------------------------------------------------------------
 _PATH_FIRST = {}  # scene -> {depth: the values of the first environment that ran}
 
 
-@pytest.mark.parametrize("env", dc.PATH_ENVS, ids=_env_id)
+@pytest.mark.parametrize("env", dc.PATH_ENVS, ids=sp.env_id)
 @pytest.mark.parametrize("name", dc.PATH_SCENES)
 def test_sample_on_the_round_pipelines_at_every_depth(name, env, scenes, oracle_api, host_api, monkeypatch):
     """Renderer::Sample with the flag clear at start depths -1 .. 7: zero to eight rounds (depth -1 is 0.05 from the host, depth 0 the
@@ -66,20 +51,20 @@ def test_sample_on_the_round_pipelines_at_every_depth(name, env, scenes, oracle_
     and the same bits under every schedule; on the default schedule the batches of the first 1 and 65 rays give the bits those rays
     have in the full batch (a ray's stream is StreamSeed(seed_base + index): nothing depends on the batch around it)."""
     ref = dc.oracle_values(scenes, oracle_api, name, dc.SAMPLE, False, dc.PATH_DEPTHS)
-    _env(monkeypatch, dc.PATH_KNOBS, env)
+    sp.clean_env(monkeypatch, env)
     o, orr, r, d = _pair(scenes, oracle_api, host_api, name)
     O, D = orr.primary_rays()
     got = {depth: r.trace_batch(host_api.RT_MODE_PATH, O, D, depth=depth, seed_base=dc.SEED_BASE, energy=dc.ENERGY) for depth in dc.PATH_DEPTHS}
     first = _PATH_FIRST.setdefault(name, got)
     for depth in dc.PATH_DEPTHS:
-        _hold(got[depth], ref[depth], "%s [%s] Sample depth %d" % (name, _env_id(env), depth))
-        assert np.array_equal(_bits(got[depth]), _bits(first[depth])), (name, env, depth)
+        _hold(got[depth], ref[depth], "%s [%s] Sample depth %d" % (name, sp.env_id(env), depth))
+        assert sp.same(got[depth], first[depth]), (name, env, depth)
     assert np.all(got[-1] == np.float32(0.05))
     if not env:
         for depth in dc.PREFIX_DEPTHS:
             for n in dc.PREFIX_SIZES:
                 part = r.trace_batch(host_api.RT_MODE_PATH, O[:n], D[:n], depth=depth, seed_base=dc.SEED_BASE, energy=dc.ENERGY)
-                assert np.array_equal(_bits(part), _bits(got[depth][:n])), (name, depth, n)
+                assert sp.same(part, got[depth][:n]), (name, depth, n)
     r.close()
 
 
@@ -146,7 +131,7 @@ def _whitted_ref(scenes, oracle_api, name):
     return _WHITTED_REF[name]
 
 
-@pytest.mark.parametrize("env", dc.WHITTED_ENVS, ids=_env_id)
+@pytest.mark.parametrize("env", dc.WHITTED_ENVS, ids=sp.env_id)
 @pytest.mark.parametrize("name", list(dc.WHITTED_CASES))
 def test_whitted_against_the_oracle_at_every_depth(name, env, scenes, oracle_api, host_api, monkeypatch):
     """Renderer::Trace with the flag set under the default schedule, the wavefront rounds (RT_MEGA=0) and the tree levels
@@ -156,16 +141,16 @@ def test_whitted_against_the_oracle_at_every_depth(name, env, scenes, oracle_api
     w, h, depths = dc.WHITTED_CASES[name]
     frames = _whitted_ref(scenes, oracle_api, name)
     rays = dc.oracle_values(scenes, oracle_api, name, dc.TRACE, True, depths)
-    _env(monkeypatch, dc.WHITTED_KNOBS, env)
+    sp.clean_env(monkeypatch, env)
     o, orr, r, d = _pair(scenes, oracle_api, host_api, name, w, h)
     o48, orr48 = dc.oracle_pair(scenes, oracle_api, name)
     O, D = orr48.primary_rays()
     for depth in depths:
         r.clear()
         r.render(host_api.RT_MODE_WHITTED, 0, 1, max_depth=depth)
-        _hold(r.accumulator()[..., :3], frames[depth], "%s [%s] %d x %d frame, max_depth %d" % (name, _env_id(env), w, h, depth))
+        _hold(r.accumulator()[..., :3], frames[depth], "%s [%s] %d x %d frame, max_depth %d" % (name, sp.env_id(env), w, h, depth))
         got = r.trace_batch(host_api.RT_MODE_WHITTED, O, D, depth=depth, seed_base=dc.SEED_BASE, energy=dc.ENERGY)
-        _hold(got, rays[depth], "%s [%s] Trace depth %d" % (name, _env_id(env), depth))
+        _hold(got, rays[depth], "%s [%s] Trace depth %d" % (name, sp.env_id(env), depth))
     r.close()
     orr48.close()
     o48.close()
@@ -192,6 +177,6 @@ def test_full_frame_stack_is_reported_as_such(mode, fits, overflows, limit, scen
         assert ("Trace" if mode == dc.TRACE else "Sample") in text and "traversal stack" not in text, text
     assert "error -6:" in str(ei.value)  # RT_E_OVERFLOW (include/rt_amd.h)
     after = r.trace_batch(mode, O, D, depth=fits, seed_base=dc.SEED_BASE, energy=dc.ENERGY)
-    assert np.array_equal(_bits(after), _bits(before))
+    assert sp.same(after, before)
     _hold(after, dc.oracle_values(scenes, oracle_api, "hall", mode, False, (fits,))[fits], "hall after the overflow, depth %d" % fits)
     r.close()

@@ -18,14 +18,14 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import adaptive_ref as ar  # noqa: E402
 import adaptive_shapes as sh  # noqa: E402
+import budget_shapes as tc  # noqa: E402
 import dilate_ref as dr  # noqa: E402
 import dilate_shapes as ds  # noqa: E402
+import support as sp  # noqa: E402
 from test_adaptive_cpu import QUALITY  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("RT_PRIMARY_TABLE", "RT_PRIMARY_TABLE_MIN", "RT_FUSE", "RT_STREAM", "RT_MIXED_MAX", "RT_DECIDE", "RT_DEFER_GAMMA", "RT_EXACT_GAMMA",
-         "RT_SLOTS", "RT_WIDE", "RT_WIDE8", "RT_SAMPLE_GIB")
 INF = float("inf")
 F32 = np.float32
 SEED = 0x12345678
@@ -33,75 +33,17 @@ DIL_CRAFT = dict(min_samples=2, max_samples=3, threshold=INF, floor=1.0)
 
 
 def _renderer(host_api, scenes, monkeypatch, name, w=97, h=41, devices=None):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    r = host_api.HostRenderer(w, h, devices=devices)
-    d = getattr(scenes, name)(r.scene)
-    r.scene.set_raytracer(False)  # Tick renders path frames
-    r.commit()
-    if d and "camera" in d:
-        c = d["camera"]
-        r.set_camera(c["cam_pos"], c["top_left"], c["top_right"], c["bottom_left"])
-    return r
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
-def _state(r):
-    return (r.accumulator(),) + tuple(r.stats())
-
-
-def _same_state(a, b):
-    return all(_same(x, y) for x, y in zip(a, b))
-
-
-# frames 0, 1, ... of a scene at a size, rendered one at a time by a context of its own: snapshot n is the state after n frames.
-# Rendered once per (scene, size) and shared, never changed.
-_SNAPSHOTS = {}
+    return sp.renderer(host_api, monkeypatch, getattr(scenes, name), w, h, devices=devices)
 
 
 def _snapshots(host_api, scenes, monkeypatch, name, w, h, upto):
-    key = (name, w, h)
-    have = _SNAPSHOTS.get(key, [])
-    if len(have) <= upto:
-        r = _renderer(host_api, scenes, monkeypatch, name, w=w, h=h)
-        r.stats_enable(True)
-        r.clear()
-        have = [_state(r)]
-        for n in range(upto):
-            r.render(host_api.RT_MODE_PATH, n, 1)
-            have.append(_state(r))
-        r.close()
-        _SNAPSHOTS[key] = have
-    return have
-
-
-def _differs_from_snapshot_of_its_count(state, snaps, where=None):
-    """None when every pixel (of 'where') with count n holds snapshot n's accumulator and sums, else what differs"""
-    acc, cnt, sy, syy = state
-    for n in np.unique(cnt if where is None else cnt[where]):
-        on = cnt == n if where is None else (cnt == n) & where
-        a, c, y, yy = snaps[int(n)]
-        if not (_same(acc[on], a[on]) and _same(sy[on], y[on]) and _same(syy[on], yy[on])):
-            return "pixels with count %d differ from %d frames rendered one at a time" % (n, n)
-    return None
+    return sp.snapshots(host_api, monkeypatch, name, getattr(scenes, name), w, h, upto)
 
 
 def _uneven(r, host_api, w, h):
     """4 whole frames, then 3 more on a seeded 30 % list: counts 4 and 7, every pixel's sample k is frame k"""
-    r.stats_enable(True)
-    r.clear()
-    r.render(host_api.RT_MODE_PATH, 0, 4)
-    r.set_active(sh.seeded_list(w, h, seed=9))
-    r.render_active(4, 3)
-    stats = r.stats()
-    assert set(np.unique(stats[0])) == {4, 7}
+    stats = sp.uneven(r, host_api, sh.seeded_list(w, h, seed=tc.UNEVEN_SEED))
+    assert set(np.unique(stats[0])) == {tc.UNEVEN_WHOLE, tc.UNEVEN_WHOLE + tc.UNEVEN_MORE}
     return stats
 
 
@@ -207,18 +149,18 @@ def test_dilated_budgets_and_their_pass(size, scenes, host_api, monkeypatch):
                 only = ~raw.reshape(-1)[lst]
                 assert only.any() and (~only).any() and (b[only] == 1).all() and b.max() > 1  # both kinds of entry are there
             # the pass of the halved plan: listed pixels move by their budgets and equal whole frames of their count; the rest is not written
-            before = _state(r)
+            before = sp.state(r)
             r.render_budget(0, SEED, 4)
-            after = _state(r)
+            after = sp.state(r)
             listed = np.zeros(w * h, bool)
             listed[lst] = True
             listed = listed.reshape(h, w)
             moved = cnt.reshape(-1).copy()
             moved[lst] += b
             assert np.array_equal(after[1].reshape(-1), moved)
-            assert all(_same(x[~listed], y[~listed]) for x, y in zip(after, before)), "an unlisted pixel was written"
-            assert _differs_from_snapshot_of_its_count(after, snaps, listed) is None
-            assert _differs_from_snapshot_of_its_count(after, snaps) is None
+            assert all(sp.same(x[~listed], y[~listed]) for x, y in zip(after, before)), "an unlisted pixel was written"
+            assert sp.differs_from_snapshot_of_its_count(after, snaps, listed) is None
+            assert sp.differs_from_snapshot_of_its_count(after, snaps) is None
     r.close()
 
 
@@ -259,8 +201,8 @@ def test_dilated_loop_dominates_and_count_decides(scenes, host_api, monkeypatch)
             r.render_budget(0, SEED, 4)
             passes += 1
         assert r.select_active(sel) == 0                           # no raw-active pixel is left
-        state = _state(r)
-        assert _differs_from_snapshot_of_its_count(state, snaps) is None
+        state = sp.state(r)
+        assert sp.differs_from_snapshot_of_its_count(state, snaps) is None
         counts[radius] = state[1]
         assert state[1].min() >= sel["min_samples"] and state[1].max() <= sel["max_samples"]
         r.close()
@@ -297,7 +239,7 @@ def test_tick_with_adaptive_dilate_equals_the_calls_by_hand(cap, scenes, host_ap
             n = total = hand.select_active_dilated(radius, P)
             hand.render_active(t, 1)
         assert (r.active_pixels(), r.pass_samples()) == (n, total), t
-        assert _same(r.tick_accumulator(), hand.accumulator()) and _same_state(_state(r), _state(hand)), t
+        assert sp.same(r.tick_accumulator(), hand.accumulator()) and sp.same_state(sp.state(r), sp.state(hand)), t
         assert np.array_equal(r.tick_pixels(), hand.resolve_adaptive()), t
     assert cap or grew
     r.close()
@@ -329,7 +271,7 @@ def test_tick_with_adaptive_dilate_0_is_the_tick_of_before(scenes, host_api, mon
                 n = hand.select_active(P)
                 hand.render_active(t, 1)
             assert r.active_pixels() == n, (cap, t)
-            assert _same_state(_state(r), _state(hand)), (cap, t)
+            assert sp.same_state(sp.state(r), sp.state(hand)), (cap, t)
         r.close()
         hand.close()
 

@@ -10,15 +10,14 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import budget_shapes as tc  # noqa: E402
 import filter_ref as fr  # noqa: E402
+import support as sp  # noqa: E402
 import test_filter_cpu as fc  # noqa: E402
 from test_filter_cpu import quality  # noqa: E402,F401  (the module-scoped fixture of the quality experiment)
-from test_gpu_adaptive import _shiny  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("RT_PRIMARY_TABLE", "RT_PRIMARY_TABLE_MIN", "RT_FUSE", "RT_STREAM", "RT_MIXED_MAX", "RT_DECIDE", "RT_DEFER_GAMMA", "RT_EXACT_GAMMA",
-         "RT_SLOTS", "RT_WIDE", "RT_WIDE8", "RT_SAMPLE_GIB")
 # the schedules the existing tests hold bit-equal in reference mode (tests/test_gpu_parity.py, tests/test_gpu_adaptive.py SWITCHES) ...
 SCHEDULES = [{}, {"RT_FUSE": "0"}, {"RT_FUSE": "1"}, {"RT_FUSE": "2"}, {"RT_STREAM": "0"}, {"RT_PRIMARY_TABLE": "0"},
              {"RT_PRIMARY_TABLE": "1", "RT_PRIMARY_TABLE_MIN": "0"}]
@@ -30,13 +29,9 @@ PARITY_SIZES = [(24, 16), (65, 3)]
 FRAME0, NFRAMES = 5, 3
 
 
-def _env_id(e):
-    return ",".join("%s=%s" % kv for kv in e.items()) or "default"
-
-
 def _scene_fn(scenes, name):
     if name == "shiny":
-        return _shiny
+        return tc.shiny
     if name == "scene3":
         return lambda b: scenes.scene3(b, force_diffuse=False)
     if name == "quality":
@@ -45,28 +40,7 @@ def _scene_fn(scenes, name):
 
 
 def _renderer(host_api, scenes, monkeypatch, name, env=None, w=24, h=16, devices=None, path_ticks=False):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
-    r = host_api.HostRenderer(w, h, devices=devices)
-    _scene_fn(scenes, name)(r.scene)
-    if path_ticks:
-        r.scene.set_raytracer(False)
-    r.commit()
-    return r
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
-def _state(r):
-    return (r.accumulator(),) + r.stats()
+    return sp.renderer(host_api, monkeypatch, _scene_fn(scenes, name), w, h, env, devices=devices, path_ticks=path_ticks, scene_camera=False)
 
 
 # ---- 1. rays ----------------------------------------------------------------------------------------------------------------
@@ -75,8 +49,7 @@ def _state(r):
                          ids=["1x1", "63x1", "65x1", "255x1", "257x3", "24x16-skewed"])
 def test_sample_rays_equal_the_restatement(size, cam, host_api, monkeypatch):
     w, h = size
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
+    sp.clean_env(monkeypatch)
     r = host_api.HostRenderer(w, h)
     if cam:
         r.set_camera(*cam)
@@ -87,19 +60,18 @@ def test_sample_rays_equal_the_restatement(size, cam, host_api, monkeypatch):
         for frame in (0, 7):
             O, D = r.sample_rays(frame, seed_base)
             O_ref, D_ref = fr.rays(fr.KINDS[name], r.camera(), w, h, frame, seed_base)
-            assert _same(O, O_ref), (name, frame)
-            assert _same(D, D_ref), (name, frame)
+            assert sp.same(O, O_ref), (name, frame)
+            assert sp.same(D, D_ref), (name, frame)
     # rows [y0, y1) are those rows of the frame
     if h > 1:
         O, D = r.sample_rays(7, seed_base, 1, h)
-        assert _same(D, D_ref[w:]) and _same(O, O_ref[w:])
+        assert sp.same(D, D_ref[w:]) and sp.same(O, O_ref[w:])
     r.close()
 
 
 def test_fisheye_point_rays_are_primary_rays(host_api, oracle_api, monkeypatch):
     w, h = 24, 16
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
+    sp.clean_env(monkeypatch)
     o = oracle_api.OracleScene()
     fc._tiny_scene(o)
     orr = oracle_api.OracleRenderer(o, w, h)
@@ -110,7 +82,7 @@ def test_fisheye_point_rays_are_primary_rays(host_api, oracle_api, monkeypatch):
     r.set_camera(*cam, fisheye=True, view_angle=0.3, y_angle=0.1)
     r.set_pixel_filter(host_api.RT_FILTER_POINT)
     O, D = r.sample_rays(2, SEED)
-    assert _same(O, O_ref) and _same(D, D_ref)
+    assert sp.same(O, O_ref) and sp.same(D, D_ref)
     r.close()
     orr.close()
     o.close()
@@ -155,13 +127,13 @@ def _check_parity(host_api, references, scenes, monkeypatch, name, env):
             r.render(host_api.RT_MODE_PATH, FRAME0, NFRAMES, SEED)
             got = r.accumulator()[..., :3]
             err, cls_ok = rel_err(got, ref)
-            print("%s %s %dx%d %s: max rel err %.3g" % (name, _env_id(env), size[0], size[1], kname, err.max()))
+            print("%s %s %dx%d %s: max rel err %.3g" % (name, sp.env_id(env), size[0], size[1], kname, err.max()))
             assert cls_ok, (size, kname)
             assert err.max() <= 1e-4, (size, kname, err.max())
         r.close()
 
 
-@pytest.mark.parametrize("env", PIPELINES, ids=_env_id)
+@pytest.mark.parametrize("env", PIPELINES, ids=sp.env_id)
 @pytest.mark.parametrize("name", ["scene3", "tlas_test2", "mixed_small"])
 def test_accumulator_equals_the_oracle_on_the_restated_rays(name, env, scenes, host_api, references, monkeypatch):
     _check_parity(host_api, references, scenes, monkeypatch, name, env)
@@ -183,7 +155,7 @@ def test_schedules_are_bit_equal_under_box(name, scenes, host_api, monkeypatch):
         r.close()
         if first is None:
             first = acc
-        assert _same(acc, first), env
+        assert sp.same(acc, first), env
 
 
 # ---- 3. composition -----------------------------------------------------------------------------------------------------------
@@ -209,10 +181,10 @@ def test_rows_lists_plans_and_split_calls_equal_render(kname, scenes, host_api, 
         r.set_pixel_filter(kind)
         r.stats_enable(True)
     # the states after F .. F + 11 frames, one frame at a time
-    stack = [_state(a)]
+    stack = [sp.state(a)]
     for n in range(12):
         a.render(PATH, F + n, 1, SEED)
-        stack.append(_state(a))
+        stack.append(sp.state(a))
     # four frames as 1 + 3 calls, and as one call
     for split in ((4,), (1, 3)):
         b.clear()
@@ -220,13 +192,13 @@ def test_rows_lists_plans_and_split_calls_equal_render(kname, scenes, host_api, 
         for n in split:
             b.render(PATH, f, n, SEED)
             f += n
-        assert all(_same(x, y) for x, y in zip(_state(b), stack[4])), split
+        assert all(sp.same(x, y) for x, y in zip(sp.state(b), stack[4])), split
         assert np.all(b.stats()[0] == 4)
     # a 3-way row interleave
     b.clear()
     for k in range(3):
         b.render_rows(PATH, F, 4, k, 3, (H - k + 2) // 3, SEED)
-    assert all(_same(x, y) for x, y in zip(_state(b), stack[4]))
+    assert all(sp.same(x, y) for x, y in zip(sp.state(b), stack[4]))
     # a 60 % list with the frame's edges: the listed pixels take frames F + 4 .. F + 6, the others keep four
     lst = _seeded_list(W, H)
     assert 0.5 < len(lst) / (W * H) < 0.7
@@ -235,18 +207,18 @@ def test_rows_lists_plans_and_split_calls_equal_render(kname, scenes, host_api, 
     on = on.reshape(H, W)
     b.set_active(lst)
     b.render_active(F + 4, 3, SEED)
-    for x, y7, y4 in zip(_state(b), stack[7], stack[4]):
-        assert _same(x[on], y7[on]) and _same(x[~on], y4[~on])
+    for x, y7, y4 in zip(sp.state(b), stack[7], stack[4]):
+        assert sp.same(x[on], y7[on]) and sp.same(x[~on], y4[~on])
     # a budgeted pass: a pixel with count n holds the state after n frames from F
     na, total, cap = b.select_budget(dict(select=dict(min_samples=6, max_samples=12, threshold=0.02, floor=1e-3), pass_cap=5))
     assert na > 0 and total >= na
     b.render_budget(F, SEED)
-    got = _state(b)
+    got = sp.state(b)
     cnt = got[1]
     assert cnt.max() <= 12 and len(np.unique(cnt)) >= 2
     for n in np.unique(cnt):
         m = cnt == n
-        assert all(_same(x[m], y[m]) for x, y in zip(got, stack[int(n)])), n
+        assert all(sp.same(x[m], y[m]) for x, y in zip(got, stack[int(n)])), n
     a.close()
     b.close()
 
@@ -263,11 +235,11 @@ def test_adaptive_tick_over_two_contexts_equals_one(kname, scenes, host_api, mon
             r.tick()
         out.append((r.tick_accumulator(),) + r.stats() + (np.int32([r.active_pixels()]),))
         r.close()
-    assert all(_same(x, y) for x, y in zip(*out))
+    assert all(sp.same(x, y) for x, y in zip(*out))
 
 
 # ---- 4. reference mode is untouched -----------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("env", [{"RT_PRIMARY_TABLE": "1", "RT_PRIMARY_TABLE_MIN": "0"}, {"RT_PRIMARY_TABLE": "0"}], ids=_env_id)
+@pytest.mark.parametrize("env", [{"RT_PRIMARY_TABLE": "1", "RT_PRIMARY_TABLE_MIN": "0"}, {"RT_PRIMARY_TABLE": "0"}], ids=sp.env_id)
 def test_reference_mode_after_a_filter_is_the_parent_s(env, scenes, host_api, monkeypatch):
     PATH = host_api.RT_MODE_PATH
     a = _renderer(host_api, scenes, monkeypatch, "mixed_small", env, W, H)
@@ -280,16 +252,16 @@ def test_reference_mode_after_a_filter_is_the_parent_s(env, scenes, host_api, mo
     a.set_pixel_filter(host_api.RT_FILTER_REFERENCE)
     for r in (a, b):
         r.render(PATH, 0, 3, SEED)
-    assert _same(a.accumulator(), b.accumulator())
-    assert not _same(boxed, b.accumulator())
+    assert sp.same(a.accumulator(), b.accumulator())
+    assert not sp.same(boxed, b.accumulator())
     # the rays of reference mode: the truncated jitter lands on the integer pixels [x - 1, x] x [y - 1, y]
     O, D = b.sample_rays(0, SEED)
     b.set_pixel_filter(host_api.RT_FILTER_POINT)
     _, P = b.sample_rays(0, SEED)
     P, inner = P.reshape(H, W, 3), D.reshape(H, W, 3)[1:, 1:]
     cands = [P[1 - dy:H - dy, 1 - dx:W - dx] for dy in (0, 1) for dx in (0, 1)]
-    assert np.all(np.any([np.all(_bits(inner) == _bits(c), axis=-1) for c in cands], axis=0))
-    assert len({tuple(np.all(_bits(inner) == _bits(c), axis=-1).reshape(-1)) for c in cands}) == 4  # ... all four of them
+    assert np.all(np.any([np.all(sp.bits(inner) == sp.bits(c), axis=-1) for c in cands], axis=0))
+    assert len({tuple(np.all(sp.bits(inner) == sp.bits(c), axis=-1).reshape(-1)) for c in cands}) == 4  # ... all four of them
     a.close()
     b.close()
 
@@ -311,7 +283,7 @@ def test_errors_and_state(scenes, host_api, monkeypatch):
     r.render_aovs(0.001)
     before = r.accumulator()
     r.set_pixel_filter(host_api.RT_FILTER_BOX)
-    assert _same(r.accumulator(), before)
+    assert sp.same(r.accumulator(), before)
     r.denoise(2)
     assert np.isfinite(r.denoised()[..., :3]).any()
     # a fisheye camera: POINT renders, BOX / TENT do not
@@ -340,7 +312,7 @@ def test_errors_and_state(scenes, host_api, monkeypatch):
     O1, D1 = np.float32([[0, 1, -2]] * 4), np.float32([[0, 0, 1], [0.1, 0, 1], [0, -0.3, 1], [0.3, 0.2, 1]])
     ref = r.trace_batch(PATH, O1, D1)
     r.set_pixel_filter(host_api.RT_FILTER_TENT)
-    assert _same(r.trace_batch(PATH, O1, D1), ref)
+    assert sp.same(r.trace_batch(PATH, O1, D1), ref)
     r.close()
 
 
@@ -356,10 +328,10 @@ def test_tick_clears_on_a_change_of_filter(scenes, host_api, monkeypatch):
     hand.set_pixel_filter(host_api.RT_FILTER_BOX)
     hand.clear()
     hand.render(PATH, 3, 1, SEED)
-    assert _same(t.tick_accumulator(), hand.accumulator())
+    assert sp.same(t.tick_accumulator(), hand.accumulator())
     t.tick()  # ... and frame 4 on top
     hand.render(PATH, 4, 1, SEED)
-    assert _same(t.tick_accumulator(), hand.accumulator())
+    assert sp.same(t.tick_accumulator(), hand.accumulator())
     t.close()
     hand.close()
 

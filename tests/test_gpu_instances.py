@@ -8,33 +8,19 @@ import numpy as np
 import pytest
 
 import instances_ref as ir
+import support as sp
 from conftest import random_rays
 from test_layout_cpu import RtSceneDesc
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-KNOBS = ("RT_TLAS_LDS", "RT_WIDE", "RT_WIDE8")
 ARRAYS = ("pairs", "reach", "inst", "scalars")
 N_SPLIT = ir.smallest_n_without_lds()  # 38: the first n whose TLAS copy leaves fewer than RT_STACK_ROWS_MIN rows
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(a, b):
-    a, b = _bits(a), _bits(b)
-    return a.shape == b.shape and np.array_equal(a, b)
-
-
 def _env(monkeypatch, env=None):
-    """the knobs are read once per context (rt_create): set them before the renderer exists"""
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
-    env = env or {}
-    return (int(env.get("RT_WIDE", -1)), int(env.get("RT_WIDE8", 0)), int(env.get("RT_TLAS_LDS", 1)))  # rt_layout_build's knobs
+    sp.clean_env(monkeypatch, env)
+    return sp.layout_knobs(env)
 
 
 def _build(scenes, scene, name, n=0):
@@ -50,18 +36,6 @@ def _renderer(host_api, scenes, name, n=0, w=16, h=8):
     _build(scenes, r.scene, name, n)
     r.commit()
     return r
-
-
-def _records(host_api, blas, Ts):
-    """rt_instance records: the transforms with the host mirror's inverse (mat4::Inverted, as SetTransform takes it)"""
-    L = host_api.host_lib()
-    rec = np.zeros(len(Ts), dtype=host_api.RT_INSTANCE_DTYPE)
-    for k, T in enumerate(Ts):
-        T = np.ascontiguousarray(T, dtype=f32).reshape(16)
-        inv = np.zeros(16, dtype=f32)
-        L.rth_mat4_inverse(T.ctypes.data_as(C.c_void_p), inv.ctypes.data_as(C.c_void_p))
-        rec[k] = (blas[k], T, inv)
-    return rec
 
 
 class Mirror:
@@ -84,7 +58,7 @@ class Mirror:
 
     def move(self, first, Ts, given=None):
         """the records of a move of instances first.. to Ts and the boxes they get: 'given' (what is sent as bounds6), or a fresh instance's"""
-        rec = _records(self.ha, [int(self.rec["blas"][first + k]) for k in range(len(Ts))], Ts)
+        rec = ir.records(self.ha, [int(self.rec["blas"][first + k]) for k in range(len(Ts))], Ts)
         self.rec[first:first + len(Ts)] = rec
         for k, T in enumerate(Ts):
             self.bounds[first + k] = given[k] if given is not None else ir.fresh_bounds(self.local[first + k], T)
@@ -107,7 +81,7 @@ def _check_layout(host_api, r, m, knobs, what):
     assert np.array_equal(nodes, ir.tlas_build(m.bounds)), "%s: rt_download_tlas differs from tlas::build on the same boxes" % what
     L = host_api.layout(m.desc(nodes), *knobs)
     for a in ARRAYS:
-        assert _same(r.scene_array(a), L[a]), "%s: %s differs from rt_layout_build of the updated description" % (what, a)
+        assert sp.same(r.scene_array(a), L[a]), "%s: %s differs from rt_layout_build of the updated description" % (what, a)
     return L
 
 
@@ -126,7 +100,7 @@ def test_layout_equals_a_fresh_layout(name, n, env, scenes, host_api, monkeypatc
     n = m.n
     L0 = host_api.layout(m.ptr, *knobs)
     for a in ARRAYS:  # before any move: what upload left
-        assert _same(r.scene_array(a), L0[a]), a
+        assert sp.same(r.scene_array(a), L0[a]), a
     assert np.array_equal(r.download_tlas(), r.scene.tlas_dump())
     s = r.scene
     new = lambda i, k: s.trs((f32(-2.0 + 0.37 * i + 0.1 * k), f32(0.1 * k), f32(3.0 + 0.11 * i)), f32(1.0 + 0.25 * k), 0.0, f32(0.3 * i + k), f32(0.05 * k))
@@ -166,7 +140,7 @@ def test_hand_made_tlas_is_replaced(scenes, host_api, monkeypatch):
     assert L0["tlasPairs"] == 2
     r.upload_desc(chained)
     for a in ARRAYS:
-        assert _same(r.scene_array(a), L0[a]), a
+        assert sp.same(r.scene_array(a), L0[a]), a
     assert np.array_equal(r.download_tlas(), chain.view(np.uint32).reshape(-1, 8))
     O, D = random_rays(1024, 9)
     before = r.find_nearest(O, D)
@@ -175,7 +149,7 @@ def test_hand_made_tlas_is_replaced(scenes, host_api, monkeypatch):
     L = _check_layout(host_api, r, m, knobs, "chain -> tlas::build")
     assert L["tlasPairs"] == 3 and len(r.scene_array("pairs")) == len(L0["pairs"]) + 16
     after = r.find_nearest(O, D)
-    assert all(_same(before[k], after[k]) for k in before)
+    assert all(sp.same(before[k], after[k]) for k in before)
     r.close()
 
 
@@ -203,7 +177,7 @@ def test_results_equal_a_fresh_upload(name, n, env, scenes, host_api, monkeypatc
     _env(monkeypatch, env)
     a, b, m = _moved_pair(host_api, scenes, name, n)
     for x in ARRAYS:
-        assert _same(a.scene_array(x), b.scene_array(x)), x
+        assert sp.same(a.scene_array(x), b.scene_array(x)), x
     O, D = ir.aimed_rays(4096, 21, m.rec["transform"])
     tmax = np.random.default_rng(4).uniform(0.1, 12.0, len(O)).astype(f32)
     out = []
@@ -221,11 +195,11 @@ def test_results_equal_a_fresh_upload(name, n, env, scenes, host_api, monkeypatc
         r.render(host_api.RT_MODE_WHITTED, 0, 1)
         out.append((hit, occ, cq, path, cp, r.accumulator()))
     (hit, occ, cq, path, cp, wh), (hit2, occ2, cq2, path2, cp2, wh2) = out
-    assert all(_same(hit[k], hit2[k]) for k in hit) and np.array_equal(occ, occ2)
+    assert all(sp.same(hit[k], hit2[k]) for k in hit) and np.array_equal(occ, occ2)
     # (coverage of the test's own rays, whatever the library answers: at least 1 in 20 ends on instanced geometry, mesh objIdx >= 1000)
     assert (hit["obj"] >= 1000).sum() >= len(O) // 20 and len(O) // 20 <= occ.sum() < len(occ), "the rays meet the instances"
     assert cq == cq2 and cq["instance_visits"] > 0 and cq["tlas_inner"] > 0, "the executed walk (reach culling included) is the fresh upload's"
-    assert _same(path, path2) and cp == cp2 and _same(wh, wh2)
+    assert sp.same(path, path2) and cp == cp2 and sp.same(wh, wh2)
     assert np.isfinite(wh[..., :3]).any() and (path[..., :3] > 0).any()
     a.close(), b.close()
 
@@ -257,9 +231,9 @@ def test_moved_scene_equals_a_fresh_oracle_scene(kind, scenes, host_api, oracle_
     got = r.find_nearest(O, D)
     cnt = r.counters()
     r.set_counting(False)
-    assert np.array_equal(got["obj"], ref["obj"]) and _same(got["t"], ref["t"])
+    assert np.array_equal(got["obj"], ref["obj"]) and sp.same(got["t"], ref["t"])
     hit = ref["obj"] != -1
-    assert (ref["obj"] >= 1000).sum() >= len(O) // 20 and _same(got["normal"][hit], ref["normal"][hit])
+    assert (ref["obj"] >= 1000).sum() >= len(O) // 20 and sp.same(got["normal"][hit], ref["normal"][hit])
     for k in ("inner_visits", "prim_tests", "tlas_inner", "instance_visits", "rays_nearest", "brute_tests", "light_tests"):
         assert cnt[k] == ref["counters"][k], k
     refo = o.is_occluded(O, D)
@@ -283,9 +257,9 @@ def test_ten_moves_without_boxes_do_not_accumulate(scenes, host_api, monkeypatch
     turn = lambda k: [a.scene.trs((0.5, 0, 3), 4, 0.0, f32(np.deg2rad(36.0 * k)), 0.0)]
     for k in range(1, 11):
         assert a.set_instances(0, m.move(0, turn(k))) == 0
-    assert b.set_instances(0, _records(host_api, [int(m.rec["blas"][0])], turn(10))) == 0
+    assert b.set_instances(0, ir.records(host_api, [int(m.rec["blas"][0])], turn(10))) == 0
     for x in ARRAYS:
-        assert _same(a.scene_array(x), b.scene_array(x)), x
+        assert sp.same(a.scene_array(x), b.scene_array(x)), x
     assert np.array_equal(a.download_tlas(), b.download_tlas())
     _check_layout(host_api, a, m, (-1, 0, 1), "ten moves")
     a.close(), b.close()
@@ -304,12 +278,12 @@ def test_commit_instances_accumulates_like_the_host_mirror(scenes, host_api, mon
     assert np.all(m.bounds[0, :3] <= want[:3]) and np.all(m.bounds[0, 3:] >= want[3:]) and not np.array_equal(m.bounds[0], want), "the box has grown"
     dev = r.download_tlas()
     assert np.array_equal(dev, s.tlas_dump()), "CommitInstances leaves the device's tree in tl"
-    assert _same(dev[1:4, 0:3], m.bounds[:, :3]) and _same(dev[1:4, 4:7], m.bounds[:, 3:]), "the leaves are instance_dump's bounds"
+    assert sp.same(dev[1:4, 0:3], m.bounds[:, :3]) and sp.same(dev[1:4, 4:7], m.bounds[:, 3:]), "the leaves are instance_dump's bounds"
     s.rebuild_tlas()  # tlas::build on the host over the same bounds
     assert np.array_equal(dev, s.tlas_dump())
     L = host_api.layout(s.describe(), *knobs)
     for x in ARRAYS:
-        assert _same(r.scene_array(x), L[x]), x
+        assert sp.same(r.scene_array(x), L[x]), x
     r.close()
 
 
@@ -332,7 +306,7 @@ def test_a_move_invalidates_what_set_time_invalidates(scenes, host_api, monkeypa
     L = host_api.rt_lib()
     assert L.rt_denoise(a.ctx, 2, None) == host_api.RT_E_STATE
     assert L.rt_reproject(a.ctx, None, None) == host_api.RT_E_STATE
-    assert _same(a.accumulator(), acc) and all(_same(x, y) for x, y in zip(a.stats(), stats)), "accumulator and statistics are not touched"
+    assert sp.same(a.accumulator(), acc) and all(sp.same(x, y) for x, y in zip(a.stats(), stats)), "accumulator and statistics are not touched"
     lst, n_act = a.active()
     assert n_act == 3 and lst.tolist() == [3, 5, 700], "an installed list survives"
     a.render_aovs(0.001)
@@ -347,8 +321,8 @@ def test_a_move_invalidates_what_set_time_invalidates(scenes, host_api, monkeypa
         r.stats_enable(False)
         r.clear()
         r.render(host_api.RT_MODE_PATH, 0, 16)
-    assert _same(a.accumulator(), b.accumulator())
-    assert not _same(a.accumulator(), acc), "the move is visible"
+    assert sp.same(a.accumulator(), b.accumulator())
+    assert not sp.same(a.accumulator(), acc), "the move is visible"
     a.close(), b.close()
 
 
@@ -398,10 +372,10 @@ def test_refusals_leave_the_scene_as_it_was(scenes, host_api, monkeypatch):
     assert L.rt_set_instances(r.ctx, 0, 3, p(rec), p(wide)) == UNSUP
     assert b"no finite union area" in L.rt_last_error(r.ctx)
     for a in ARRAYS:
-        assert _same(r.scene_array(a), before[a]), a
+        assert sp.same(r.scene_array(a), before[a]), a
     assert np.array_equal(r.download_tlas(), tl)
     after = r.find_nearest(O, D)
-    assert all(_same(hits[k], after[k]) for k in hits)
+    assert all(sp.same(hits[k], after[k]) for k in hits)
     assert L.rt_denoise(r.ctx, 1, None) == 0, "a refused call invalidates nothing: the G-buffer is still current"
     # rt_scene_array's own refusals
     nbytes = C.c_size_t(0)
@@ -419,11 +393,11 @@ def test_refusals_leave_the_scene_as_it_was(scenes, host_api, monkeypatch):
     scenes.mixed_small(g.scene)
     g.commit()
     before = {a: g.scene_array(a) for a in ARRAYS}
-    assert len(before["reach"]) == 0 and len(before["inst"]) == 0 and _same(before["pairs"], host_api.layout(g.scene.describe())["pairs"])
+    assert len(before["reach"]) == 0 and len(before["inst"]) == 0 and sp.same(before["pairs"], host_api.layout(g.scene.describe())["pairs"])
     assert L.rt_set_instances(g.ctx, 0, 1, p(rec), None) == UNSUP
     assert L.rt_download_tlas(g.ctx, p(np.zeros((7, 8), np.uint32)), C.byref(used)) == UNSUP
     for a in ARRAYS:
-        assert _same(g.scene_array(a), before[a]), a
+        assert sp.same(g.scene_array(a), before[a]), a
     with pytest.raises(RuntimeError, match="no TLAS"):
         g.scene.commit_instances()
     g.close()
@@ -459,22 +433,14 @@ def test_commit_instances_reaches_every_context(scenes, host_api, monkeypatch):
             ctx = r.ctx_at(k)
             assert ctx.value and (k == 0) == (ctx.value == r.ctx.value)
             for a in ARRAYS:
-                assert _same(r.scene_array(a, ctx), L[a]), (k, a)
+                assert sp.same(r.scene_array(a, ctx), L[a]), (k, a)
         r.tick()  # a Whitted Tick; with two contexts the rows are interleaved over them
         frames.append(r.tick_accumulator().copy())
         r.close()
-    assert _same(frames[0], frames[1]) and (frames[0][..., :3] > 0).any()
+    assert sp.same(frames[0], frames[1]) and (frames[0][..., :3] > 0).any()
 
 
 # ---- the example's --spin ---------------------------------------------------------------------------------------------------------------
-def _mat_mul(A, B):
-    """rapt::operator*(mat4, mat4): ((a0 b0 + a1 b4) + a2 b8) + a3 b12 per entry, every operation rounded to f32"""
-    A, B = np.asarray(A, dtype=f32).reshape(4, 4), np.asarray(B, dtype=f32).reshape(4, 4)
-    s = A[:, 0:1] * B[0:1, :] + A[:, 1:2] * B[1:2, :]
-    s = s + A[:, 2:3] * B[2:3, :]
-    return (s + A[:, 3:4] * B[3:4, :]).astype(f32).reshape(16)
-
-
 def test_example_spin(tmp_path, scenes, host_api, monkeypatch):
     """examples/render_scene.cpp --spin DEG: instance 0 turned about y with SetTransform + Scene::CommitInstances before the last Tick.  The
     Whitted image is the one a renderer shows whose scene was moved the same way; the path run ends on the moved scene too."""
@@ -502,7 +468,7 @@ def test_example_spin(tmp_path, scenes, host_api, monkeypatch):
     r.commit()
     s = r.scene
     ang = f32(f32(f32(40.0) * f32(3.14159265358979)) / f32(180.0))
-    s.set_transforms(0, [_mat_mul(s.instance_dump(0)["T"], s.trs((0, 0, 0), 1, 0.0, ang, 0.0))])
+    s.set_transforms(0, [ir.mat_mul(s.instance_dump(0)["T"], s.trs((0, 0, 0), 1, 0.0, ang, 0.0))])
     s.commit_instances()
     r.tick()
     px = r.tick_pixels()

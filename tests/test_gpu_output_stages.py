@@ -14,15 +14,12 @@ from conftest import rel_err
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import denoise_ref as dr  # noqa: E402
 import resolve_ref as rr  # noqa: E402
+import support as sp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 RADIANCE_TOL = 1e-4
 INF = float("inf")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 class Bound:
@@ -85,7 +82,7 @@ def _render(r, host_api, how):
 
 @pytest.mark.parametrize("how,stream", [("path", "1"), ("path", "0"), ("whitted", "1"), ("rows", "1")])
 def test_bound_render_equals_owned(how, stream, scenes, host_api, monkeypatch):
-    monkeypatch.setenv("RT_STREAM", stream)
+    sp.clean_env(monkeypatch, {"RT_STREAM": stream})
     a, _ = make(scenes, host_api, "mixed_small", 64, 40)
     b, _ = make(scenes, host_api, "mixed_small", 64, 40)
     t = Bound(b)
@@ -93,8 +90,8 @@ def test_bound_render_equals_owned(how, stream, scenes, host_api, monkeypatch):
     _render(b, host_api, how)
     ref = a.accumulator()
     assert np.any(ref[..., :3] != 0)
-    assert np.array_equal(bits(b.accumulator()), bits(ref))
-    assert np.array_equal(bits(t.read()), bits(ref))  # the rendering is in the tensor itself
+    assert sp.same(b.accumulator(), ref)
+    assert sp.same(t.read(), ref)  # the rendering is in the tensor itself
     a.close(), b.close()
 
 
@@ -108,19 +105,19 @@ def test_bind_after_render_and_rebind(scenes, host_api):
     assert np.all(t1.read() == 0) and np.all(r.accumulator() == 0)
     r.render(host_api.RT_MODE_PATH, 0, 2)
     first = t1.read()
-    assert np.array_equal(bits(first), bits(owned))
+    assert sp.same(first, owned)
     t2 = Bound(r)
     r.render(host_api.RT_MODE_PATH, 0, 2)
-    assert np.array_equal(bits(t2.read()), bits(owned))
+    assert sp.same(t2.read(), owned)
     r.render(host_api.RT_MODE_PATH, 2, 2)
     r.clear()
     r.render(host_api.RT_MODE_PATH, 4, 1)
-    assert np.array_equal(bits(t1.read()), bits(first))
+    assert sp.same(t1.read(), first)
     last = t2.read()
-    assert not np.array_equal(bits(last), bits(first))
+    assert not sp.same(last, first)
     r.close()
     t2.torch.cuda.synchronize()
-    assert np.array_equal(bits(t2.t.cpu().numpy()), bits(last)) and np.array_equal(bits(t1.t.cpu().numpy()), bits(first))
+    assert sp.same(t2.t.cpu().numpy(), last) and sp.same(t1.t.cpu().numpy(), first)
 
 
 def test_clear_zeroes_bound_memory(scenes, host_api):
@@ -128,7 +125,7 @@ def test_clear_zeroes_bound_memory(scenes, host_api):
     t = Bound(r)
     t.fill(rr.pixels(rr.crafted_values(), 33 * 9))
     r.clear()
-    assert np.all(bits(t.read()) == 0)
+    assert np.all(sp.bits(t.read()) == 0)
     r.close()
 
 
@@ -139,13 +136,13 @@ def test_reads_never_write_bound_memory(scenes, host_api):
     t = Bound(r)
     px = rr.pixels(rr.crafted_values(), w * h).reshape(h, w, 4)
     t.fill(px)
-    assert np.array_equal(bits(r.accumulator()), bits(px))
+    assert sp.same(r.accumulator(), px)
     assert np.array_equal(r.resolve(3), rr.resolve(px, 3))
     r.render_aovs(0.001)
     r.denoise(3)
     r.resolve_denoised()
     r.denoise(1, dict(iterations=8, sigma_color=INF))
-    assert np.array_equal(bits(t.read()), bits(px))
+    assert sp.same(t.read(), px)
     r.close()
 
 
@@ -187,7 +184,7 @@ def test_resolve_equals_the_restatement(w, h, host_api):
                 assert bad.size == 0, "it %d rows [%d, %d): %d pixels differ, first at %s" % (it, y0, y1, len(bad), bad[0])
     out = np.zeros((h, w), np.uint32)
     assert host_api.rt_lib().rt_resolve(r.ctx, 0, 0, h, host_api._p(out)) == host_api.RT_E_ARG
-    assert np.array_equal(bits(t.read()), bits(px))
+    assert sp.same(t.read(), px)
     r.close()
 
 
@@ -230,7 +227,7 @@ def test_every_row_range_is_checked_alike(scenes, host_api):
         for a in outs:  # one row arrived, at the start of the output, and nothing after it
             row = a.view(np.uint8).reshape(h + 1, -1)
             assert np.any(row[0] != 0xA5) and np.all(row[1:] == 0xA5), name + ": the last row's output"
-    assert np.array_equal(bits(entries[0][2][0][0]), bits(r.accumulator(h - 1, h)[0]))
+    assert sp.same(entries[0][2][0][0], r.accumulator(h - 1, h)[0])
     r.close()
 
 
@@ -290,19 +287,19 @@ def _check_denoise(r, t, g, pos, mean, it, params, label, resolve_rows=False):
     r.denoise(it, params)
     again = r.denoised()
     ref = dr.denoise(acc, it, g, pos, params)
-    assert np.array_equal(bits(got), bits(again)), label + ": a second run differs"
-    assert np.all(bits(got[..., 3]) == 0), label + ": w channel"
+    assert sp.same(got, again), label + ": a second run differs"
+    assert np.all(sp.bits(got[..., 3]) == 0), label + ": w channel"
     err, cls_ok = rel_err(got[..., :3], ref)
     assert cls_ok, label + ": non-finite pixels differ from the restatement"
     assert err.max() <= RADIANCE_TOL, "%s: denoised error %g" % (label, err.max())
     fin = np.all(np.isfinite(dr.mean_color(acc, it)), -1)
     assert np.all(np.isfinite(got[..., :3][fin])), label + ": %d finite pixels came out non-finite" % (~np.isfinite(got[..., :3][fin])).any(-1).sum()
-    assert np.array_equal(bits(t.read()), bits(acc)), label + ": the accumulator was written"
+    assert sp.same(t.read(), acc), label + ": the accumulator was written"
     if resolve_rows:
         h = got.shape[0]
         for y0, y1 in _row_ranges(h):
             assert np.array_equal(r.resolve_denoised(y0, y1), rr.resolve(got[y0:y1], 1)), label + ": rt_resolve_denoised rows %d..%d" % (y0, y1)
-            assert np.array_equal(bits(r.denoised(y0, y1)), bits(got[y0:y1]))
+            assert sp.same(r.denoised(y0, y1), got[y0:y1])
 
 
 @pytest.mark.parametrize("name", DENOISE_SCENES)

@@ -11,6 +11,7 @@ import pytest
 
 from build_cases import same_tree as _same_tree, tlas_reference
 from conftest import random_rays, rel_err
+from support import clean_env
 
 pytestmark = pytest.mark.gpu
 
@@ -388,10 +389,7 @@ def test_exact_gamma_switch(name, kw, w, h, frames, scenes, oracle_api, host_api
     own last-ulp differences, which the gamma passes on), never below the fast form's, and the two forms agree to a few ulp."""
     out = {}
     for key, env in (("exact_stream", {"RT_EXACT_GAMMA": "1", "RT_STREAM": "1"}), ("exact_slot", {"RT_EXACT_GAMMA": "1", "RT_STREAM": "0"}), ("fast", {})):
-        for k in ("RT_EXACT_GAMMA", "RT_STREAM"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+        clean_env(monkeypatch, env)
         o, orr, r, d = make_pair(scenes.REGISTRY[name], oracle_api, host_api, w, h, **kw)
         assert ("exact_gamma=%d" % (1 if "RT_EXACT_GAMMA" in env else 0)) in r.build_info()
         err, same = check_frames(orr, r, "path", frames, host_api)
@@ -808,7 +806,7 @@ def test_full_size_config5_with_the_sampler_on(scenes, oracle_api, host_api):
     r.close()
 
 
-def test_gamma_of_finished_samples(host_api):
+def test_gamma_of_finished_samples(host_api, monkeypatch):
     """The gamma of a finished path-mode sample (renderer.cpp:279-282: pow(c, 1 / 2.2) per channel, a double-precision pow rounded
     to float in the reference) is evaluated in SINGLE precision since round 4 (csrc/rt_kernels.h gamma_powf): an
     output transform that feeds no ray, no texel index and no random draw.  Its error against the rounded double-precision value
@@ -818,30 +816,27 @@ def test_gamma_of_finished_samples(host_api):
     g32 = np.float32(0.57142857142857142857143)
     frames = {}
     for lut in ("1", "0"):
-        os.environ["RT_GAMMA_LUT"] = lut
-        try:
-            r = host_api.HostRenderer(8, 8)
-            s = r.scene
-            m = s.diffuse(0.8, (1, 1, 1))
-            s.sphere(0, m, (0, -10, 0), 1.0)  # below the camera, which looks straight up: every camera ray leaves the scene
-            s.area_light(11, (0, -20, 0), 1.0, (1, 1, 1), 0.5, (0, -1, 0))
-            got = []
-            for b0 in range(0, 256, 3):
-                tex = np.zeros((2, 4, 3), np.uint8)
-                tex[...] = [b0, min(b0 + 1, 255), min(b0 + 2, 255)]
-                s.sky(tex)
-                s.build(0)
-                r.commit()
-                r.set_camera((0, 0, 0), (-0.5, 2, 0.5), (0.5, 2, 0.5), (-0.5, 2, -0.5))
-                r.clear()
-                r.render(host_api.RT_MODE_PATH, 0, 1)
-                a = r.accumulator()[..., :3]
-                assert np.array_equal(a.view(np.uint32), np.broadcast_to(a[0, 0], a.shape).view(np.uint32))  # every pixel is the sky's colour
-                got.append(a[0, 0].copy())
-            frames[lut] = np.concatenate(got)[:256]
-            r.close()
-        finally:
-            del os.environ["RT_GAMMA_LUT"]
+        clean_env(monkeypatch, {"RT_GAMMA_LUT": lut})
+        r = host_api.HostRenderer(8, 8)
+        s = r.scene
+        m = s.diffuse(0.8, (1, 1, 1))
+        s.sphere(0, m, (0, -10, 0), 1.0)  # below the camera, which looks straight up: every camera ray leaves the scene
+        s.area_light(11, (0, -20, 0), 1.0, (1, 1, 1), 0.5, (0, -1, 0))
+        got = []
+        for b0 in range(0, 256, 3):
+            tex = np.zeros((2, 4, 3), np.uint8)
+            tex[...] = [b0, min(b0 + 1, 255), min(b0 + 2, 255)]
+            s.sky(tex)
+            s.build(0)
+            r.commit()
+            r.set_camera((0, 0, 0), (-0.5, 2, 0.5), (0.5, 2, 0.5), (-0.5, 2, -0.5))
+            r.clear()
+            r.render(host_api.RT_MODE_PATH, 0, 1)
+            a = r.accumulator()[..., :3]
+            assert np.array_equal(a.view(np.uint32), np.broadcast_to(a[0, 0], a.shape).view(np.uint32))  # every pixel is the sky's colour
+            got.append(a[0, 0].copy())
+        frames[lut] = np.concatenate(got)[:256]
+        r.close()
     assert np.array_equal(frames["0"].view(np.uint32), frames["1"].view(np.uint32))  # table and k_accumulate: one function
     c = (np.arange(256, dtype=np.float32) / np.float32(255)).astype(np.float32)
     ref = np.power(c.astype(np.float64), np.float64(g32)).astype(np.float32)
@@ -1312,9 +1307,8 @@ def test_fewer_slots_than_samples(slots, name, kw, scenes, oracle_api, host_api,
     r.clear()
     r.render(host_api.RT_MODE_PATH, 0, 12)
     full = r.accumulator()
-    monkeypatch.setenv("RT_SLOTS", slots)  # (read when a context is created: csrc/rt_ctx.h Knobs)
+    clean_env(monkeypatch, {"RT_SLOTS": slots})
     o2, orr2, r2, d2 = make_pair(scenes.REGISTRY[name], oracle_api, host_api, 96, 54, **kw)
-    monkeypatch.delenv("RT_SLOTS")
     err, _ = check_frames(orr2, r2, "path", 12, host_api)
     assert np.array_equal(r2.accumulator().view(np.uint32), full.view(np.uint32))
     # Whitted: pending branches + pool
@@ -1339,10 +1333,7 @@ def test_stream_pipeline_equals_slot_pipeline(name, kw, w, h, frames, scenes, or
     pO = pD = None
     for key, env in (("slot", {"RT_STREAM": "0"}), ("stream", {}), ("stream_serial", {"RT_FUSE": "0"}), ("stream_two_streams", {"RT_FUSE": "2"}), ("stream_one_launch_per_round", {"RT_FUSE": "1"}), ("stream_nodecide", {"RT_DECIDE": "0"}),
                      ("stream_gamma_at_the_store", {"RT_DEFER_GAMMA": "0"})):
-        for k in ("RT_STREAM", "RT_FUSE", "RT_DECIDE", "RT_DEFER_GAMMA"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+        clean_env(monkeypatch, env)
         o, orr, r, d = make_pair(scenes.REGISTRY[name], oracle_api, host_api, w, h, **kw)
         r.set_counting(host_api.RT_COUNT_EXECUTED); r.counters()
         r.clear()
@@ -1426,9 +1417,7 @@ def test_glass_absorption_with_zero_components(scenes, oracle_api, host_api, mon
     for mode, frames, var, values in (("whitted", 1, "RT_MEGA", ("0", "1", None)), ("path", 3, "RT_STREAM", ("0", None))):
         out = []
         for v in values:
-            monkeypatch.delenv(var, raising=False)
-            if v is not None:
-                monkeypatch.setenv(var, v)
+            clean_env(monkeypatch, {} if v is None else {var: v})
             o, orr, r, d = make_pair(scenes.mixed_small, oracle_api, host_api, w, h, absorption=absorption)
             if v is None:
                 check_frames(orr, r, mode, frames, host_api)  # the default pipeline against the oracle
@@ -1468,10 +1457,7 @@ def test_whitted_longest_first_order(name, kw, w, h, scenes, oracle_api, host_ap
     frames = {}
     for key, env in (("rounds", {"RT_MEGA": "0"}), ("plain", {"RT_MEGA_LEVELS": "0", "RT_MEGA_LPT": "0"}), ("lpt", {"RT_MEGA_LEVELS": "0"}),
                      ("levels", {"RT_MEGA_LEVELS": "1"}), ("auto", {})):
-        for k in ("RT_MEGA", "RT_MEGA_LPT", "RT_MEGA_LEVELS"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+        clean_env(monkeypatch, env)
         r = host_api.HostRenderer(w, h)
         d = scenes.REGISTRY[name](r.scene, **kw)
         r.commit()
@@ -1509,10 +1495,7 @@ def test_whitted_levels_depths_and_batches(name, kw, w, h, scenes, host_api, mon
     shards: identical accumulator bits."""
     out = {}
     for key, env in (("rounds", {"RT_MEGA": "0"}), ("levels", {"RT_MEGA_LEVELS": "1"}), ("levels_overflow", {"RT_MEGA_LEVELS": "1", "RT_LEVEL_CAP": "256"})):
-        for k in ("RT_MEGA", "RT_MEGA_LEVELS", "RT_LEVEL_CAP"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+        clean_env(monkeypatch, env)
         r = host_api.HostRenderer(w, h)
         d = scenes.REGISTRY[name](r.scene, **kw)
         r.commit()

@@ -15,7 +15,8 @@ import re
 import numpy as np
 import pytest
 
-KNOBS = ("RT_PRIMARY_TABLE", "RT_PRIMARY_TABLE_MIN", "RT_FUSE", "RT_DECIDE", "RT_DEFER_GAMMA", "RT_GAMMA_LUT", "RT_EXACT_GAMMA", "RT_STREAM", "RT_MIXED_MAX")
+import support as sp
+
 ON = {"RT_PRIMARY_TABLE": "1", "RT_PRIMARY_TABLE_MIN": "0"}  # MIN=0: the first batch builds the table, whatever its size
 OFF = {"RT_PRIMARY_TABLE": "0"}
 gpu = pytest.mark.gpu
@@ -58,20 +59,9 @@ def test_jitter_range():
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
-def _set_env(monkeypatch, env):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-
-
 def _builds(r):
     """table builds of this renderer so far: the launches of the profile's query slot (profiling on; these tests run no other query)"""
     return r.profile(reset=False)["query"]["launches"]
-
-
-def _same(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 FISHEYE = dict(fisheye=True, view_angle=0.4, y_angle=0.3)
@@ -98,7 +88,7 @@ def _renderer(host_api, scenes, name, kw, w, h, cam):
 
 
 def _frame(host_api, scenes, monkeypatch, env, name, kw, w, h, cam, frames):
-    _set_env(monkeypatch, env)
+    sp.clean_env(monkeypatch, env)
     r = _renderer(host_api, scenes, name, kw, w, h, cam)
     r.clear()
     r.render(host_api.RT_MODE_PATH, 0, frames)
@@ -122,7 +112,7 @@ def test_table_frames_equal_traced_frames(name, kw, w, h, cam, scenes, host_api,
         got, b1 = _frame(host_api, scenes, monkeypatch, dict(env, **ON), name, kw, w, h, cam, frames)
         assert b0 == 0 and b1 == 1, (env, b0, b1)
         assert np.isfinite(ref[..., :3]).mean() > 0.5
-        assert _same(ref, got), env
+        assert sp.same(ref, got), env
 
 
 @gpu
@@ -130,14 +120,14 @@ def test_table_frames_equal_traced_frames(name, kw, w, h, cam, scenes, host_api,
 def test_one_frame_and_many(frames, scenes, host_api, monkeypatch):
     ref, _ = _frame(host_api, scenes, monkeypatch, OFF, "mixed_small", {}, 96, 64, None, frames)
     got, b = _frame(host_api, scenes, monkeypatch, ON, "mixed_small", {}, 96, 64, None, frames)
-    assert b == 1 and _same(ref, got)
+    assert b == 1 and sp.same(ref, got)
 
 
 @gpu
 def test_oracle_frame(scenes, oracle_api, host_api, monkeypatch):
     """the oracle's frame within the project's tolerance, and its primary rays' Sample() untouched by a current table"""
     from test_gpu_parity import check_frames, make_pair
-    _set_env(monkeypatch, ON)
+    sp.clean_env(monkeypatch, ON)
     o, orr, r, d = make_pair(scenes.mixed_small, oracle_api, host_api, 96, 64)
     r.set_profiling(True)
     check_frames(orr, r, "path", 3, host_api)
@@ -152,7 +142,7 @@ def test_trace_batch_keeps_its_rays(scenes, oracle_api, host_api, monkeypatch):
     from test_gpu_parity import make_pair
     out = {}
     for key, env in (("off", OFF), ("on", ON)):
-        _set_env(monkeypatch, env)
+        sp.clean_env(monkeypatch, env)
         o, orr, r, d = make_pair(scenes.mixed_small, oracle_api, host_api, 64, 40)
         r.set_profiling(True)
         r.clear()
@@ -162,7 +152,7 @@ def test_trace_batch_keeps_its_rays(scenes, oracle_api, host_api, monkeypatch):
         assert _builds(r) == (1 if key == "on" else 0)
         r.close()
     for a, b in zip(out["off"], out["on"]):
-        assert _same(a, b)
+        assert sp.same(a, b)
 
 
 @gpu
@@ -170,28 +160,28 @@ def test_row_shards(scenes, host_api, monkeypatch):
     """two interleaved row shards against the whole frame: one table (always of the whole frame) serves both"""
     w, h, frames = 96, 63, 4
     ref, _ = _frame(host_api, scenes, monkeypatch, OFF, "mixed_small", {}, w, h, None, frames)
-    _set_env(monkeypatch, ON)
+    sp.clean_env(monkeypatch, ON)
     r = _renderer(host_api, scenes, "mixed_small", {}, w, h, None)
     r.clear()
     r.render_rows(host_api.RT_MODE_PATH, 0, frames, 0, 2, (h + 1) // 2)
     r.render_rows(host_api.RT_MODE_PATH, 0, frames, 1, 2, h // 2)
-    assert _same(ref, r.accumulator()) and _builds(r) == 1
+    assert sp.same(ref, r.accumulator()) and _builds(r) == 1
     r.clear()
     r.render(host_api.RT_MODE_PATH, 0, frames)
-    assert _same(ref, r.accumulator()) and _builds(r) == 1
+    assert sp.same(ref, r.accumulator()) and _builds(r) == 1
     r.close()
 
 
 @gpu
 def test_with_sampler(host_api, monkeypatch):
     """the Q-learning sampler's round 0 is the same round 0: frame, table and pending reward sums"""
-    from test_gpu_shadow_records import _lit_scene
+    from lit_scene import lit_scene
     w, h, frames = 64, 40, 3
     out = {}
     for key, env in (("off", OFF), ("on", ON)):
-        _set_env(monkeypatch, env)
+        sp.clean_env(monkeypatch, env)
         r = host_api.HostRenderer(w, h)
-        _lit_scene(r.scene, "AD")
+        lit_scene(r.scene, "AD")
         r.commit()
         r.set_profiling(True)
         r.qlearn_enable(8, (-4, -1, -4), (4, 5, 6), 0.3, 0.2, 1.0, 0)
@@ -204,7 +194,7 @@ def test_with_sampler(host_api, monkeypatch):
         assert _builds(r) == (1 if key == "on" else 0)
         r.close()
     a, b = out["off"], out["on"]
-    assert _same(a[0], b[0]) and _same(a[1], b[1])
+    assert sp.same(a[0], b[0]) and sp.same(a[1], b[1])
     for k in (2, 3):
         assert np.array_equal(a[k][0], b[k][0]) and np.array_equal(a[k][1], b[k][1])
     assert a[2][1].sum() > 0  # rewards were paid
@@ -218,7 +208,7 @@ def test_staleness(scenes, host_api, monkeypatch):
     cam2 = None
 
     def fresh(steps):
-        _set_env(monkeypatch, OFF)
+        sp.clean_env(monkeypatch, OFF)
         f = _renderer(host_api, scenes, "mixed_small", {}, w, h, None)
         for s in steps:
             s(f)
@@ -243,7 +233,7 @@ def test_staleness(scenes, host_api, monkeypatch):
     def animate(x):
         x.scene.set_time(1.3)
 
-    _set_env(monkeypatch, ON)
+    sp.clean_env(monkeypatch, ON)
     r = _renderer(host_api, scenes, "mixed_small", {}, w, h, None)
     again(r)  # (the record as set_camera's defaults write it)
     steps, frames_seen = [], []
@@ -257,13 +247,13 @@ def test_staleness(scenes, host_api, monkeypatch):
         assert _builds(r) == builds, (len(steps), _builds(r), builds)
         r.clear()
         r.render(host_api.RT_MODE_PATH, 0, frames)  # ... and once more from the table as it stands
-        assert _same(got, r.accumulator()) and _builds(r) == builds
+        assert sp.same(got, r.accumulator()) and _builds(r) == builds
         frames_seen.append(got)
-        _set_env(monkeypatch, OFF)
+        sp.clean_env(monkeypatch, OFF)
         ref = fresh(list(steps))
-        _set_env(monkeypatch, ON)
-        assert _same(ref, got), len(steps)
-    assert not _same(frames_seen[0], frames_seen[2]) and not _same(frames_seen[4], frames_seen[5])  # the camera and the geometry really moved
+        sp.clean_env(monkeypatch, ON)
+        assert sp.same(ref, got), len(steps)
+    assert not sp.same(frames_seen[0], frames_seen[2]) and not sp.same(frames_seen[4], frames_seen[5])  # the camera and the geometry really moved
     r.close()
 
 
@@ -275,7 +265,7 @@ def test_counting(name, kw, w, h, scenes, host_api, monkeypatch):
     frames = 8
     cnt = {}
     for key, env in (("off", OFF), ("on", ON), ("on_current", ON)):
-        _set_env(monkeypatch, env)
+        sp.clean_env(monkeypatch, env)
         r = _renderer(host_api, scenes, name, kw, w, h, None)
         if key == "on_current":
             r.render(host_api.RT_MODE_PATH, 0, 1)
@@ -287,7 +277,7 @@ def test_counting(name, kw, w, h, scenes, host_api, monkeypatch):
         counted = r.accumulator().copy()
         r.clear()
         r.render(host_api.RT_MODE_PATH, 0, frames)
-        assert _same(counted, r.accumulator())  # counting launches render the same frame
+        assert sp.same(counted, r.accumulator())  # counting launches render the same frame
         cnt[key] = (near, occl, counted)
         r.close()
     for key in ("on", "on_current"):
@@ -295,7 +285,7 @@ def test_counting(name, kw, w, h, scenes, host_api, monkeypatch):
             assert cnt[key][0][k] == cnt["off"][0][k], (key, k, cnt[key][0][k], cnt["off"][0][k])
         assert cnt[key][1]["rays_occluded"] == cnt["off"][1]["rays_occluded"], key
         assert cnt[key][0]["inner_visits"] < cnt["off"][0]["inner_visits"], key
-        assert _same(cnt[key][2], cnt["off"][2])
+        assert sp.same(cnt[key][2], cnt["off"][2])
     assert cnt["on_current"][0]["inner_visits"] <= cnt["on"][0]["inner_visits"]
     assert cnt["off"][0]["rays_nearest"] >= frames * w * h
 
@@ -307,7 +297,7 @@ def test_default_rebuild_rule(scenes, host_api, monkeypatch):
     w, h = 64, 40
     out = {}
     for key, env in (("off", OFF), ("default", {})):
-        _set_env(monkeypatch, env)
+        sp.clean_env(monkeypatch, env)
         r = _renderer(host_api, scenes, "mixed_small", {}, w, h, None)
         need = int(re.search(r"primary_table_min=(\d+)", r.build_info()).group(1))
         assert need >= 2
@@ -331,4 +321,4 @@ def test_default_rebuild_rule(scenes, host_api, monkeypatch):
         out[key] = got
         r.close()
     for a, b in zip(out["off"], out["default"]):
-        assert _same(a, b)
+        assert sp.same(a, b)

@@ -12,96 +12,25 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import adaptive_ref as ar  # noqa: E402
 import reproject_ref as rr  # noqa: E402
+import support as sp  # noqa: E402
 from test_reproject_cpu import QUALITY, mse_ratio  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
-KNOBS = ("RT_PRIMARY_TABLE", "RT_PRIMARY_TABLE_MIN", "RT_FUSE", "RT_STREAM", "RT_MIXED_MAX", "RT_DECIDE", "RT_DEFER_GAMMA", "RT_EXACT_GAMMA")
-ADAPTIVE = dict(min_samples=4, max_samples=64, threshold=0.05, floor=1e-3)
-MOVES = dict(none=(0.0, 0.0, 0.0), small=(0.05, 0.0, 0.0), large=(0.2, 0.05, 0.1), behind=(0.0, 0.0, -20.0))  # behind: the new camera sees ground that lies behind the old one
-PARAMS = dict(defaults={}, view_dependent=dict(carry_view_dependent=1), capped=dict(max_history=8), exact=dict(normal_tolerance=0.0, plane_tolerance=0.0))
+ADAPTIVE, MOVES, PARAMS = rr.ADAPTIVE, rr.MOVES, rr.PARAMS
 # 1 x 1: the frame's one ray is the top left corner's; this camera points it at the floor beside the meshes
 ONE_PIXEL_CAMERA = np.array([(0, 1, -2), (2, 0.2, 0), (3, 0.2, 0), (2, -0.8, 0)], F32)
 
 
-class _SceneDesc(C.Structure):  # include/rt_amd.h rt_scene_desc, up to the materials
-    _fields_ = [("use_tlas", C.c_int32), ("blas", C.c_void_p), ("n_blas", C.c_uint32), ("instances", C.c_void_p), ("n_instances", C.c_uint32),
-                ("tlas_nodes", C.c_void_p), ("tlas_nodes_used", C.c_uint32), ("brute_spheres", C.c_void_p), ("n_brute_spheres", C.c_uint32),
-                ("brute_planes", C.c_void_p), ("n_brute_planes", C.c_uint32), ("lights", C.c_void_p), ("n_lights", C.c_uint32),
-                ("materials", C.c_void_p), ("n_materials", C.c_uint32)]
-
-
-def _materials(r):
-    """(type, shinieness) of the materials the scene uploads (rt_material: 16 words, type at 0, shinieness at 10)"""
-    d = C.cast(r.scene.describe(), C.POINTER(_SceneDesc)).contents
-    n = int(d.n_materials)
-    words = np.ctypeslib.as_array(C.cast(d.materials, C.POINTER(C.c_uint32)), shape=(n, 16)).copy()
-    return words[:, 0].view(np.int32).copy(), words[:, 10].view(F32).copy()
-
-
 def _renderer(host_api, scenes, monkeypatch, name, w, h, camera=None):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    r = host_api.HostRenderer(w, h)
-    d = getattr(scenes, name)(r.scene)
-    r.scene.set_raytracer(False)
-    r.commit()
-    if camera is None and d and "camera" in d:
-        c = d["camera"]
-        camera = np.array([c["cam_pos"], c["top_left"], c["top_right"], c["bottom_left"]], F32)
-    if camera is not None:
-        r.set_camera(*camera)
-    return r
-
-
-def _moved(camera, move):
-    return (np.asarray(camera, F32) + np.array(move, F32)).astype(F32)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
+    return sp.renderer(host_api, monkeypatch, getattr(scenes, name), w, h, camera=camera)
 
 
 def _gbuffer(r):
     """the current G-buffer as the device holds it"""
     a = r.aovs()
     return dict(pos=r.aov_positions(), normal=a["normal"], t=a["t"], obj=a["obj"], mat=a["mat"])
-
-
-def _state(r):
-    return (r.accumulator(),) + tuple(r.stats())
-
-
-def _same_state(a, b):
-    return all(_same(x, y) for x, y in zip(a, b))
-
-
-def _list_mask(w, h, seed=5):
-    """about 60 % of the pixels, never pixel 0 unless it is the only one, always the last"""
-    on = np.random.default_rng(seed).random(w * h) < 0.6
-    on[0] = False
-    on[w * h - 1] = True
-    return on
-
-
-def _make_history(r, host_api, kind, w, h):
-    PATH = host_api.RT_MODE_PATH
-    r.clear()
-    if kind == "uniform":
-        r.render(PATH, 0, 12)
-    elif kind == "adaptive":
-        r.render(PATH, 0, ADAPTIVE["min_samples"])
-        for f in range(ADAPTIVE["min_samples"], ADAPTIVE["min_samples"] + 6):
-            r.select_active(ADAPTIVE)
-            r.render_active(f, 1)
-    else:
-        r.set_active(np.flatnonzero(_list_mask(w, h)).astype(np.uint32))
-        r.render_active(0, 5)
 
 
 # ---- 1. the kernel against the restatement ---------------------------------------------------------------------------------
@@ -115,13 +44,13 @@ def test_kernel_equals_the_restatement(name, size, scenes, host_api, monkeypatch
     w, h = size
     r = _renderer(host_api, scenes, monkeypatch, name, w, h, ONE_PIXEL_CAMERA if size == (1, 1) else None)
     A = r.camera()
-    mt, ms = _materials(r)
+    mt, ms = rr.materials(r)
     r.stats_enable(True)
     for kind in ("uniform", "adaptive", "list"):
         r.set_camera(*A)
-        _make_history(r, host_api, kind, w, h)
+        rr.make_history(r, host_api, kind, w, h)
         r.render_aovs(0.001)
-        g_a, hist = _gbuffer(r), _state(r)
+        g_a, hist = _gbuffer(r), sp.state(r)
         cnt_a = hist[1]
         if kind == "adaptive" and w * h > 1:
             assert len(np.unique(cnt_a)) > 1, "the adaptive history has even counts"
@@ -131,7 +60,7 @@ def test_kernel_equals_the_restatement(name, size, scenes, host_api, monkeypatch
             assert np.all(cnt_a == 12)  # above max_history = 8: the capped case scales every carried pixel
         r.history_capture()
         for move_name, move in MOVES.items():
-            B = _moved(A, move)
+            B = rr.moved(A, move)
             r.set_camera(*B)
             r.render_aovs(0.001)
             g_b = _gbuffer(r)
@@ -140,12 +69,12 @@ def test_kernel_equals_the_restatement(name, size, scenes, host_api, monkeypatch
                 assert ((g_b["obj"] != -1) & ~(lam > 0)).any(), "nothing the new camera sees lies behind the old one"
             for pname, P in PARAMS.items():
                 n = r.reproject(P)
-                got = _state(r)
+                got = sp.state(r)
                 acc, cnt, sy, syy, n_ref, src, el = rr.reproject(g_b, g_a, *hist, A, mt, ms, **P)
                 what = (kind, move_name, pname)
                 assert n == n_ref, what
                 assert np.array_equal(got[1], cnt), what
-                assert _same(got[0], acc) and _same(got[2], sy) and _same(got[3], syy), what
+                assert sp.same(got[0], acc) and sp.same(got[2], sy) and sp.same(got[3], syy), what
                 carried, rejected = n_ref / (w * h), (el.sum() - n_ref) / max(1, el.sum())
                 if move_name in ("small", "large") and pname != "exact" and w * h > 1:
                     assert carried >= 0.10 and rejected >= 0.01, (what, carried, rejected)
@@ -155,7 +84,7 @@ def test_kernel_equals_the_restatement(name, size, scenes, host_api, monkeypatch
                     assert np.array_equal(src >= 0, keep), what
                     assert np.array_equal(src[keep], np.arange(w * h).reshape(h, w)[keep]), what
                     for g, b in zip(got, hist):
-                        assert _same(g[keep], b[keep]) and not _bits(g[~keep]).any(), what
+                        assert sp.same(g[keep], b[keep]) and not sp.bits(g[~keep]).any(), what
                     if kind == "uniform":
                         assert keep.any(), "nothing is eligible"
     r.close()
@@ -167,31 +96,31 @@ def test_reproject_twice_and_untouched_state(scenes, host_api, monkeypatch):
     r = _renderer(host_api, scenes, monkeypatch, "mixed_small", w, h)
     A = r.camera()
     r.stats_enable(True)
-    _make_history(r, host_api, "adaptive", w, h)
+    rr.make_history(r, host_api, "adaptive", w, h)
     r.render_aovs(0.001)
     r.history_capture()
-    lst = np.flatnonzero(_list_mask(w, h, seed=9)).astype(np.uint32)
+    lst = np.flatnonzero(rr.list_mask(w, h, seed=9)).astype(np.uint32)
     r.set_active(lst)
-    r.set_camera(*_moved(A, MOVES["large"]))
+    r.set_camera(*rr.moved(A, MOVES["large"]))
     r.render_aovs(0.001)
     g_b = _gbuffer(r)
     n1 = r.reproject()
-    first = _state(r)
+    first = sp.state(r)
     n2 = r.reproject()
-    assert n1 == n2 > 0 and _same_state(first, _state(r))
+    assert n1 == n2 > 0 and sp.same_state(first, sp.state(r))
     # the history is the capture's, whatever has happened to the accumulator since
     r.clear()
-    assert r.reproject() == n1 and _same_state(first, _state(r))
+    assert r.reproject() == n1 and sp.same_state(first, sp.state(r))
     r.render(host_api.RT_MODE_PATH, 50, 2)
-    assert r.reproject(None) == n1 and _same_state(first, _state(r))
+    assert r.reproject(None) == n1 and sp.same_state(first, sp.state(r))
     # NULL parameters are the defaults, a NULL count is allowed
-    assert r.reproject(dict(host_api.REPROJECT_DEFAULTS)) == n1 and _same_state(first, _state(r))
-    assert r.rt.rt_reproject(r.ctx, None, None) == 0 and _same_state(first, _state(r))
+    assert r.reproject(dict(host_api.REPROJECT_DEFAULTS)) == n1 and sp.same_state(first, sp.state(r))
+    assert r.rt.rt_reproject(r.ctx, None, None) == 0 and sp.same_state(first, sp.state(r))
     # the active-pixel list and the G-buffer are not touched
     got, k = r.active()
     assert k == len(lst) and np.array_equal(got, lst)
     after = _gbuffer(r)
-    assert all(_same(g_b[key], after[key]) for key in g_b)
+    assert all(sp.same(g_b[key], after[key]) for key in g_b)
     # rt_clear and rt_set_camera leave the history alone: back at the old camera every eligible pixel is carried from itself
     r.clear()
     r.set_camera(*A)
@@ -208,10 +137,10 @@ def test_select_and_render_active_after_a_reproject(scenes, host_api, monkeypatc
     lists, states = [], []
     for r in pair:
         r.stats_enable(True)
-        _make_history(r, host_api, "adaptive", w, h)
+        rr.make_history(r, host_api, "adaptive", w, h)
         r.render_aovs(0.001)
         r.history_capture()
-        r.set_camera(*_moved(A, MOVES["small"]))
+        r.set_camera(*rr.moved(A, MOVES["small"]))
         r.render_aovs(0.001)
         r.reproject()
         cnt, sy, syy = r.stats()
@@ -226,8 +155,8 @@ def test_select_and_render_active_after_a_reproject(scenes, host_api, monkeypatc
         on[lst] = True
         assert np.array_equal(after.reshape(-1), cnt.reshape(-1) + 2 * on)
         lists.append(lst)
-        states.append(_state(r))
-    assert np.array_equal(lists[0], lists[1]) and _same_state(states[0], states[1])
+        states.append(sp.state(r))
+    assert np.array_equal(lists[0], lists[1]) and sp.same_state(states[0], states[1])
     for r in pair:
         r.close()
 
@@ -264,19 +193,19 @@ def test_errors_and_invalidation(scenes, host_api, monkeypatch):
     for y0, y1 in ((-1, h), (0, h + 1), (3, 3), (5, 2)):
         assert L.rt_download_aov_positions(ctx, y0, y1, pxyz) == ARG
     assert L.rt_download_aov_positions(ctx, 0, h, None) == ARG
-    assert _same(r.aov_positions(3, 9), r.aov_positions()[3:9])
+    assert sp.same(r.aov_positions(3, 9), r.aov_positions()[3:9])
     r.stats_enable(True)
     r.render(host_api.RT_MODE_PATH, 0, 3)
     # no history yet
     assert rep() == STATE and "history" in why()
     # a stale G-buffer (the camera changed since rt_render_aovs): no capture
-    r.set_camera(*_moved(A, MOVES["small"]))
+    r.set_camera(*rr.moved(A, MOVES["small"]))
     assert L.rt_history_capture(ctx) == STATE and "G-buffer" in why()
     r.set_camera(*A)
     r.render_aovs(0.001)
     r.history_capture()
     # ... and no reproject
-    r.set_camera(*_moved(A, MOVES["small"]))
+    r.set_camera(*rr.moved(A, MOVES["small"]))
     assert rep() == STATE and "G-buffer" in why()
     r.render_aovs(0.001)
     assert rep() == 0 and n.value > 0
@@ -303,7 +232,7 @@ def test_errors_and_invalidation(scenes, host_api, monkeypatch):
     # rt_clear and rt_set_camera do not
     recapture()
     r.clear()
-    r.set_camera(*_moved(A, MOVES["large"]))
+    r.set_camera(*rr.moved(A, MOVES["large"]))
     r.render_aovs(0.001)
     assert rep() == 0
     r.close()
@@ -354,7 +283,7 @@ def test_tick_reproject_equals_the_sequence_by_hand(scenes, host_api, monkeypatc
     carried = []
     for t in range(13):
         if t in moves:
-            cam = _moved(cam, moves[t])
+            cam = rr.moved(cam, moves[t])
             if t in unsynced:
                 _set_camera_unsynced(r, cam)
             else:
@@ -376,9 +305,9 @@ def test_tick_reproject_equals_the_sequence_by_hand(scenes, host_api, monkeypatc
         if t in moves:
             assert r.carried_pixels() == carried[-1] > 0, t
             assert np.all(off.stats()[0] == 1), t
-        assert _same(r.tick_accumulator(), hand.accumulator()) and _same_state(_state(r), _state(hand)), t
+        assert sp.same(r.tick_accumulator(), hand.accumulator()) and sp.same_state(sp.state(r), sp.state(hand)), t
         assert np.array_equal(r.tick_pixels(), hand.resolve_adaptive()), t
-        assert _same(off.tick_accumulator(), plain.accumulator()) and _same_state(_state(off), _state(plain)), t
+        assert sp.same(off.tick_accumulator(), plain.accumulator()) and sp.same_state(sp.state(off), sp.state(plain)), t
         assert np.array_equal(off.tick_pixels(), plain.resolve_adaptive()), t
     assert len(carried) == 3
     # a fisheye on either side of the move: the Tick clears as ever
@@ -394,7 +323,7 @@ def test_tick_reproject_equals_the_sequence_by_hand(scenes, host_api, monkeypatc
     r.scene.set_raytracer(True)
     r.tick()
     r.scene.set_raytracer(False)
-    r.set_camera(*_moved(cam, MOVES["small"]))
+    r.set_camera(*rr.moved(cam, MOVES["small"]))
     r.tick()
     assert np.all(r.stats()[0] == 1) and r.active_pixels() == w * h
     # reproject without adaptive: refused, naming the limit
@@ -424,7 +353,7 @@ def test_carried_samples_beat_fresh_ones(scenes, host_api, monkeypatch):
     r.history_capture()
     ratios = []
     for move in q["moves"]:
-        r.set_camera(*_moved(A, move))
+        r.set_camera(*rr.moved(A, move))
         r.render_aovs(0.001)
         n = r.reproject()
         acc, cnt = r.accumulator(), r.stats()[0]

@@ -10,28 +10,22 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import instances_ref as ir  # noqa: E402
 import reproject_ref as rr  # noqa: E402
 import reproject_motion_ref as rm  # noqa: E402
 import reproject_motion_shapes as shapes  # noqa: E402
+import support as sp  # noqa: E402
 from test_gpu_denoise import Recorder, check_aovs  # noqa: E402
-from test_gpu_reproject import ADAPTIVE, KNOBS, MOVES, PARAMS, _make_history, _materials, _moved, _same, _same_state, _state  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 SEED = 0x12345678
+ADAPTIVE, MOVES, PARAMS = rr.ADAPTIVE, rr.MOVES, rr.PARAMS
 
 
 def _renderer(host_api, monkeypatch, n, w, h, camera=shapes.CAMERA, scene=None):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    r = host_api.HostRenderer(w, h)
-    scene(r.scene) if scene else shapes.build(r.scene, n)
-    r.scene.set_raytracer(False)
-    r.commit()
-    if camera is not None:
-        r.set_camera(*camera)
-    return r
+    return sp.renderer(host_api, monkeypatch, scene or (lambda b: shapes.build(b, n)), w, h, scene_camera=False, camera=camera)
 
 
 def _gbuffer(r):
@@ -78,7 +72,7 @@ def test_instance_aov(size, scenes, host_api, oracle_api, monkeypatch):
     for k in np.unique(flat[flat >= 0]):
         sel = flat == k
         hit = r.scope_nearest(3, int(k), O[sel], D[sel])
-        assert _same(hit["t"], g["t"].reshape(-1)[sel]), k
+        assert sp.same(hit["t"], g["t"].reshape(-1)[sel]), k
         assert np.array_equal(hit["obj"], g["obj"].reshape(-1)[sel]), k
     # the meshes are objects 2 and 3 (their triangles count on from 2000 and 3000); spheres 6 .. 9, the plane 1, lights 11, 12, a miss -1
     mesh = g["obj"] >= 1000
@@ -101,11 +95,11 @@ def test_instance_aov(size, scenes, host_api, oracle_api, monkeypatch):
         got = check_aovs(o, orr, r, recs[-1], 0.001)
         want = rr.gbuffer_of(o, orr)
         hitp = want["obj"] != -1
-        assert hitp.any() and (got["albedo"][hitp] != 0).any() and _same(r.aov_positions()[hitp], want["pos"][hitp])
+        assert hitp.any() and (got["albedo"][hitp] != 0).any() and sp.same(r.aov_positions()[hitp], want["pos"][hitp])
         orr.close(), o.close()
 
     same_as_before(r, lambda o: scenes.pretty_tlas(o, 3))
-    assert all(_same(g[k], v) for k, v in _gbuffer(r).items())  # (and the checks left the G-buffer as it was)
+    assert all(sp.same(g[k], v) for k, v in _gbuffer(r).items())  # (and the checks left the G-buffer as it was)
     r.close()
     # a scene without a TLAS
     r = _renderer(host_api, monkeypatch, 0, w, h, scene=recorded(scenes.mixed_small), camera=shapes.CAMERA)
@@ -132,15 +126,15 @@ def test_kernel_equals_the_restatement(size, n, host_api, monkeypatch):
     w, h = size
     A = shapes.one_pixel_camera(n) if size == (1, 1) else shapes.CAMERA
     r = _renderer(host_api, monkeypatch, n, w, h, A)
-    mt, ms = _materials(r)
+    mt, ms = rr.materials(r)
     blas, base = _base(host_api, r, n)
     r.stats_enable(True)
     for kind in ("uniform", "adaptive"):
         _apply(host_api, r, blas, base, [])
         r.set_camera(*A)
-        _make_history(r, host_api, kind, w, h)
+        rr.make_history(r, host_api, kind, w, h)
         r.render_aovs(0.001)
-        g_a, hist, xf_a = _gbuffer(r), _state(r), shapes.tables(r)
+        g_a, hist, xf_a = _gbuffer(r), sp.state(r), shapes.tables(r)
         if size == (1, 1):
             assert g_a["inst"][0, 0] == 0, "the one pixel does not see instance 0"
         r.history_capture()
@@ -150,18 +144,18 @@ def test_kernel_equals_the_restatement(size, n, host_api, monkeypatch):
             mv = rm.moved(xf_b, xf_a)
             assert mv.any() == (mname != "there_and_back") and (mname != "all" or mv.all()), mname
             for cname in ("none", "small"):
-                r.set_camera(*_moved(A, MOVES[cname]))
+                r.set_camera(*rr.moved(A, MOVES[cname]))
                 r.render_aovs(0.001)
                 g_b = _gbuffer(r)
                 for pname, P in PARAMS.items():
                     got_n = r.reproject_motion(P)
-                    got = _state(r)
+                    got = sp.state(r)
                     acc, cnt, sy, syy, n_ref, src, el = rm.reproject(g_b, g_a, *hist, A, xf_b, xf_a, mt, ms, **P)
                     what = (kind, mname, cname, pname)
                     print(what, "carried %d of %d, eligible %d" % (n_ref, w * h, el.sum()))
                     assert got_n == n_ref, what
                     assert np.array_equal(got[1], cnt), what
-                    assert _same(got[0], acc) and _same(got[2], sy) and _same(got[3], syy), what
+                    assert sp.same(got[0], acc) and sp.same(got[2], sy) and sp.same(got[3], syy), what
                     if w * h > 1 and pname != "exact" and mname != "there_and_back":
                         carried, rejected = n_ref / (w * h), (el.sum() - n_ref) / max(1, el.sum())
                         assert carried >= 0.10 and rejected >= 0.01, (what, carried, rejected)
@@ -184,15 +178,15 @@ def test_unmoved_equals_rt_reproject(tlas, scenes, host_api, monkeypatch):
     pair = [_renderer(host_api, monkeypatch, 3, w, h, scene=None if tlas else scenes.mixed_small) for _ in range(2)]
     for r in pair:
         r.stats_enable(True)
-        _make_history(r, host_api, "adaptive", w, h)
+        rr.make_history(r, host_api, "adaptive", w, h)
         r.render_aovs(0.001)
         r.history_capture()
-        r.set_camera(*_moved(shapes.CAMERA, MOVES["small"]))
+        r.set_camera(*rr.moved(shapes.CAMERA, MOVES["small"]))
         r.render_aovs(0.001)
     assert (pair[0].aov_instances() >= 0).any() == tlas
     for pname, P in PARAMS.items():
         a, b = pair[0].reproject(P), pair[1].reproject_motion(P)
-        assert a == b > 0 and _same_state(_state(pair[0]), _state(pair[1])), pname
+        assert a == b > 0 and sp.same_state(sp.state(pair[0]), sp.state(pair[1])), pname
     for r in pair:
         r.close()
 
@@ -203,28 +197,28 @@ def test_twice_and_untouched_state(host_api, monkeypatch):
     r = _renderer(host_api, monkeypatch, n, w, h)
     blas, base = _base(host_api, r, n)
     r.stats_enable(True)
-    _make_history(r, host_api, "adaptive", w, h)
+    rr.make_history(r, host_api, "adaptive", w, h)
     r.render_aovs(0.001)
     r.history_capture()
     _apply(host_api, r, blas, base, shapes.motions(n, base)["all"])
-    r.set_camera(*_moved(shapes.CAMERA, MOVES["small"]))
+    r.set_camera(*rr.moved(shapes.CAMERA, MOVES["small"]))
     r.render_aovs(0.001)
     g_b = _gbuffer(r)
     lst = np.flatnonzero(np.random.default_rng(9).random(w * h) < 0.6).astype(np.uint32)
     r.set_active(lst)
     n1 = r.reproject_motion()
-    first = _state(r)
-    assert r.reproject_motion() == n1 > 0 and _same_state(first, _state(r))
+    first = sp.state(r)
+    assert r.reproject_motion() == n1 > 0 and sp.same_state(first, sp.state(r))
     # the history is the capture's, whatever has happened to the accumulator since; NULL parameters are the defaults, a NULL count is allowed
     r.clear()
-    assert r.reproject_motion(dict(host_api.REPROJECT_DEFAULTS)) == n1 and _same_state(first, _state(r))
+    assert r.reproject_motion(dict(host_api.REPROJECT_DEFAULTS)) == n1 and sp.same_state(first, sp.state(r))
     r.render(host_api.RT_MODE_PATH, 50, 2)
-    assert r.rt.rt_reproject_motion(r.ctx, None, None) == 0 and _same_state(first, _state(r))
+    assert r.rt.rt_reproject_motion(r.ctx, None, None) == 0 and sp.same_state(first, sp.state(r))
     # the active-pixel list and the G-buffer are not touched
     got, k = r.active()
     assert k == len(lst) and np.array_equal(got, lst)
     after = _gbuffer(r)
-    assert all(_same(g_b[key], after[key]) for key in g_b)
+    assert all(sp.same(g_b[key], after[key]) for key in g_b)
     # a budget plan is dropped: every pixel's count was rewritten
     assert r.select_budget(dict(select=ADAPTIVE, pass_cap=4))[0] > 0
     r.reproject_motion()
@@ -281,7 +275,7 @@ def test_states_and_errors(host_api, monkeypatch):
     assert rep(L.rt_reproject_motion) == 0 and cnt.value > 0
     # ... across any number of moves, and a camera move as well
     _apply(host_api, r, blas, base, shapes.motions(n, base)["two_calls"])
-    r.set_camera(*_moved(shapes.CAMERA, MOVES["small"]))
+    r.set_camera(*rr.moved(shapes.CAMERA, MOVES["small"]))
     r.render_aovs(0.001)
     assert rep(L.rt_reproject) == STATE and rep(L.rt_reproject_motion) == 0 and cnt.value > 0
     # a failed rt_set_instances (a blas mismatch) leaves both calls as they were: here rt_reproject valid, there not
@@ -346,7 +340,7 @@ def test_renderer_commit_instances_equals_the_sequence_by_hand(host_api, monkeyp
             plain.clear()
             whole[id(plain)] = 0
             if cmove is not None:
-                cam = _moved(cam, cmove)
+                cam = rr.moved(cam, cmove)
                 for x in (r, off, hand, plain):
                     x.set_camera(*cam)
             hand.render_aovs(0.001)
@@ -359,9 +353,9 @@ def test_renderer_commit_instances_equals_the_sequence_by_hand(host_api, monkeyp
         if t in moves:
             assert r.carried_pixels() == carried > 0, t
             assert np.all(off.stats()[0] == 1), t
-        assert _same(r.tick_accumulator(), hand.accumulator()) and _same_state(_state(r), _state(hand)), t
+        assert sp.same(r.tick_accumulator(), hand.accumulator()) and sp.same_state(sp.state(r), sp.state(hand)), t
         assert np.array_equal(r.tick_pixels(), hand.resolve_adaptive()), t
-        assert _same(off.tick_accumulator(), plain.accumulator()) and _same_state(_state(off), _state(plain)), t
+        assert sp.same(off.tick_accumulator(), plain.accumulator()) and sp.same_state(sp.state(off), sp.state(plain)), t
     # a Commit() between CommitInstances and the Tick: the upload ended the captured history, so the Tick clears (and does not throw)
     r.scene.set_transforms(0, [base[0].reshape(4, 4)])
     r.commit_instances()
@@ -397,9 +391,7 @@ def test_example_spin_carry(tmp_path, scenes, host_api, monkeypatch):
     not the one of the clearing --spin."""
     import subprocess
     from conftest import ROOT, pkg
-    from test_gpu_instances import _mat_mul
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
+    sp.clean_env(monkeypatch)
     sf = pkg("scene_file")
     exe = str(tmp_path / "render_scene")
     host, csrc = os.path.join(ROOT, "ray-and-pathtracer_amd", "host"), os.path.join(ROOT, "ray-and-pathtracer_amd", "csrc")
@@ -426,7 +418,7 @@ def test_example_spin_carry(tmp_path, scenes, host_api, monkeypatch):
         r.tick()
     s = r.scene
     ang = F32(F32(F32(20.0) * F32(3.14159265358979)) / F32(180.0))
-    s.set_transforms(0, [_mat_mul(s.instance_dump(0)["T"], s.trs((0, 0, 0), 1, 0.0, ang, 0.0))])
+    s.set_transforms(0, [ir.mat_mul(s.instance_dump(0)["T"], s.trs((0, 0, 0), 1, 0.0, ang, 0.0))])
     r.commit_instances()
     r.tick()
     assert r.carried_pixels() > 0

@@ -20,11 +20,10 @@ import adaptive_shapes as sh  # noqa: E402
 import budget_ref as br  # noqa: E402
 import budget_shapes as tc  # noqa: E402
 import dilate_ref as dr  # noqa: E402
+import support as sp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("RT_PRIMARY_TABLE", "RT_PRIMARY_TABLE_MIN", "RT_FUSE", "RT_STREAM", "RT_MIXED_MAX", "RT_DECIDE", "RT_DEFER_GAMMA", "RT_EXACT_GAMMA",
-         "RT_SLOTS", "RT_WIDE", "RT_WIDE8", "RT_SAMPLE_GIB")
 SEED = 0x12345678
 CAP = 7
 NOISY = dict(min_samples=4, max_samples=64, threshold=0.1, floor=1e-3)  # both counts are at min_samples: the raw list is the noisy pixels
@@ -32,13 +31,7 @@ SIZES = {(1, 1): "one lane", (65, 1): "a wave and a lane", (257, 3): "a block an
 
 
 def _renderer(host_api, scenes, monkeypatch, w, h):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    r = host_api.HostRenderer(w, h)
-    scenes.mixed_small(r.scene)
-    r.scene.set_raytracer(False)
-    r.commit()
-    return r
+    return sp.renderer(host_api, monkeypatch, scenes.mixed_small, w, h, scene_camera=False)
 
 
 def _more_list(w, h):
@@ -52,13 +45,8 @@ def _more_list(w, h):
 
 
 def _uneven(r, host_api, w, h):
-    """test_gpu_budget.py _uneven: counts 4 and 7 (a 1 x 1 frame: 7), every pixel's sample k is frame k"""
-    r.stats_enable(True)
-    r.clear()
-    r.render(host_api.RT_MODE_PATH, 0, tc.UNEVEN_WHOLE)
-    r.set_active(_more_list(w, h))
-    r.render_active(tc.UNEVEN_WHOLE, tc.UNEVEN_MORE)
-    stats = r.stats()
+    """counts 4 and 7 (a 1 x 1 frame: 7)"""
+    stats = sp.uneven(r, host_api, _more_list(w, h))
     assert set(np.unique(stats[0])) == ({tc.UNEVEN_WHOLE, tc.UNEVEN_WHOLE + tc.UNEVEN_MORE} if w * h > 1 else {tc.UNEVEN_WHOLE + tc.UNEVEN_MORE})
     return stats
 

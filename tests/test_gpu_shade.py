@@ -19,27 +19,16 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import depth_cases as dc  # noqa: E402
 import shade_cases as sc  # noqa: E402
+import support as sp  # noqa: E402
 from conftest import rel_err  # noqa: E402
 from test_gpu_parity import RADIANCE_TOL  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-KNOBS = tuple(sorted(set(sc.PATH_KNOBS) | set(sc.WHITTED_KNOBS) | set(dc.PATH_KNOBS) | set(dc.WHITTED_KNOBS)))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _env_id(env):
-    return ",".join("%s=%s" % kv for kv in env.items()) or "default"
 
 
 def _device(host_api, scene, rt, monkeypatch, env):
     """a context reads its switches when it is created (csrc/rt_ctx.h Knobs)"""
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    sp.clean_env(monkeypatch, env)
     r = host_api.HostRenderer(8, 8)
     sc.SCENES[scene](r.scene, rt=rt)
     r.commit()
@@ -67,7 +56,7 @@ def _run(r, oracle_api, scene, pipeline, what):
 
 def _agree(got, first, what, exact):
     for depth in got:
-        same = np.array_equal(_bits(got[depth]), _bits(first[depth]))
+        same = sp.same(got[depth], first[depth])
         err, cls_ok = rel_err(got[depth], first[depth])
         print("%s depth %d against the first schedule: %s, max relative difference %.3g" % (what, depth, "same bits" if same else "other bits", err.max()))
         assert cls_ok and err.max() <= RADIANCE_TOL, (what, depth, err.max())
@@ -78,7 +67,7 @@ def _agree(got, first, what, exact):
 _FIRST = {}
 
 
-@pytest.mark.parametrize("env", dc.PATH_ENVS + sc.OWN_ENVS, ids=_env_id)
+@pytest.mark.parametrize("env", dc.PATH_ENVS + sc.OWN_ENVS, ids=sp.env_id)
 @pytest.mark.parametrize("scene", sc.SAMPLE_SCENES)
 def test_sample_on_the_wavefronts(scene, env, oracle_api, host_api, monkeypatch):
     """Renderer::Sample with the flag clear: k_shade_s / k_light_s (dense) under the fuse modes, with the producer-side decisions off and
@@ -87,19 +76,19 @@ def test_sample_on_the_wavefronts(scene, env, oracle_api, host_api, monkeypatch)
     if env.get("RT_SLOTS") == str(sc.SLOT_BUDGET):
         assert env.get("RT_STREAM") == "0" and all(len(O) > sc.SLOT_BUDGET for _, O, _, _ in sc.batches(scene, "sample"))  # fewer slots than samples in every batch
     r = _device(host_api, scene, True, monkeypatch, env)
-    got = _run(r, oracle_api, scene, "sample", _env_id(env))
-    _agree(got, _FIRST.setdefault(("sample", scene), got), "%s Sample [%s]" % (scene, _env_id(env)), exact=True)
+    got = _run(r, oracle_api, scene, "sample", sp.env_id(env))
+    _agree(got, _FIRST.setdefault(("sample", scene), got), "%s Sample [%s]" % (scene, sp.env_id(env)), exact=True)
     r.close()
 
 
-@pytest.mark.parametrize("env", dc.WHITTED_ENVS, ids=_env_id)
+@pytest.mark.parametrize("env", dc.WHITTED_ENVS, ids=sp.env_id)
 @pytest.mark.parametrize("scene", sc.TRACE_SCENES)
 def test_trace_on_the_whitted_schedules(scene, env, oracle_api, host_api, monkeypatch):
     """Renderer::Trace with the flag set: the Whitted policies of rt_mega.h under the default schedule, the wavefront rounds (RT_MEGA=0)
     and the tree levels (RT_MEGA_LEVELS=1); 'shiny' adds the mirror branch of a diffuse hit"""
     r = _device(host_api, scene, True, monkeypatch, env)
-    got = _run(r, oracle_api, scene, "trace", _env_id(env))
-    _agree(got, _FIRST.setdefault(("trace", scene), got), "%s Trace [%s]" % (scene, _env_id(env)), exact=False)
+    got = _run(r, oracle_api, scene, "trace", sp.env_id(env))
+    _agree(got, _FIRST.setdefault(("trace", scene), got), "%s Trace [%s]" % (scene, sp.env_id(env)), exact=False)
     r.close()
 
 

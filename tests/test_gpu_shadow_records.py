@@ -6,58 +6,22 @@ two draws each) with lights that do not (directional lights), in both orders, wi
 scene may have, on every schedule of the round loop (one traversal launch per round, two streams, one kernel at a time --
 the schedule of batches of 100 M samples and more), through the 2-, 4- and 8-wide occlusion walks, and with the
 Q-learning sampler (which always takes the dense pipeline: its schedules must agree with one another and with the oracle)."""
-import importlib
-import math
-
 import numpy as np
 import pytest
+
+import support as sp
+from lit_scene import lit_scene
 from test_gpu_parity import RADIANCE_TOL, rel_err
 
 pytestmark = pytest.mark.gpu
 
 SCHEDULES = (("one_launch_per_round", {"RT_FUSE": "1"}), ("two_streams", {"RT_FUSE": "2"}), ("one_kernel_at_a_time", {"RT_FUSE": "0"}))
-KNOBS = ("RT_STREAM", "RT_FUSE", "RT_WIDE", "RT_WIDE8", "RT_MIXED_MAX")
-
-
-def _lit_scene(b, kinds="AD"):
-    """a floor, two diffuse spheres, a glass sphere and a metal mesh under the lights 'kinds' names in order: A = area light
-    (light_position draws twice), D = directional light (no draw)"""
-    assets = importlib.import_module("ray-and-pathtracer_amd.assets")
-    fl = b.diffuse(0.8, (1, 1, 1), 0.0, 1.0, 4)
-    d1 = b.diffuse(0.8, (0.2, 0.9, 0.3), 0.6, 0.4, 10)
-    d2 = b.diffuse(0.7, (0.9, 0.4, 0.2), 0.5, 0.5, 6)
-    gl = b.glass(1.5, (0.8, 0.9, 1.0))
-    me = b.metal(0.7, (1.0, 0.8, 0.3))
-    n = len(kinds)
-    for i, k in enumerate(kinds):
-        a = 2 * math.pi * i / n
-        pos = (2.5 * math.cos(a), 3.0 + 0.05 * i, 1.0 + 2.5 * math.sin(a))
-        col = (1.0, 0.9 - 0.02 * i, 0.6 + 0.01 * i)
-        if k == "A":
-            b.area_light(11 + i, pos, 3.0, col, 0.6, (0, -1, 0))
-        else:
-            nrm = (-0.3 * math.cos(a), -1.0, -0.3 * math.sin(a))
-            b.dir_light(11 + i, pos, 2.0, col, nrm, 0.5)
-    b.sphere(1, d1, (0.4, 0.5, 1.2), 0.5)
-    b.sphere(2, gl, (-0.8, 0.4, 0.6), 0.4)
-    b.sphere(4, d2, (-0.2, 0.3, 2.0), 0.3)
-    b.mesh_obj(3, assets.obj_path("ico"), me, (1.3, 0.6, 0.4), 0.5)
-    b.plane(0, fl, (0, 1, 0), 0)
-    b.build(0)
-    return dict(name="lit_" + kinds)
-
-
-def _set_env(monkeypatch, env):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
 
 
 def _frame(host_api, kinds, env, monkeypatch, w, h, frames, qlearn=False):
-    _set_env(monkeypatch, env)
+    sp.clean_env(monkeypatch, env)
     r = host_api.HostRenderer(w, h)
-    _lit_scene(r.scene, kinds)
+    lit_scene(r.scene, kinds)
     r.commit()
     if qlearn:
         r.qlearn_enable(8, (-4, -1, -4), (4, 5, 6), 0.3, 0.2, 1.0, 0)
@@ -72,10 +36,6 @@ def _frame(host_api, kinds, env, monkeypatch, w, h, frames, qlearn=False):
     return out, table
 
 
-def _same(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 @pytest.mark.parametrize("kinds", ["A", "D", "AD", "DA", "ADDA", "DAAD", "A" * 32, ("AD" * 16)])
 def test_stream_shadow_records_equal_slot_pipeline(kinds, host_api, monkeypatch):
     """every schedule of the dense pipeline against the slot pipeline (RT_STREAM=0, which stores every sampled position)"""
@@ -85,7 +45,7 @@ def test_stream_shadow_records_equal_slot_pipeline(kinds, host_api, monkeypatch)
     assert fin.mean() > 0.5 and (ref[..., :3][fin] > 0).mean() > 0.2  # lit: a light's disk seen directly is +inf or NaN (Q7)
     for key, env in SCHEDULES:
         got, _ = _frame(host_api, kinds, env, monkeypatch, w, h, frames)
-        assert _same(ref, got), (kinds, key)
+        assert sp.same(ref, got), (kinds, key)
 
 
 @pytest.mark.parametrize("walk", [{"RT_WIDE": "1"}, {"RT_WIDE8": "1"}])
@@ -96,7 +56,7 @@ def test_stream_shadow_records_wide_walks(kinds, walk, host_api, monkeypatch):
     ref, _ = _frame(host_api, kinds, {"RT_STREAM": "0"}, monkeypatch, w, h, frames)
     for key, env in SCHEDULES:
         got, _ = _frame(host_api, kinds, dict(env, **walk), monkeypatch, w, h, frames)
-        assert _same(ref, got), (kinds, walk, key)
+        assert sp.same(ref, got), (kinds, walk, key)
 
 
 def test_stream_shadow_records_larger_batch(host_api, monkeypatch):
@@ -106,7 +66,7 @@ def test_stream_shadow_records_larger_batch(host_api, monkeypatch):
     ref, _ = _frame(host_api, kinds, {"RT_STREAM": "0"}, monkeypatch, w, h, frames)
     for key, env in (("default", {"RT_MIXED_MAX": "100000"}), ("one_kernel_at_a_time", {"RT_FUSE": "0"})):
         got, _ = _frame(host_api, kinds, env, monkeypatch, w, h, frames)
-        assert _same(ref, got), key
+        assert sp.same(ref, got), key
 
 
 @pytest.mark.parametrize("kinds", ["AD", "DA"])
@@ -119,15 +79,15 @@ def test_stream_shadow_records_with_sampler(kinds, host_api, oracle_api, monkeyp
         out[key] = _frame(host_api, kinds, env, monkeypatch, w, h, frames, qlearn=True)
     first = out[SCHEDULES[0][0]]
     for key, _ in SCHEDULES[1:]:
-        assert _same(first[0], out[key][0]) and _same(first[1], out[key][1]), (kinds, key)
+        assert sp.same(first[0], out[key][0]) and sp.same(first[1], out[key][1]), (kinds, key)
     o = oracle_api.OracleScene()
-    _lit_scene(o, kinds)
+    lit_scene(o, kinds)
     orr = oracle_api.OracleRenderer(o, w, h)
     orr.scene.set_raytracer(False)
     orr.qlearn_enable(8, (-4, -1, -4), (4, 5, 6), 0.3, 0.2, 1.0, 0)
     orr.clear()
     orr.render(0, frames, nthreads=0); orr.qlearn_apply()
     orr.render(frames, frames, nthreads=0)
-    assert _same(orr.qlearn_state()[2], first[1])
+    assert sp.same(orr.qlearn_state()[2], first[1])
     err, cls_ok = rel_err(first[0][..., :3], orr.accumulator()[..., :3])
     assert cls_ok and err.max() <= RADIANCE_TOL, err.max()

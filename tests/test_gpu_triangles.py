@@ -10,33 +10,18 @@ import numpy as np
 import pytest
 
 import instances_ref as ir
+import support as sp
 import triangles_desc as td
 import triangles_ref as tr
-from test_gpu_instances import _records
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-KNOBS = ("RT_TLAS_LDS", "RT_WIDE", "RT_WIDE8")
 HOWS = ("twist", "scale", "collapse")
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(a, b):
-    a, b = _bits(a), _bits(b)
-    return a.shape == b.shape and np.array_equal(a, b)
-
-
 def _env(monkeypatch, env=None):
-    """the knobs are read once per context (rt_create): set them before the renderer exists"""
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in (env or {}).items():
-        monkeypatch.setenv(k, v)
-    env = env or {}
-    return (int(env.get("RT_WIDE", -1)), int(env.get("RT_WIDE8", 0)), int(env.get("RT_TLAS_LDS", 1)))  # rt_layout_build's knobs
+    sp.clean_env(monkeypatch, env)
+    return sp.layout_knobs(env)
 
 
 def _scalars(s):
@@ -55,10 +40,10 @@ def _check_layout(host_api, r, d, knobs, what, ctx=None):
     """the context's arrays equal rt_layout_build's of the updated description"""
     L = host_api.layout(d.desc(), *knobs)
     for k, (p0, p1, s0, s1) in enumerate(d.ranges()):
-        assert _same(r.blas_array(k, "pairs", ctx), L["pairs"][16 * p0:16 * p1]), "%s: the pair records of blas %d" % (what, k)
-        assert _same(r.blas_array(k, "prims", ctx), L["prims"][16 * s0:16 * s1]), "%s: the primitive records of blas %d" % (what, k)
+        assert sp.same(r.blas_array(k, "pairs", ctx), L["pairs"][16 * p0:16 * p1]), "%s: the pair records of blas %d" % (what, k)
+        assert sp.same(r.blas_array(k, "prims", ctx), L["prims"][16 * s0:16 * s1]), "%s: the primitive records of blas %d" % (what, k)
     for a in ("pairs", "reach", "inst"):
-        assert _same(r.scene_array(a, ctx), L[a]), "%s: %s differs from rt_layout_build of the updated description" % (what, a)
+        assert sp.same(r.scene_array(a, ctx), L[a]), "%s: %s differs from rt_layout_build of the updated description" % (what, a)
     assert np.array_equal(_scalars(r.scene_array("scalars", ctx)), _scalars(L["scalars"])), "%s: scalars" % what
     if d.use_tlas and ctx is None:
         assert np.array_equal(r.download_tlas(), d.tlas), "%s: rt_download_tlas differs from tlas::build over the boxes" % what
@@ -91,19 +76,19 @@ def test_layout_equals_a_fresh_layout(name, env, scenes, host_api, monkeypatch):
         assert r.set_triangles(k, d.deform(k, v9, N)) == 0, how
         L = _check_layout(host_api, r, d, knobs, how)
         for j, pairs, prims in other:
-            assert _same(r.blas_array(j, "pairs"), pairs) and _same(r.blas_array(j, "prims"), prims), "blas %d is untouched" % j
+            assert sp.same(r.blas_array(j, "pairs"), pairs) and sp.same(r.blas_array(j, "prims"), prims), "blas %d is untouched" % j
     if not d.use_tlas:
         # spheres and planes in leaves keep their records; a later rt_set_time deforms from the new vertices
-        kind = _bits(L["prims"]).reshape(-1, 16)[:, 15] & 3
-        got = _bits(r.blas_array(0, "prims")).reshape(-1, 16)
-        assert np.array_equal(got[kind != 0], _bits(host_api.layout(r.scene.describe(), *knobs)["prims"]).reshape(-1, 16)[kind != 0])
+        kind = sp.bits(L["prims"]).reshape(-1, 16)[:, 15] & 3
+        got = sp.bits(r.blas_array(0, "prims")).reshape(-1, 16)
+        assert np.array_equal(got[kind != 0], sp.bits(host_api.layout(r.scene.describe(), *knobs)["prims"]).reshape(-1, 16)[kind != 0])
         fresh = host_api.HostRenderer(16, 8)
         fresh.upload_desc(d.desc())
         for x in (r, fresh):
             x.set_time(0.7)
         for a in ("pairs", "prims"):
-            assert _same(r.blas_array(0, a), fresh.blas_array(0, a)), "rt_set_time after the call: " + a
-        assert not _same(r.blas_array(0, "prims"), L["prims"])
+            assert sp.same(r.blas_array(0, a), fresh.blas_array(0, a)), "rt_set_time after the call: " + a
+        assert not sp.same(r.blas_array(0, "prims"), L["prims"])
         fresh.close()
     r.close()
 
@@ -116,16 +101,16 @@ def test_composes_with_set_instances(scenes, host_api, monkeypatch):
     d = td.Desc(host_api, r.scene)
     s = r.scene
     Ts = [s.trs((f32(-1.0 + 0.8 * i), f32(0.2 * i), f32(3.0 + 0.3 * i)), f32(1.0 + 0.2 * i), 0.0, f32(0.4 * i + 0.2), 0.0) for i in range(d.n)]
-    rec = _records(host_api, [int(b) for b in d.inst["blas"]], Ts)
+    rec = ir.records(host_api, [int(b) for b in d.inst["blas"]], Ts)
     given = np.stack([np.concatenate([d.bounds[i, :3] - f32(0.5 + i), d.bounds[i, 3:] + f32(1.5 + i)]) for i in range(d.n)]).astype(f32)
     assert r.set_instances(0, rec, given) == 0
     d.move(0, rec, given)
     _check_layout(host_api, r, d, knobs, "moved, boxes given")
     v9 = tr.twist(tr.v9_of(d.tris[1]))
     assert r.set_triangles(1, d.deform(1, v9)) == 0
-    assert _same(d.bounds[0], given[0]) and _same(d.bounds[2], given[2]) and not _same(d.bounds[1], given[1])
+    assert sp.same(d.bounds[0], given[0]) and sp.same(d.bounds[2], given[2]) and not sp.same(d.bounds[1], given[1])
     _check_layout(host_api, r, d, knobs, "deformed after the move")
-    rec1 = _records(host_api, [1], [s.trs((0.3, 0.4, 2.5), 1.5, 0.0, 1.0, 0.0)])
+    rec1 = ir.records(host_api, [1], [s.trs((0.3, 0.4, 2.5), 1.5, 0.0, 1.0, 0.0)])
     assert r.set_instances(1, rec1) == 0
     d.move(1, rec1)
     _check_layout(host_api, r, d, knobs, "moved after the deformation")
@@ -174,14 +159,14 @@ def test_results_equal_a_fresh_upload(how, env, host_api, monkeypatch):
         r.render(host_api.RT_MODE_WHITTED, 0, 1)
         out.append((hit, occ, cq, scoped, socc, path4, path16, r.accumulator()))
     (hit, occ, cq, scoped, socc, p4, p16, wh), (hit2, occ2, cq2, scoped2, socc2, p4b, p16b, wh2) = out
-    assert all(_same(hit[k], hit2[k]) for k in hit) and np.array_equal(occ, occ2)
+    assert all(sp.same(hit[k], hit2[k]) for k in hit) and np.array_equal(occ, occ2)
     assert (hit["obj"] >= 2000).sum() >= len(O) // 4 and 0 < occ.sum() < len(occ), "the rays meet the deformed mesh"
     assert cq == cq2 and cq["instance_visits"] > 0 and cq["tlas_inner"] > 0, "the executed walk is the fresh upload's"
     for x, y in zip(scoped, scoped2):
-        assert all(_same(x[k], y[k]) for k in x)
+        assert all(sp.same(x[k], y[k]) for k in x)
     assert (scoped[1]["obj"] >= 2000).any()
     assert all(np.array_equal(x, y) for x, y in zip(socc, socc2))
-    assert _same(p4, p4b) and _same(p16, p16b) and _same(wh, wh2)
+    assert sp.same(p4, p4b) and sp.same(p16, p16b) and sp.same(wh, wh2)
     assert np.isfinite(wh[..., :3]).any() and (p16[..., :3] > 0).any()
     a.close(), b.close()
 
@@ -195,9 +180,9 @@ def test_deformed_scene_equals_a_fresh_oracle_scene(how, host_api, oracle_api, m
     tr.mesh_scene(o, [tr.SMALL, new], tr.spread_transforms(o, tr.BEHAVIOUR_INSTANCES))  # its own build over the deformed triangles: another tree
     O, D = tr.aimed_rays(tr.BEHAVIOUR_RAYS, 41, Ts[1::2], new)
     ref, got = o.find_nearest(O, D), a.find_nearest(O, D)
-    assert np.array_equal(got["obj"], ref["obj"]) and _same(got["t"], ref["t"])
+    assert np.array_equal(got["obj"], ref["obj"]) and sp.same(got["t"], ref["t"])
     hit = ref["obj"] != -1
-    assert (ref["obj"] >= 2000).sum() >= len(O) // 4 and _same(got["normal"][hit], ref["normal"][hit])
+    assert (ref["obj"] >= 2000).sum() >= len(O) // 4 and sp.same(got["normal"][hit], ref["normal"][hit])
     assert np.array_equal(a.is_occluded(O, D), o.is_occluded(O, D)["occluded"])
     a.close()
 
@@ -226,7 +211,7 @@ def test_a_deformation_invalidates_what_set_time_invalidates(host_api, monkeypat
     assert a.set_triangles(1, d.deform(1, tr.twist(tr.grid_mesh()))) == 0
     assert L.rt_denoise(a.ctx, 2, None) == host_api.RT_E_STATE
     assert L.rt_reproject(a.ctx, None, None) == host_api.RT_E_STATE and L.rt_reproject_motion(a.ctx, None, None) == host_api.RT_E_STATE
-    assert _same(a.accumulator(), acc) and all(_same(x, y) for x, y in zip(a.stats(), stats)), "accumulator and statistics are not touched"
+    assert sp.same(a.accumulator(), acc) and all(sp.same(x, y) for x, y in zip(a.stats(), stats)), "accumulator and statistics are not touched"
     lst, n_act = a.active()
     assert n_act == 3 and lst.tolist() == [3, 5, 70], "an installed list survives"
     a.render_aovs(0.001)
@@ -302,21 +287,21 @@ def test_refusals_leave_the_scene_as_it_was(host_api, monkeypatch):
     assert b"no finite union area" in L.rt_last_error(r.ctx)
     after = _snapshot(r, 2)
     for a in before:
-        assert _same(after[a], before[a]), a
+        assert sp.same(after[a], before[a]), a
     assert np.array_equal(r.download_tlas(), tl)
     again = r.find_nearest(O, D)
-    assert all(_same(hits[k], again[k]) for k in hits)
+    assert all(sp.same(hits[k], again[k]) for k in hits)
     assert L.rt_denoise(r.ctx, 1, None) == 0, "a refused call invalidates nothing: the G-buffer is still current"
     # a transform that could take the new box beyond 1e30: instance 1 scaled by 1e9 (its box given, so the move itself is accepted) and
     # vertices of 3.5e20
-    rec = _records(host_api, [1], [r.scene.trs((0, 0, 3), 1e9, 0.0, 0.0, 0.0)])
+    rec = ir.records(host_api, [1], [r.scene.trs((0, 0, 3), 1e9, 0.0, 0.0, 0.0)])
     assert r.set_instances(1, rec, d.bounds[1:2]) == 0
     d.move(1, rec, d.bounds[1:2])
     before = _snapshot(r, 2)
     assert L.rt_set_triangles(r.ctx, 1, p(tr.triangles(t, tr.scale(tr.grid_mesh(), 1e21))), n) == ARG
     after = _snapshot(r, 2)
     for a in before:
-        assert _same(after[a], before[a]), a
+        assert sp.same(after[a], before[a]), a
     # rt_blas_array's own refusals
     nbytes = C.c_size_t(0)
     assert L.rt_blas_array(r.ctx, 1, 2, None, 0, C.byref(nbytes)) == UNSUP  # RT_LAYOUT_WIDE
@@ -362,8 +347,8 @@ def test_an_instance_without_a_box_is_refused(host_api, monkeypatch):
     assert b"no box yet" in host_api.rt_lib().rt_last_error(r.ctx)
     after = _snapshot(r, 2)
     for a in before:
-        assert _same(after[a], before[a]), a
-    rec = _records(host_api, [0], [d.inst["transform"][2]])
+        assert sp.same(after[a], before[a]), a
+    rec = ir.records(host_api, [0], [d.inst["transform"][2]])
     assert r.set_instances(2, rec) == 0
     d.move(2, rec)
     assert r.set_triangles(1, d.deform(1, tr.twist(tr.grid_mesh()))) == 0
@@ -385,7 +370,7 @@ def test_commit_triangles_reaches_every_context(host_api, monkeypatch):
         s.commit_triangles(1)
         assert np.array_equal(r.download_tlas(), s.tlas_dump()), "CommitTriangles leaves the device's tree in tl"
         d = td.Desc(host_api, s)  # the mirror's own description after the deformation: refitted nodes, fresh boxes, the downloaded TLAS
-        assert _same(tr.v9_of(d.tris[1]), new)
+        assert sp.same(tr.v9_of(d.tris[1]), new)
         for k in range(2 if devs else 1):
             ctx = r.ctx_at(k)
             assert ctx.value and (k == 0) == (ctx.value == r.ctx.value)
@@ -395,4 +380,4 @@ def test_commit_triangles_reaches_every_context(host_api, monkeypatch):
         r.tick()  # a Whitted Tick; with two contexts the rows are interleaved over them
         frames.append(r.tick_accumulator().copy())
         r.close()
-    assert _same(frames[0], frames[1]) and (frames[0][..., :3] > 0).any()
+    assert sp.same(frames[0], frames[1]) and (frames[0][..., :3] > 0).any()

@@ -41,7 +41,7 @@ LIGHT = np.dtype([("kind", np.int32), ("obj_idx", np.int32), ("pos", np.float32,
                   ("radius", np.float32), ("sin_angle", np.float32)])
 
 
-def _arr(ptr, n, dtype):
+def desc_array(ptr, n, dtype):
     return np.frombuffer(C.string_at(ptr, n * dtype.itemsize), dtype=dtype).copy() if ptr and n else np.zeros(0, dtype)
 
 
@@ -50,10 +50,10 @@ def read_desc(host_api, ptr):
     d = RtSceneDesc.from_address(ptr.value)
     blas = []
     for b in (RtBlas * d.n_blas).from_address(d.blas):
-        blas.append(dict(nodes=_arr(b.nodes, b.nodes_used, host_api.RT_BVH_NODE_DTYPE), prim_idx=_arr(b.prim_idx, b.n_prims, np.dtype(np.uint32)),
-                         tris=_arr(b.tris, b.n_tri, host_api.RT_TRIANGLE_DTYPE), n_prims=b.n_prims, n_tri=b.n_tri, n_sph=b.n_sph, n_pla=b.n_pla))
-    return dict(use_tlas=d.use_tlas, blas=blas, instances=_arr(d.instances, d.n_instances, INSTANCE), tlas=_arr(d.tlas_nodes, d.tlas_nodes_used, TLAS_NODE),
-                materials=_arr(d.materials, d.n_materials, MATERIAL))
+        blas.append(dict(nodes=desc_array(b.nodes, b.nodes_used, host_api.RT_BVH_NODE_DTYPE), prim_idx=desc_array(b.prim_idx, b.n_prims, np.dtype(np.uint32)),
+                         tris=desc_array(b.tris, b.n_tri, host_api.RT_TRIANGLE_DTYPE), n_prims=b.n_prims, n_tri=b.n_tri, n_sph=b.n_sph, n_pla=b.n_pla))
+    return dict(use_tlas=d.use_tlas, blas=blas, instances=desc_array(d.instances, d.n_instances, INSTANCE), tlas=desc_array(d.tlas_nodes, d.tlas_nodes_used, TLAS_NODE),
+                materials=desc_array(d.materials, d.n_materials, MATERIAL))
 
 
 def built(scenes, host_api, name, kw):

@@ -8,7 +8,7 @@ import numpy as np
 
 import instances_ref as ir
 import triangles_ref as tr
-from test_layout_cpu import INSTANCE, RtBlas, RtSceneDesc, _arr, read_desc
+from test_layout_cpu import INSTANCE, RtBlas, RtSceneDesc, desc_array, read_desc
 
 f32 = np.float32
 
@@ -24,8 +24,8 @@ class Desc:
         self.blas = d["blas"]
         self.tris = [np.array(b["tris"], dtype=tr.TRIANGLE) for b in self.blas]
         self.nodes = [np.array(b["nodes"], dtype=tr.BVH_NODE) for b in self.blas]
-        self.spheres = [_arr(b.spheres, b.n_sph, tr.SPHERE) for b in self.rawblas]
-        self.planes = [_arr(b.planes, b.n_pla, tr.PLANE) for b in self.rawblas]
+        self.spheres = [desc_array(b.spheres, b.n_sph, tr.SPHERE) for b in self.rawblas]
+        self.planes = [desc_array(b.planes, b.n_pla, tr.PLANE) for b in self.rawblas]
         self.inst = np.array(d["instances"], dtype=INSTANCE)
         self.n = len(self.inst)
         self.tlas = np.ascontiguousarray(d["tlas"]).view(np.uint32).reshape(-1, 8).copy()
