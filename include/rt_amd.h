@@ -517,13 +517,19 @@ int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_var_params* params);
  * rt_download_aov_instances: rows [y0, y1) of the G-buffer's instance indices, one int32 per pixel: the TLAS instance whose BLAS holds the
  *   primitive the pixel's ray hit; -1 for a miss, a light, a brute-force sphere or plane, and every hit of a scene without a TLAS.  The
  *   array is made by rt_render_aovs with the other three and goes stale with them.  Errors as rt_download_aov_positions.
+ * rt_download_aov_prims: rows [y0, y1) of the G-buffer's primitive indices, one int32 per pixel: the index of the record the pixel's ray hit
+ *   in the context's RT_LAYOUT_PRIMS array (the per-BLAS slices rt_blas_array(..., RT_LAYOUT_PRIMS) returns, in BLAS order); -1 for a
+ *   miss, a light and a brute-force sphere or plane.  Made by rt_render_aovs in the same launch, stale with the others.  Errors as
+ *   rt_download_aov_instances.
  * rt_history_capture: copies the bound accumulator, the three statistics arrays, the G-buffer arrays (the instance indices included), the
  *   current camera record and, of a scene with a TLAS, every instance's transform and inv_transform (rows 0..2: 12 + 12 floats, as they
  *   are at this moment) into history buffers of the context (allocated on first use, freed by rt_destroy): device to device on the context's stream, without
  *   synchronising.  RT_E_STATE: statistics off; the G-buffer missing or stale (rt_render_aovs first).  RT_E_UNSUPPORTED: the current
  *   camera is a fisheye.  A history stays valid until rt_upload_scene, rt_set_time, rt_set_instances or rt_stats_enable(ctx, 0); rt_clear and rt_set_camera
  *   do not touch it.  Validity has two levels: rt_set_instances ends it for rt_reproject only -- for rt_reproject_motion the history stays
- *   valid across any number of rt_set_instances calls (a failed one changes nothing for either).
+ *   valid across any number of rt_set_instances calls (a failed one changes nothing for either).  A third level is rt_reproject_deform's:
+ *   for it the history also outlives rt_set_triangles and rt_set_time, and ends with rt_upload_scene and rt_stats_enable(ctx, 0) alone
+ *   (which also frees the history's buffers).
  * rt_reproject: rewrites the accumulator and the statistics of EVERY pixel: carried from the history, or zeroed (a zero float4, count 0,
  *   sums 0).  On the context's stream; *n_carried_out (may be NULL) receives the number of carried pixels, and reading those 4 bytes back
  *   is the only synchronisation of the call.  The history is not modified (a second call gives the same result), the active-pixel list
@@ -588,7 +594,46 @@ int rt_denoise_variance(rt_ctx* ctx, const rt_denoise_var_params* params);
  *   What it does not do: it moves SAMPLES, not light.  Radiance on and around a moved object changes -- its shadow, what it reflects onto
  *   its neighbours, its own lighting as it turns towards or away from the lights -- and the carried samples there are biased until new
  *   ones outweigh them: max_history is the remedy (a small value lets new samples take over quickly).  Deforming meshes (rt_set_time,
- *   rt_set_triangles) still invalidate the history, and so does rt_upload_scene. */
+ *   rt_set_triangles) still invalidate the history for this call, and so does rt_upload_scene; rt_reproject_deform follows deformations.
+ * rt_reproject_deform: rt_reproject_motion with a third way back: a surface point of a triangle that has been rewritten since the capture
+ *   (rt_set_triangles, rt_set_time; a refit keeps the tree's shape and the leaf order, so a leaf slot names the same triangle before and
+ *   after) takes its barycentric coordinates in the current triangle to the triangle the capture saw.  The caller's sequence:
+ *     rt_render_aovs - rt_history_capture - rt_set_triangles / rt_set_time / rt_set_instances ... [- rt_set_camera] - rt_render_aovs -
+ *     rt_reproject_deform - rt_select_active / ...
+ *   Same parameters, defaults, outputs, stream ordering, single read-back, profiling entry (k_reproject_deform: one launch of
+ *   rt_profile.query), dropped budget plan and errors as rt_reproject_motion, except that RT_E_STATE follows the third level of validity:
+ *   any number of rt_set_triangles, rt_set_time and rt_set_instances calls since the capture is no error.
+ *   The capture's triangles are kept on first write: while a history is valid at this level, the first rt_set_triangles of BLAS b (and the
+ *   first rt_set_time, for BLAS 0 of a scene without a TLAS) after a capture first queues a device-to-device copy of that BLAS's
+ *   primitive records (64 B per leaf slot) into a buffer of the history, on the context's stream ahead of the rewrite; later rewrites
+ *   of b leave the copy alone, rt_history_capture makes the current records the capture's again, and the buffers grow only until
+ *   rt_destroy or rt_stats_enable(ctx, 0) frees them.  COST: with a valid history, one more copy of the BLAS's records in time and in
+ *   memory (537 MB for an 8.4 M-triangle mesh); without one, nothing is queued and nothing allocated.  The results of rt_set_triangles and
+ *   rt_set_time do not depend on a history.  A failed rt_set_triangles restores the records: the kept copy then equals them and the
+ *   bitwise rule below makes it harmless.
+ *   The definition is rt_reproject_motion's with these changes (all f32, IEEE division, no contraction; tests/reproject_deform_ref.py
+ *   restates it).  For pixel p let k = inst_p and s = prim_p (rt_download_aov_prims); R_s the current record at slot s, R'_s the
+ *   capture's: the kept copy if the BLAS of s (under a TLAS the BLAS of instance k, otherwise BLAS 0) has one, else the current record:
+ *     deformed_p = s >= 0 && the BLAS of s has a kept copy && R_s is a triangle record
+ *                  && any of the 12 words v0, v1, v2, N of R_s differs BITWISE from R'_s
+ *     !deformed_p:  x_h, n_h exactly as rt_reproject_motion defines them (an untouched triangle of a deformed mesh keeps its bits)
+ *      deformed_p:  x_o  = k >= 0 ? xform_pos(invT_k, x_p) : x_p          invT_k: the CURRENT inv_transform
+ *                   e1 = v1 - v0;  e2 = v2 - v0;  w = x_o - v0            (current vertices)
+ *                   d11 = dot(e1,e1); d12 = dot(e1,e2); d22 = dot(e2,e2); w1 = dot(w,e1); w2 = dot(w,e2)
+ *                   den = d11 * d22 - d12 * d12
+ *                   bu  = (d22 * w1 - d12 * w2) / den;   bv = (d11 * w2 - d12 * w1) / den
+ *                   e1' = v1' - v0';  e2' = v2' - v0'                     (the capture's vertices)
+ *                   x_o' = (v0' + bu * e1') + bv * e2'                    (per component)
+ *                   x_h  = k >= 0 ? xform_pos(T'_k, x_o') : x_o'          T'_k: the capture's transform
+ *                   n_h  = k >= 0 ? normalize(xform_vec(T'_k, N')) : N'   N': the capture's record's normal
+ *   n_h is the normal the capture stored for any pixel that saw the triangle.  The projection starts from d = x_h - cam'; the acceptance
+ *   is rt_reproject_motion's, unchanged (q need not have seen the same triangle: nearest-pixel snapping crosses edges on a smooth
+ *   mesh).  A degenerate current triangle (den == 0) or a singular inverse makes a NaN, which fails a comparison: the pixel starts empty.
+ *   Consequences: with no deformation since the capture, or every deformed triangle rewritten back to the same bits, the result is
+ *   bit-equal to rt_reproject_motion's (and with no instance moved either, to rt_reproject's); a second call gives the same result; the
+ *   history, the active-pixel list and the G-buffer are not touched.
+ *   What it does not do: like the motion carry it moves samples, not light -- carried samples on and around a deformed surface are biased
+ *   until new ones outweigh them (max_history) -- and it does not follow a change of topology: rt_upload_scene ends the history. */
 typedef struct { float normal_tolerance, plane_tolerance; int32_t max_history; int32_t carry_view_dependent; } rt_reproject_params;
 #define RT_REPROJECT_DEFAULTS { 0.25f, 0.01f, 0, 0 }   /* a starting point, NOT tuned */
 int rt_history_capture(rt_ctx* ctx);
@@ -596,6 +641,8 @@ int rt_reproject(rt_ctx* ctx, const rt_reproject_params* params, int* n_carried_
 int rt_reproject_motion(rt_ctx* ctx, const rt_reproject_params* params, int* n_carried_out);
 int rt_download_aov_positions(rt_ctx* ctx, int y0, int y1, float* xyz_out);
 int rt_download_aov_instances(rt_ctx* ctx, int y0, int y1, int32_t* inst_out);
+int rt_reproject_deform(rt_ctx* ctx, const rt_reproject_params* params, int* n_carried_out);
+int rt_download_aov_prims(rt_ctx* ctx, int y0, int y1, int32_t* prim_out);
 
 /* ---- Q-learning guided sampling ("next" row N4) ------------------------------------------------------
  * The reference snapshot has no code for it: README.md:36-42 names Dahm & Keller 2017, "Learning Light Transport
@@ -718,7 +765,7 @@ int rt_scene_array(rt_ctx* ctx, int which, void* out, size_t cap_bytes, size_t* 
  *     the records it had rewritten are copied back on the device: the scene is byte-equal to what it was.  (Also RT_E_UNSUPPORTED: the
  *     uploaded nodes of the BLAS were not a tree.)
  *   Invalidation is rt_set_time's: the G-buffer goes stale, the primary-hit table is rebuilt by the next dense batch, a captured history
- *     becomes invalid for rt_reproject AND rt_reproject_motion (a deformed surface has no rigid motion to take back).  Accumulator,
+ *     becomes invalid for rt_reproject AND rt_reproject_motion (a deformed surface has no rigid motion to take back; rt_reproject_deform follows it).  Accumulator,
  *     statistics and lists are untouched; a failed call invalidates nothing.  With rt_set_profiling on, the call is one entry of
  *     rt_profile.query.
  * rt_blas_array: the context's records of one BLAS, read back from the device: which in { RT_LAYOUT_PAIRS, RT_LAYOUT_PRIMS }, in

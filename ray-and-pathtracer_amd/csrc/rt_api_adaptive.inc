@@ -10,6 +10,10 @@ int rt_stats_enable(rt_ctx* c, int on)
 		c->hist.gen = 0; // a captured history (rt_history_capture) belongs to the statistics it was taken with
 		if (!c->stats.count) return RT_OK;
 		HIPCHK(c, hipStreamSynchronize(c->stream));
+		// ... and goes with them, the triangles it kept included (up to a copy of every deformed BLAS's records)
+		free_pool(c->historyAllocs);
+		c->hist = rt_ctx::History{};
+		c->keptBuf.clear(), c->keptCap.clear(), c->keptMark.clear(), c->keptDeltaHost.clear();
 		free_pool(c->adaptiveAllocs);
 		c->stats = PixelStats{};
 		return RT_OK;

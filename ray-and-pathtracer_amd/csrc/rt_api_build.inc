@@ -206,11 +206,33 @@ static void refit_launch(rt_ctx* c, const uint* order, const int* levelDev, cons
 	if (top > 0) hipLaunchKernelGGL(k_refit, dim3(1), dim3(1024), 0, c->stream, c->pairsMut, c->primsMut, order, levelDev, top);
 }
 
+// rt_reproject_deform's copy on first write (rt_ctx.h History): called by whatever is about to rewrite the primitive records of BLAS b,
+// before it queues the rewrite.  While a history is valid at the deform level and b has no kept copy yet, the records as they are -- the
+// capture's -- are copied aside on the context's stream and the kernel's table entry follows; otherwise nothing is queued.
+static int history_keep_blas(rt_ctx* c, uint32_t b)
+{
+	rt_ctx::History& H = c->hist;
+	if (!H.acc || H.gen == 0 || H.topoGen != c->topoGen) return RT_OK;
+	if (b >= c->blasKeep.size() || b >= c->keptMark.size() || b >= H.keptDeltaCap || c->keptMark[b]) return RT_OK;
+	const rt_ctx::BlasKeep& K = c->blasKeep[b];
+	if (K.slotCount == 0) return RT_OK;
+	if (c->keptCap[b] < K.slotCount) {
+		HIPCHK(c, dalloc(c->historyAllocs, &c->keptBuf[b], (size_t)K.slotCount * 4));
+		c->keptCap[b] = K.slotCount;
+	}
+	const float4* at = c->primsMut + 4 * (size_t)K.slotFirst;
+	HIPCHK(c, hipMemcpyAsync(c->keptBuf[b], at, (size_t)K.slotCount * 64, hipMemcpyDeviceToDevice, c->stream));
+	c->keptDeltaHost[b] = (long long)((const char*)c->keptBuf[b] - (const char*)at);
+	HIPCHK(c, hipMemcpyAsync(H.keptDelta + b, &c->keptDeltaHost[b], sizeof(long long), hipMemcpyHostToDevice, c->stream));
+	c->keptMark[b] = 1;
+	return RT_OK;
+}
+
 int rt_set_time(rt_ctx* c, float t)
 {
 	if (!c) return RT_E_ARG;
 	c->sceneGen++; // the G-buffer (rt_render_aovs) is stale from here on
-	c->geomGen++, c->shapeGen++;  // ... and so is a captured history (rt_history_capture)
+	c->geomGen++, c->shapeGen++;  // ... and so is a captured history, for rt_reproject and rt_reproject_motion (rt_reproject_deform follows: topoGen stays)
 	if (!c->sceneLoaded) return fail(c, RT_E_STATE, "rt_set_time: no scene uploaded");
 	if (c->S.useTLAS) return fail(c, RT_E_UNSUPPORTED, "rt_set_time: the reference animates only without the TLAS (animOn, template/scene.h:1389)");
 	if (!c->primsOrig) return RT_OK; // nothing to animate
@@ -219,6 +241,7 @@ int rt_set_time(rt_ctx* c, float t)
 	// float r = fmodf(t, 2 * PI); float a = sinf(r) * 0.5f;  (template/scene.h:1229-1230; sinf in f64, rounded once)
 	const float r = fmodf(t, 2 * RT_PI);
 	const float a = (float)sin((double)r) * 0.5f;
+	{ const int rc = history_keep_blas(c, 0); if (rc != RT_OK) return rc; } // k_animate rewrites the scene BVH's records in place
 	hipLaunchKernelGGL(k_animate, dim3((c->animSlots + 255) / 256), dim3(256), 0, c->stream, c->primsOrig, c->primsMut, c->animSlots, a);
 	refit_launch(c, c->refitOrder, c->refitLevelStart, c->refitLevelHost.data(), c->refitLevels);
 	if (c->S.wide && c->wideNodes > 0) hipLaunchKernelGGL(k_wide_sync, dim3((c->wideNodes * 4 + 255) / 256), dim3(256), 0, c->stream, c->wideMut, c->pairsMut, c->wideNodes);

@@ -11,20 +11,21 @@ int rt_render_aovs(rt_ctx* c, float t_min)
 	const size_t n = (size_t)c->width * c->height;
 	if (!c->aovNrm) {
 		float4 *nrm = nullptr, *pos = nullptr, *alb = nullptr; // (what was allocated before a failure is freed by rt_destroy)
-		int* inst = nullptr;
+		int *inst = nullptr, *prim = nullptr;
 		hipError_t e = dalloc(c->denoiseAllocs, &nrm, n);
 		if (e == hipSuccess) e = dalloc(c->denoiseAllocs, &pos, n);
 		if (e == hipSuccess) e = dalloc(c->denoiseAllocs, &alb, n);
 		if (e == hipSuccess) e = dalloc(c->denoiseAllocs, &inst, n);
+		if (e == hipSuccess) e = dalloc(c->denoiseAllocs, &prim, n);
 		if (e != hipSuccess) return fail(c, RT_E_HIP, "rt_render_aovs: %s", hipGetErrorString(e));
-		c->aovNrm = nrm, c->aovPos = pos, c->aovAlb = alb, c->aovInst = inst;
+		c->aovNrm = nrm, c->aovPos = pos, c->aovAlb = alb, c->aovInst = inst, c->aovPrim = prim;
 	}
 	c->aovGen = 0; // not current until the pass has finished
 	(void)hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), c->stream); // work heads
 	const int grid = std::min(query_grid(c, (int)n), c->gridAovs);
 	prof_begin(c, K_QUERY);
-	if (c->counting) hipLaunchKernelGGL(k_primary_aovs<true>, dim3(grid), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, t_min, tuning(c), c->aovNrm, c->aovPos, c->aovAlb, c->aovInst, c->spill, c->flags, c->counters);
-	else hipLaunchKernelGGL(k_primary_aovs<false>, dim3(grid), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, t_min, tuning(c), c->aovNrm, c->aovPos, c->aovAlb, c->aovInst, c->spill, c->flags, c->counters);
+	if (c->counting) hipLaunchKernelGGL(k_primary_aovs<true>, dim3(grid), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, t_min, tuning(c), c->aovNrm, c->aovPos, c->aovAlb, c->aovInst, c->aovPrim, c->spill, c->flags, c->counters);
+	else hipLaunchKernelGGL(k_primary_aovs<false>, dim3(grid), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, t_min, tuning(c), c->aovNrm, c->aovPos, c->aovAlb, c->aovInst, c->aovPrim, c->spill, c->flags, c->counters);
 	prof_end(c);
 	HIPCHK(c, hipGetLastError());
 	HIPCHK(c, hipStreamSynchronize(c->stream));

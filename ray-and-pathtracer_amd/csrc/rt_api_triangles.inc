@@ -70,6 +70,7 @@ int rt_set_triangles(rt_ctx* c, uint32_t blas, const rt_triangle* tris, uint32_t
 	float4* const primsAt = c->primsMut + 4 * (size_t)K.slotFirst;
 	const size_t pairBytes = (size_t)K.pairCount * 64, primBytes = (size_t)K.slotCount * 64;
 	float* const boxAt = useTLAS ? I.blasBox + (size_t)6 * blas : nullptr;
+	{ const int rc = history_keep_blas(c, blas); if (rc != RT_OK) return rc; } // a live history keeps the capture's records (rt_reproject_deform)
 
 	prof_begin(c, K_QUERY);
 	if (useTLAS) { // the undo copies
@@ -118,7 +119,8 @@ int rt_set_triangles(rt_ctx* c, uint32_t blas, const rt_triangle* tris, uint32_t
 	}
 	c->S.wide8 = nullptr; // the quantised boxes were rounded around the uploaded geometry: a refitted tree is walked through the exact nodes
 	c->sceneGen++;               // everything rt_set_time invalidates: the G-buffer and the primary-hit table ...
-	c->geomGen++, c->shapeGen++; // ... and a captured history, for rt_reproject and rt_reproject_motion alike (a deformed surface has no rigid motion to take back)
+	c->geomGen++, c->shapeGen++; // ... and a captured history, for rt_reproject and rt_reproject_motion alike (a deformed surface has no rigid motion to
+	                             // take back); rt_reproject_deform follows the deformation through the records kept above (topoGen stays)
 	return RT_OK;
 }
 

@@ -93,7 +93,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
 {
 	if (!c || !d) return fail(c, RT_E_ARG, "rt_upload_scene: null argument");
 	c->sceneGen++; // the G-buffer (rt_render_aovs) is stale from here on, whatever the outcome
-	c->geomGen++, c->shapeGen++;  // ... and so is a captured history (rt_history_capture)
+	c->geomGen++, c->shapeGen++, c->topoGen++;  // ... and so is a captured history (rt_history_capture), at every level
 	HIPCHK(c, hipSetDevice(c->device));
 	SceneLayout L;
 	std::string err;

@@ -14,7 +14,8 @@
 //   rt_api_output.inc   the output stage's shared helpers: row ranges, row downloads, the resolve, the a-trous drivers' common part
 //   rt_api_denoise.inc  rt_render_aovs, rt_denoise, rt_denoise_variance and their downloads
 //   rt_api_adaptive.inc rt_stats_*, rt_select_active, the active-pixel list, rt_render_active, rt_resolve_adaptive
-//   rt_api_reproject.inc rt_history_capture, rt_reproject, rt_reproject_motion, rt_download_aov_positions, rt_download_aov_instances
+//   rt_api_reproject.inc rt_history_capture, rt_reproject, rt_reproject_motion, rt_reproject_deform, rt_download_aov_positions,
+//                       rt_download_aov_instances, rt_download_aov_prims
 #pragma once
 #include "../../include/rt_amd.h" // first: the kernels read its enums (RT_FILTER_*)
 #include "rt_kernels.h"
@@ -281,6 +282,7 @@ struct rt_ctx {
 	std::vector<void*> denoiseAllocs;
 	float4* aovNrm = nullptr; float4* aovPos = nullptr; float4* aovAlb = nullptr; // width * height each, allocated on first use
 	int* aovInst = nullptr; // the hit's TLAS instance per pixel (-1: none), allocated and current with the three above
+	int* aovPrim = nullptr; // the hit's leaf slot in prims[] per pixel (-1: a miss, a light, a brute-force primitive), likewise
 	float4* denoiseBuf[2] = { nullptr, nullptr }; // ping-pong of the filter's iterations
 	float4* denoised = nullptr; // the buffer holding the last rt_denoise result (null: none yet)
 	float4* samples = nullptr; // finished samples of the current batch, [frame][tile pixel]
@@ -310,6 +312,11 @@ struct rt_ctx {
 	// and the history is valid for it while hist.gen != 0 && hist.shapeGen == shapeGen.  For that call the capture also keeps the G-buffer's
 	// instance indices and the instance records of its moment: xf on the device (a copy of inst[], what the kernel reads T' from), xfHost
 	// beside the host mirror InstanceState::inst (what decides, bitwise, which instances have moved).
+	// rt_reproject_deform follows deformations too, the third level: topoGen counts what shapeGen counts EXCEPT rt_set_triangles and
+	// rt_set_time, and the history is valid for it while hist.gen != 0 && hist.topoGen == topoGen.  What it needs of the capture's
+	// triangles is kept on first write (history_keep_blas, rt_api_build.inc): the first call that rewrites the records of BLAS b after a
+	// capture copies them into keptBuf[b] (history pool, grows only) and writes keptDelta[b], the kernel's table: the distance in bytes
+	// from a current record of BLAS b to its kept copy, 0 while there is none.  keptMark[b] says the copy is the capture's.
 	struct History {
 		float4* acc; float4* nrm; float4* pos; float4* alb;
 		PixelStats stats;
@@ -317,12 +324,16 @@ struct rt_ctx {
 		rt_camera cam;
 		unsigned long long gen;
 		int* inst; DInstance* xf; // width * height indices; RT_TLAS_MAX records
-		unsigned long long shapeGen;
+		unsigned long long shapeGen, topoGen;
+		long long* keptDelta; size_t keptDeltaCap; // one entry per BLAS (at least one)
 	};
 	History hist{};
 	std::vector<DInstance> histXfHost; // empty: the captured scene had no TLAS
+	std::vector<float4*> keptBuf; std::vector<size_t> keptCap; // per BLAS: its kept records, their capacity in slots
+	std::vector<char> keptMark;
+	std::vector<long long> keptDeltaHost; // what keptDelta holds (and where its updates are copied from)
 	std::vector<void*> historyAllocs;
-	unsigned long long geomGen = 1, shapeGen = 1;
+	unsigned long long geomGen = 1, shapeGen = 1, topoGen = 1;
 };
 
 // whatever changes a pixel's count or the installed list takes the budget plan made from them along (rt_api_budget.inc)

@@ -1231,9 +1231,11 @@ __global__ void __launch_bounds__(RT_BLOCK) k_primary_hits(DScene S, DCamera C, 
 //   alb   albedo rgb, w = material bits: col * albedo for a diffuse hit, col for metal / glass, the light's col for a
 //         light (objIdx in [11, 11 + nLights), the test the path kernels make), 0 for a miss
 // and one int32, inst: the TLAS instance the hit's primitive belongs to (HitRef::inst), -1 for a miss, a light, a brute-force sphere or
-// plane and every hit of a scene without a TLAS -- what rt_reproject_motion takes a point back through (rt_reproject.h)
+// plane and every hit of a scene without a TLAS -- what rt_reproject_motion takes a point back through (rt_reproject.h); and another, prim:
+// the leaf slot of the hit's record in prims[] (HitRef::prim), -1 for a miss, a light and a brute-force sphere or plane -- the triangle
+// rt_reproject_deform takes a point back through
 struct AovPolicy {
-	const DScene& S; const DCamera& C; float4* nrm; float4* pos; float4* alb; int* inst;
+	const DScene& S; const DCamera& C; float4* nrm; float4* pos; float4* alb; int* inst; int* prim;
 	__device__ __forceinline__ int slot_of(int i) const { return i; }
 	__device__ __forceinline__ bool load(int i, f3& O, f3& D, float& tm, HitRef&) const { primary_ray(C, i % C.width, i / C.width, O, D); tm = 1e34f; return true; }
 	__device__ __forceinline__ void store(int i, const HitRef& hit, const f3&, const f3&) const
@@ -1259,17 +1261,18 @@ struct AovPolicy {
 		pos[i] = mk4(P, __int_as_float(objIdx));
 		alb[i] = mk4(a, __int_as_float(mat));
 		inst[i] = hit.kind == 0 ? hit.inst : -1;
+		prim[i] = hit.kind == 0 ? (int)hit.prim : -1;
 	}
 };
 
 template <bool COUNT>
-__global__ void __launch_bounds__(RT_BLOCK) k_primary_aovs(DScene S, DCamera C, float t_min, int tuning, float4* nrm, float4* pos, float4* alb, int* inst, uint* spill, int* work, DCounters* counters)
+__global__ void __launch_bounds__(RT_BLOCK) k_primary_aovs(DScene S, DCamera C, float t_min, int tuning, float4* nrm, float4* pos, float4* alb, int* inst, int* prim, uint* spill, int* work, DCounters* counters)
 {
 	__shared__ __attribute__((aligned(16))) uint ldsStack[RT_LDS_WORDS];
 	LaneCounters lc;
 	lc.clear();
 	uint rays = 0;
-	AovPolicy pol{ S, C, nrm, pos, alb, inst };
+	AovPolicy pol{ S, C, nrm, pos, alb, inst, prim };
 	trace_persistent<false, COUNT, true>(S, pol, C.width * C.height, work + 16, t_min, tuning, ldsStack, spill, &work[1], lc, rays);
 	if (COUNT) flush_counters(counters, lc, rays, 0);
 }

@@ -304,6 +304,16 @@ int rth_renderer_commit_instances(void* h)
 	GUARD(r, r->r->CommitInstances());
 	return 0;
 }
+// Renderer::CommitTriangles of BLAS 'blas' (rth_scene_commit_triangles' numbering)
+int rth_renderer_commit_triangles(void* h, int blas)
+{
+	RthRenderer* r = (RthRenderer*)h;
+	Scene& sc = r->r->scene;
+	if (blas >= 0 && (!sc.useTLAS || blas >= rth_blas_count(&r->scene))) { r->err = "rth_renderer_commit_triangles: no such BLAS"; return -1; }
+	if (blas < 0 && !sc.b) { r->err = "rth_renderer_commit_triangles: no scene BVH"; return -1; }
+	GUARD(r, r->r->CommitTriangles(const_cast<bvh*>(pick(sc, blas))));
+	return 0;
+}
 int rth_renderer_carried_pixels(void* h) { return ((RthRenderer*)h)->r->carriedPixels; }
 int rth_renderer_active_pixels(void* h) { return ((RthRenderer*)h)->r->activePixels; }
 const float* rth_renderer_accumulator(void* h) { return &((RthRenderer*)h)->r->accumulator[0].x; }

@@ -454,6 +454,12 @@ public:
 	// A Commit() before that Tick (a new upload ends the captured history) makes it clear as well.  If scene.CommitInstances() throws, no
 	// carry is pending; context 0 then holds the camera of the last Tick until the next Tick syncs the renderer's camera, as every Tick does.
 	void CommitInstances();
+	// Scene::CommitTriangles(bv) (after the triangles of bv's mesh were rewritten) for such a renderer, the sibling of CommitInstances: under
+	// the same conditions it captures the history the same way, then calls scene.CommitTriangles(bv), and the next adaptive Tick carries
+	// the samples with rt_reproject_deform -- which subsumes the motion and the camera carry, so any sequence of CommitInstances and
+	// CommitTriangles before that Tick is one capture and one carry.  Otherwise it commits and the next Tick clears.  If
+	// scene.CommitTriangles throws, this call leaves no carry pending.
+	void CommitTriangles(bvh* bv);
 	float4* accumulator = nullptr; // host copy, refreshed by Tick
 	uint32_t* screenPixels = nullptr; // Surface::pixels analogue (template/precomp.h:134)
 	Scene scene;
@@ -477,7 +483,9 @@ private:
 	rt_camera syncedCam{};            // the record of the last SyncCamera
 	bool lastTickAdaptive = false;    // the last Tick was TickAdaptive: the accumulator holds its samples, taken under sampledCam
 	rt_camera sampledCam{};           // ... and of the last adaptive Tick: the camera the accumulator's samples were taken with
-	bool motionPending = false;       // CommitInstances captured a history and moved instances: the next adaptive Tick carries across it
+	bool CaptureForCarry();           // CommitInstances' and CommitTriangles' common head
+	bool motionPending = false;       // CommitInstances / CommitTriangles captured a history and changed the scene: the next adaptive Tick carries across it
+	bool deformPending = false;       // ... and one of the changes was a deformation: the carry is rt_reproject_deform
 	bool clearPending = false;        // CommitInstances moved instances without a capture, or Commit() followed one: the next Tick clears, with no carry
 };
 

@@ -117,24 +117,48 @@ void Renderer::Commit()
 	if (!ctx) Init();
 	scene.Commit(ctx);
 	for (size_t k = 1; k < ctxs.size(); k++) scene.CommitAlso(ctxs[k]);
-	if (motionPending) motionPending = false, clearPending = true, camera.SetChange(true); // the upload ended the history CommitInstances captured: the next Tick clears
+	if (motionPending) motionPending = deformPending = false, clearPending = true, camera.SetChange(true); // the upload ended the history CommitInstances / CommitTriangles captured: the next Tick clears
+}
+
+// what CommitInstances and CommitTriangles do before the scene's own commit: may the next adaptive Tick carry?  If so, and no capture is
+// pending yet, the history is captured under the camera of the samples
+bool Renderer::CaptureForCarry()
+{
+	const bool carry = reproject && adaptive && !scene.raytracer && adaptiveOn && lastTickAdaptive && !sampledCam.fisheye && !camera.fishEye;
+	if (carry && !motionPending) { // (a second change before the Tick: the history of the first capture still holds the samples' moment)
+		check(ctx, rt_set_camera(ctx, &sampledCam)); // the camera of the samples: already the context's unless a caller synced the new one early
+		check(ctx, rt_render_aovs(ctx, 0.001f));     // a no-op when the G-buffer is current
+		check(ctx, rt_history_capture(ctx));
+	}
+	return carry;
 }
 
 // Scene::CommitInstances for a renderer that may keep its samples: see rapt.h
 void Renderer::CommitInstances()
 {
 	if (!ctx) Init();
-	const bool carry = reproject && adaptive && !scene.raytracer && adaptiveOn && lastTickAdaptive && !sampledCam.fisheye && !camera.fishEye;
-	if (carry && !motionPending) { // (a second move before the Tick: the history of the first capture still holds the samples' moment)
-		check(ctx, rt_set_camera(ctx, &sampledCam)); // the camera of the samples: already the context's unless a caller synced the new one early
-		check(ctx, rt_render_aovs(ctx, 0.001f));     // a no-op when the G-buffer is current
-		check(ctx, rt_history_capture(ctx));
-	}
+	const bool carry = CaptureForCarry();
 	// (if this throws after the capture, context 0 keeps the camera of the samples until the next Tick syncs the renderer's, as every Tick
 	// does; nothing is pending, so that Tick treats the frame as it would have without this call)
 	scene.CommitInstances();
 	if (carry) motionPending = true;
 	else clearPending = true, camera.SetChange(true); // the accumulator holds the scene before the move: the next Tick clears (no camera carry either)
+}
+
+// Scene::CommitTriangles likewise: see rapt.h
+void Renderer::CommitTriangles(bvh* bv)
+{
+	if (!ctx) Init();
+	const bool carry = CaptureForCarry();
+	// (a throw leaves no carry pending: with several contexts the update may have reached some of them only, so a carry that an earlier
+	// call left pending becomes a clear)
+	try { scene.CommitTriangles(bv); }
+	catch (...) {
+		if (motionPending) motionPending = deformPending = false, clearPending = true, camera.SetChange(true);
+		throw;
+	}
+	if (carry) motionPending = deformPending = true;
+	else clearPending = true, camera.SetChange(true);
 }
 
 void Renderer::SyncCamera()
@@ -175,7 +199,7 @@ void Renderer::Tick(float /*deltaTime*/)
 		}
 	}
 	lastTickAdaptive = false;
-	if (motionPending) motionPending = false, camera.SetChange(true); // the carry was for an adaptive Tick: this one clears (path) or redraws
+	if (motionPending) motionPending = deformPending = false, camera.SetChange(true); // the carry was for an adaptive Tick: this one clears (path) or redraws
 	clearPending = false; // (this Tick clears on the camera change that was set with it)
 	scene.totIterationNumber++;
 	const int it = scene.GetIterationNumber();
@@ -248,7 +272,8 @@ void Renderer::TickAdaptive()
 	SyncPixelFilter();
 	sampledFilter = pixelFilter;
 	const bool motion = motionPending; // CommitInstances captured the history and moved the instances: carry with rt_reproject_motion
-	motionPending = false;
+	const bool deform = deformPending; // ... CommitTriangles deformed a mesh as well: rt_reproject_deform, which subsumes the other two carries
+	motionPending = deformPending = false;
 	const bool mustClear = clearPending; // the instances moved without a capture (or the scene was committed again): nothing to carry from
 	clearPending = false;
 	bool reset = camera.GetChange() || filterChanged || motion || mustClear;
@@ -269,7 +294,8 @@ void Renderer::TickAdaptive()
 		}
 		SyncCamera();
 		check(ctx, rt_render_aovs(ctx, 0.001f));
-		if (motion) check(ctx, rt_reproject_motion(ctx, &reprojectParams, &carriedPixels));
+		if (motion && deform) check(ctx, rt_reproject_deform(ctx, &reprojectParams, &carriedPixels));
+		else if (motion) check(ctx, rt_reproject_motion(ctx, &reprojectParams, &carriedPixels));
 		else check(ctx, rt_reproject(ctx, &reprojectParams, &carriedPixels));
 		// every pixel of context 0 is rewritten: each context gets its own rows back before it selects over them
 		for (int k = 1; k < n; k++) {

@@ -33,6 +33,7 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_render_active", "rt_resolve_adaptive", "rt_denoise_variance",
               "rt_select_budget", "rt_download_budgets", "rt_render_budget",
               "rt_history_capture", "rt_reproject", "rt_download_aov_positions", "rt_reproject_motion", "rt_download_aov_instances",
+              "rt_reproject_deform", "rt_download_aov_prims",
               "rt_select_active_rows", "rt_select_budget_rows", "rt_gather_stats_rows", "rt_gather_active",
               "rt_select_active_dilated", "rt_select_budget_dilated",
               "rt_set_pixel_filter", "rt_get_pixel_filter", "rt_sample_rays",
@@ -236,6 +237,8 @@ def rt_lib():
         L.rt_download_aov_positions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.rt_reproject_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_download_aov_instances.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.rt_reproject_deform.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_download_aov_prims.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.rt_select_active_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.rt_select_budget_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_gather_stats_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
@@ -608,6 +611,12 @@ class HostRenderer:
         the next adaptive Tick carries the samples across the move (rt_reproject_motion), otherwise it clears"""
         self._chk(self.L.rth_renderer_commit_instances(self.h))
 
+    def commit_triangles(self, blas=-1):
+        """rapt::Renderer::CommitTriangles of BLAS 'blas' (scene.commit_triangles' numbering; -1: the scene BVH): the mesh's rewritten
+        triangles (scene.set_mesh_vertices) sent on; with reproject and adaptive set the next adaptive Tick carries the samples across
+        the deformation (rt_reproject_deform), otherwise it clears"""
+        self._chk(self.L.rth_renderer_commit_triangles(self.h, int(blas)))
+
     def carried_pixels(self):
         """rapt::Renderer::carriedPixels: the pixels the last reprojecting Tick carried"""
         return int(self.L.rth_renderer_carried_pixels(self.h))
@@ -914,6 +923,19 @@ class HostRenderer:
         y1, out = self._rows(y0, y1, np.int32)
         self._rt(self.rt.rt_download_aov_instances(self.ctx, y0, y1, _p(out)))
         return out
+
+    def aov_prims(self, y0=0, y1=None):
+        """rows [y0, y1) of the G-buffer's primitive indices (int32: the record's index in the RT_LAYOUT_PRIMS array, -1: none), shaped (rows, width)"""
+        y1, out = self._rows(y0, y1, np.int32)
+        self._rt(self.rt.rt_download_aov_prims(self.ctx, y0, y1, _p(out)))
+        return out
+
+    def reproject_deform(self, params=None):
+        """rt_reproject_deform: rt_reproject_motion that also follows the meshes deformed (rt_set_triangles, rt_set_time) since the capture"""
+        p = reproject_params(params)
+        n = C.c_int(-1)
+        self._rt(self.rt.rt_reproject_deform(self.ctx, C.byref(p) if p is not None else None, C.byref(n)))
+        return n.value
 
     def history_capture(self):
         self._rt(self.rt.rt_history_capture(self.ctx))
