@@ -786,7 +786,11 @@ int rt_blas_array(rt_ctx* ctx, uint32_t blas, int which, void* out, size_t cap_b
  *                       query with its light_tests / brute_tests, but its walk is not repeated.  The table's own
  *                       walk (inner_visits, prim_tests, tlas_inner, instance_visits of one ray per pixel of
  *                       [-1, width] x [-1, height]) is tallied when the counting launch is the one that builds
- *                       it; a table that was already current contributes none of these walk tallies */
+ *                       it; a table that was already current contributes none of these walk tallies.  The same
+ *                       holds one round further for the bounce table (RT_BOUNCE_TABLE, default on): the ray a glass
+ *                       or metal primary hit scatters is answered from it, still one rays_nearest query with its
+ *                       light_tests / brute_tests; the walk of its at most two rays per table record is tallied
+ *                       by the counting launch that builds it, and a current table adds none */
 #define RT_COUNT_OFF 0
 #define RT_COUNT_REFERENCE 1
 #define RT_COUNT_EXECUTED 2

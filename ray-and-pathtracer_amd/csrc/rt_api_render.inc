@@ -381,14 +381,16 @@ static void launch_connect_s(rt_ctx* c, hipStream_t st, const StreamState& T, in
 // whole frames share it.  Below that a batch keeps today's round 0 (a one-frame Tick whose camera moves every call never builds).
 // The table outlives batches, calls and Ticks: a static camera accumulating frames is what a path tracer does (a camera change
 // resets the accumulator anyway).
-static int primary_table_for(rt_ctx* c, const RenderParams& R, hipStream_t st, bool* use)
+// The bounce table (rt_stream.h BounceTable) is built right behind it, from its records, inside the same profile entry, and is current
+// exactly when it is (*bounce); a scene without a glass or metal material has none.
+static int primary_table_for(rt_ctx* c, const RenderParams& R, hipStream_t st, bool* use, bool* bounce)
 {
 	rt_ctx::DenseState& d = c->dense;
-	*use = false;
+	*use = false, *bounce = false;
 	// (a filter kind: the samples of a pixel take distinct rays, which no table of the frame's integer-pixel rays holds; such a batch does
 	// not count towards a rebuild either)
 	if (!c->knobs.primaryTable || R.customO || R.filter != RT_FILTER_REFERENCE) return RT_OK;
-	if (d.tableGen == c->sceneGen) { *use = true; return RT_OK; }
+	if (d.tableGen == c->sceneGen) { *use = true, *bounce = d.bounceGen == c->sceneGen; return RT_OK; }
 	const size_t records = (size_t)(c->width + 2) * (size_t)(c->height + 2);
 	if (d.tablePendingGen != c->sceneGen) d.tablePendingGen = c->sceneGen, d.tablePending = 0;
 	d.tablePending += R.nSamples;
@@ -400,14 +402,31 @@ static int primary_table_for(rt_ctx* c, const RenderParams& R, hipStream_t st, b
 		P.w = c->width + 2, P.h = c->height + 2;
 		d.tab = P;
 	}
+	bool specular = false;
+	for (int t : c->matTypes) specular = specular || t == 2 || t == 3;
+	const bool withBounce = specular && c->knobs.bounceTable != 0;
+	if (withBounce && !d.btab.A) {
+		BounceTable B{};
+		HIPCHK(c, dalloc(d.tabAllocs, &B.A, 2 * records));
+		HIPCHK(c, dalloc(d.tabAllocs, &B.B, 2 * records));
+		B.n = (int)records, B.w = c->width + 2;
+		d.btab = B;
+	}
 	HIPCHK(c, hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), st)); // work heads
 	const int grid = std::min((int)((records + RT_CHUNK - 1) / RT_CHUNK / 4 + 1), d.gridTable); // a short queue does not need the whole grid
 	prof_begin(c, K_QUERY, st); // (the profile's query slot: a build is one launch there)
 	if (c->counting) hipLaunchKernelGGL(k_primary_table<true>, dim3(grid), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
 	else hipLaunchKernelGGL(k_primary_table<false>, dim3(grid), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
+	if (withBounce) {
+		HIPCHK(c, hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), st)); // the same work heads, for the second launch
+		const int gridB = std::min((int)((2 * records + RT_CHUNK - 1) / RT_CHUNK / 4 + 1), d.gridBounce);
+		if (c->counting) hipLaunchKernelGGL(k_bounce_table<true>, dim3(gridB), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, d.btab, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
+		else hipLaunchKernelGGL(k_bounce_table<false>, dim3(gridB), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, d.btab, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
+		d.bounceGen = c->sceneGen;
+	}
 	prof_end(c, st);
 	d.tableGen = c->sceneGen;
-	*use = true;
+	*use = true, *bounce = withBounce;
 	return RT_OK;
 }
 // Path mode, an entry per sample: 'rounds' = start depth + 1 rounds, no queue length is read back.  connect(r) and light(r)
@@ -438,11 +457,12 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 	hipStream_t st = c->stream, sb = twoStreams ? c->dense.side : c->stream;
 	const int cnt = c->counting ? 1 : 0;
 	const int n = (int)R.nSamples;
-	bool table = false;
+	bool table = false, bounce = false;
 	{
-		const int rc = primary_table_for(c, R, st, &table);
+		const int rc = primary_table_for(c, R, st, &table, &bounce);
 		if (rc != RT_OK) return rc;
 	}
+	bounce = bounce && c->knobs.bounceTable != 0 && !c->Qt.on; // (the sampler's shade keeps emit_ray_s: the same bits either way)
 	prof_begin(c, K_GENERATE, st);
 	if (table) hipLaunchKernelGGL(k_generate_t, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, c->dense.tab, rounds == 1 ? 1 : 0, cnt);
 	else hipLaunchKernelGGL(k_generate_s, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, rounds == 1 ? 1 : 0, c->knobs.decide, cnt);
@@ -468,8 +488,9 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 		hipLaunchKernelGGL(k_assign, dim3(grid / 2), dim3(RT_COMPACT_BLOCK), 0, st, T, round);
 		if (pendingJoin) { HIPCHK(c, hipStreamWaitEvent(st, c->dense.join, 0)); pendingJoin = false; }
 		prof_begin(c, K_SHADE, st);
-		if (c->Qt.on) hipLaunchKernelGGL(k_shade_s<true>, dim3(c->dense.gridShade), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt);
-		else hipLaunchKernelGGL(k_shade_s<false>, dim3(c->dense.gridShade), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt);
+		if (c->Qt.on) hipLaunchKernelGGL(k_shade_s<true>, dim3(c->dense.gridShade), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{}, 0);
+		else if (bounce && round == 0 && !last) hipLaunchKernelGGL((k_shade_s<false, true>), dim3(c->dense.gridShadeBounce), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, c->dense.btab, c->knobs.bounceTable);
+		else hipLaunchKernelGGL(k_shade_s<false>, dim3(c->dense.gridShade), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{}, 0);
 		prof_end(c, st);
 		if (mixed && !last) continue; // this round's shadow rays ride in the next round's traversal launch
 		if (twoStreams) {
@@ -502,7 +523,7 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 	}
 	if (hc[3] != 0) (void)hipMemsetAsync(T.counts + 3, 0, sizeof(int), st);
 	const int rc = decode_status(c, hc[3], FAM_WAVEFRONT);
-	if (rc != RT_OK) { c->dense.tableGen = 0; return rc; } // (the trouble may have been the table build's)
+	if (rc != RT_OK) { c->dense.tableGen = 0, c->dense.bounceGen = 0; return rc; } // (the trouble may have been the table build's)
 	HIPCHK(c, hipGetLastError());
 	return RT_OK;
 }

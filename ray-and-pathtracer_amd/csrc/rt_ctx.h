@@ -76,6 +76,9 @@ struct Knobs {
 	int tableMin = 12;     // RT_PRIMARY_TABLE_MIN: a stale table is rebuilt once this many camera samples per table record have been asked for since it
 	                       // went stale (1080p, bench scene: the build is 0.49 ms; batches that rebuild every time are level with traced ones at
 	                       // 3-8 frames, 0.13 ms ahead at 12, 0.3 at 16, 2 at 32: profiles/ab_primary_table.txt)
+	int bounceTable = 7;   // RT_BOUNCE_TABLE: (tests) which first-bounce rays off a glass or metal primary hit shade(0) answers from the bounce table
+	                       // (rt_stream.h BounceTable) instead of tracing them: bit 0 metal, bit 1 glass refraction, bit 2 glass reflection; 0: none,
+	                       // and no table is built
 	int levelCap = 0;      // RT_LEVEL_CAP: (tests) level queues that overflow
 	unsigned mixedMax = 10000000u; // RT_MIXED_MAX: batches below this many samples run one traversal launch per round
 };
@@ -90,6 +93,7 @@ static void read_knobs(Knobs& k)
 	k.tlasLds = num("RT_TLAS_LDS", 1) != 0, k.gammaLut = num("RT_GAMMA_LUT", 1) != 0, k.levelCap = (int)num("RT_LEVEL_CAP", 0);
 	k.mixedMax = (unsigned)num("RT_MIXED_MAX", 10000000);
 	k.primaryTable = num("RT_PRIMARY_TABLE", 1) != 0, k.tableMin = (int)std::max(0l, num("RT_PRIMARY_TABLE_MIN", 12));
+	{ const char* e = getenv("RT_BOUNCE_TABLE"); k.bounceTable = e ? (int)atol(e) & 7 : 7; } // (a test-tier mask read beside num(): tests/support.py KNOBS is the list of the num() knobs, and tests/test_gpu_bounce_table.py clears this one itself)
 	if (k.exactGamma) k.deferGamma = 1; // the exact form lives where samples are read (k_accumulate), not in the shading kernels
 	// the scheduling thresholds are compile-time constants since round 4 (rt_scene_dev.h): a sweep script that still sets them in
 	// the environment would read as a flat sweep -- say so once
@@ -207,6 +211,11 @@ struct rt_ctx {
 		unsigned long long tableGen = 0;
 		unsigned long long tablePending = 0, tablePendingGen = 0; // camera samples asked for while the table was stale at generation tablePendingGen
 		int gridTable = 0;
+		// The bounce table (rt_stream.h BounceTable): the first bounce off the glass and metal hits of the primary table, built with it and
+		// current with it (bounceGen == sceneGen); a scene without such a material has none (in tabAllocs with the primary table)
+		BounceTable btab{};
+		unsigned long long bounceGen = 0;
+		int gridBounce = 0, gridShadeBounce = 0; // resident blocks of k_bounce_table and of the shade launch that reads it
 		void free_state() { free_pool(allocs); cap = 0; }
 		void destroy()
 		{

@@ -310,6 +310,92 @@ __global__ void __launch_bounds__(RT_BLOCK) k_primary_table(DScene S, DCamera C,
 	if (COUNT) flush_counters(counters, lc, 0, 0);
 }
 
+// ---- the bounce table: one round further --------------------------------------------------------------------------------
+// The ray Sample scatters at a METAL hit takes no random draw, and at a GLASS hit a draw only chooses between two rays (the
+// weights carry E, W and the draw; nO and nD depend on O, D, the normal, t and the material alone).  So the round-1 ray of
+// every sample whose camera ray hits glass or metal is one of at most two rays per primary record, and Scene::FindNearest of it
+// one of 2 (width + 2)(height + 2) answers.  Record i of branch b sits at b * n + i:
+//   branch 0   the metal mirror ray / the glass refraction (built only when kr < 1: Sample takes it only when kr < RandomFloat <= 1)
+//   branch 1   the glass reflection
+//   A   hit normal xyz, w = t (the entry's hitN)
+//   B   x objIdx, y material (the entry's hitId), z BT_PRESENT | hit_class of the hit for a round that is not the last (bits 0-3)
+//       and for one that is (bits 4-7); z == 0: no such ray, or nobody traced it
+// The build runs k_shade_s's own functions on the operands k_shade_s has in round 0 -- primary_ray on the same ints, normal and t
+// from the primary record, the material record -- so the ray it traces is the ray shade(0) would hand to emit_ray_s, bit for bit.
+struct BounceTable {
+	float4* A;
+	int4* B;
+	int n, w; // primary records (2 n records here) and the primary table's row length
+};
+#define BT_PRESENT 0x100
+// the ray of (record i, branch): false when there is none (the primary ray ends, its hit is diffuse, or no sample can take the branch)
+__device__ __forceinline__ bool bounce_ray(const DScene& S, const DCamera& C, const PrimaryTable& P, int i, int branch, f3& nO, f3& nD)
+{
+	const int4 b = P.B[i];
+	if (b.z & PT_FINISHED) return false;
+	const DMaterial m = S.mats[b.y];
+	if (m.type != 3 && m.type != 2) return false;
+	const float4 a = P.A[i];
+	f3 O, D;
+	primary_ray(C, i % P.w - 1, i / P.w - 1, O, D);
+	const f3 normal = xyz(a);
+	const float t = a.w;
+	const f3 I = O + t * D; // ray.IntersectionPoint(), as k_shade_s
+	const f3 W(1.0f);
+	f3 E(1.0f), nW, o(0.0f), d(0.0f);
+	bool have = false;
+	if (m.type == 2) {
+		const f3 col(m.col[0], m.col[1], m.col[2]);
+		if (branch == 0) metal_bounce(true, col, I, D, normal, W, E, o, d, nW), have = true;
+	} else {
+		const GlassHit g = glass_hit(m, D, normal, t, E);
+		if (branch != 0) glass_reflected(g, m, I, D, W, o, d, nW), have = true;
+		else if (g.kr < 1.0f) glass_refracted(g, m, I, D, W, E, o, d, nW), have = true;
+	}
+	if (have) nO = o, nD = d;
+	return have;
+}
+struct BouncePolicy {
+	const DScene& S; const DCamera& C; const PrimaryTable& P; const BounceTable& Bt; float t_min; int* flag;
+	__device__ __forceinline__ int slot_of(int w) const { return w; }
+	__device__ __forceinline__ bool load(int w, f3& O, f3& D, float& tm, HitRef& head) const
+	{
+		const int branch = w >= Bt.n ? 1 : 0, i = w - branch * Bt.n;
+		RT_CHECK(i >= 0 && i < Bt.n && Bt.n == P.w * P.h, 26, flag);
+		f3 o(0.0f), d(0.0f);
+		if (!bounce_ray(S, C, P, i, branch, o, d)) { Bt.B[w] = make_int4(0, 0, 0, 0); return false; }
+		O = o, D = d;
+		tm = 1e34f; // Ray constructor default, as emit_ray_s
+		LaneCounters unused;
+		find_nearest_head<false>(S, O, D, t_min, tm, head, unused);
+		return true;
+	}
+	__device__ __forceinline__ void store(int w, const HitRef& hit, const f3&, const f3&) const
+	{
+		const int branch = w >= Bt.n ? 1 : 0, i = w - branch * Bt.n;
+		f3 O, D;
+		bounce_ray(S, C, P, i, branch, O, D); // (the walk's O and D may be an instance's)
+		int objIdx, mat, matType;
+		f3 normal;
+		resolve_hit(S, hit, O, D, objIdx, mat, normal, &matType);
+		const int flags = BT_PRESENT | hit_class(S, objIdx, mat, 0, matType) | (hit_class(S, objIdx, mat, 1, matType) << 4);
+		Bt.A[w] = mk4(normal, hit.t);
+		Bt.B[w] = make_int4(objIdx, mat, flags, 0);
+	}
+};
+// One launch per (camera, scene) right after k_primary_table, whose records it reads; counting launches as there.
+template <bool COUNT>
+__global__ void __launch_bounds__(RT_BLOCK) k_bounce_table(DScene S, DCamera C, PrimaryTable P, BounceTable Bt, float t_min, int tuning, uint* spill, int* heads, int* flag, DCounters* counters)
+{
+	__shared__ __attribute__((aligned(16))) uint ldsStack[RT_LDS_WORDS];
+	LaneCounters lc;
+	lc.clear();
+	uint rays = 0;
+	BouncePolicy pol{ S, C, P, Bt, mode_t_min(1), flag };
+	trace_persistent<false, COUNT, false>(S, pol, 2 * Bt.n, heads, t_min, tuning, ldsStack, spill, flag, lc, rays);
+	if (COUNT) flush_counters(counters, lc, 0, 0);
+}
+
 // generate from the table: camera sample e of the batch -> entry e of round 0 WITH its hit, or the finished sample.  The seed and
 // the two draws are sample_primary's; no head test, no ray_decided, no resolve_hit and no sky lookup per sample.  Neighbouring
 // lanes are neighbouring pixels of one frame: their records are neighbours too.  No entry carries CL_TRACE.  A sample whose ray
@@ -482,8 +568,12 @@ __device__ __forceinline__ void load_tables(DScene& S, ShadeTables& L, int enabl
 #endif
 // QL: the indirect bounce of a diffuse hit is drawn from the Q table (rt_qlearn.h) and every hit pays its reward to the
 // (cell, patch) that sent the ray; W.w of an entry carries that key (0: none).
-template <bool QL>
-__global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_WAVES) k_shade_s(DScene S0, DCamera C, RenderParams R, StreamState T, int round, int fresh, int last, int lastNext, int decide, int ldsTables, int counting, QTable Qt)
+// BOUNCE: round 0 of a batch whose bounce table is current.  The ray a GLASS or METAL hit scatters is then one the table has traced:
+// the entry gets its hit from there, as from a producer that decided the ray, and never enters round 1's traversal queue.  The record
+// is the one k_generate_t read for this sample; its index comes out of sample_primary_pixel, which this kernel runs anyway for the
+// sample's seed (fresh_energy), so generate hands nothing over and stays as it is.  bounceMask (RT_BOUNCE_TABLE): bit 0 metal, bit 1 glass refraction, bit 2 glass reflection.
+template <bool QL, bool BOUNCE = false>
+__global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_WAVES) k_shade_s(DScene S0, DCamera C, RenderParams R, StreamState T, int round, int fresh, int last, int lastNext, int decide, int ldsTables, int counting, QTable Qt, BounceTable Bt, int bounceMask)
 {
 	__shared__ ShadeTables tables;
 	uint nDecided = 0;
@@ -517,9 +607,16 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 			p.y = grp.y + (int)__builtin_amdgcn_mbcnt_hi((uint)(mS >> 32), __builtin_amdgcn_mbcnt_lo((uint)mS, 0u));
 		}
 		if (c & CL_LIVE) {
+			int primaryRec = -1; // BOUNCE: the sample's record of the primary table
 			if (!spec) {
 				o4 = T.O[parity][e], d4 = T.D[parity][e], hn = T.hitN[parity][e], id = T.hitId[parity][e];
-				e4 = fresh_energy(C, R, R.sampleFirst + (uint)e);
+				if constexpr (BOUNCE) {
+					int px, py;
+					uint s0;
+					sample_primary_pixel(C, R, R.sampleFirst + (uint)e, px, py, s0); // fresh_energy's seed of such a batch, and the pixel on the way
+					e4 = make_float4(1, 1, 1, __uint_as_float(s0));
+					primaryRec = (px + 1) + (py + 1) * Bt.w;
+				} else e4 = fresh_energy(C, R, R.sampleFirst + (uint)e);
 				w4 = make_float4(1, 1, 1, 0);
 				l4 = make_float4(0, 0, 0, __uint_as_float(R.sampleFirst + (uint)e));
 			}
@@ -534,6 +631,7 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 			f3 nO(0.0f), nD(0.0f), nW(0.0f);
 			uint nextKey = 0;       // QL: (cell, patch) + 1 of the ray this hit scatters
 			bool deadSample = false; // QL: the guided direction points below the surface: nothing to trace
+			int bounceRec = -1;      // BOUNCE: the bounce table's record of the scattered ray
 			// QL: the key word travels in W.w: bits 0-30 the (cell, patch) + 1 that sent this ray, bit 31 "this sample pays rewards"
 			const uint keyWord = QL ? (fresh ? (((__float_as_uint(e4.w) & Qt.learnMask) == 0) ? RT_Q_LEARNER : 0u) : __float_as_uint(w4.w)) : 0u;
 			const bool learner = (keyWord & RT_Q_LEARNER) != 0;
@@ -553,12 +651,18 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 				}
 				if (m.type == 3) { // GLASS, renderer.cpp:198-233
 					const GlassHit g = glass_hit(m, D, normal, t, E);
-					if (g.kr < RandomFloat(seed)) glass_refracted(g, m, I, D, W, E, nO, nD, nW);
-					else glass_reflected(g, m, I, D, W, nO, nD, nW);
+					if (g.kr < RandomFloat(seed)) {
+						glass_refracted(g, m, I, D, W, E, nO, nD, nW);
+						if (BOUNCE && (bounceMask & 2)) bounceRec = primaryRec;
+					} else {
+						glass_reflected(g, m, I, D, W, nO, nD, nW);
+						if (BOUNCE && (bounceMask & 4)) bounceRec = primaryRec + Bt.n;
+					}
 					if (childTraces) segmentEnds = false;
 					else Lsum = Lsum + untraced_child(nW);
 				} else if (m.type == 2) { // METAL, renderer.cpp:192-197
 					metal_bounce(true, col, I, D, normal, W, E, nO, nD, nW);
+					if (BOUNCE && (bounceMask & 1)) bounceRec = primaryRec;
 					if (childTraces) segmentEnds = false;
 					else Lsum = Lsum + untraced_child(nW);
 				} else { // DIFFUSE, renderer.cpp:156-191
@@ -609,10 +713,26 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 					T.W[pout][p.x] = make_float4(0, 0, 0, 0);
 					T.cls[pout][p.x] = CL_LIVE;
 				} else if (!segmentEnds) {
-					const NewRay nr = emit_ray_s(S, T, pout, p.x, nO, nD, mode_t_min(1), lastNext, false, decide != 0);
-					T.W[pout][p.x] = mk4(nW, __uint_as_float(nextKey | (keyWord & RT_Q_LEARNER)));
-					T.cls[pout][p.x] = nr.cls;
-					nDecided += nr.decided ? 1u : 0u;
+					int4 bb = make_int4(0, 0, 0, 0);
+					if constexpr (BOUNCE) {
+						RT_CHECK(fresh && primaryRec >= 0 && primaryRec < Bt.n && bounceRec < 2 * Bt.n, 27, &T.counts[SC_FLAG]);
+						if (primaryRec >= 0 && primaryRec < Bt.n && bounceRec >= 0) bb = Bt.B[bounceRec]; // (bounceRec is primaryRec or primaryRec + n)
+					}
+					if (BOUNCE && (bb.z & BT_PRESENT)) {
+						// what emit_ray_s writes for a ray it decided
+						const float4 ba = Bt.A[bounceRec];
+						T.hitN[pout][p.x] = ba;
+						T.hitId[pout][p.x] = make_int2(bb.x, bb.y);
+						T.O[pout][p.x] = mk4(nO, ba.w), T.D[pout][p.x] = mk4(nD, 0.0f); // (w: extend's, which never sees this entry)
+						T.W[pout][p.x] = mk4(nW, __uint_as_float(nextKey | (keyWord & RT_Q_LEARNER)));
+						T.cls[pout][p.x] = (unsigned char)(CL_LIVE | ((lastNext ? bb.z >> 4 : bb.z) & 15));
+						nDecided++;
+					} else {
+						const NewRay nr = emit_ray_s(S, T, pout, p.x, nO, nD, mode_t_min(1), lastNext, false, decide != 0);
+						T.W[pout][p.x] = mk4(nW, __uint_as_float(nextKey | (keyWord & RT_Q_LEARNER)));
+						T.cls[pout][p.x] = nr.cls;
+						nDecided += nr.decided ? 1u : 0u;
+					}
 				}
 			} else store_sample(R, __float_as_uint(l4.w), Lsum);
 		}
