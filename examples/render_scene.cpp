@@ -6,10 +6,12 @@
 //   g++ -std=c++17 -O2 examples/render_scene.cpp -Iray-and-pathtracer_amd/host \
 //       -Lray-and-pathtracer_amd/host -lrapt_host -Lray-and-pathtracer_amd/csrc -lrt_amd \
 //       -Wl,-rpath,$PWD/ray-and-pathtracer_amd/host -Wl,-rpath,$PWD/ray-and-pathtracer_amd/csrc -o render_scene
-//   ./render_scene scene.rapt out.ppm 640 360 path 16 [all | d0,d1,...] [--filter reference|point|box|tent] [--spin DEG [--carry]]
+//   ./render_scene scene.rapt out.ppm 640 360 path 16 [all | d0,d1,...] [--filter reference|point|box|tent] [--aperture R --focus D | --focus-pixel X,Y] [--spin DEG [--carry]]
 // The optional last argument spreads every Tick over several GPUs (one rt_ctx and one host thread per device,
 // rows interleaved, rt_gather_rows into device d0): "all" = every visible device.  --filter (anywhere after the frame count) sets
 // Renderer::pixelFilter: the sub-pixel camera samples of path mode (rt_set_pixel_filter; default: the reference's truncated jitter).
+// --aperture R (path mode, with a --filter other than reference) gives the camera a thin lens of radius R (Renderer::lensRadius, rt_set_lens)
+// focused at --focus D, or on what pixel X,Y sees with --focus-pixel X,Y (Renderer::FocusAt, rt_focus_at), which also prints that distance.
 // --spin DEG (a TLAS scene): before the last frame instance 0 is turned by DEG degrees about y (bvhInstance::SetTransform) and sent on with
 // Scene::CommitInstances (rt_set_instances: no re-upload); that Tick clears, so the image is the moved scene's.
 // --carry (path mode with --spin only; refused otherwise): the Ticks are adaptive with Renderer::reproject set and the move goes through Renderer::CommitInstances,
@@ -26,7 +28,7 @@ using namespace rapt;
 
 int main(int argc, char** argv)
 {
-	if (argc < 7) { fprintf(stderr, "usage: %s scene.rapt out.ppm width height whitted|path frames [all | d0,d1,...] [--filter reference|point|box|tent] [--spin DEG [--carry]]\n", argv[0]); return 2; }
+	if (argc < 7) { fprintf(stderr, "usage: %s scene.rapt out.ppm width height whitted|path frames [all | d0,d1,...] [--filter reference|point|box|tent] [--aperture R --focus D | --focus-pixel X,Y] [--spin DEG [--carry]]\n", argv[0]); return 2; }
 	int filter = RT_FILTER_REFERENCE;
 	float spin = 0;
 	bool carry = false;
@@ -39,6 +41,17 @@ int main(int argc, char** argv)
 	for (int a = 7; a + 1 < argc; a++) {
 		if (strcmp(argv[a], "--spin") != 0) continue;
 		spin = (float)atof(argv[a + 1]);
+		for (int b = a; b + 2 < argc; b++) argv[b] = argv[b + 2];
+		argc -= 2, a--;
+	}
+	float aperture = 0, focus = 1;
+	int focusX = -1, focusY = -1;
+	for (int a = 7; a + 1 < argc; a++) {
+		const bool ap = strcmp(argv[a], "--aperture") == 0, fo = strcmp(argv[a], "--focus") == 0, fp = strcmp(argv[a], "--focus-pixel") == 0;
+		if (!ap && !fo && !fp) continue;
+		if (ap) aperture = (float)atof(argv[a + 1]);
+		if (fo) focus = (float)atof(argv[a + 1]);
+		if (fp && sscanf(argv[a + 1], "%d,%d", &focusX, &focusY) != 2) { fprintf(stderr, "--focus-pixel X,Y\n"); return 2; }
 		for (int b = a; b + 2 < argc; b++) argv[b] = argv[b + 2];
 		argc -= 2, a--;
 	}
@@ -71,6 +84,12 @@ int main(int argc, char** argv)
 		app.scene.LoadFile(argv[1]);         // meshes, materials, lights, BVH / TLAS (host builders)
 		if (path) app.scene.toogleRaytracer(); // key 'P' in the reference: path tracing, lights sampled
 		app.Commit();                        // flatten + rt_upload_scene on every context
+		if (focusX >= 0) {
+			focus = app.FocusAt(focusX, focusY);
+			printf("focus distance at pixel %d,%d: %g%s\n", focusX, focusY, focus, focus > 0 ? "" : " (the sky: the lens stays off)");
+			if (!(focus > 0)) aperture = 0;
+		}
+		app.lensRadius = aperture, app.focusDistance = focus;
 		const int ticks = path ? frames : 1;
 		for (int f = 0; f < ticks; f++) {
 			if (spin != 0 && f == ticks - 1) {

@@ -210,6 +210,53 @@ enum { RT_FILTER_REFERENCE = 0, RT_FILTER_POINT = 1, RT_FILTER_BOX = 2, RT_FILTE
 int rt_set_pixel_filter(rt_ctx* ctx, int kind);
 int rt_get_pixel_filter(const rt_ctx* ctx);
 int rt_sample_rays(rt_ctx* ctx, uint32_t frame, uint32_t seed_base, int y0, int y1, float* O_out, float* D_out);
+/* ---- thin lens: depth of field for path-mode camera samples ------------------------------------------------------------------
+ * The reference's camera is a pinhole: every sample of a pixel leaves from cam_pos.  rt_set_lens gives the camera a circular aperture of
+ * 'radius' (world units) focused on the plane parallel to the screen rectangle, focus_distance from cam_pos along its normal.  The
+ * reference has no lens: this is the library's own definition, restated in numpy by tests/lens_ref.py.  radius 0 (a context's default,
+ * and what a NULL lens sets) is off: no lens draw is made and every bit is the pixel filter's.
+ * Definition of camera sample (pixel (x, y), frame f, seed_base) with radius > 0; all arithmetic f32, IEEE divide and square root, no
+ * contraction; s, StreamSeed, RandomFloat, o(), u, v are rt_set_pixel_filter's above; dot, cross and normalize are rt_reproject's and
+ * rt_reproject_motion's below; TL, TR, BL, cam are the camera's top_left, top_right, bottom_left, cam_pos:
+ *   the path's random stream: StreamSeed(s), nothing drawn (unchanged)
+ *   js = StreamSeed(~s)
+ *   BOX / TENT: u1 = RandomFloat(js); u2 = RandomFloat(js); dx = o(u1); dy = o(u2)        (POINT: no draw, dx = dy = 0)
+ *   the lens point, by rejection, on the SAME stream js, behind the filter's draws:
+ *     a = b = 0
+ *     for k in 0 .. RT_LENS_TRIES - 1:
+ *         ca = RandomFloat(js) * 2 - 1;  cb = RandomFloat(js) * 2 - 1
+ *         if ca * ca + cb * cb <= 1.0f: a = ca; b = cb; stop       (a sample refused RT_LENS_TRIES times looks through the lens centre)
+ *   A = TR - TL;  B = BL - TL;  N = cross(A, B);  E = TL - cam
+ *   screen_dist = fabsf(dot(E, N)) / sqrtf(dot(N, N))
+ *   lam = focus_distance / screen_dist                              (one number per camera and lens; the library computes it on the host)
+ *   P = (TL + u * A) + v * B   with u = (x + dx) * (1.0f / width), v = (y + dy) * (1.0f / height)          (GetPrimaryRay's P)
+ *   F = cam + lam * (P - cam)                                       (the point of the focal plane the pinhole ray looks at)
+ *   O = (cam + (a * radius) * normalize(A)) + (b * radius) * normalize(B)
+ *   D = normalize(F - O)
+ * The lens applies to the RT_MODE_PATH camera samples of rt_render, rt_render_rows, rt_render_active and rt_render_budget and to
+ * rt_sample_rays; Whitted mode, rt_trace_batch*, rt_render_aovs and rt_primary_hits ignore it.  A sample stays a function of (seed_base,
+ * pixel, frame, kind, lens) and is accumulated into its own pixel: lists, budget plans, row shards, the statistics and the split of frames
+ * into calls compose with it as with the filter.  From those calls, with radius > 0, RT_E_UNSUPPORTED (never a silent pinhole):
+ *   - kind RT_FILTER_REFERENCE (its jitter lives on the path's own stream, and the primary-hit and bounce tables serve that mode: set a
+ *     kind with rt_set_pixel_filter first);
+ *   - a fisheye camera;
+ *   - lam not finite and > 0 (a degenerate screen rectangle);
+ *   - (the Q-learning sampler is refused with any filter kind already).
+ * rt_set_lens does not clear the accumulator, does not make the G-buffer stale, does not end a captured history and drops no list or
+ * plan.  RT_E_ARG, checked before the context is touched: a radius that is negative or not finite; with radius > 0 a focus_distance
+ * that is not finite and > 0.
+ * Limits: the G-buffer, both denoisers and the three reprojections keep seeing the pinhole ray through the pixel.  A pixel far out of focus
+ * mixes surfaces its G-buffer record does not describe: the denoisers' edge stops are too sharp there, and a carry moves its samples as if
+ * the point were in focus (rt_reproject_params::max_history is the remedy at hand).  A circular aperture only: no blades, no anamorphic lens.
+ * rt_focus_at (autofocus): the focus distance that puts what pixel (x, y) sees in focus -- Camera::GetPrimaryRay(x, y) and
+ *   Scene::FindNearest(0.001f): *distance_out = t * (fabsf(dot(D, N)) / sqrtf(dot(N, N))), N as above; a miss writes 0.0f and returns
+ *   RT_OK.  It does NOT set the lens.  Synchronous; one query in rt_get_profile.  RT_E_ARG: a pixel outside the frame, a null pointer;
+ *   RT_E_STATE: no scene; RT_E_UNSUPPORTED: a fisheye camera. */
+typedef struct { float radius; float focus_distance; } rt_lens;   /* radius 0: off (a context's default) */
+#define RT_LENS_TRIES 16
+int rt_set_lens(rt_ctx* ctx, const rt_lens* lens);     /* NULL: off */
+int rt_get_lens(const rt_ctx* ctx, rt_lens* out);
+int rt_focus_at(rt_ctx* ctx, int x, int y, float* distance_out);
 /* memset of the accumulator (renderer.cpp:9, :274) */
 int rt_clear(rt_ctx* ctx);
 /* rows [y0, y1) of the float4 accumulator -> host (Renderer::accumulator, renderer.h:98) */

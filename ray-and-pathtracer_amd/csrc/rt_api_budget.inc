@@ -129,8 +129,9 @@ int rt_render_budget(rt_ctx* c, uint32_t frame_base, uint32_t seed_base, int max
 	if (!c->sceneLoaded) return fail(c, RT_E_STATE, "rt_render_budget: no scene uploaded");
 	if (!c->stats.count) return fail(c, RT_E_STATE, "rt_render_budget: statistics are off (rt_stats_enable)");
 	if (c->Qt.on) return fail(c, RT_E_UNSUPPORTED, "rt_render_budget: not with the Q-learning sampler on"); // rt_render_active's rule
+	float lam = 0.0f;
 	{
-		const int frc = filter_check(c, "rt_render_budget");
+		const int frc = filter_check(c, "rt_render_budget", &lam);
 		if (frc != RT_OK) return frc;
 	}
 	if (c->planSamples < 0 || c->nActive < 0) return fail(c, RT_E_STATE, "rt_render_budget: no budget plan (rt_select_budget; a plan serves one pass, and a render, a clear, a reprojection or a new list drops it)");
@@ -145,6 +146,7 @@ int rt_render_budget(rt_ctx* c, uint32_t frame_base, uint32_t seed_base, int max
 	R.mode = RT_MODE_PATH, R.frame0 = frame_base, R.nSamples = (uint)total, R.tilePixels = (uint)total, R.samples = c->samples;
 	R.seedBase = seed_base, R.rowFirst = 0, R.rowStride = 1, R.maxDepth = max_depth, R.accum = c->accum;
 	R.filter = c->pixelFilter;
+	set_lens(c, R, lam);
 	R.plan = c->plan.records; // sample sid is (pixel, frame_base + first + k) of its entry; the pool is entry-major
 	R.deferGamma = c->knobs.deferGamma;
 	R.sceneRt = -1;

@@ -581,13 +581,47 @@ static int stats_clear(rt_ctx* c)
 	return RT_OK;
 }
 
-// rt_set_pixel_filter's rules for a path-mode render call (include/rt_amd.h); fn: the entry point the caller came through
-static int filter_check(rt_ctx* c, const char* fn)
+// dot and cross as include/rt_amd.h defines them (rt_reproject), on the host: this translation unit is compiled with -ffp-contract=off
+// (csrc/Makefile), so these are the bits the definition of rt_set_lens names
+static float host_dot(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+// N = cross(TR - TL, BL - TL) of the camera's screen rectangle
+static void screen_normal(const DCamera& C, float* N)
 {
-	if (c->pixelFilter == RT_FILTER_REFERENCE) return RT_OK;
+	float A[3], B[3];
+	for (int i = 0; i < 3; i++) A[i] = C.topRight[i] - C.topLeft[i], B[i] = C.bottomLeft[i] - C.topLeft[i];
+	N[0] = A[1] * B[2] - A[2] * B[1], N[1] = A[2] * B[0] - A[0] * B[2], N[2] = A[0] * B[1] - A[1] * B[0];
+}
+// rt_set_lens's rules for a call that takes path-mode camera samples (include/rt_amd.h), and the lens's one derived number:
+// *lam = focus_distance / screen_dist, or 0 with the lens off
+static int lens_check(rt_ctx* c, const char* fn, float* lam)
+{
+	*lam = 0.0f;
+	if (!(c->lens.radius > 0.0f)) return RT_OK;
+	if (c->pixelFilter == RT_FILTER_REFERENCE)
+		return fail(c, RT_E_UNSUPPORTED, "%s: a lens (rt_set_lens) with RT_FILTER_REFERENCE: the reference's jitter lives on the path's own stream; set a kind with rt_set_pixel_filter first", fn);
+	if (c->C.fisheye) return fail(c, RT_E_UNSUPPORTED, "%s: a lens (rt_set_lens) under a fisheye camera", fn);
+	float N[3], E[3];
+	screen_normal(c->C, N);
+	for (int i = 0; i < 3; i++) E[i] = c->C.topLeft[i] - c->C.camPos[i];
+	const float screenDist = fabsf(host_dot(E, N)) / sqrtf(host_dot(N, N));
+	const float l = c->lens.focus_distance / screenDist;
+	if (!(std::isfinite(l) && l > 0.0f)) return fail(c, RT_E_UNSUPPORTED, "%s: a lens (rt_set_lens) over a degenerate screen rectangle (focus_distance / screen_dist = %g)", fn, (double)l);
+	*lam = l;
+	return RT_OK;
+}
+// rt_set_pixel_filter's and rt_set_lens's rules for a path-mode render call (include/rt_amd.h); fn: the entry point the caller came through
+static int filter_check(rt_ctx* c, const char* fn, float* lam)
+{
+	const int rc = lens_check(c, fn, lam);
+	if (rc != RT_OK || c->pixelFilter == RT_FILTER_REFERENCE) return rc;
 	if (c->Qt.on) return fail(c, RT_E_UNSUPPORTED, "%s: a pixel filter with the Q-learning sampler on (its learn_mask is defined on the post-jitter state)", fn);
 	if (c->C.fisheye && c->pixelFilter != RT_FILTER_POINT) return fail(c, RT_E_UNSUPPORTED, "%s: RT_FILTER_BOX / RT_FILTER_TENT under a fisheye camera", fn);
 	return RT_OK;
+}
+// the lens of a batch of camera samples (lam: filter_check's / lens_check's)
+static void set_lens(const rt_ctx* c, RenderParams& R, float lam)
+{
+	if (lam > 0.0f) R.lensRadius = c->lens.radius, R.lensLam = lam;
 }
 
 // Frames [frame0, frame0 + nframes) of one tile of pixels -- tilePixels of them: the rows row_first + k * row_stride of rt_render_rows, or
@@ -595,8 +629,9 @@ static int filter_check(rt_ctx* c, const char* fn)
 // buffer (<= 4 GiB), which k_accumulate adds to the accumulator (and, with rt_stats_enable, to the pixels' statistics) in frame order.
 static int render_batches(rt_ctx* c, int mode, uint32_t frame0, int nframes, uint32_t seed_base, int row_first, int row_stride, size_t tilePixels, const uint* pixelList, int max_depth, const char* fn)
 {
+	float lam = 0.0f;
 	if (mode == RT_MODE_PATH) {
-		const int rc = filter_check(c, fn);
+		const int rc = filter_check(c, fn, &lam);
 		if (rc != RT_OK) return rc;
 		drop_plan(c); // the batch moves the counts a budget plan was made from
 	}
@@ -619,6 +654,7 @@ static int render_batches(rt_ctx* c, int mode, uint32_t frame0, int nframes, uin
 		R.seedBase = seed_base, R.rowFirst = row_first, R.rowStride = row_stride, R.maxDepth = max_depth, R.accum = c->accum;
 		R.pixelList = pixelList;
 		R.filter = mode == RT_MODE_PATH ? c->pixelFilter : RT_FILTER_REFERENCE;
+		set_lens(c, R, lam); // (lam is 0 in Whitted mode)
 		R.deferGamma = mode == RT_MODE_PATH ? c->knobs.deferGamma : 0;
 		R.sceneRt = -1; // (rt_render is Tick's loop: the flag is what the mode says)
 		if (mode == RT_MODE_PATH && c->Qt.on && !c->pathUnsupported && !stream_eligible(c, mode, total))
@@ -721,6 +757,11 @@ int rt_sample_rays(rt_ctx* c, uint32_t frame, uint32_t seed_base, int y0, int y1
 	if (!c || !O_out || !D_out) return fail(c, RT_E_ARG, "rt_sample_rays: null argument");
 	if (y0 < 0 || y1 > c->height || y0 >= y1) return fail(c, RT_E_ARG, "rt_sample_rays: rows [%d,%d) outside 0..%d", y0, y1, c->height);
 	if (c->C.fisheye && c->pixelFilter > RT_FILTER_POINT) return fail(c, RT_E_UNSUPPORTED, "rt_sample_rays: RT_FILTER_BOX / RT_FILTER_TENT under a fisheye camera");
+	float lam = 0.0f;
+	{
+		const int lrc = lens_check(c, "rt_sample_rays", &lam);
+		if (lrc != RT_OK) return lrc;
+	}
 	HIPCHK(c, hipSetDevice(c->device));
 	const size_t n = (size_t)c->width * (size_t)(y1 - y0);
 	float *dO = nullptr, *dD = nullptr;
@@ -732,6 +773,7 @@ int rt_sample_rays(rt_ctx* c, uint32_t frame, uint32_t seed_base, int y0, int y1
 	memset(&R, 0, sizeof(R));
 	R.mode = RT_MODE_PATH, R.frame0 = frame, R.nSamples = (uint)n, R.tilePixels = (uint)n, R.seedBase = seed_base, R.rowFirst = y0, R.rowStride = 1;
 	R.sceneRt = -1, R.filter = c->pixelFilter;
+	set_lens(c, R, lam);
 	prof_begin(c, K_QUERY);
 	hipLaunchKernelGGL(k_sample_rays, dim3((unsigned)((n + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, c->stream, c->C, R, dO, dD);
 	prof_end(c);
@@ -739,5 +781,48 @@ int rt_sample_rays(rt_ctx* c, uint32_t frame, uint32_t seed_base, int y0, int y1
 	HIPCHK(c, hipMemcpyAsync(O_out, dO, 12 * n, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(c, hipMemcpyAsync(D_out, dD, 12 * n, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
+	return RT_OK;
+}
+
+// ---- thin lens (include/rt_amd.h) ------------------------------------------------------------------
+int rt_set_lens(rt_ctx* c, const rt_lens* lens)
+{
+	if (!c) return fail(c, RT_E_ARG, "rt_set_lens: null context");
+	const rt_lens off = { 0.0f, c->lens.focus_distance };
+	const rt_lens l = lens ? *lens : off;
+	if (!std::isfinite(l.radius) || l.radius < 0.0f) return fail(c, RT_E_ARG, "rt_set_lens: radius %g", (double)l.radius);
+	if (l.radius > 0.0f && !(std::isfinite(l.focus_distance) && l.focus_distance > 0.0f)) return fail(c, RT_E_ARG, "rt_set_lens: focus_distance %g", (double)l.focus_distance);
+	c->lens = l; // the accumulator, the G-buffer, a captured history, a list and a plan do not depend on it
+	return RT_OK;
+}
+int rt_get_lens(const rt_ctx* c, rt_lens* out)
+{
+	if (!c || !out) return RT_E_ARG;
+	*out = c->lens;
+	return RT_OK;
+}
+
+// Autofocus: Camera::GetPrimaryRay(x, y) on the host -- primary_ray_f's operations on whole coordinates, the bits k_primary_aovs gives the
+// pixel's ray -- then one ray through rt_intersect_batch (one launch, one query of the profile).
+int rt_focus_at(rt_ctx* c, int x, int y, float* distance_out)
+{
+	if (!c || !distance_out) return fail(c, RT_E_ARG, "rt_focus_at: null argument");
+	if (x < 0 || x >= c->width || y < 0 || y >= c->height) return fail(c, RT_E_ARG, "rt_focus_at: pixel (%d, %d) outside %d x %d", x, y, c->width, c->height);
+	if (!c->sceneLoaded) return fail(c, RT_E_STATE, "rt_focus_at: no scene uploaded");
+	if (c->C.fisheye) return fail(c, RT_E_UNSUPPORTED, "rt_focus_at: a fisheye camera");
+	const DCamera& C = c->C;
+	const float u = (float)x * (1.0f / C.width), v = (float)y * (1.0f / C.height);
+	float O[3], D[3], N[3];
+	for (int i = 0; i < 3; i++) {
+		const float P = C.topLeft[i] + u * (C.topRight[i] - C.topLeft[i]) + v * (C.bottomLeft[i] - C.topLeft[i]);
+		O[i] = C.camPos[i], D[i] = P - C.camPos[i];
+	}
+	const float invLen = 1.0f / sqrtf(host_dot(D, D));
+	for (int i = 0; i < 3; i++) D[i] = D[i] * invLen;
+	rt_hit hit;
+	const int rc = rt_intersect_batch(c, 1, O, D, nullptr, 0.001f, &hit);
+	if (rc != RT_OK) return rc;
+	screen_normal(C, N);
+	*distance_out = hit.obj_idx < 0 ? 0.0f : hit.t * (fabsf(host_dot(D, N)) / sqrtf(host_dot(N, N)));
 	return RT_OK;
 }

@@ -178,6 +178,7 @@ struct rt_ctx {
 	DCamera C{};
 	bool cameraSet = false;
 	int pixelFilter = RT_FILTER_REFERENCE; // rt_set_pixel_filter: the kind of the path-mode camera samples (RenderParams::filter of their batches)
+	rt_lens lens{ 0.0f, 1.0f }; // rt_set_lens: the thin lens of the path-mode camera samples (radius 0: off); lens_params puts it into a batch's RenderParams
 	// accumulator
 	float4* accum = nullptr;
 	bool accumOwned = true;

@@ -65,7 +65,13 @@ struct RenderParams {
 	int maxDepth;      // depth argument of Trace
 	float4* accum;     // accumulator, whole image
 	// rt_trace_batch: caller rays instead of camera rays, raw radiance out instead of accumulation
-	const float* customO; const float* customD; float4* customOut; int customDepth;
+	const float* customO;
+	// customO is the tag of these eight bytes: caller rays have their directions here, camera samples (customO null) the thin lens of a
+	// path batch (rt_set_lens): its radius (0: a pinhole) and lam = focus_distance / screen_dist, computed by the host once per launch.
+	// Nothing reads customD without customO set, and camera_sample() alone reads the lens.  (RenderParams has no padding left, and a
+	// longer DCamera or RenderParams would move the arguments of every kernel that takes one behind it.)
+	union { const float* customD; struct { float lensRadius, lensLam; }; };
+	float4* customOut; int customDepth;
 	float customE[3];  // rt_trace_batch_energy: the 'energy' argument of Trace / Sample
 	uint permShift;    // rt_mega.h: log2 of the tile the permutation deals out
 	uint permMul;      // rt_mega.h: work item w is sample (w * permMul) % nSamples (0: w itself), see run_whitted_mega
@@ -370,10 +376,44 @@ __device__ __forceinline__ float filter_offset(int kind, float u)
 	if (kind == RT_FILTER_TENT) return u < 0.5f ? sqrtf(2 * u) - 1 : 1 - sqrtf(2 - 2 * u);
 	return 0.0f;
 }
-// The ONE place that reads R.filter: camera sample (x, y, frame) of a path batch -> the state its path's random stream starts in and its
-// ray.  REFERENCE (renderer.cpp:263-278): the stream's first two draws are the jitter, truncated by primary_ray's int parameters.
+// rt_set_lens's lens point (include/rt_amd.h): rejection from the square on the jitter stream, behind the filter's draws; a lane leaves
+// the loop at its first accepted pair (probability pi / 4 a try); refused RT_LENS_TRIES times, the sample looks through the lens centre.
+__device__ __forceinline__ void lens_point(uint& js, float& a, float& b)
+{
+	a = 0.0f, b = 0.0f;
+	for (int k = 0; k < RT_LENS_TRIES; k++) {
+		const float ca = RandomFloat(js) * 2 - 1;
+		const float cb = RandomFloat(js) * 2 - 1;
+		if (ca * ca + cb * cb <= 1.0f) { a = ca, b = cb; break; }
+	}
+}
+// The thin-lens ray through the point (u, v) of the screen rectangle: primary_ray_f's P, the point F of the focal plane the pinhole ray
+// through P looks at (lam = focus_distance / screen_dist), an origin on the lens disk along the screen's two directions, and the ray from
+// there to F.  A called function, like store_gamma_sample, with everything passed by value: the kernels that start camera samples sit close
+// to occupancy steps.  Inlined, the loop and the two normalisations took k_finish from 89 to 97 VGPRs (5 -> 4 waves) and
+// k_sample_general from 166 to 175 (3 -> 2), profiles/lens_kernel_asm_diff.json.
+struct LensRay { float ox, oy, oz, dx, dy, dz; };
+__device__ __noinline__ LensRay lens_ray(f3 camPos, f3 TL, f3 TR, f3 BL, float u, float v, float radius, float lam, uint js)
+{
+	float a, b;
+	lens_point(js, a, b);
+	const f3 A = TR - TL, B = BL - TL;
+	const f3 P = TL + u * A + v * B;
+	const f3 F = camPos + lam * (P - camPos);
+	const f3 O = camPos + (a * radius) * normalize(A) + (b * radius) * normalize(B);
+	const f3 D = normalize(F - O);
+	return LensRay{ O.x, O.y, O.z, D.x, D.y, D.z };
+}
+// radius > 0, as a compare of the float's bits: the host stores a finite radius >= 0 (rt_set_lens), and an integer compare of a kernel
+// argument stays on the scalar unit
+__device__ __forceinline__ bool lens_on(const RenderParams& R) { return __float_as_int(R.lensRadius) > 0; }
+// The ONE place that reads R.filter and the lens: camera sample (x, y, frame) of a path batch -> the state its path's random stream starts
+// in and its ray.  REFERENCE (renderer.cpp:263-278): the stream's first two draws are the jitter, truncated by primary_ray's int parameters.
 // A filter kind (include/rt_amd.h rt_set_pixel_filter): the path's stream starts at StreamSeed(s) with nothing drawn, the jitter has
-// the stream StreamSeed(~s) of its own, and the ray goes through (x + dx, y + dy).  R.filter is the same for every lane of a launch.
+// the stream StreamSeed(~s) of its own, and the ray goes through (x + dx, y + dy); with a lens (rt_set_lens, radius > 0) it leaves from a
+// point of the lens disk drawn from the same jitter stream.  R.filter and R.lensRadius are the same for every lane of a launch.
+// The lens has a branch of its own BESIDE the pinhole filter's, which stays the parent's: folded into it (one jitter, then lens or
+// pinhole) k_sample_general took 169 VGPRs, one past its third wave; apart it takes 167 and k_finish its parent's 89.
 __device__ __forceinline__ void camera_sample(const DCamera& C, const RenderParams& R, int x, int y, uint frame, f3& O, f3& D, uint& seed)
 {
 	const uint s = R.seedBase + (uint)(y * C.width + x) + frame * (uint)(C.width * C.height);
@@ -383,6 +423,17 @@ __device__ __forceinline__ void camera_sample(const DCamera& C, const RenderPara
 		float newX = x + (RandomFloat(seed) * 2 - 1);
 		float newY = y + (RandomFloat(seed) * 2 - 1);
 		px = (int)newX, py = (int)newY; // jitter truncated by the int parameters (renderer.cpp:276-278)
+	} else if (lens_on(R)) { // (never under a fisheye camera or with the reference's jitter: the host refuses a lens there)
+		uint js = StreamSeed(~s);
+		float fx = (float)x, fy = (float)y;
+		if (R.filter != RT_FILTER_POINT) {
+			const float u1 = RandomFloat(js), u2 = RandomFloat(js);
+			fx = (float)x + filter_offset(R.filter, u1), fy = (float)y + filter_offset(R.filter, u2);
+		}
+		const LensRay l = lens_ray(f3(C.camPos[0], C.camPos[1], C.camPos[2]), f3(C.topLeft[0], C.topLeft[1], C.topLeft[2]), f3(C.topRight[0], C.topRight[1], C.topRight[2]),
+		                           f3(C.bottomLeft[0], C.bottomLeft[1], C.bottomLeft[2]), fx * (1.0f / C.width), fy * (1.0f / C.height), R.lensRadius, R.lensLam, js);
+		O = f3(l.ox, l.oy, l.oz), D = f3(l.dx, l.dy, l.dz);
+		return;
 	} else if (R.filter != RT_FILTER_POINT && !C.fisheye) { // (a fisheye camera has whole pixels only: the host refuses BOX / TENT there)
 		uint js = StreamSeed(~s);
 		const float u1 = RandomFloat(js), u2 = RandomFloat(js);
@@ -401,6 +452,16 @@ __device__ __forceinline__ void sample_primary(const DCamera& C, const RenderPar
 		seed = StreamSeed(R.seedBase + (uint)(y * C.width + x) + frame * (uint)(C.width * C.height));
 		primary_ray(C, x, y, O, D);
 	} else camera_sample(C, R, x, y, frame, O, D, seed);
+}
+// sample_primary's Whitted case alone, for k_whitted_mega (rt_mega.h), which serves Whitted batches only and needs no seed: compiling the
+// path branch it never takes cost it 16 to 64 bytes of scratch once the lens joined that branch.  (k_whitted_level keeps sample_primary:
+// with this function it would gain 16 bytes of scratch, with sample_primary it loses 48.)
+__device__ __forceinline__ void whitted_primary(const DCamera& C, const RenderParams& R, uint sid, f3& O, f3& D)
+{
+	int x, y;
+	uint frame;
+	sample_pixel_frame(C, R, sid, x, y, frame);
+	primary_ray(C, x, y, O, D);
 }
 // The pixel whose ray a path-mode camera sample gets: sample_primary up to its primary_ray call, on the same operands (seed: after
 // the two draws).  RandomFloat is uint * 2^-32 rounded to float: 0 gives 0 and 2^32 - 1 rounds to 1.0f, so the jitter r * 2 - 1 lies in

@@ -164,8 +164,7 @@ struct WhittedMegaPolicy {
 			D = f3(R.customD[3 * sid], R.customD[3 * sid + 1], R.customD[3 * sid + 2]);
 			E = f3(R.customE[0], R.customE[1], R.customE[2]);
 		} else {
-			uint seed;
-			sample_primary(C, R, sid, O, D, seed);
+			whitted_primary(C, R, sid, O, D);
 		}
 		M.W[gl] = make_float4(1, 1, 1, __int_as_float(start_depth(R)));
 		M.E[gl] = mk4(E, __int_as_float(0));

@@ -295,6 +295,21 @@ int rth_renderer_set_pixel_filter(void* h, int kind)
 	return 0;
 }
 int rth_renderer_pixel_filter(void* h) { return ((RthRenderer*)h)->r->pixelFilter; }
+// Renderer::lensRadius / focusDistance, sent to every context at once like the filter; a refused lens leaves the one before
+int rth_renderer_set_lens(void* h, float radius, float focusDistance)
+{
+	RthRenderer* r = (RthRenderer*)h;
+	const float r0 = r->r->lensRadius, f0 = r->r->focusDistance;
+	r->r->lensRadius = radius, r->r->focusDistance = focusDistance;
+	try { r->r->SyncLens(); } catch (const std::exception& e) { r->r->lensRadius = r0, r->r->focusDistance = f0; r->err = e.what(); return -1; }
+	return 0;
+}
+int rth_renderer_focus_at(void* h, int x, int y, float* out)
+{
+	RthRenderer* r = (RthRenderer*)h;
+	try { *out = r->r->FocusAt(x, y); } catch (const std::exception& e) { r->err = e.what(); return -1; }
+	return 0;
+}
 void rth_renderer_set_adaptive_dilate(void* h, int radius) { ((RthRenderer*)h)->r->adaptiveDilate = radius; }
 int rth_renderer_pass_samples(void* h) { return ((RthRenderer*)h)->r->passSamples; }
 // Renderer::CommitInstances: the scene's instance transforms (rth_scene_set_transforms) sent on; the next adaptive Tick carries or clears

@@ -391,6 +391,15 @@ public:
 	// other than REFERENCE with the Q-learning sampler, the path Tick throws (RT_E_UNSUPPORTED).
 	int pixelFilter = RT_FILTER_REFERENCE;
 	void SyncPixelFilter();           // pixelFilter -> every context, now (Tick does it anyway)
+	// Thin lens of the path-mode camera samples (rt_set_lens): lensRadius 0, the default, is the pinhole; with lensRadius > 0 the camera is
+	// focused on the plane focusDistance from it (FocusAt gives the distance of what a pixel sees).  Tick sends the lens with the camera and
+	// the filter, and treats a change of lens between two path Ticks as it treats a change of filter kind: it clears, with no reprojection
+	// carry.  A lens needs a pixelFilter other than REFERENCE and a pinhole camera: otherwise the path Tick throws (RT_E_UNSUPPORTED).
+	// (The G-buffer, the denoisers and the carries keep seeing the pinhole ray through the pixel: include/rt_amd.h rt_set_lens, "Limits".)
+	float lensRadius = 0.0f;
+	float focusDistance = 1.0f;
+	void SyncLens();                  // the lens -> every context, now (Tick does it anyway)
+	float FocusAt(int x, int y);      // rt_focus_at of context 0 under 'camera' (sent first) and the committed scene: 0 where the pixel sees the sky; sets nothing
 	// Denoised preview (path mode only): Tick refreshes the G-buffer when something changed (rt_render_aovs, 0.001f as Sample), filters the
 	// mean with rt_denoise and shows rt_resolve_denoised in screenPixels; 'accumulator' stays the raw download.  Off: Tick is unchanged.
 	// (The G-buffer's ray of a pixel is GetPrimaryRay(x, y): in reference mode one of the up to four integer-pixel rays its samples take,
@@ -480,6 +489,8 @@ private:
 	int wholeFrames = 0;              // whole frames rendered since the accumulator was last cleared
 	uint32_t frameBase = 0;           // 'frame' at the last clear or reprojection carry: rt_render_budget's frame_base
 	int sampledFilter = RT_FILTER_REFERENCE; // pixelFilter of the last path Tick: the kind the accumulator's samples were taken with
+	rt_lens sampledLens{ 0.0f, 1.0f }; // ... and the lens of the last path Tick
+	bool LensChanged() const { return lensRadius != sampledLens.radius || (lensRadius > 0.0f && focusDistance != sampledLens.focus_distance); }
 	rt_camera syncedCam{};            // the record of the last SyncCamera
 	bool lastTickAdaptive = false;    // the last Tick was TickAdaptive: the accumulator holds its samples, taken under sampledCam
 	rt_camera sampledCam{};           // ... and of the last adaptive Tick: the camera the accumulator's samples were taken with

@@ -179,6 +179,21 @@ void Renderer::SyncPixelFilter()
 	for (rt_ctx* k : ctxs) check(k, rt_set_pixel_filter(k, pixelFilter));
 }
 
+void Renderer::SyncLens()
+{
+	const rt_lens l = { lensRadius, focusDistance };
+	for (rt_ctx* k : ctxs) check(k, rt_set_lens(k, &l));
+}
+
+float Renderer::FocusAt(int x, int y)
+{
+	if (!ctx) Init();
+	float d = 0.0f;
+	SyncCamera(); // (an unchanged camera keeps the G-buffer current)
+	check(ctx, rt_focus_at(ctx, x, y, &d));
+	return d;
+}
+
 // renderer.cpp:240-305 without the animation, input and printf parts.  As in the reference, 'it' is read before a
 // camera change resets the iteration number (:247 vs :253-255): the frame on which the camera changed is resolved
 // with the stale count and does not advance it (:293-294).
@@ -204,9 +219,10 @@ void Renderer::Tick(float /*deltaTime*/)
 	scene.totIterationNumber++;
 	const int it = scene.GetIterationNumber();
 	SyncPixelFilter();
-	// (a path Tick under another filter kind than the last one's: like a camera change)
-	const bool camChanged = camera.GetChange() || (!scene.raytracer && pixelFilter != sampledFilter);
-	if (!scene.raytracer) sampledFilter = pixelFilter;
+	SyncLens();
+	// (a path Tick under another filter kind or lens than the last one's: like a camera change)
+	const bool camChanged = camera.GetChange() || (!scene.raytracer && (pixelFilter != sampledFilter || LensChanged()));
+	if (!scene.raytracer) sampledFilter = pixelFilter, sampledLens = { lensRadius, focusDistance };
 	if (camChanged && !scene.raytracer) {
 		scene.SetIterationNumber(1);
 		for (rt_ctx* k : ctxs) check(k, rt_clear(k)); // accumulator[...] = float3(0) for every pixel (:273-275)
@@ -268,9 +284,10 @@ void Renderer::TickAdaptive()
 	scene.totIterationNumber++;
 	const int it = scene.GetIterationNumber();
 	const int n = (int)ctxs.size();
-	const bool filterChanged = pixelFilter != sampledFilter; // like a camera change, without a carry: the carried samples would be the old kind's
+	const bool filterChanged = pixelFilter != sampledFilter || LensChanged(); // like a camera change, without a carry: the carried samples would be the old kind's or the old lens's
 	SyncPixelFilter();
-	sampledFilter = pixelFilter;
+	SyncLens();
+	sampledFilter = pixelFilter, sampledLens = { lensRadius, focusDistance };
 	const bool motion = motionPending; // CommitInstances captured the history and moved the instances: carry with rt_reproject_motion
 	const bool deform = deformPending; // ... CommitTriangles deformed a mesh as well: rt_reproject_deform, which subsumes the other two carries
 	motionPending = deformPending = false;

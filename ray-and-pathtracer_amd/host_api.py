@@ -37,6 +37,7 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_select_active_rows", "rt_select_budget_rows", "rt_gather_stats_rows", "rt_gather_active",
               "rt_select_active_dilated", "rt_select_budget_dilated",
               "rt_set_pixel_filter", "rt_get_pixel_filter", "rt_sample_rays",
+              "rt_set_lens", "rt_get_lens", "rt_focus_at",
               "rt_layout_build", "rt_layout_array", "rt_layout_free",
               "rt_set_instances", "rt_download_tlas", "rt_scene_array",
               "rt_set_triangles", "rt_blas_array"]
@@ -45,6 +46,8 @@ RT_E_ARG, RT_E_STATE = -2, -5
 # include/rt_amd.h rt_set_pixel_filter
 RT_FILTER_REFERENCE, RT_FILTER_POINT, RT_FILTER_BOX, RT_FILTER_TENT = 0, 1, 2, 3
 RT_E_UNSUPPORTED = -4
+# include/rt_amd.h rt_set_lens
+RT_LENS_TRIES = 16
 # include/rt_amd.h RT_ADAPTIVE_DEFAULTS (a starting point, not tuned)
 ADAPTIVE_DEFAULTS = dict(min_samples=16, max_samples=1024, threshold=0.05, floor=1e-3)
 # include/rt_amd.h RT_DENOISE_DEFAULTS
@@ -53,6 +56,10 @@ DENOISE_DEFAULTS = dict(iterations=5, sigma_color=0.5, sigma_normal=0.25, sigma_
 
 class RtQlearnParams(C.Structure):
     _fields_ = [("grid", C.c_int32), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("alpha", C.c_float), ("epsilon", C.c_float), ("q_init", C.c_float), ("learn_mask", C.c_uint32)]
+
+
+class RtLens(C.Structure):
+    _fields_ = [("radius", C.c_float), ("focus_distance", C.c_float)]
 
 
 class RtDenoiseParams(C.Structure):
@@ -248,6 +255,9 @@ def rt_lib():
         L.rt_set_pixel_filter.argtypes = [C.c_void_p, C.c_int]
         L.rt_get_pixel_filter.argtypes = [C.c_void_p]
         L.rt_sample_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.rt_set_lens.argtypes = [C.c_void_p, C.c_void_p]
+        L.rt_get_lens.argtypes = [C.c_void_p, C.c_void_p]
+        L.rt_focus_at.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.rt_layout_build.restype = C.c_void_p
         L.rt_layout_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.rt_layout_array.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -565,6 +575,22 @@ class HostRenderer:
     def pixel_filter(self):
         """rt_get_pixel_filter of context 0"""
         return int(self.rt.rt_get_pixel_filter(self.ctx))
+
+    def set_lens(self, radius, focus_distance=1.0):
+        """rapt::Renderer::lensRadius / focusDistance, sent to every context at once: the thin lens of the path-mode camera samples (radius 0: off)"""
+        self._chk(self.L.rth_renderer_set_lens(self.h, C.c_float(radius), C.c_float(focus_distance)))
+
+    def lens(self):
+        """rt_get_lens of context 0: (radius, focus_distance)"""
+        l = RtLens()
+        self._rt(self.rt.rt_get_lens(self.ctx, C.byref(l)))
+        return float(l.radius), float(l.focus_distance)
+
+    def focus_at(self, x, y):
+        """rapt::Renderer::FocusAt: the focus distance (np.float32) that puts what pixel (x, y) sees in focus, 0 for the sky; sets nothing"""
+        d = C.c_float(0.0)
+        self._chk(self.L.rth_renderer_focus_at(self.h, int(x), int(y), C.byref(d)))
+        return np.float32(d.value)
 
     def sample_rays(self, frame, seed_base=0x12345678, y0=0, y1=None):
         """rt_sample_rays: the camera rays (O, D), each (rows * width, 3), of frame 'frame' of the path samples under the context's filter"""
