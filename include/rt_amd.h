@@ -700,6 +700,15 @@ int rt_download_aov_prims(rt_ctx* ctx, int y0, int y1, int32_t* prim_out);
  *   [lo, hi] x 64 direction patches, P(patch) = (1 - epsilon) Q / sum Q + epsilon / 64, and collect rewards (integer sums);
  *   the table starts at q_init everywhere.  params == NULL switches the sampler off and frees the table.  Batches larger than
  *   the slot budget, and scenes that need the general path kernel, return RT_E_UNSUPPORTED while it is on.
+ *   Refused with RT_E_ARG: grid outside 1..64, a box that is empty or not finite on an axis, alpha outside (0, 1], epsilon outside
+ *   [0, 1], q_init that is not a finite number above 0 (an infinite one would make every P NaN).  The previous table is freed before
+ *   the arguments are looked at: after ANY refused rt_qlearn_enable the sampler is off, as after rt_qlearn_enable(NULL), and path
+ *   frames have the bits they had before it was ever on.
+ * rt_trace_batch* in path mode with the sampler on is a batch like any other: ray i is guided at every diffuse hit, it pays rewards
+ *   iff (the state its stream starts Sample with, InitSeed(seed_base + i)) & learn_mask == 0 -- there is no pixel jitter to draw
+ *   first -- and its rewards are added to the pending sums.  A batch that cannot have an entry per sample (n above the slot
+ *   budget, RT_COUNT_REFERENCE) returns RT_E_UNSUPPORTED as rt_render does: rgb_out, the pending sums and the accumulator stay as
+ *   they were.
  * rt_qlearn_apply: Q <- (1 - alpha) Q + alpha * mean reward, for every (cell, patch) that received one; call it BETWEEN
  *   batches (within a batch the table is read-only, so a frame does not depend on scheduling or sharding).
  * rt_qlearn_get_sums / rt_qlearn_set_sums: the pending rewards (int64 sums in 48.16 fixed point, uint32 counts, grid^3 * 64

@@ -66,6 +66,30 @@ def resolve_values(rgba, it):
     return out
 
 
+def qlearn_direction(i, j, u1, u2):
+    """QLearn::direction of each (band, sector, u1, u2): [n, 3]"""
+    i, j, u1, u2 = np.broadcast_arrays(np.asarray(i), np.asarray(j), np.asarray(u1, np.float32), np.asarray(u2, np.float32))
+    ij = np.ascontiguousarray(np.stack([i.ravel(), j.ravel()], 1), np.int32)
+    u = np.ascontiguousarray(np.stack([u1.ravel(), u2.ravel()], 1), np.float32)
+    out = np.zeros((len(ij), 3), np.float32)
+    lib().orc_qlearn_direction(len(ij), _p(ij), _p(u), _p(out))
+    return out
+
+
+def qlearn_patch_of(n):
+    """QLearn::patch_of of each vector of n [k, 3]"""
+    n = np.ascontiguousarray(n, np.float32).reshape(-1, 3)
+    return np.array([lib().orc_qlearn_patch_of(_p(v)) for v in n], np.int64)
+
+
+def qlearn_reward_fixed(R):
+    """the integer QLearn::reward adds for each reward"""
+    R = np.ascontiguousarray(R, np.float32).ravel()
+    out = np.zeros(len(R), np.int64)
+    lib().orc_qlearn_reward_fixed(len(R), _p(R), _p(out))
+    return out
+
+
 class OracleScene:
     """Scene builder + queries over the CPU restatement (oracle)."""
 
@@ -307,6 +331,26 @@ class OracleRenderer:
 
     def qlearn_patch_of(self, n):
         return int(self.L.orc_qlearn_patch_of(_f3(n)))
+
+    def qlearn_cell(self, x):
+        """QLearn::cell of each point of x [n, 3]"""
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, 3)
+        out = np.zeros(len(x), np.int32)
+        self.L.orc_qlearn_cell(self.h, len(x), _p(x), _p(out))
+        return out
+
+    def qlearn_sample(self, cells, states):
+        """QLearn::sample once per (cell, stream state): (patch, P, direction [n, 3], the state after the four draws)"""
+        cells, states = np.ascontiguousarray(cells, np.int32), np.ascontiguousarray(states, np.uint32)
+        n = len(cells)
+        patch, P, d, after = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+        self.L.orc_qlearn_sample(self.h, n, _p(cells), _p(states), _p(patch), _p(P), _p(d), _p(after))
+        return patch, P, d, after
+
+    def qlearn_weights(self):
+        w = np.zeros((64, 64), np.float32)
+        self.L.orc_qlearn_get_wgt(self.h, _p(w))
+        return w
 
     def qlearn_state(self):
         """(sums int64, counts uint32, table float32), each [grid^3, 64]"""

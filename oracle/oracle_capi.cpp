@@ -360,6 +360,34 @@ void orc_qlearn_get(void* h, long long* sums, unsigned* counts, float* table)
 }
 void orc_qlearn_set_table(void* h, const float* table) { ((OrcRenderer*)h)->r.ql.set_table(table); }
 int orc_qlearn_patch_of(const float* n) { return QLearn::patch_of(float3(n[0], n[1], n[2])); }
+// the cell of n points (x: n*3 floats) and one guided pick per (cell, stream state): patch, P, direction and the state after the four draws
+void orc_qlearn_cell(void* h, int n, const float* x, int* out)
+{
+	const QLearn& q = ((OrcRenderer*)h)->r.ql;
+	for (int i = 0; i < n; i++) out[i] = q.cell(f3(x + 3 * i));
+}
+void orc_qlearn_sample(void* h, int n, const int* cell, const unsigned* seedIn, int* patch, float* P, float* dir, unsigned* seedOut)
+{
+	const QLearn& q = ((OrcRenderer*)h)->r.ql;
+	for (int i = 0; i < n; i++) {
+		uint seed = seedIn[i];
+		const float3 d = q.sample(cell[i], seed, P[i], patch[i]);
+		dir[3 * i] = d.x, dir[3 * i + 1] = d.y, dir[3 * i + 2] = d.z, seedOut[i] = seed;
+	}
+}
+// QLearn::direction of n (band, sector, u1, u2) and the fixed-point word QLearn::reward adds for n rewards
+void orc_qlearn_direction(int n, const int* ij, const float* u, float* dir)
+{
+	for (int i = 0; i < n; i++) {
+		const float3 d = QLearn::direction(ij[2 * i], ij[2 * i + 1], u[2 * i], u[2 * i + 1]);
+		dir[3 * i] = d.x, dir[3 * i + 1] = d.y, dir[3 * i + 2] = d.z;
+	}
+}
+void orc_qlearn_reward_fixed(int n, const float* R, long long* out)
+{
+	for (int i = 0; i < n; i++) out[i] = QLearn::reward_fixed(R[i]);
+}
+void orc_qlearn_get_wgt(void* h, float* wgt) { memcpy(wgt, ((OrcRenderer*)h)->r.ql.wgt, 64 * 64 * 4); }
 void orc_qlearn_get_v(void* h, float* v, float* centres)
 {
 	const QLearn& q = ((OrcRenderer*)h)->r.ql;
@@ -393,7 +421,7 @@ void orc_trace_rays(void* h, int mode, int n, const float* O, const float* D, in
 	for (int i = 0; i < n; i++) {
 		uint seed = StreamSeed(seedBase + (uint)i);
 		Ray ray(f3(O + 3 * i), f3(D + 3 * i));
-		const float3 c = mode == 0 ? r.Trace(ray, depth, f3(energy), seed, cnt) : r.Sample(ray, depth, f3(energy), seed, cnt);
+		const float3 c = mode == 0 ? r.Trace(ray, depth, f3(energy), seed, cnt) : r.Sample(ray, depth, f3(energy), seed, cnt, 0, r.ql.on && (seed & r.ql.learnMask) == 0);
 		rgb[3 * i] = c.x, rgb[3 * i + 1] = c.y, rgb[3 * i + 2] = c.z;
 	}
 }

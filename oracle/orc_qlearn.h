@@ -97,10 +97,14 @@ struct QLearn {
 		}
 		return (i[2] * grid + i[1]) * grid + i[0];
 	}
-	void reward(uint key, float R)
+	static long long reward_fixed(float R)
 	{
 		R = (R >= 0) ? (R < 64.0f ? R : 64.0f) : 0.0f;
-		const long long fixed = llrintf(R * 65536.0f);
+		return llrintf(R * 65536.0f);
+	}
+	void reward(uint key, float R)
+	{
+		const long long fixed = reward_fixed(R);
 		__atomic_fetch_add(&sum[key - 1], fixed, __ATOMIC_RELAXED);
 		__atomic_fetch_add(&cnt[key - 1], 1u, __ATOMIC_RELAXED);
 	}

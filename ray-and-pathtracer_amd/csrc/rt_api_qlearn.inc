@@ -9,8 +9,8 @@ int rt_qlearn_enable(rt_ctx* c, const rt_qlearn_params* p)
 	if (!p) return RT_OK;
 	if (p->grid < 1 || p->grid > 64) return fail(c, RT_E_ARG, "rt_qlearn_enable: grid %d (1..64)", p->grid);
 	for (int a = 0; a < 3; a++)
-		if (!(p->hi[a] > p->lo[a])) return fail(c, RT_E_ARG, "rt_qlearn_enable: empty box on axis %d", a);
-	if (!(p->alpha > 0 && p->alpha <= 1) || !(p->epsilon >= 0 && p->epsilon <= 1) || !(p->q_init > 0)) return fail(c, RT_E_ARG, "rt_qlearn_enable: alpha in (0, 1], epsilon in [0, 1], q_init > 0");
+		if (!(p->hi[a] > p->lo[a]) || !std::isfinite(p->lo[a]) || !std::isfinite(p->hi[a])) return fail(c, RT_E_ARG, "rt_qlearn_enable: empty or non-finite box on axis %d", a);
+	if (!(p->alpha > 0 && p->alpha <= 1) || !(p->epsilon >= 0 && p->epsilon <= 1) || !(p->q_init > 0) || !std::isfinite(p->q_init)) return fail(c, RT_E_ARG, "rt_qlearn_enable: alpha in (0, 1], epsilon in [0, 1], finite q_init > 0");
 	if (c->pathUnsupported) return fail(c, RT_E_UNSUPPORTED, "rt_qlearn_enable: this scene's path mode runs the general kernel (%s)", c->pathUnsupportedWhy.c_str());
 	QTable Q;
 	memset(&Q, 0, sizeof(Q));

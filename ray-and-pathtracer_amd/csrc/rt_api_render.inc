@@ -711,6 +711,9 @@ int rt_trace_batch_energy(rt_ctx* c, int mode, int n, const float* O, const floa
 		for (int i = 0; i < 3 * n; i++) rgb_out[i] = v;
 		return RT_OK;
 	}
+	// the slot wavefront has no guided sampling (rt_render's rule, render_batches)
+	if (mode == RT_MODE_PATH && c->Qt.on && !c->pathUnsupported && c->sceneRaytracer != 1 && !stream_eligible(c, mode, (size_t)n))
+		return fail(c, RT_E_UNSUPPORTED, "rt_trace_batch: the Q-learning sampler needs a path batch with an entry per sample (within the slot budget, no RT_COUNT_REFERENCE)");
 	int rc = RT_OK;
 	float *dO = nullptr, *dD = nullptr;
 	float4* dOut = nullptr;
