@@ -463,10 +463,20 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 		if (rc != RT_OK) return rc;
 	}
 	bounce = bounce && c->knobs.bounceTable != 0 && !c->Qt.on; // (the sampler's shade keeps emit_ray_s: the same bits either way)
+	// round 0 straight from the table (k_generate_c, k_shade_s / k_light_s TABLE0): no round-0 entry is written or read.  The pinhole ray is
+	// what the kernels rebuild from the pixel, and the sampler's shade keeps its entries; RT_ROUND0_ENTRIES=1 keeps them for everybody.
+	const bool direct = table && !c->Qt.on && !c->C.fisheye && c->knobs.round0Entries != 1;
 	prof_begin(c, K_GENERATE, st);
-	if (table) hipLaunchKernelGGL(k_generate_t, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, c->dense.tab, rounds == 1 ? 1 : 0, cnt);
+	if (direct) hipLaunchKernelGGL(k_generate_c, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, c->dense.tab, rounds == 1 ? 1 : 0, cnt);
+	else if (table) hipLaunchKernelGGL(k_generate_t, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, c->dense.tab, rounds == 1 ? 1 : 0, cnt);
 	else hipLaunchKernelGGL(k_generate_s, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, rounds == 1 ? 1 : 0, c->knobs.decide, cnt);
 	prof_end(c, st);
+	if (direct && c->knobs.round0Entries == 2) { // (tests) whoever still read a round-0 entry would see NaNs and ids of -1
+		HIPCHK(c, hipMemsetAsync(T.O[0], 0xFF, (size_t)n * sizeof(float4), st));
+		HIPCHK(c, hipMemsetAsync(T.D[0], 0xFF, (size_t)n * sizeof(float4), st));
+		HIPCHK(c, hipMemsetAsync(T.hitN[0], 0xFF, (size_t)n * sizeof(float4), st));
+		HIPCHK(c, hipMemsetAsync(T.hitId[0], 0xFF, (size_t)n * sizeof(int2), st));
+	}
 	bool pendingJoin = false;
 	for (int round = 0; round < rounds; round++) {
 		const int last = round + 1 == rounds ? 1 : 0, lastNext = round + 2 == rounds ? 1 : 0;
@@ -482,15 +492,18 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 		}
 		if (mixed && round > 0) { // the shadow answers of the round before came with this round's hits
 			prof_begin(c, K_SHADE, st);
-			hipLaunchKernelGGL(k_light_s, dim3(c->dense.gridLight), dim3(RT_BLOCK), 0, st, c->S, R, T, round - 1, 0, c->knobs.shadeLds);
+			if (direct && round == 1) hipLaunchKernelGGL(k_light_s<true>, dim3(c->dense.gridLightDirect), dim3(RT_BLOCK), 0, st, c->S, R, T, round - 1, 0, c->knobs.shadeLds, c->C, c->dense.tab);
+			else hipLaunchKernelGGL(k_light_s<false>, dim3(c->dense.gridLight), dim3(RT_BLOCK), 0, st, c->S, R, T, round - 1, 0, c->knobs.shadeLds, c->C, PrimaryTable{});
 			prof_end(c, st);
 		}
 		hipLaunchKernelGGL(k_assign, dim3(grid / 2), dim3(RT_COMPACT_BLOCK), 0, st, T, round);
 		if (pendingJoin) { HIPCHK(c, hipStreamWaitEvent(st, c->dense.join, 0)); pendingJoin = false; }
 		prof_begin(c, K_SHADE, st);
-		if (c->Qt.on) hipLaunchKernelGGL(k_shade_s<true>, dim3(c->dense.gridShade), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{}, 0);
-		else if (bounce && round == 0 && !last) hipLaunchKernelGGL((k_shade_s<false, true>), dim3(c->dense.gridShadeBounce), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, c->dense.btab, c->knobs.bounceTable);
-		else hipLaunchKernelGGL(k_shade_s<false>, dim3(c->dense.gridShade), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{}, 0);
+		if (c->Qt.on) hipLaunchKernelGGL(k_shade_s<true>, dim3(c->dense.gridShade), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{}, 0, PrimaryTable{});
+		else if (direct && round == 0 && bounce && !last) hipLaunchKernelGGL((k_shade_s<false, true, true>), dim3(c->dense.gridShadeDirectBounce), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, c->dense.btab, c->knobs.bounceTable, c->dense.tab);
+		else if (direct && round == 0) hipLaunchKernelGGL((k_shade_s<false, false, true>), dim3(c->dense.gridShadeDirect), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{}, 0, c->dense.tab);
+		else if (bounce && round == 0 && !last) hipLaunchKernelGGL((k_shade_s<false, true>), dim3(c->dense.gridShadeBounce), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, c->dense.btab, c->knobs.bounceTable, PrimaryTable{});
+		else hipLaunchKernelGGL(k_shade_s<false>, dim3(c->dense.gridShade), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{}, 0, PrimaryTable{});
 		prof_end(c, st);
 		if (mixed && !last) continue; // this round's shadow rays ride in the next round's traversal launch
 		if (twoStreams) {
@@ -501,7 +514,8 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 		launch_connect_s(c, sb, T, round, twoStreams ? c->dense.sideSpill : c->spill);
 		prof_end(c, sb);
 		prof_begin(c, K_SHADE, sb);
-		hipLaunchKernelGGL(k_light_s, dim3(c->dense.gridLight), dim3(RT_BLOCK), 0, sb, c->S, R, T, round, last, c->knobs.shadeLds);
+		if (direct && round == 0) hipLaunchKernelGGL(k_light_s<true>, dim3(c->dense.gridLightDirect), dim3(RT_BLOCK), 0, sb, c->S, R, T, round, last, c->knobs.shadeLds, c->C, c->dense.tab);
+		else hipLaunchKernelGGL(k_light_s<false>, dim3(c->dense.gridLight), dim3(RT_BLOCK), 0, sb, c->S, R, T, round, last, c->knobs.shadeLds, c->C, PrimaryTable{});
 		prof_end(c, sb);
 		if (twoStreams) { HIPCHK(c, hipEventRecord(c->dense.join, sb)); pendingJoin = true; }
 	}

@@ -79,6 +79,9 @@ struct Knobs {
 	int bounceTable = 7;   // RT_BOUNCE_TABLE: (tests) which first-bounce rays off a glass or metal primary hit shade(0) answers from the bounce table
 	                       // (rt_stream.h BounceTable) instead of tracing them: bit 0 metal, bit 1 glass refraction, bit 2 glass reflection; 0: none,
 	                       // and no table is built
+	int round0Entries = 0; // RT_ROUND0_ENTRIES: 0 round 0 of a batch with a current primary table shades straight from the table (k_generate_c writes class
+	                       // bytes only; rt_stream.h k_shade_s TABLE0), 1 generate copies the records into round-0 entries first (k_generate_t),
+	                       // 2 (tests) as 0, and the entry arrays nobody may read are filled with 0xFF bytes behind every such generate
 	int levelCap = 0;      // RT_LEVEL_CAP: (tests) level queues that overflow
 	unsigned mixedMax = 10000000u; // RT_MIXED_MAX: batches below this many samples run one traversal launch per round
 };
@@ -94,6 +97,7 @@ static void read_knobs(Knobs& k)
 	k.mixedMax = (unsigned)num("RT_MIXED_MAX", 10000000);
 	k.primaryTable = num("RT_PRIMARY_TABLE", 1) != 0, k.tableMin = (int)std::max(0l, num("RT_PRIMARY_TABLE_MIN", 12));
 	{ const char* e = getenv("RT_BOUNCE_TABLE"); k.bounceTable = e ? (int)atol(e) & 7 : 7; } // (a test-tier mask read beside num(): tests/support.py KNOBS is the list of the num() knobs, and tests/test_gpu_bounce_table.py clears this one itself)
+	{ const char* e = getenv("RT_ROUND0_ENTRIES"); const long v = e ? atol(e) : 0; k.round0Entries = v == 1 || v == 2 ? (int)v : 0; } // (beside num() too: tests/test_gpu_round0_direct.py clears it itself)
 	if (k.exactGamma) k.deferGamma = 1; // the exact form lives where samples are read (k_accumulate), not in the shading kernels
 	// the scheduling thresholds are compile-time constants since round 4 (rt_scene_dev.h): a sweep script that still sets them in
 	// the environment would read as a flat sweep -- say so once
@@ -217,6 +221,7 @@ struct rt_ctx {
 		BounceTable btab{};
 		unsigned long long bounceGen = 0;
 		int gridBounce = 0, gridShadeBounce = 0; // resident blocks of k_bounce_table and of the shade launch that reads it
+		int gridShadeDirect = 0, gridShadeDirectBounce = 0, gridLightDirect = 0; // ... and of the round-0 launches that read the primary table (TABLE0)
 		void free_state() { free_pool(allocs); cap = 0; }
 		void destroy()
 		{

@@ -432,6 +432,32 @@ __global__ void __launch_bounds__(RT_BLOCK) k_generate_t(DScene S, DCamera C, Re
 	}
 	if (counting) flush_decided(T.counts, valid ? 1u : 0u);
 }
+// generate for a round 0 that shades straight from the table (k_shade_s TABLE0, k_light_s TABLE0): the class byte and the finished
+// samples, exactly k_generate_t's, and no entry.  O is the camera position, D a function of the integer pixel, the rest the record's:
+// shade(0) runs sample_primary_pixel anyway and reads the 32-byte record itself instead of the 56 bytes of a copy of it.  A is read
+// only where a finished sample is not a sky texel.  Pinhole cameras only (the host: run_rounds_stream).
+__global__ void __launch_bounds__(RT_BLOCK) k_generate_c(DScene S, DCamera C, RenderParams R, StreamState T, PrimaryTable P, int last, int counting)
+{
+	const int e = blockIdx.x * blockDim.x + threadIdx.x;
+	const bool valid = e < (int)R.nSamples;
+	prepare_round(T, 0, (int)R.nSamples);
+	if (valid) {
+		const uint sid = R.sampleFirst + (uint)e;
+		int px, py;
+		uint seed;
+		sample_primary_pixel(C, R, sid, px, py, seed);
+		RT_CHECK(px >= -1 && px <= C.width && py >= -1 && py <= C.height, 25, &T.counts[SC_FLAG]);
+		const size_t i = (size_t)(px + 1) + (size_t)(py + 1) * (size_t)P.w;
+		const int4 b = P.B[i];
+		unsigned char cls = 0;
+		if (b.z & PT_FINISHED) {
+			if ((b.z & PT_TEXEL) && S.gammaLut) R.samples[sid] = make_float4(S.gammaLut[b.w & 255], S.gammaLut[(b.w >> 8) & 255], S.gammaLut[(b.w >> 16) & 255], 0.0f);
+			else store_sample(R, sid, xyz(P.A[i]));
+		} else cls = (unsigned char)(CL_LIVE | ((last ? b.z >> 4 : b.z) & 15));
+		T.cls[0][e] = cls;
+	}
+	if (counting) flush_decided(T.counts, valid ? 1u : 0u);
+}
 
 // extend: Scene::FindNearest for the entries of the traversal queue
 struct StreamExtendPolicy {
@@ -572,9 +598,14 @@ __device__ __forceinline__ void load_tables(DScene& S, ShadeTables& L, int enabl
 // the entry gets its hit from there, as from a producer that decided the ray, and never enters round 1's traversal queue.  The record
 // is the one k_generate_t read for this sample; its index comes out of sample_primary_pixel, which this kernel runs anyway for the
 // sample's seed (fresh_energy), so generate hands nothing over and stays as it is.  bounceMask (RT_BOUNCE_TABLE): bit 0 metal, bit 1 glass refraction, bit 2 glass reflection.
-template <bool QL, bool BOUNCE = false>
-__global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_WAVES) k_shade_s(DScene S0, DCamera C, RenderParams R, StreamState T, int round, int fresh, int last, int lastNext, int decide, int ldsTables, int counting, QTable Qt, BounceTable Bt, int bounceMask)
+// TABLE0: round 0 of a batch whose generate was k_generate_c: no round-0 entry exists.  The hit is read from the sample's record of the
+// primary table P (the index out of the same sample_primary_pixel call), O is the camera position and D the pinhole ray of the integer
+// pixel: primary_ray_f on the ints k_primary_table and k_generate_t hand to primary_ray, so the bits are theirs.  The shadow record
+// refers to the table record instead of the entry (shX.x: k_light_s TABLE0).  Always launched with round 0 and fresh set.
+template <bool QL, bool BOUNCE = false, bool TABLE0 = false>
+__global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_WAVES) k_shade_s(DScene S0, DCamera C, RenderParams R, StreamState T, int round, int fresh, int last, int lastNext, int decide, int ldsTables, int counting, QTable Qt, BounceTable Bt, int bounceMask, PrimaryTable P)
 {
+	static_assert(!(QL && TABLE0), "the sampler's round 0 keeps its entries");
 	__shared__ ShadeTables tables;
 	uint nDecided = 0;
 	uint qOld = 0; // QL: the words this lane's rewards were added to, or-ed (q_reward: bit 31 = a count field past its limit)
@@ -590,7 +621,7 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 		const int e = it * (int)(gridDim.x * blockDim.x) + (int)(blockIdx.x * blockDim.x + threadIdx.x);
 		// after round 0 every entry is live: all of an entry's loads go out together, the class byte among them (round 0
 		// looks at the class first: the entries of samples finished by generate hold nothing, and they come in long runs)
-		const bool spec = !fresh && e < n;
+		const bool spec = !TABLE0 && !fresh && e < n;
 		float4 o4, d4, hn, e4, w4, l4;
 		int2 id;
 		const int2 grp = e < n ? T.pos[e >> 6] : make_int2(0, 0); // the bases of this wave's group of 64 entries (k_assign); the same for every lane that has an entry (the grid's last iteration reaches past n, and past pos[])
@@ -607,8 +638,22 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 			p.y = grp.y + (int)__builtin_amdgcn_mbcnt_hi((uint)(mS >> 32), __builtin_amdgcn_mbcnt_lo((uint)mS, 0u));
 		}
 		if (c & CL_LIVE) {
-			int primaryRec = -1; // BOUNCE: the sample's record of the primary table
-			if (!spec) {
+			int primaryRec = -1; // BOUNCE, TABLE0: the sample's record of the primary table
+			if constexpr (TABLE0) {
+				int px, py;
+				uint s0;
+				sample_primary_pixel(C, R, R.sampleFirst + (uint)e, px, py, s0);
+				primaryRec = (px + 1) + (py + 1) * P.w;
+				RT_CHECK(fresh && round == 0 && primaryRec >= 0 && primaryRec < P.w * P.h && (!BOUNCE || (Bt.w == P.w && Bt.n == P.w * P.h)), 28, &T.counts[SC_FLAG]);
+				hn = P.A[primaryRec];
+				id = *(const int2*)(P.B + primaryRec); // x objIdx, y material
+				f3 o, d;
+				primary_ray_f(C, (float)px, (float)py, o, d);
+				o4 = mk4(o, 0.0f), d4 = mk4(d, 0.0f);
+				e4 = make_float4(1, 1, 1, __uint_as_float(s0));
+				w4 = make_float4(1, 1, 1, 0);
+				l4 = make_float4(0, 0, 0, __uint_as_float(R.sampleFirst + (uint)e));
+			} else if (!spec) {
 				o4 = T.O[parity][e], d4 = T.D[parity][e], hn = T.hitN[parity][e], id = T.hitId[parity][e];
 				if constexpr (BOUNCE) {
 					int px, py;
@@ -701,7 +746,7 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 			RT_CHECK(((c & CL_SHADOW) != 0) == wantShadow && ((c & CL_CONT) != 0) == (!segmentEnds || wantShadow), 22, &T.counts[SC_FLAG]);
 			if (wantShadow) {
 				T.shI[p.y] = mk4(I, __uint_as_float(shadowSeed));
-				T.shX[p.y] = make_int2(e, p.x);
+				T.shX[p.y] = make_int2(TABLE0 ? primaryRec : e, p.x);
 			}
 			if (!segmentEnds || wantShadow) {
 				T.E[pout][p.x] = mk4(E, __uint_as_float(seed));
@@ -813,7 +858,10 @@ __global__ void __launch_bounds__(RT_BLOCK, RT_TRAVERSE_WAVES) k_traverse_s(DSce
 
 // light: the direct-light terms of a diffuse hit, in light order (renderer.cpp:158-176: occlusion test first, scatter
 // only when visible), added to the radiance of the path's continuation entry; in the last round the sample is complete.
-__global__ void RT_LIGHT_BOUNDS k_light_s(DScene S0, RenderParams R, StreamState T, int round, int last, int ldsTables)
+// TABLE0: light(0) behind a shade(0) that read the primary table: shX.x is the table record, the normal and the material are its
+// fields and D the pinhole ray of its pixel (TablePolicy::ray's ints); W stays 1.
+template <bool TABLE0>
+__global__ void RT_LIGHT_BOUNDS k_light_s(DScene S0, RenderParams R, StreamState T, int round, int last, int ldsTables, DCamera C, PrimaryTable P)
 {
 	__shared__ ShadeTables tables;
 	DScene S = S0;
@@ -825,11 +873,18 @@ __global__ void RT_LIGHT_BOUNDS k_light_s(DScene S0, RenderParams R, StreamState
 		const float4 i4 = T.shI[s];
 		const int2 x = T.shX[s];
 		const int e = x.x, cp = x.y;
-		RT_CHECK(e >= 0 && e < T.cap && cp >= 0 && cp < T.cap, 24, &T.counts[SC_FLAG]);
+		RT_CHECK(e >= 0 && e < (TABLE0 ? P.w * P.h : T.cap) && cp >= 0 && cp < T.cap && (!TABLE0 || round == 0), 24, &T.counts[SC_FLAG]);
 		// the hit's own fields from entry e of this round (shade(round + 1) has not run yet); a round-0 entry has no W: shade took 1 (fresh)
-		const float4 n4 = T.hitN[p][e], d4 = T.D[p][e];
-		const int mat = T.hitId[p][e].y;
-		const f3 W = round == 0 ? f3(1.0f) : xyz(T.W[p][e]);
+		float4 n4, d4;
+		int mat;
+		if constexpr (TABLE0) {
+			n4 = P.A[e];
+			mat = P.B[e].y;
+			f3 o, d;
+			primary_ray_f(C, (float)(e % P.w - 1), (float)(e / P.w - 1), o, d);
+			d4 = mk4(d, 0.0f);
+		} else n4 = T.hitN[p][e], d4 = T.D[p][e], mat = T.hitId[p][e].y;
+		const f3 W = TABLE0 || round == 0 ? f3(1.0f) : xyz(T.W[p][e]);
 		const float4 e4 = T.E[pout][cp], l4 = T.L[pout][cp];
 		const f3 I = xyz(i4), normal = xyz(n4), D = xyz(d4);
 		f3 E = xyz(e4), Lsum = xyz(l4);
