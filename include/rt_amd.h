@@ -831,6 +831,44 @@ int rt_scene_array(rt_ctx* ctx, int which, void* out, size_t cap_bytes, size_t* 
 int rt_set_triangles(rt_ctx* ctx, uint32_t blas, const rt_triangle* tris, uint32_t n_tri);
 int rt_blas_array(rt_ctx* ctx, uint32_t blas, int which, void* out, size_t cap_bytes, size_t* bytes_out);
 
+/* ---- deforming an indexed mesh from its vertices alone -----------------------------------------------------------
+ * A triangle record is 56 bytes, repeats every shared vertex and carries a normal the caller derived on the host.  An indexed mesh is
+ * deformed by sending its vertex array alone, from host memory or straight from device memory (a skinning, cloth or morph step that already
+ * runs on the GPU): the records are assembled, the normals derived and the call's checks reduced on the device.
+ * rt_set_mesh_indices binds an index buffer to BLAS 'blas' of the loaded scene: triangle p has the corners idx[3p], idx[3p + 1],
+ *   idx[3p + 2], 0-based.  idx is host memory; it is checked, then copied to the device and kept per BLAS (12 bytes per triangle); it has
+ *   been read when the call returns.  RT_E_ARG, before anything is copied: n_tri different from the uploaded n_tri, n_vertices < 1, an
+ *   index >= n_vertices (the message names the first such triangle), blas >= n_blas.  idx == NULL unbinds (n_tri and n_vertices are not
+ *   looked at).  The binding survives rt_set_triangles, rt_set_instances, rt_set_time and the two calls below and ends with
+ *   rt_upload_scene and rt_destroy.  It touches nothing of the scene and invalidates nothing.  RT_E_STATE: no scene.
+ * rt_set_vertices: xyz is n_vertices points of three floats in host memory.  The context ends byte for byte as after
+ *   rt_set_triangles(ctx, blas, T, n_tri) with, for every primitive p,
+ *     T[p].v0 = V[idx[3p]], T[p].v1 = V[idx[3p + 1]], T[p].v2 = V[idx[3p + 2]],
+ *     T[p].N = Triangle::update's (template/scene.h:238-246): normalize(cross(v1 - v0, v2 - v0)), cross as a.y * b.z - a.z * b.y ..., dot
+ *       as (xx + yy) + zz, N = c * (1 / sqrtf(dot)), every operation rounded to f32 on its own (IEEE divide and square root, no contraction),
+ *     T[p].obj_idx, T[p].material = what primitive p's record holds now (from the upload or the last rt_set_triangles; a primitive prim_idx
+ *       never names has no record and gets none).
+ *   A degenerate triangle gets the NaN normal the reference gives it; which NaN (sign, payload) is the device's, in N.x, N.y, N.z and d of
+ *   that one record.  Everything else is rt_set_triangles' own: with and without a TLAS, atomic failure, the same invalidation, the kept
+ *   records for rt_reproject_deform, the 8-wide walk switched off, the originals of a later rt_set_time refreshed, one rt_profile.query
+ *   entry.  The refusals are that call's on the assembled triangles -- RT_E_ARG: a coordinate of a REFERENCED vertex that is non-finite or
+ *   beyond 1e29 (the message names a triangle that has one; a vertex no triangle names is never looked at and may hold anything), a
+ *   transform that takes the new box beyond 1e30, an instance of another BLAS without a box; RT_E_UNSUPPORTED: a BLAS that is not a tree,
+ *   a TLAS build without a finite union area (the records restored) -- and three of its own: RT_E_STATE: no indices are bound to the
+ *   BLAS; RT_E_ARG: n_vertices differs from the bound count; RT_E_ARG: a null pointer.
+ * rt_set_vertices_device: the same call with dev_xyz in device memory of the context's device.  The pointer is looked up with
+ *   hipPointerGetAttributes before anything is queued: RT_E_ARG if it is not device memory of that device, not 4-byte aligned, or if
+ *   n_vertices points do not fit the allocation behind it.  The library reads the array on its OWN stream: the caller orders the work that
+ *   produces the array before the call (synchronise the producing stream, or make the context's stream wait for it).
+ *   Synchronisation: both calls read one 56-byte record (boxes and flags) back before any byte of the scene is rewritten; with the TLAS
+ *     build's 4-byte read-back these are their only synchronisations.  That read-back follows the kernel that reads the vertices: when
+ *     either call returns, successful or refused, xyz / dev_xyz has been read in full and is the caller's again (page-locked memory
+ *     included).  This differs from rt_set_triangles, which without a TLAS does not synchronise at all: here the read-back is the one
+ *     synchronisation such a scene's call has. */
+int rt_set_mesh_indices(rt_ctx* ctx, uint32_t blas, const uint32_t* idx, uint32_t n_tri, uint32_t n_vertices);
+int rt_set_vertices(rt_ctx* ctx, uint32_t blas, const float* xyz, uint32_t n_vertices);            /* host memory   */
+int rt_set_vertices_device(rt_ctx* ctx, uint32_t blas, const float* dev_xyz, uint32_t n_vertices); /* device memory */
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Kernels tally rt_counters (slower; keep off when timing).
  *   RT_COUNT_REFERENCE  the walk bvh::BIntersect / tlas::Intersect make: the DataCollector tallies

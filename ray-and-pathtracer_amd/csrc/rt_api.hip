@@ -83,7 +83,7 @@ rt_ctx* rt_create(int device, int width, int height)
 	ok = ok && hipMemset(c->flags, 0, (16 + RT_HEADS * RT_HEAD_STRIDE) * sizeof(int)) == hipSuccess;
 	ok = ok && hipMalloc((void**)&c->counters, 2 * sizeof(DCounters)) == hipSuccess;
 	ok = ok && hipMemset(c->counters, 0, 2 * sizeof(DCounters)) == hipSuccess;
-	ok = ok && hipHostMalloc((void**)&c->hostCounts, 16 * sizeof(int)) == hipSuccess;
+	ok = ok && hipHostMalloc((void**)&c->hostCounts, 32 * sizeof(int)) == hipSuccess;
 	ok = ok && hipMalloc((void**)&c->gammaLut, 256 * sizeof(float)) == hipSuccess;
 	if (ok) {
 		const int exact = c->knobs.exactGamma; // rt_kernels.h gamma_powf
@@ -160,6 +160,7 @@ int rt_set_camera(rt_ctx* c, const rt_camera* cam)
 #include "rt_api_build.inc"
 #include "rt_api_instances.inc"
 #include "rt_api_triangles.inc"
+#include "rt_api_vertices.inc"
 #include "rt_api_render.inc"
 #include "rt_api_output.inc"
 

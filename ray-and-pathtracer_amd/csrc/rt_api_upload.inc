@@ -66,6 +66,7 @@ static int triangles_keep(rt_ctx* c, const rt_scene_desc* d, const SceneLayout& 
 	c->blasKeep.assign(d->n_blas, rt_ctx::BlasKeep());
 	c->slotOf = nullptr, c->refitOrderAll = nullptr, c->refitLevelAll = nullptr;
 	c->triStage = nullptr, c->triStageCap = 0, c->undoPairs = nullptr, c->undoPrims = nullptr, c->undoPairCap = 0, c->undoPrimCap = 0;
+	c->vtxStage = nullptr, c->vtxStageCap = 0, c->vtxVerdict = nullptr; // (rt_api_vertices.inc; the bound indices go with blasKeep)
 	std::vector<uint> slotOf, order;
 	std::vector<int> levelAll;
 	uint pairOff = 0, primOff = 0;

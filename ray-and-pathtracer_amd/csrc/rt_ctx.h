@@ -7,6 +7,7 @@
 //   rt_api_build.inc    device builders, refit
 //   rt_api_instances.inc rt_set_instances (kernels: rt_instances.h), rt_download_tlas, rt_scene_array
 //   rt_api_triangles.inc rt_set_triangles (kernels: rt_triangles.h), rt_blas_array
+//   rt_api_vertices.inc rt_set_mesh_indices, rt_set_vertices, rt_set_vertices_device (kernel: rt_vertices.h)
 //   rt_api_render.inc   rt_render*, rt_trace_batch*: round loops and batches
 //   rt_api_gather.inc   rt_gather_*
 //   rt_api_query.inc    batch queries
@@ -24,6 +25,7 @@
 #include "rt_build.h"
 #include "rt_instances.h"
 #include "rt_triangles.h"
+#include "rt_vertices.h"
 #include "rt_layout.h"
 #include "rt_denoise.h"
 #include "rt_adaptive.h"
@@ -170,12 +172,20 @@ struct rt_ctx {
 		size_t levelFirst = 0;  // this BLAS's first entry of refitLevelAll
 		std::vector<int> level; // its level boundaries (levels + 1 entries)
 		bool refittable = true; // false: its tree is not one (a node is its own ancestor)
+		// rt_set_mesh_indices (rt_api_vertices.inc): the bound index buffer, 3 nTri words in the scene pool (allocated by the first binding,
+		// kept across an unbinding), and the vertex count it was checked against.  Ends with the scene, like everything above.
+		uint* meshIdx = nullptr; uint nVertices = 0;
+		bool idxBound = false;
 	};
 	std::vector<BlasKeep> blasKeep;
 	uint* slotOf = nullptr; uint* refitOrderAll = nullptr; int* refitLevelAll = nullptr;
 	float* triStage = nullptr; size_t triStageCap = 0;        // triangles
 	float4* undoPairs = nullptr; float4* undoPrims = nullptr; // records
 	size_t undoPairCap = 0, undoPrimCap = 0;
+	// rt_set_vertices (rt_api_vertices.inc): the host-memory form's copy of the vertices and the reduction record k_assemble_triangles fills
+	// (scene pool, allocated by the first call that needs them; the record is read back into hostCounts[16..29])
+	float* vtxStage = nullptr; size_t vtxStageCap = 0;
+	VertexVerdict* vtxVerdict = nullptr;
 	uint blasPairs = 0;          // pair records in front of the TLAS's: pairs[] holds blasPairs + S.tlasPairs records
 	int32_t layoutScalars[14] = { 0 }; // RT_LAYOUT_SCALARS of the loaded scene (rt_scene_array)
 	// camera
@@ -286,7 +296,7 @@ struct rt_ctx {
 	rt_profile prof{};
 	std::vector<Timer> timers; // pending event pairs, resolved lazily
 	std::vector<int> timerKind;
-	int* hostCounts = nullptr; // pinned
+	int* hostCounts = nullptr; // pinned, 32 words
 	uint* resolveBuf = nullptr; // rt_resolve's device pixels (width * height), allocated on first use
 	// G-buffer + denoiser (rt_api_denoise.inc).  sceneGen counts what makes the G-buffer stale (rt_upload_scene, rt_set_time, a camera
 	// record that differs byte-wise): the G-buffer is current while aovGen == sceneGen
@@ -440,6 +450,15 @@ static void prof_end(rt_ctx* c, hipStream_t stream = nullptr)
 {
 	if (!c->profiling) return;
 	(void)hipEventRecord(c->timers.back().b, stream ? stream : c->stream);
+}
+// a call that opened an entry and then refused: the entry is taken back
+static void prof_cancel(rt_ctx* c)
+{
+	if (!c->profiling || c->timers.empty()) return;
+	(void)hipEventDestroy(c->timers.back().a);
+	(void)hipEventDestroy(c->timers.back().b);
+	c->timers.pop_back();
+	c->timerKind.pop_back();
 }
 static void prof_collect(rt_ctx* c)
 {

@@ -329,6 +329,15 @@ int rth_renderer_commit_triangles(void* h, int blas)
 	GUARD(r, r->r->CommitTriangles(const_cast<bvh*>(pick(sc, blas))));
 	return 0;
 }
+// Renderer::CommitVertices of BLAS 'blas' (the TLAS numbering above; a scene BVH is not over one mesh)
+int rth_renderer_commit_vertices(void* h, int blas)
+{
+	RthRenderer* r = (RthRenderer*)h;
+	Scene& sc = r->r->scene;
+	if (blas < 0 || !sc.useTLAS || blas >= rth_blas_count(&r->scene)) { r->err = "rth_renderer_commit_vertices: no such BLAS"; return -1; }
+	GUARD(r, r->r->CommitVertices(const_cast<bvh*>(pick(sc, blas))));
+	return 0;
+}
 int rth_renderer_carried_pixels(void* h) { return ((RthRenderer*)h)->r->carriedPixels; }
 int rth_renderer_active_pixels(void* h) { return ((RthRenderer*)h)->r->activePixels; }
 const float* rth_renderer_accumulator(void* h) { return &((RthRenderer*)h)->r->accumulator[0].x; }
@@ -397,6 +406,47 @@ int rth_scene_commit_triangles(void* h, int blas)
 	if (blas >= 0 && (!s->sc->useTLAS || blas >= rth_blas_count(h))) { s->err = "rth_scene_commit_triangles: no such BLAS"; return -1; }
 	if (blas < 0 && !s->sc->b) { s->err = "rth_scene_commit_triangles: no scene BVH"; return -1; }
 	GUARD(s, s->sc->CommitTriangles(const_cast<bvh*>(pick(*s->sc, blas))));
+	return 0;
+}
+// Scene::CommitVertices of BLAS 'blas' (the same numbering; a scene BVH is not over one mesh)
+int rth_scene_commit_vertices(void* h, int blas)
+{
+	RthScene* s = (RthScene*)h;
+	if (blas < 0 || !s->sc->useTLAS || blas >= rth_blas_count(h)) { s->err = "rth_scene_commit_vertices: no such BLAS"; return -1; }
+	GUARD(s, s->sc->CommitVertices(const_cast<bvh*>(pick(*s->sc, blas))));
+	return 0;
+}
+// Mesh::vertices of mesh 'mesh' replaced (n must be its vertex count); the triangles follow at Scene::CommitVertices (Mesh::update)
+int rth_mesh_set_vertex_array(void* h, int mesh, const float* xyz, int n)
+{
+	RthScene* s = (RthScene*)h;
+	if (mesh < 0 || mesh >= (int)s->sc->meshes.size()) { s->err = "rth_mesh_set_vertex_array: no such mesh"; return -1; }
+	Mesh& m = s->sc->meshes[mesh];
+	if ((size_t)n != m.vertices.size()) { s->err = "rth_mesh_set_vertex_array: the mesh does not have that many vertices"; return -1; }
+	for (int i = 0; i < n; i++) m.vertices[i] = f3(xyz + 3 * i);
+	return 0;
+}
+// the mesh's vertex count; its vertices (xyz: room for 3 n floats) and its faces as the reference keeps them, 1-based (faces: 3 per triangle)
+int rth_mesh_vertex_count(void* h, int mesh)
+{
+	RthScene* s = (RthScene*)h;
+	return mesh < 0 || mesh >= (int)s->sc->meshes.size() ? -1 : (int)s->sc->meshes[mesh].vertices.size();
+}
+int rth_mesh_indexed(void* h, int mesh, float* xyz, int* faces)
+{
+	RthScene* s = (RthScene*)h;
+	if (mesh < 0 || mesh >= (int)s->sc->meshes.size()) { s->err = "rth_mesh_indexed: no such mesh"; return -1; }
+	const Mesh& m = s->sc->meshes[mesh];
+	for (size_t i = 0; xyz && i < m.vertices.size(); i++) xyz[3 * i] = m.vertices[i].x, xyz[3 * i + 1] = m.vertices[i].y, xyz[3 * i + 2] = m.vertices[i].z;
+	for (size_t i = 0; faces && i < m.faces.size(); i++) faces[3 * i] = m.faces[i].x, faces[3 * i + 1] = m.faces[i].y, faces[3 * i + 2] = m.faces[i].z;
+	return (int)m.faces.size();
+}
+// Mesh::update alone (no device): the triangles re-derived from vertices and faces
+int rth_mesh_update(void* h, int mesh)
+{
+	RthScene* s = (RthScene*)h;
+	if (mesh < 0 || mesh >= (int)s->sc->meshes.size()) { s->err = "rth_mesh_update: no such mesh"; return -1; }
+	s->sc->meshes[mesh].update();
 	return 0;
 }
 // tlas::build on the host over the instances' current bounds (what CommitInstances makes the device do)

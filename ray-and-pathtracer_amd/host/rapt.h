@@ -18,6 +18,7 @@
 #pragma once
 #include "rapt_math.h"
 #include "../../include/rt_amd.h"
+#include <map>
 #include <string>
 #include <vector>
 
@@ -315,6 +316,12 @@ public:
 	// bounds6 == NULL -- RESETS the 'bounds' of bv's instances to the box of a fresh instance under their current transform (they do not
 	// accumulate across a deformation); then tl is refreshed from rt_download_tlas.  Throws for what rt_set_triangles refuses.
 	void CommitTriangles(bvh* bv);
+	// The same for an indexed mesh, from its vertices alone (rt_set_mesh_indices, rt_set_vertices): call it after rewriting
+	// bv->mesh->vertices (same count).  bv must be a BLAS over ONE Mesh that has faces (1-based there, as in the reference; the C ABI's are
+	// 0-based).  It runs Mesh::update() (the triangles follow the vertices), then what CommitTriangles runs, but sends the vertex array
+	// in place of the triangle records; the first call after a Commit binds the faces to every committed context.  The device derives the
+	// normals Mesh::update derives here.  Throws for a bvh without such a mesh and for what rt_set_vertices refuses.
+	void CommitVertices(bvh* bv);
 	void FindNearest(Ray& ray, float t_min) const;   // template/scene.h:1248
 	bool IsOccluded(Ray& ray) const;                 // template/scene.h:1286
 	float3 GetSkyColor(Ray& ray) const;              // template/scene.h:1312, evaluated on the device (rt_sky_color_batch)
@@ -351,6 +358,7 @@ public:
 	bool useTLAS = false;
 	rt_ctx* ctx = nullptr;
 	std::vector<rt_ctx*> alsoCtx; // the further contexts the scene was committed to (CommitAlso): SetTime animates every copy
+	std::map<const bvh*, std::vector<rt_ctx*>> facesBound; // CommitVertices: the contexts that hold bv's faces (a binding ends with the upload)
 private:
 	struct Flat;
 	Flat* flat = nullptr;
@@ -469,6 +477,8 @@ public:
 	// CommitTriangles before that Tick is one capture and one carry.  Otherwise it commits and the next Tick clears.  If
 	// scene.CommitTriangles throws, this call leaves no carry pending.
 	void CommitTriangles(bvh* bv);
+	// Scene::CommitVertices(bv) under the same rules (the carry is rt_reproject_deform's as well)
+	void CommitVertices(bvh* bv);
 	float4* accumulator = nullptr; // host copy, refreshed by Tick
 	uint32_t* screenPixels = nullptr; // Surface::pixels analogue (template/precomp.h:134)
 	Scene scene;
@@ -495,6 +505,7 @@ private:
 	bool lastTickAdaptive = false;    // the last Tick was TickAdaptive: the accumulator holds its samples, taken under sampledCam
 	rt_camera sampledCam{};           // ... and of the last adaptive Tick: the camera the accumulator's samples were taken with
 	bool CaptureForCarry();           // CommitInstances' and CommitTriangles' common head
+	void CommitDeformation(bvh* bv, bool fromVertices); // CommitTriangles and CommitVertices
 	bool motionPending = false;       // CommitInstances / CommitTriangles captured a history and changed the scene: the next adaptive Tick carries across it
 	bool deformPending = false;       // ... and one of the changes was a deformation: the carry is rt_reproject_deform
 	bool clearPending = false;        // CommitInstances moved instances without a capture, or Commit() followed one: the next Tick clears, with no carry

@@ -145,14 +145,14 @@ void Renderer::CommitInstances()
 	else clearPending = true, camera.SetChange(true); // the accumulator holds the scene before the move: the next Tick clears (no camera carry either)
 }
 
-// Scene::CommitTriangles likewise: see rapt.h
-void Renderer::CommitTriangles(bvh* bv)
+// Scene::CommitTriangles and Scene::CommitVertices likewise: see rapt.h
+void Renderer::CommitDeformation(bvh* bv, bool fromVertices)
 {
 	if (!ctx) Init();
 	const bool carry = CaptureForCarry();
 	// (a throw leaves no carry pending: with several contexts the update may have reached some of them only, so a carry that an earlier
 	// call left pending becomes a clear)
-	try { scene.CommitTriangles(bv); }
+	try { if (fromVertices) scene.CommitVertices(bv); else scene.CommitTriangles(bv); }
 	catch (...) {
 		if (motionPending) motionPending = deformPending = false, clearPending = true, camera.SetChange(true);
 		throw;
@@ -160,6 +160,8 @@ void Renderer::CommitTriangles(bvh* bv)
 	if (carry) motionPending = deformPending = true;
 	else clearPending = true, camera.SetChange(true);
 }
+void Renderer::CommitTriangles(bvh* bv) { CommitDeformation(bv, false); }
+void Renderer::CommitVertices(bvh* bv) { CommitDeformation(bv, true); }
 
 void Renderer::SyncCamera()
 {

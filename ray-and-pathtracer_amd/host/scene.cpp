@@ -380,6 +380,7 @@ void Scene::Commit(rt_ctx* c)
 {
 	ctx = c;
 	alsoCtx.clear(); // a re-commit starts over: Renderer::Commit names the other contexts again
+	facesBound.clear(); // (the upload ended every binding of context c; the other contexts are uploaded to again by CommitAlso)
 	check(ctx, rt_upload_scene(ctx, &Describe()));
 	// the accelerator objects learn where they live, for their own Intersect / IsOccluded members
 	if (!useTLAS) { if (b) b->owner = this, b->blasIndex = 0; }
@@ -399,6 +400,7 @@ void Scene::CommitAlso(rt_ctx* other)
 {
 	if (!ctx) throw std::runtime_error("Scene: Commit() has not been called");
 	check(other, rt_upload_scene(other, &Describe()));
+	for (auto& kv : facesBound) kv.second.erase(std::remove(kv.second.begin(), kv.second.end(), other), kv.second.end()); // the upload ended its bindings
 	if (other != ctx && std::find(alsoCtx.begin(), alsoCtx.end(), other) == alsoCtx.end()) alsoCtx.push_back(other);
 }
 
@@ -432,14 +434,35 @@ void Scene::CommitInstances()
 	tl->nodesUsed = used;
 }
 
+// what CommitTriangles and CommitVertices do on the host before the device call: bvh::Refit and bvh::bounds (bvh.cpp:48-49) from the refitted root
+static void refit_host(bvh* bv)
+{
+	bv->Refit();
+	bv->bounds = aabb();
+	bv->bounds.grow(bv->bvhNode[bv->rootNodeIdx].aabbMin);
+	bv->bounds.grow(bv->bvhNode[bv->rootNodeIdx].aabbMax);
+}
+// ... and after it: the library's choice, as rt_set_instances' bounds6 == NULL: the instances of a deformed mesh get the box of a fresh
+// instance; tl is the tree the device walks
+static void refresh_instances(Scene& s, bvh* bv)
+{
+	if (!s.useTLAS || !s.tl) return;
+	for (uint i = 0; i < s.bvhCount; i++) {
+		if (s.bvhList[i].blas != bv) continue;
+		s.bvhList[i].bounds = bv->bounds;
+		mat4 M = s.bvhList[i].matTransform;
+		s.bvhList[i].SetTransform(M);
+	}
+	uint32_t used = 0;
+	check(s.ctx, rt_download_tlas(s.ctx, (rt_tlas_node*)s.tl->tlasNode, &used));
+	s.tl->nodesUsed = used;
+}
+
 void Scene::CommitTriangles(bvh* bv)
 {
 	if (!ctx) throw std::runtime_error("Scene: Commit() has not been called");
 	if (!bv || bv->owner != this || bv->blasIndex < 0) throw std::runtime_error("rt_amd: Scene::CommitTriangles: not a bvh of the committed scene");
-	bv->Refit();
-	bv->bounds = aabb(); // bvh::bounds (bvh.cpp:48-49), from the refitted root
-	bv->bounds.grow(bv->bvhNode[bv->rootNodeIdx].aabbMin);
-	bv->bounds.grow(bv->bvhNode[bv->rootNodeIdx].aabbMax);
+	refit_host(bv);
 	std::vector<rt_triangle> T;
 	auto flatten = [&](const Triangle& t) {
 		rt_triangle r;
@@ -451,17 +474,35 @@ void Scene::CommitTriangles(bvh* bv)
 	else for (auto& t : bv->mesh->tri) flatten(t);
 	check(ctx, rt_set_triangles(ctx, (uint32_t)bv->blasIndex, T.data(), (uint32_t)T.size()));
 	for (rt_ctx* o : alsoCtx) check(o, rt_set_triangles(o, (uint32_t)bv->blasIndex, T.data(), (uint32_t)T.size()));
-	if (!useTLAS || !tl) return;
-	// the library's choice, as rt_set_instances' bounds6 == NULL: the instances of a deformed mesh get the box of a fresh instance
-	for (uint i = 0; i < bvhCount; i++) {
-		if (bvhList[i].blas != bv) continue;
-		bvhList[i].bounds = bv->bounds;
-		mat4 M = bvhList[i].matTransform;
-		bvhList[i].SetTransform(M);
+	refresh_instances(*this, bv);
+}
+
+void Scene::CommitVertices(bvh* bv)
+{
+	if (!ctx) throw std::runtime_error("Scene: Commit() has not been called");
+	if (!bv || bv->owner != this || bv->blasIndex < 0) throw std::runtime_error("rt_amd: Scene::CommitVertices: not a bvh of the committed scene");
+	Mesh* m = bv->mesh;
+	if (bv->scene || !m || m->faces.empty() || m->faces.size() != m->tri.size()) throw std::runtime_error("rt_amd: Scene::CommitVertices: the bvh is not over one mesh with faces");
+	const int nv = (int)m->vertices.size();
+	std::vector<uint32_t> idx; // 0-based for the C ABI
+	for (const int3& f : m->faces) {
+		if (f.x < 1 || f.y < 1 || f.z < 1 || f.x > nv || f.y > nv || f.z > nv) throw std::runtime_error("rt_amd: Scene::CommitVertices: a face names a vertex the mesh does not have");
+		idx.push_back((uint32_t)f.x - 1), idx.push_back((uint32_t)f.y - 1), idx.push_back((uint32_t)f.z - 1);
 	}
-	uint32_t used = 0;
-	check(ctx, rt_download_tlas(ctx, (rt_tlas_node*)tl->tlasNode, &used));
-	tl->nodesUsed = used;
+	m->update(); // the triangles follow the vertices
+	refit_host(bv);
+	static_assert(sizeof(float3) == 12, "Mesh::vertices is the xyz array rt_set_vertices takes");
+	std::vector<rt_ctx*>& bound = facesBound[bv];
+	auto send = [&](rt_ctx* c) {
+		if (std::find(bound.begin(), bound.end(), c) == bound.end()) {
+			check(c, rt_set_mesh_indices(c, (uint32_t)bv->blasIndex, idx.data(), (uint32_t)m->faces.size(), (uint32_t)nv));
+			bound.push_back(c);
+		}
+		check(c, rt_set_vertices(c, (uint32_t)bv->blasIndex, &m->vertices[0].x, (uint32_t)nv));
+	};
+	send(ctx);
+	for (rt_ctx* o : alsoCtx) send(o);
+	refresh_instances(*this, bv);
 }
 
 void Scene::FindNearestBatch(int n, const float* O, const float* D, const float* tmax, float t_min, rt_hit* out) const

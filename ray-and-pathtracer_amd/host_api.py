@@ -40,7 +40,8 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_set_lens", "rt_get_lens", "rt_focus_at",
               "rt_layout_build", "rt_layout_array", "rt_layout_free",
               "rt_set_instances", "rt_download_tlas", "rt_scene_array",
-              "rt_set_triangles", "rt_blas_array"]
+              "rt_set_triangles", "rt_blas_array",
+              "rt_set_mesh_indices", "rt_set_vertices", "rt_set_vertices_device"]
 
 RT_E_ARG, RT_E_STATE = -2, -5
 # include/rt_amd.h rt_set_pixel_filter
@@ -267,6 +268,9 @@ def rt_lib():
         L.rt_scene_array.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         L.rt_set_triangles.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.rt_blas_array.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rt_set_mesh_indices.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.rt_set_vertices.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.rt_set_vertices_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         _rt = L
     return _rt
 
@@ -417,6 +421,32 @@ class HostScene:
         rt_set_triangles to every committed context, the BLAS's instances under the box of a fresh instance, the scene's tlas refreshed
         from the device.  Needs a committed scene."""
         self._chk(self.L.rth_scene_commit_triangles(self.h, int(blas)))
+
+    def mesh_indexed(self, mesh):
+        """Mesh::vertices as (n_vertices, 3) float32 and Mesh::faces as (n_tri, 3) int32, 1-based as the reference keeps them"""
+        nv = self.L.rth_mesh_vertex_count(self.h, int(mesh))
+        if nv < 0:
+            raise IndexError("mesh %d of %d" % (mesh, self.n_meshes()))
+        xyz = np.zeros((nv, 3), dtype=np.float32)
+        faces = np.zeros((self.L.rth_mesh_indexed(self.h, int(mesh), None, None), 3), dtype=np.int32)
+        self._chk(self.L.rth_mesh_indexed(self.h, int(mesh), _p(xyz), _p(faces)))
+        return xyz, faces
+
+    def set_mesh_vertex_array(self, mesh, xyz):
+        """Mesh::vertices of mesh 'mesh' replaced by (n_vertices, 3) floats (the same count); the faces stay.  commit_vertices() runs
+        Mesh::update (the triangles follow) and sends the array to the device; mesh_update() runs Mesh::update alone"""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        self._chk(self.L.rth_mesh_set_vertex_array(self.h, int(mesh), _p(xyz), len(xyz)))
+
+    def mesh_update(self, mesh):
+        """Mesh::update on the host alone: mesh_tris() then shows the triangles re-derived from vertices and faces"""
+        self._chk(self.L.rth_mesh_update(self.h, int(mesh)))
+
+    def commit_vertices(self, blas):
+        """Scene::CommitVertices of BLAS 'blas' (describe()'s order), a BLAS over one mesh with faces: Mesh::update, the host bvh::Refit,
+        the faces bound on the first call (rt_set_mesh_indices), rt_set_vertices with Mesh::vertices to every committed context, the
+        instances and the scene's tlas refreshed as commit_triangles does.  Needs a committed scene."""
+        self._chk(self.L.rth_scene_commit_vertices(self.h, int(blas)))
 
     def rebuild_tlas(self):
         """tlas::build on the host over the instances' current bounds"""
@@ -643,6 +673,10 @@ class HostRenderer:
         the deformation (rt_reproject_deform), otherwise it clears"""
         self._chk(self.L.rth_renderer_commit_triangles(self.h, int(blas)))
 
+    def commit_vertices(self, blas):
+        """rapt::Renderer::CommitVertices of BLAS 'blas': scene.commit_vertices under commit_triangles' carry logic"""
+        self._chk(self.L.rth_renderer_commit_vertices(self.h, int(blas)))
+
     def carried_pixels(self):
         """rapt::Renderer::carriedPixels: the pixels the last reprojecting Tick carried"""
         return int(self.L.rth_renderer_carried_pixels(self.h))
@@ -756,12 +790,30 @@ class HostRenderer:
         self._rt(self.rt.rt_download_tlas(self.ctx, _p(nodes), C.byref(used)))
         return nodes[:used.value].copy()
 
-    # ---- deforming meshes (include/rt_amd.h rt_set_triangles, rt_blas_array) ----
+    # ---- deforming meshes (include/rt_amd.h rt_set_triangles, rt_blas_array, rt_set_mesh_indices, rt_set_vertices, rt_set_vertices_device) ----
     def set_triangles(self, blas, tris, ctx=None):
         """rt_set_triangles: tris is an RT_TRIANGLE_DTYPE array holding ALL triangles of BLAS 'blas' (v0, v1, v2, N, obj_idx, material).
         Returns the rt_status (0: done)."""
         t = np.ascontiguousarray(tris, dtype=RT_TRIANGLE_DTYPE).reshape(-1)
         return int(self.rt.rt_set_triangles(self.ctx if ctx is None else ctx, int(blas), _p(t) if len(t) else None, len(t)))
+
+    def set_mesh_indices(self, blas, idx, n_vertices, ctx=None):
+        """rt_set_mesh_indices: idx is an (n_tri, 3) array of 0-based vertex indices of BLAS 'blas' (None: unbind).  Returns the rt_status."""
+        ctx = self.ctx if ctx is None else ctx
+        if idx is None:
+            return int(self.rt.rt_set_mesh_indices(ctx, int(blas), None, 0, 0))
+        i = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1, 3)
+        return int(self.rt.rt_set_mesh_indices(ctx, int(blas), _p(i) if len(i) else None, len(i), int(n_vertices)))
+
+    def set_vertices(self, blas, xyz, ctx=None):
+        """rt_set_vertices: xyz is the (n_vertices, 3) float32 vertex array of BLAS 'blas', whose indices are bound.  Returns the rt_status."""
+        v = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        return int(self.rt.rt_set_vertices(self.ctx if ctx is None else ctx, int(blas), _p(v) if len(v) else None, len(v)))
+
+    def set_vertices_device(self, blas, ptr, n_vertices, ctx=None):
+        """rt_set_vertices_device: ptr is the address of n_vertices * 3 floats in device memory of the context's device (a torch tensor's
+        data_ptr(), as with bind_accumulator); the work that produced them must be done (torch.cuda.synchronize).  Returns the rt_status."""
+        return int(self.rt.rt_set_vertices_device(self.ctx if ctx is None else ctx, int(blas), C.c_void_p(ptr), int(n_vertices)))
 
     def blas_array(self, blas, name, ctx=None):
         """rt_blas_array: 'pairs' or 'prims' of BLAS 'blas' as the context (ctx None: context 0) holds them: the BLAS's slice of layout()'s"""
