@@ -788,8 +788,8 @@ int rt_build_tlas(rt_ctx* ctx, const float* bounds6, uint32_t n, rt_tlas_node* n
  *   = 2 n after an rt_set_instances; before the first one, the uploaded tlas_nodes and their count (RT_E_UNSUPPORTED if they are more than
  *   2 n + 1).  Synchronous.  RT_E_STATE: no scene; RT_E_UNSUPPORTED: no TLAS.
  * rt_scene_array: what the context holds of the layout rt_layout_build describes, read back from the device: which in { RT_LAYOUT_PAIRS,
- *   RT_LAYOUT_REACH, RT_LAYOUT_INST, RT_LAYOUT_SCALARS }, the element formats and the 14 scalars of rt_layout_array; any other array:
- *   RT_E_UNSUPPORTED (the context does not keep its size).  *bytes_out receives the array's size; out == NULL asks for the size alone;
+ *   RT_LAYOUT_REACH, RT_LAYOUT_BRUTE, RT_LAYOUT_INST, RT_LAYOUT_LIGHTS, RT_LAYOUT_MATS, RT_LAYOUT_SCALARS }, the element formats, sizes
+ *   and the 14 scalars of rt_layout_array; any other array: RT_E_UNSUPPORTED (RT_LAYOUT_PRIMS is read per BLAS: rt_blas_array).  *bytes_out receives the array's size; out == NULL asks for the size alone;
  *   cap_bytes below it: RT_E_ARG.  Synchronous; for tests and tools.  RT_E_STATE: no scene. */
 int rt_set_instances(rt_ctx* ctx, uint32_t first, uint32_t count, const rt_instance* instances, const float* bounds6);
 int rt_download_tlas(rt_ctx* ctx, rt_tlas_node* nodes_out, uint32_t* nodes_used_out);
@@ -868,6 +868,42 @@ int rt_blas_array(rt_ctx* ctx, uint32_t blas, int which, void* out, size_t cap_b
 int rt_set_mesh_indices(rt_ctx* ctx, uint32_t blas, const uint32_t* idx, uint32_t n_tri, uint32_t n_vertices);
 int rt_set_vertices(rt_ctx* ctx, uint32_t blas, const float* xyz, uint32_t n_vertices);            /* host memory   */
 int rt_set_vertices_device(rt_ctx* ctx, uint32_t blas, const float* dev_xyz, uint32_t n_vertices); /* device memory */
+
+/* ---- relighting without a re-upload: lights, materials, skydome ------------------------------------------------------
+ * The lights, the materials and the skydome are the smallest parts of a scene (56 bytes per light, 64 per material) and the ones an
+ * interactive renderer changes most: a lamp dimmed, a wall turned from diffuse to metal, another sky.  The three calls below replace them
+ * in the loaded scene; no BLAS is laid out or copied again.  The yardstick is rt_set_instances': afterwards the context holds, byte for
+ * byte, what rt_upload_scene would hold of the updated description -- the uploaded one, as rt_set_instances / rt_set_triangles /
+ * rt_set_time have left it, with lights / n_lights, materials[first .. first + count) or sky_* replaced -- and every query, frame and
+ * executed-walk counter equals a freshly uploaded context's bit for bit.  rt_scene_array reads the tables back.
+ * rt_set_lights replaces the WHOLE light table: n_lights may differ from the uploaded count, 0 .. 32 (lights may be NULL only with
+ *   n_lights == 0).  The fields are not validated, as at upload.  The first call gives the device table room for 32 records (scene
+ *   pool); later calls allocate nothing.  The per-light planes of the path state re-size themselves at the next batch that needs them.
+ *   RT_E_UNSUPPORTED: more than 32 lights (rt_upload_scene's rule).
+ * rt_set_materials replaces materials [first, first + count).  The NUMBER of materials cannot change: primitive records hold indices.
+ *   A primitive record carries the type of its material in its kind word (csrc/rt_layout.h pack_prim), so a material that changes its
+ *   'type' has that word rewritten, on the device (csrc/rt_materials.h k_retype_prims), in every primitive record the context keeps:
+ *   all BLASes, the brute-force spheres and planes, the originals rt_set_time deforms from.  A call that changes no type queues the
+ *   table copy alone: its cost does not depend on the size of the scene.  What path mode runs follows the new table (a diffuse material
+ *   with shinieness != 0 or raytracer == 0 anywhere in it: the general kernel; RT_LAYOUT_SCALARS word 11), and so does the bounce table.
+ *   RT_E_ARG: first + count beyond the uploaded count, count == 0, a null pointer, a type outside 1..3.  RT_E_UNSUPPORTED, with the
+ *   Q-learning sampler on: an edit after which path mode would need the general kernel (rt_qlearn_enable's refusal, mirrored).
+ * rt_set_sky replaces the skydome: pixels in rt_scene_desc's format (8-bit, n channels, w x h).  pixels == NULL switches the sky off --
+ *   misses return black -- and w, h, n are not looked at.  The device array is reused when the new image fits it (also after a NULL),
+ *   otherwise a new one comes from the scene pool.  RT_E_ARG: w or h below 1, or n below 3, with non-null pixels.
+ *   Common to the three.  RT_E_STATE: no scene loaded.  Everything refusable is refused on the host before anything is queued: after a
+ *     refusal the scene, the generations and the G-buffer are as they were.  Ordering: queued on the context's stream behind what is
+ *     there.  The caller's array has been read when the call returns (the tables are copied to the host mirror first; a sky image in
+ *     page-locked memory, which a copy reads only when the stream gets there, makes rt_set_sky wait for its copy); there is no other
+ *     synchronisation.  With rt_set_profiling on, each call is one entry of rt_profile.query.
+ *   Invalidation: the G-buffer goes stale (its albedo and light hits changed; rt_denoise is RT_E_STATE until rt_render_aovs), the next
+ *     dense batch rebuilds the primary-hit and bounce tables, and a captured history ends at EVERY level, as after rt_upload_scene: every
+ *     carried sample holds radiance computed under the old lights, materials or sky, so rt_reproject, rt_reproject_motion and
+ *     rt_reproject_deform return RT_E_STATE until a new rt_history_capture.  Not touched: the accumulator, the statistics, the active
+ *     list, a budget plan, the Q table, bound mesh indices, the lens, the filter.  The caller clears. */
+int rt_set_lights(rt_ctx* ctx, const rt_light* lights, uint32_t n_lights);
+int rt_set_materials(rt_ctx* ctx, uint32_t first, uint32_t count, const rt_material* materials);
+int rt_set_sky(rt_ctx* ctx, const uint8_t* pixels, int32_t w, int32_t h, int32_t n);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Kernels tally rt_counters (slower; keep off when timing).

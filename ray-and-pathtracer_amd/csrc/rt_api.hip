@@ -1,6 +1,6 @@
 // librt_amd.so: implementation of the C ABI in include/rt_amd.h for gfx950.
 // This file: context, camera, accumulator access, counters and timers, build / tuning info; the other units of the library
-// (scene upload, whose host-only layout builder is rt_layout.h, device builders, instance updates, the render loops, gather, batch queries, the Q-learning sampler, the output stage's helpers, the denoisers, adaptive sampling, budgeted passes, reprojection) are the rt_api_*.inc files
+// (scene upload, whose host-only layout builder is rt_layout.h, device builders, instance updates, relighting, the render loops, gather, batch queries, the Q-learning sampler, the output stage's helpers, the denoisers, adaptive sampling, budgeted passes, reprojection) are the rt_api_*.inc files
 // included below -- one translation unit, see rt_ctx.h.
 #include "rt_ctx.h"
 #include "rt_layout.h"
@@ -161,6 +161,7 @@ int rt_set_camera(rt_ctx* c, const rt_camera* cam)
 #include "rt_api_instances.inc"
 #include "rt_api_triangles.inc"
 #include "rt_api_vertices.inc"
+#include "rt_api_materials.inc"
 #include "rt_api_render.inc"
 #include "rt_api_output.inc"
 

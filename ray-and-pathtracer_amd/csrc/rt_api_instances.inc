@@ -145,7 +145,11 @@ int rt_scene_array(rt_ctx* c, int which, void* out, size_t cap_bytes, size_t* by
 	case RT_LAYOUT_REACH: src = c->instances.reachMut, need = c->S.useTLAS ? ((size_t)c->S.tlasPairs * 12 + 16) * sizeof(float) : 0; break;
 	case RT_LAYOUT_INST: src = c->instances.instMut, need = c->S.useTLAS ? (size_t)c->nInstances * sizeof(DInstance) : 0; break;
 	case RT_LAYOUT_SCALARS: src = c->layoutScalars, need = sizeof(c->layoutScalars), device = false; break;
-	default: return fail(c, RT_E_UNSUPPORTED, "rt_scene_array: array %d (PAIRS, REACH, INST and SCALARS are kept where they can be read back)", which);
+	// what rt_set_lights / rt_set_materials (rt_api_materials.inc) rewrite: the two tables (one zeroed record for none) and the brute-force records with their 16 spare words
+	case RT_LAYOUT_LIGHTS: src = c->S.lights, need = (size_t)(c->S.nLights > 0 ? c->S.nLights : 1) * sizeof(DLight); break;
+	case RT_LAYOUT_MATS: src = c->S.mats, need = (size_t)c->S.nMats * sizeof(DMaterial); break;
+	case RT_LAYOUT_BRUTE: src = c->S.brute, need = c->S.useTLAS ? ((size_t)(c->S.nBruteSph + c->S.nBrutePla) * 16 + 16) * sizeof(float) : 0; break;
+	default: return fail(c, RT_E_UNSUPPORTED, "rt_scene_array: array %d (PAIRS, REACH, BRUTE, INST, LIGHTS, MATS and SCALARS are kept where they can be read back)", which);
 	}
 	*bytes_out = need;
 	if (!out) return RT_OK; // the size alone

@@ -170,6 +170,11 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
 	DMaterial* dm = nullptr;
 	SCENE_ARRAY(&dm, L.mats);
 	S.mats = dm, S.nMats = (int)L.mats.size();
+	// what rt_set_lights / rt_set_materials / rt_set_sky (rt_api_materials.inc) start from
+	c->matsHost.assign(d->materials, d->materials + d->n_materials), c->nMaterials = d->n_materials;
+	c->lightsHost = L.lights, c->lightsCap = 0;
+	c->primSlots = (uint32_t)(L.prims.size() / 16);
+	c->skyMut = nullptr, c->skyCap = 0;
 	S.gammaLut = c->knobs.gammaLut ? c->gammaLut : nullptr;
 	if (d->sky_pixels && d->sky_w > 0 && d->sky_h > 0 && d->sky_n >= 3) {
 		unsigned char* ds = nullptr;
@@ -177,6 +182,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
 		HIPCHK(c, dalloc(c->sceneAllocs, &ds, nbytes));
 		HIPCHK(c, hipMemcpy(ds, d->sky_pixels, nbytes, hipMemcpyHostToDevice));
 		S.sky = ds, S.skyW = d->sky_w, S.skyH = d->sky_h, S.skyN = d->sky_n;
+		c->skyMut = ds, c->skyCap = nbytes;
 	}
 	c->S = S;
 	c->blasPairs = (uint)(L.pairs.size() / 16) - (uint)L.tlasPairs;

@@ -8,6 +8,7 @@
 //   rt_api_instances.inc rt_set_instances (kernels: rt_instances.h), rt_download_tlas, rt_scene_array
 //   rt_api_triangles.inc rt_set_triangles (kernels: rt_triangles.h), rt_blas_array
 //   rt_api_vertices.inc rt_set_mesh_indices, rt_set_vertices, rt_set_vertices_device (kernel: rt_vertices.h)
+//   rt_api_materials.inc rt_set_lights, rt_set_materials, rt_set_sky (kernel: rt_materials.h)
 //   rt_api_render.inc   rt_render*, rt_trace_batch*: round loops and batches
 //   rt_api_gather.inc   rt_gather_*
 //   rt_api_query.inc    batch queries
@@ -26,6 +27,7 @@
 #include "rt_instances.h"
 #include "rt_triangles.h"
 #include "rt_vertices.h"
+#include "rt_materials.h"
 #include "rt_layout.h"
 #include "rt_denoise.h"
 #include "rt_adaptive.h"
@@ -186,6 +188,15 @@ struct rt_ctx {
 	// (scene pool, allocated by the first call that needs them; the record is read back into hostCounts[16..29])
 	float* vtxStage = nullptr; size_t vtxStageCap = 0;
 	VertexVerdict* vtxVerdict = nullptr;
+	// rt_set_lights, rt_set_materials, rt_set_sky (rt_api_materials.inc): the material table as the description gave it (check_path_support's
+	// rule runs over ALL of it after an edit) and the light table on the host, what the next copy is made from; the records in prims[] of
+	// all BLASes; the light table's room on the device (0 until the first rt_set_lights gives it RT_MAX_LIGHTS records); the skydome's
+	// array and its size in bytes (kept while the sky is off, so that switching it on again reuses it)
+	std::vector<rt_material> matsHost;
+	std::vector<DLight> lightsHost;
+	uint32_t nMaterials = 0, primSlots = 0;
+	int lightsCap = 0;
+	unsigned char* skyMut = nullptr; size_t skyCap = 0;
 	uint blasPairs = 0;          // pair records in front of the TLAS's: pairs[] holds blasPairs + S.tlasPairs records
 	int32_t layoutScalars[14] = { 0 }; // RT_LAYOUT_SCALARS of the loaded scene (rt_scene_array)
 	// camera
@@ -286,7 +297,7 @@ struct rt_ctx {
 	// traversal stack spill of the context's stream (rounds and batch queries) + flags
 	uint* spill = nullptr;
 	int gridBlocks = 0;
-	std::vector<int> matTypes; // material types of the uploaded scene (measurement builds)
+	std::vector<int> matTypes; // material types of the loaded scene, as rt_set_materials has left them (the bounce table's existence; measurement builds)
 	int gridQuery = 0; // resident blocks of the query kernels
 	float* gammaLut = nullptr; // DScene::gammaLut
 	int* flags = nullptr; // [1] the status word of the Whitted, general and query kernels, [2] the leftover count of the wide occlusion query, [16..] their work heads

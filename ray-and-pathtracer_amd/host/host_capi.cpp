@@ -338,6 +338,13 @@ int rth_renderer_commit_vertices(void* h, int blas)
 	GUARD(r, r->r->CommitVertices(const_cast<bvh*>(pick(sc, blas))));
 	return 0;
 }
+// Renderer::CommitLights / CommitMaterials / CommitSky (which: 0 / 1 / 2): the edit sent on, the next Tick clears
+int rth_renderer_commit_look(void* h, int which)
+{
+	RthRenderer* r = (RthRenderer*)h;
+	GUARD(r, which == 0 ? r->r->CommitLights() : which == 1 ? r->r->CommitMaterials() : r->r->CommitSky());
+	return 0;
+}
 int rth_renderer_carried_pixels(void* h) { return ((RthRenderer*)h)->r->carriedPixels; }
 int rth_renderer_active_pixels(void* h) { return ((RthRenderer*)h)->r->activePixels; }
 const float* rth_renderer_accumulator(void* h) { return &((RthRenderer*)h)->r->accumulator[0].x; }
@@ -414,6 +421,43 @@ int rth_scene_commit_vertices(void* h, int blas)
 	RthScene* s = (RthScene*)h;
 	if (blas < 0 || !s->sc->useTLAS || blas >= rth_blas_count(h)) { s->err = "rth_scene_commit_vertices: no such BLAS"; return -1; }
 	GUARD(s, s->sc->CommitVertices(const_cast<bvh*>(pick(*s->sc, blas))));
+	return 0;
+}
+// ---- relighting (Scene::CommitLights / CommitMaterials / CommitSky) ----
+// Scene::ReplaceMaterial(index, a new diffuse / metal / glass): the arguments of rth_add_diffuse / rth_add_metal / rth_add_glass
+static int replace_material(RthScene* s, int index, material* m)
+{
+	GUARD(s, s->sc->ReplaceMaterial(index, m));
+	return 0;
+}
+int rth_replace_diffuse(void* h, int index, const float* albedo, const float* col, float ks, float kd, int n, float emission, float shininess, int rt)
+{
+	return replace_material((RthScene*)h, index, new diffuse(f3(albedo), f3(col), ks, kd, n, rt != 0, emission, shininess));
+}
+int rth_replace_metal(void* h, int index, float fuzzy, const float* col, int rt) { return replace_material((RthScene*)h, index, new metal(fuzzy, f3(col), rt != 0)); }
+int rth_replace_glass(void* h, int index, float ir, const float* col, const float* absorption, int rt)
+{
+	return replace_material((RthScene*)h, index, new glass(ir, f3(col), f3(absorption), 0.0f, 0, rt != 0));
+}
+// every light of the scene removed (rth_add_area_light / rth_add_dir_light then make the new table)
+void rth_clear_lights(void* h)
+{
+	Scene& sc = *((RthScene*)h)->sc;
+	for (auto* l : sc.lights) delete l;
+	sc.lights.clear();
+}
+// no skydome: misses are black
+void rth_clear_sky(void* h)
+{
+	Scene& sc = *((RthScene*)h)->sc;
+	sc.skydome.clear();
+	sc.skydomeX = sc.skydomeY = 0, sc.skydomeN = 3;
+}
+// Scene::CommitLights / CommitMaterials / CommitSky (which: 0 / 1 / 2)
+int rth_scene_commit_look(void* h, int which)
+{
+	RthScene* s = (RthScene*)h;
+	GUARD(s, which == 0 ? s->sc->CommitLights() : which == 1 ? s->sc->CommitMaterials() : s->sc->CommitSky());
 	return 0;
 }
 // Mesh::vertices of mesh 'mesh' replaced (n must be its vertex count); the triangles follow at Scene::CommitVertices (Mesh::update)

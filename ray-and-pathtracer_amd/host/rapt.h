@@ -322,6 +322,18 @@ public:
 	// in place of the triangle records; the first call after a Commit binds the faces to every committed context.  The device derives the
 	// normals Mesh::update derives here.  Throws for a bvh without such a mesh and for what rt_set_vertices refuses.
 	void CommitVertices(bvh* bv);
+	// Relighting without a re-upload (rt_set_lights, rt_set_materials, rt_set_sky), to ctx and every context of CommitAlso.
+	// CommitLights: after changing, adding or removing entries of 'lights' (at most 32): the whole table is sent.
+	// CommitMaterials: after changing the fields of the materials (col, albedo, shinieness, ir, ...), or after ReplaceMaterial: every
+	//   material of the committed scene is sent, index for index; their number cannot change.
+	// ReplaceMaterial(index, m): materials[index] becomes m (owned from here on; the old object is deleted) and every mesh, triangle,
+	//   sphere and plane that named the old one names m: how a material changes its class -- diffuse to metal -- on the host.
+	// CommitSky: after rewriting skydome / skydomeX / skydomeY / skydomeN (an empty skydome: no sky, misses are black).
+	// Each throws for what its rt_set_* refuses.  The accumulator is the caller's to clear (Renderer: the calls of the same names).
+	void CommitLights();
+	void CommitMaterials();
+	void ReplaceMaterial(int index, material* m);
+	void CommitSky();
 	void FindNearest(Ray& ray, float t_min) const;   // template/scene.h:1248
 	bool IsOccluded(Ray& ray) const;                 // template/scene.h:1286
 	float3 GetSkyColor(Ray& ray) const;              // template/scene.h:1312, evaluated on the device (rt_sky_color_batch)
@@ -479,6 +491,12 @@ public:
 	void CommitTriangles(bvh* bv);
 	// Scene::CommitVertices(bv) under the same rules (the carry is rt_reproject_deform's as well)
 	void CommitVertices(bvh* bv);
+	// Scene::CommitLights / CommitMaterials / CommitSky for a renderer: they commit and the next Tick clears (the clearPending path).  There
+	// is no carry, deliberately: every sample holds radiance computed under the old lights, materials or sky, and the device ends a
+	// captured history at every level.  A carry that CommitInstances / CommitTriangles left pending becomes that clear.
+	void CommitLights();
+	void CommitMaterials();
+	void CommitSky();
 	float4* accumulator = nullptr; // host copy, refreshed by Tick
 	uint32_t* screenPixels = nullptr; // Surface::pixels analogue (template/precomp.h:134)
 	Scene scene;
@@ -506,6 +524,7 @@ private:
 	rt_camera sampledCam{};           // ... and of the last adaptive Tick: the camera the accumulator's samples were taken with
 	bool CaptureForCarry();           // CommitInstances' and CommitTriangles' common head
 	void CommitDeformation(bvh* bv, bool fromVertices); // CommitTriangles and CommitVertices
+	void CommitLook(void (Scene::*commit)());           // CommitLights, CommitMaterials and CommitSky
 	bool motionPending = false;       // CommitInstances / CommitTriangles captured a history and changed the scene: the next adaptive Tick carries across it
 	bool deformPending = false;       // ... and one of the changes was a deformation: the carry is rt_reproject_deform
 	bool clearPending = false;        // CommitInstances moved instances without a capture, or Commit() followed one: the next Tick clears, with no carry

@@ -163,6 +163,21 @@ void Renderer::CommitDeformation(bvh* bv, bool fromVertices)
 void Renderer::CommitTriangles(bvh* bv) { CommitDeformation(bv, false); }
 void Renderer::CommitVertices(bvh* bv) { CommitDeformation(bv, true); }
 
+// Scene::CommitLights / CommitMaterials / CommitSky: the next Tick clears, whatever was pending (see rapt.h)
+void Renderer::CommitLook(void (Scene::*commit)())
+{
+	if (!ctx) Init();
+	try { (scene.*commit)(); }
+	catch (...) { // (with several contexts the edit may have reached some of them only)
+		motionPending = deformPending = false, clearPending = true, camera.SetChange(true);
+		throw;
+	}
+	motionPending = deformPending = false, clearPending = true, camera.SetChange(true);
+}
+void Renderer::CommitLights() { CommitLook(&Scene::CommitLights); }
+void Renderer::CommitMaterials() { CommitLook(&Scene::CommitMaterials); }
+void Renderer::CommitSky() { CommitLook(&Scene::CommitSky); }
+
 void Renderer::SyncCamera()
 {
 	rt_camera c;

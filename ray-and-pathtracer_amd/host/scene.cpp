@@ -267,11 +267,9 @@ void Scene::BuildTLAS(const std::vector<int>& meshOfInstance, const std::vector<
 	else tl->build();
 }
 
-int Scene::materialIndex(const material* m) const
+// a material as the C ABI's record (the record depends on the object alone: CommitMaterials re-derives it in place)
+static rt_material flatten_material(const material* m)
 {
-	auto it = flat->matIndex.find(m);
-	if (it != flat->matIndex.end()) return it->second;
-	int idx = (int)flat->materials.size();
 	rt_material r;
 	memset(&r, 0, sizeof(r));
 	r.type = m->type, r.raytracer = m->raytracer ? 1 : 0;
@@ -284,12 +282,31 @@ int Scene::materialIndex(const material* m) const
 		const glass* g = static_cast<const glass*>(m);
 		r.ir = g->ir, r.absorption[0] = g->absorption.x, r.absorption[1] = g->absorption.y, r.absorption[2] = g->absorption.z;
 	}
-	flat->materials.push_back(r);
+	return r;
+}
+
+int Scene::materialIndex(const material* m) const
+{
+	auto it = flat->matIndex.find(m);
+	if (it != flat->matIndex.end()) return it->second;
+	int idx = (int)flat->materials.size();
+	flat->materials.push_back(flatten_material(m));
 	flat->matIndex[m] = idx;
 	return idx;
 }
 
 static void put3(float* d, const float3& v) { d[0] = v.x, d[1] = v.y, d[2] = v.z; }
+
+static rt_light flatten_light(Light* l)
+{
+	rt_light r;
+	memset(&r, 0, sizeof(r));
+	r.kind = l->kind(), r.obj_idx = l->objIdx, r.strength = l->strength;
+	put3(r.pos, l->pos), put3(r.col, l->col), put3(r.normal, l->normal);
+	if (r.kind == RT_LIGHT_AREA) r.radius = static_cast<AreaLight*>(l)->radius;
+	if (r.kind == RT_LIGHT_DIRECTIONAL) r.sin_angle = static_cast<DirectionalLight*>(l)->sinAngle;
+	return r;
+}
 
 const rt_scene_desc& Scene::Describe()
 {
@@ -353,15 +370,7 @@ const rt_scene_desc& Scene::Describe()
 		F.blas[i].tris = F.tris[i].data();
 		if (!useTLAS) F.blas[i].spheres = F.spheres.data(), F.blas[i].planes = F.planes.data();
 	}
-	for (auto* l : lights) {
-		rt_light r;
-		memset(&r, 0, sizeof(r));
-		r.kind = l->kind(), r.obj_idx = l->objIdx, r.strength = l->strength;
-		put3(r.pos, l->pos), put3(r.col, l->col), put3(r.normal, l->normal);
-		if (r.kind == RT_LIGHT_AREA) r.radius = static_cast<AreaLight*>(l)->radius;
-		if (r.kind == RT_LIGHT_DIRECTIONAL) r.sin_angle = static_cast<DirectionalLight*>(l)->sinAngle;
-		F.lights.push_back(r);
-	}
+	for (auto* l : lights) F.lights.push_back(flatten_light(l));
 	F.desc.use_tlas = useTLAS ? 1 : 0;
 	F.desc.blas = F.blas.data(), F.desc.n_blas = (uint32_t)F.blas.size();
 	F.desc.lights = F.lights.data(), F.desc.n_lights = (uint32_t)F.lights.size();
@@ -503,6 +512,51 @@ void Scene::CommitVertices(bvh* bv)
 	send(ctx);
 	for (rt_ctx* o : alsoCtx) send(o);
 	refresh_instances(*this, bv);
+}
+
+// ---- relighting without a re-upload (rt_set_lights, rt_set_materials, rt_set_sky): see rapt.h ----
+void Scene::CommitLights()
+{
+	if (!ctx) throw std::runtime_error("Scene: Commit() has not been called");
+	std::vector<rt_light> L;
+	for (auto* l : lights) L.push_back(flatten_light(l));
+	check(ctx, rt_set_lights(ctx, L.data(), (uint32_t)L.size()));
+	for (rt_ctx* o : alsoCtx) check(o, rt_set_lights(o, L.data(), (uint32_t)L.size()));
+}
+
+void Scene::ReplaceMaterial(int index, material* m)
+{
+	if (index < 0 || index >= (int)materials.size() || !m) { delete m; throw std::runtime_error("rt_amd: Scene::ReplaceMaterial: no such material"); }
+	material* old = materials[index];
+	if (old == m) return;
+	for (auto& ms : meshes) { if (ms.mat == old) ms.mat = m; for (auto& t : ms.tri) if (t.mat == old) t.mat = m; }
+	for (auto& s : spheres) if (s.mat == old) s.mat = m;
+	for (auto& p : planes) if (p.mat == old) p.mat = m;
+	auto it = flat->matIndex.find(old);
+	if (it != flat->matIndex.end()) { const int idx = it->second; flat->matIndex.erase(it); flat->matIndex[m] = idx; }
+	materials[index] = m;
+	delete old;
+}
+
+void Scene::CommitMaterials()
+{
+	if (!ctx) throw std::runtime_error("Scene: Commit() has not been called");
+	// the committed table, index for index (Describe's order: the registered materials first), every record re-derived from its object
+	std::vector<rt_material> M(flat->materials.size());
+	if (M.empty()) return;
+	if (flat->matIndex.size() != M.size()) throw std::runtime_error("rt_amd: Scene::CommitMaterials: the scene has not been described");
+	for (auto& kv : flat->matIndex) M[(size_t)kv.second] = flatten_material(kv.first);
+	flat->materials = M;
+	check(ctx, rt_set_materials(ctx, 0, (uint32_t)M.size(), M.data()));
+	for (rt_ctx* o : alsoCtx) check(o, rt_set_materials(o, 0, (uint32_t)M.size(), M.data()));
+}
+
+void Scene::CommitSky()
+{
+	if (!ctx) throw std::runtime_error("Scene: Commit() has not been called");
+	const uint8_t* px = skydome.empty() ? nullptr : skydome.data();
+	check(ctx, rt_set_sky(ctx, px, skydomeX, skydomeY, skydomeN));
+	for (rt_ctx* o : alsoCtx) check(o, rt_set_sky(o, px, skydomeX, skydomeY, skydomeN));
 }
 
 void Scene::FindNearestBatch(int n, const float* O, const float* D, const float* tmax, float t_min, rt_hit* out) const

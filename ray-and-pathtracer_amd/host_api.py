@@ -41,7 +41,8 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_layout_build", "rt_layout_array", "rt_layout_free",
               "rt_set_instances", "rt_download_tlas", "rt_scene_array",
               "rt_set_triangles", "rt_blas_array",
-              "rt_set_mesh_indices", "rt_set_vertices", "rt_set_vertices_device"]
+              "rt_set_mesh_indices", "rt_set_vertices", "rt_set_vertices_device",
+              "rt_set_lights", "rt_set_materials", "rt_set_sky"]
 
 RT_E_ARG, RT_E_STATE = -2, -5
 # include/rt_amd.h rt_set_pixel_filter
@@ -156,6 +157,10 @@ RT_PLANE_DTYPE = np.dtype([("N", np.float32, 3), ("d", np.float32), ("obj_idx", 
 RT_BVH_NODE_DTYPE = np.dtype([("aabb_min", np.float32, 3), ("left_first", np.uint32), ("aabb_max", np.float32, 3), ("prim_count", np.uint32)])
 RT_INSTANCE_DTYPE = np.dtype([("blas", np.int32), ("transform", np.float32, 16), ("inv_transform", np.float32, 16)])
 RT_TLAS_NODE_DTYPE = np.dtype([("aabb_min", np.float32, 3), ("left_right", np.uint32), ("aabb_max", np.float32, 3), ("blas", np.uint32)])
+RT_LIGHT_DTYPE = np.dtype([("kind", np.int32), ("obj_idx", np.int32), ("pos", np.float32, 3), ("strength", np.float32), ("col", np.float32, 3), ("normal", np.float32, 3),
+                           ("radius", np.float32), ("sin_angle", np.float32)])
+RT_MATERIAL_DTYPE = np.dtype([("type", np.int32), ("raytracer", np.int32), ("col", np.float32, 3), ("albedo", np.float32, 3), ("specu", np.float32), ("diffu", np.float32),
+                              ("shinieness", np.float32), ("N", np.int32), ("ir", np.float32), ("absorption", np.float32, 3)])
 RT_HIT_DTYPE = np.dtype([("t", np.float32), ("obj_idx", np.int32), ("material", np.int32), ("normal", np.float32, 3)])
 
 
@@ -271,6 +276,9 @@ def rt_lib():
         L.rt_set_mesh_indices.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
         L.rt_set_vertices.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.rt_set_vertices_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.rt_set_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.rt_set_materials.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.rt_set_sky.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
         _rt = L
     return _rt
 
@@ -447,6 +455,41 @@ class HostScene:
         the faces bound on the first call (rt_set_mesh_indices), rt_set_vertices with Mesh::vertices to every committed context, the
         instances and the scene's tlas refreshed as commit_triangles does.  Needs a committed scene."""
         self._chk(self.L.rth_scene_commit_vertices(self.h, int(blas)))
+
+    # ---- relighting: the host half (Scene::ReplaceMaterial, the lights, the skydome) and Scene::CommitLights / CommitMaterials / CommitSky ----
+    def replace_diffuse(self, index, albedo, col, ks=0.2, kd=0.8, n=2, emission=0.0, shininess=0.0, rt=True):
+        """Scene::ReplaceMaterial(index, a new diffuse): diffuse()'s arguments; every primitive that named the old material names the new one"""
+        a = albedo if hasattr(albedo, "__len__") else (albedo,) * 3
+        self._chk(self.L.rth_replace_diffuse(self.h, int(index), _f3(a), _f3(col), C.c_float(ks), C.c_float(kd), int(n),
+                                             C.c_float(emission), C.c_float(shininess), int(rt)))
+
+    def replace_metal(self, index, fuzzy, col, rt=True):
+        """Scene::ReplaceMaterial(index, a new metal): metal()'s arguments"""
+        self._chk(self.L.rth_replace_metal(self.h, int(index), C.c_float(fuzzy), _f3(col), int(rt)))
+
+    def replace_glass(self, index, ir, col, absorption=(0, 0, 0), rt=True):
+        """Scene::ReplaceMaterial(index, a new glass): glass()'s arguments"""
+        self._chk(self.L.rth_replace_glass(self.h, int(index), C.c_float(ir), _f3(col), _f3(absorption), int(rt)))
+
+    def clear_lights(self):
+        """every light removed; area_light() / dir_light() then make the new table, commit_lights() sends it"""
+        self.L.rth_clear_lights(self.h)
+
+    def clear_sky(self):
+        """no skydome (misses are black); commit_sky() sends that on"""
+        self.L.rth_clear_sky(self.h)
+
+    def commit_lights(self):
+        """Scene::CommitLights: the whole light table through rt_set_lights, to every committed context.  Needs a committed scene."""
+        self._chk(self.L.rth_scene_commit_look(self.h, 0))
+
+    def commit_materials(self):
+        """Scene::CommitMaterials: every material of the committed scene, re-derived from its object, through rt_set_materials"""
+        self._chk(self.L.rth_scene_commit_look(self.h, 1))
+
+    def commit_sky(self):
+        """Scene::CommitSky: the skydome (sky() / clear_sky()) through rt_set_sky"""
+        self._chk(self.L.rth_scene_commit_look(self.h, 2))
 
     def rebuild_tlas(self):
         """tlas::build on the host over the instances' current bounds"""
@@ -677,6 +720,18 @@ class HostRenderer:
         """rapt::Renderer::CommitVertices of BLAS 'blas': scene.commit_vertices under commit_triangles' carry logic"""
         self._chk(self.L.rth_renderer_commit_vertices(self.h, int(blas)))
 
+    def commit_lights(self):
+        """rapt::Renderer::CommitLights: scene.commit_lights, and the next Tick clears (there is no carry across a relight)"""
+        self._chk(self.L.rth_renderer_commit_look(self.h, 0))
+
+    def commit_materials(self):
+        """rapt::Renderer::CommitMaterials: scene.commit_materials, and the next Tick clears"""
+        self._chk(self.L.rth_renderer_commit_look(self.h, 1))
+
+    def commit_sky(self):
+        """rapt::Renderer::CommitSky: scene.commit_sky, and the next Tick clears"""
+        self._chk(self.L.rth_renderer_commit_look(self.h, 2))
+
     def carried_pixels(self):
         """rapt::Renderer::carriedPixels: the pixels the last reprojecting Tick carried"""
         return int(self.L.rth_renderer_carried_pixels(self.h))
@@ -815,6 +870,26 @@ class HostRenderer:
         data_ptr(), as with bind_accumulator); the work that produced them must be done (torch.cuda.synchronize).  Returns the rt_status."""
         return int(self.rt.rt_set_vertices_device(self.ctx if ctx is None else ctx, int(blas), C.c_void_p(ptr), int(n_vertices)))
 
+    # ---- relighting (include/rt_amd.h rt_set_lights, rt_set_materials, rt_set_sky) ----
+    def set_lights(self, lights, ctx=None):
+        """rt_set_lights: lights is an RT_LIGHT_DTYPE array, the WHOLE new table (empty: no lights).  Returns the rt_status (0: done)."""
+        l = np.ascontiguousarray(lights, dtype=RT_LIGHT_DTYPE).reshape(-1)
+        return int(self.rt.rt_set_lights(self.ctx if ctx is None else ctx, _p(l) if len(l) else None, len(l)))
+
+    def set_materials(self, first, materials, ctx=None):
+        """rt_set_materials: materials is an RT_MATERIAL_DTYPE array replacing materials first, first + 1, ...  Returns the rt_status."""
+        m = np.ascontiguousarray(materials, dtype=RT_MATERIAL_DTYPE).reshape(-1)
+        return int(self.rt.rt_set_materials(self.ctx if ctx is None else ctx, int(first), len(m), _p(m) if len(m) else None))
+
+    def set_sky(self, pixels, ctx=None):
+        """rt_set_sky: pixels is an (h, w, n) uint8 array, or None: no sky.  Returns the rt_status."""
+        ctx = self.ctx if ctx is None else ctx
+        if pixels is None:
+            return int(self.rt.rt_set_sky(ctx, None, 0, 0, 0))
+        px = np.ascontiguousarray(pixels, dtype=np.uint8)
+        hgt, w, n = px.shape
+        return int(self.rt.rt_set_sky(ctx, _p(px), w, hgt, n))
+
     def blas_array(self, blas, name, ctx=None):
         """rt_blas_array: 'pairs' or 'prims' of BLAS 'blas' as the context (ctx None: context 0) holds them: the BLAS's slice of layout()'s"""
         ctx = self.ctx if ctx is None else ctx
@@ -832,7 +907,7 @@ class HostRenderer:
         return C.c_void_p(self.L.rth_renderer_ctx_at(self.h, int(k)))
 
     def scene_array(self, name, ctx=None):
-        """rt_scene_array: 'pairs', 'reach', 'inst' or 'scalars' as the context (ctx None: context 0) holds them, in layout()'s formats"""
+        """rt_scene_array: 'pairs', 'reach', 'brute', 'inst', 'lights', 'mats' or 'scalars' as the context (ctx None: context 0) holds them, in layout()'s formats"""
         ctx = self.ctx if ctx is None else ctx
         which = [k for k, _ in LAYOUT_ARRAYS].index(name)
         nbytes = C.c_size_t(0)
