@@ -795,6 +795,40 @@ int rt_set_instances(rt_ctx* ctx, uint32_t first, uint32_t count, const rt_insta
 int rt_download_tlas(rt_ctx* ctx, rt_tlas_node* nodes_out, uint32_t* nodes_used_out);
 int rt_scene_array(rt_ctx* ctx, int which, void* out, size_t cap_bytes, size_t* bytes_out);
 
+/* ---- adding, removing and re-pointing instances without a re-upload -----------------------------------------------
+ * rt_set_instances moves the objects of a scene; rt_set_instance_list changes WHICH objects there are.  It replaces the whole instance list
+ * of the loaded TLAS scene by 'instances': n records, 1 <= n <= 256, n free to differ from the current count, instances[i].blas any BLAS
+ * of the upload (several instances may share one, a BLAS may end up with none -- it stays loaded and can be named again; a BLAS needs no
+ * instance at upload either, so a library of meshes can be uploaded once and the scene populated from it).  No BLAS is laid out or copied
+ * again.  The yardstick is rt_set_instances': afterwards the context holds, byte for byte, what rt_upload_scene would hold of the updated
+ * description -- the uploaded one as the earlier rt_set_* calls have left it, with instances / n_instances replaced and tlas_nodes =
+ * tlas::build over the n boxes: inst[], the TLAS pair records at the tail of pairs[], reach[], scalars 0-6 of RT_LAYOUT_SCALARS (nInst
+ * included; rt_scene_array), and rt_download_tlas returns the 2 n nodes rt_build_tlas makes of the boxes.  Queries, frames and counters
+ * equal a freshly uploaded context's bit for bit.
+ *   Records: transform / inv_transform are the caller's; the root words are the ones the upload made per BLAS (the 8-wide root RT_EMPTY
+ *     where the upload had no 8-wide walk).  The wide arrays and scalars 9-10 keep their upload-time shape, as under rt_set_triangles.
+ *   Boxes: bounds6 != NULL: n * 6 floats, used as given (the caller's bvhInstance::bounds, accumulating or not); bounds6 == NULL: the box
+ *     of a FRESH instance for every entry (rt_set_instances' NULL rule).  Every instance has a box afterwards.
+ *   What follows n: n == 1 has no TLAS pair record (root = the instance, tlasBase 0); the split of a traversal block's LDS is re-evaluated
+ *     (the TLAS copy in LDS switches off from 38 instances on under the default build, and comes back below that).  Later
+ *     rt_set_instances / rt_set_triangles calls work against the new list: its range, its BLASes, the instances of a deformed BLAS.
+ *   Room: under a TLAS rt_upload_scene reserves room for 256 instances in every per-instance array (under 100 KB); this call never
+ *     allocates or copies a large array.  rt_scene_array's sizes follow the current count.
+ *   Ordering and failure: rt_set_instances' -- boxes and nodes go to scratch, the 4-byte read-back of the build is the only
+ *     synchronisation, the scene is written only after it.  If the build finds no finite union area the call returns RT_E_UNSUPPORTED,
+ *     the scene is byte-equal to what it was and nothing is invalidated.
+ *   Invalidation: an upload's, for everything that names an instance -- the G-buffer is stale (its instance indices renumber), the
+ *     primary-hit and bounce tables are rebuilt by the next dense batch, and a captured history ends at EVERY level: rt_reproject,
+ *     rt_reproject_motion and rt_reproject_deform return RT_E_STATE until a new rt_history_capture.  There is deliberately no carry: an
+ *     instance index no longer names the same object.  Not touched: accumulator, statistics, active list, budget plan, Q table, bound
+ *     mesh indices (they are per BLAS), lens, filter, lights, materials, sky.  With rt_set_profiling on, one rt_profile.query entry.
+ *   Errors, all checked on the host before anything is queued.  RT_E_STATE: no scene.  RT_E_UNSUPPORTED: the scene has no TLAS.  RT_E_ARG:
+ *     a null ctx or instances; n outside 1..256; a blas outside the uploaded BLASes; a non-finite matrix entry; a bound that is non-finite
+ *     or beyond 1e30 (with bounds6 == NULL: a transform that could take the BLAS's box there).
+ *   Limits: 256 instances (the reference's nodeIdx[256]); no new BLAS (it would shift tlasBase and the wide arrays and grow pairs[] /
+ *     prims[]: rt_upload_scene); the brute-force spheres and planes of a TLAS scene are not edited; no carry across a list edit. */
+int rt_set_instance_list(rt_ctx* ctx, uint32_t n, const rt_instance* instances, const float* bounds6);
+
 /* ---- deforming a mesh without a re-upload ----------------------------------------------------------------------
  * A skinned character, cloth or a morph target changes its vertices and keeps its topology.  rt_set_triangles replaces ALL triangles of BLAS
  * 'blas' of the loaded scene and runs bvh::Refit (bvh.cpp:556-594) over that BLAS's tree on the device: the tree keeps its shape and its

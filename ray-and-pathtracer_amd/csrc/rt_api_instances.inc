@@ -1,17 +1,18 @@
-// rt_set_instances: bvhInstance::SetTransform + tlas::build into the loaded scene, without a re-upload; rt_download_tlas; rt_scene_array.
+// rt_set_instances: bvhInstance::SetTransform + tlas::build into the loaded scene, without a re-upload; rt_set_instance_list: the whole list
+// replaced, its length and the instances' BLASes included; rt_download_tlas; rt_scene_array.
 // The host side of rt_instances.h, which states why the result is byte-equal to a fresh rt_upload_scene of the updated description.
 // Included by rt_api.hip (one translation unit).
 static_assert(sizeof(InstReach) == sizeof(Reach) && sizeof(Reach) == 64, "the reach record the host uploads is pack_reach's");
 
-// The tail rt_set_instances and rt_set_triangles (rt_api_triangles.inc) share: from every instance's new box in I.boundsNew to the TLAS in the
+// The tail rt_set_instances, rt_set_instance_list and rt_set_triangles (rt_api_triangles.inc) share: from every instance's new box in I.boundsNew to the TLAS in the
 // traversal layout.  tlas::build into scratch and the call's one synchronisation (did it succeed?); then, and only then, the commit: the
 // caller's own (commit: its mirrors and copies), the reach records, k_pack_tlas, the scalars.  A build that fails runs undo (whatever the
 // caller has queued into the scene so far is taken back), closes the profile entry and returns RT_E_UNSUPPORTED.
+//   n       the number of instances after the change (rt_set_instance_list: another than c->nInstances, which its commit sets)
 //   reach   instance_reach of every instance after the change; swapped into the context on success
-static int tlas_tail(rt_ctx* c, const char* who, std::vector<Reach>& reach, const std::function<int()>& commit, const std::function<int()>& undo)
+static int tlas_tail(rt_ctx* c, const char* who, uint32_t n, std::vector<Reach>& reach, const std::function<int()>& commit, const std::function<int()>& undo)
 {
 	rt_ctx::InstanceState& I = c->instances;
-	const uint32_t n = (uint32_t)c->nInstances;
 	const double originMax = reach_origin_max(reach.data(), reach.size());
 	// the scalars that follow from n alone (rt_instances.h, fact 1)
 	SceneLayout L;
@@ -43,10 +44,32 @@ static int tlas_tail(rt_ctx* c, const char* who, std::vector<Reach>& reach, cons
 	prof_end(c);
 	HIPCHK(c, hipGetLastError());
 	I.built = true;
-	c->S.rootLink = L.root, c->S.tlasBase = L.tlasBase, c->S.tlasPairs = L.tlasPairs, c->S.reachOriginMax = L.reachOriginMax;
+	c->S.rootLink = L.root, c->S.tlasBase = L.tlasBase, c->S.tlasPairs = L.tlasPairs, c->S.nInst = L.nInst, c->S.reachOriginMax = L.reachOriginMax;
 	c->S.tlasLds = L.tlasLds, c->S.stackRows = L.stackRows;
 	int32_t* s = c->layoutScalars; // rootLink, tlasBase, tlasPairs, nInst, reachOriginMax, tlasLds, stackRows: the first seven words
-	s[0] = (int32_t)L.root, s[1] = (int32_t)L.tlasBase, s[2] = L.tlasPairs, memcpy(&s[4], &L.reachOriginMax, 4), s[5] = L.tlasLds, s[6] = L.stackRows;
+	s[0] = (int32_t)L.root, s[1] = (int32_t)L.tlasBase, s[2] = L.tlasPairs, s[3] = L.nInst, memcpy(&s[4], &L.reachOriginMax, 4), s[5] = L.tlasLds, s[6] = L.stackRows;
+	return RT_OK;
+}
+
+// What both calls refuse of one instance record (in.blas is a BLAS of the scene): a non-finite matrix entry; box6, the caller's box, beyond
+// 1e30; without one, a transform that could take the BLAS's local box there.  'at': the instance's index, for the message.
+static int check_instance(rt_ctx* c, const char* who, uint32_t at, const rt_instance& in, const float* box6)
+{
+	for (int j = 0; j < 16; j++)
+		if (!std::isfinite(in.transform[j]) || !std::isfinite(in.inv_transform[j])) return fail(c, RT_E_ARG, "%s: instance %u has a non-finite matrix entry", who, at);
+	if (box6) {
+		for (int j = 0; j < 6; j++)
+			if (!(std::fabs(box6[j]) <= 1e30f)) return fail(c, RT_E_ARG, "%s: instance %u has a non-finite bound or one beyond 1e30", who, at);
+		return RT_OK;
+	}
+	// the box the device will compute stays within the +-1e30 of every stored box: |row . corner| <= sum |c_j| max|corner_j| + |c_3|
+	const float* bb = &c->instances.blasBox6[(size_t)6 * in.blas];
+	for (int r = 0; r < 3; r++) {
+		double reachMax = std::fabs((double)in.transform[4 * r + 3]);
+		for (int j = 0; j < 3; j++) reachMax += std::fabs((double)in.transform[4 * r + j]) * std::max(std::fabs((double)bb[j]), std::fabs((double)bb[3 + j]));
+		if (!(reachMax <= 1e29) || !(std::fabs(bb[r]) <= 1e30f) || !(std::fabs(bb[3 + r]) <= 1e30f))
+			return fail(c, RT_E_ARG, "%s: the transform of instance %u takes its box beyond 1e30", who, at);
+	}
 	return RT_OK;
 }
 
@@ -62,21 +85,8 @@ int rt_set_instances(rt_ctx* c, uint32_t first, uint32_t count, const rt_instanc
 	for (uint32_t k = 0; k < count; k++) {
 		const rt_instance& in = instances[k];
 		if (in.blas != I.blasOf[first + k]) return fail(c, RT_E_ARG, "rt_set_instances: instance %u is an instance of blas %d, not %d (an instance cannot be re-pointed)", first + k, I.blasOf[first + k], in.blas);
-		for (int j = 0; j < 16; j++)
-			if (!std::isfinite(in.transform[j]) || !std::isfinite(in.inv_transform[j])) return fail(c, RT_E_ARG, "rt_set_instances: instance %u has a non-finite matrix entry", first + k);
-		if (bounds6) {
-			for (int j = 0; j < 6; j++)
-				if (!(std::fabs(bounds6[6 * k + j]) <= 1e30f)) return fail(c, RT_E_ARG, "rt_set_instances: instance %u has a non-finite bound or one beyond 1e30", first + k);
-		} else {
-			// the box the device will compute stays within the +-1e30 of every stored box: |row . corner| <= sum |c_j| max|corner_j| + |c_3|
-			const float* bb = &I.blasBox6[(size_t)6 * in.blas];
-			for (int r = 0; r < 3; r++) {
-				double reachMax = std::fabs((double)in.transform[4 * r + 3]);
-				for (int j = 0; j < 3; j++) reachMax += std::fabs((double)in.transform[4 * r + j]) * std::max(std::fabs((double)bb[j]), std::fabs((double)bb[3 + j]));
-				if (!(reachMax <= 1e29) || !(std::fabs(bb[r]) <= 1e30f) || !(std::fabs(bb[3 + r]) <= 1e30f))
-					return fail(c, RT_E_ARG, "rt_set_instances: the transform of instance %u takes its box beyond 1e30", first + k);
-			}
-		}
+		const int rc = check_instance(c, "rt_set_instances", first + k, in, bounds6 ? bounds6 + 6 * (size_t)k : nullptr);
+		if (rc != RT_OK) return rc;
 	}
 	for (uint32_t i = 0; i < n; i++)
 		if (!I.boundsKnown[i] && (i < first || i >= first + count)) return fail(c, RT_E_ARG, "rt_set_instances: instance %u has no leaf in the uploaded TLAS and no box yet; include it in the update", i);
@@ -98,7 +108,7 @@ int rt_set_instances(rt_ctx* c, uint32_t first, uint32_t count, const rt_instanc
 		HIPCHK(c, hipMemcpyAsync(I.xform, xform.data(), xform.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
 		hipLaunchKernelGGL(k_instance_bounds, dim3(1), dim3(RT_TLAS_MAX), 0, c->stream, I.xform, I.blasOfDev + first, I.blasBox, (int)count, I.boundsNew + (size_t)6 * first, (const int*)nullptr);
 	}
-	const int rc = tlas_tail(c, "rt_set_instances", reach,
+	const int rc = tlas_tail(c, "rt_set_instances", n, reach,
 		[&]() -> int {
 			std::copy(inst.begin(), inst.end(), I.inst.begin() + first);
 			for (uint32_t k = 0; k < count; k++) I.boundsKnown[first + k] = 1;
@@ -109,6 +119,64 @@ int rt_set_instances(rt_ctx* c, uint32_t first, uint32_t count, const rt_instanc
 	if (rc != RT_OK) return rc;
 	c->sceneGen++; // everything rt_set_time invalidates: the G-buffer and the primary-hit table ...
 	c->geomGen++;  // ... and a captured history, for rt_reproject; rt_reproject_motion follows the move (shapeGen stays)
+	return RT_OK;
+}
+
+// The whole list replaced: n records of pack_instances' (the roots per BLAS as the upload kept them), n boxes, tlas::build over them.  The
+// device work is rt_set_instances' over all n instances; what differs is on the host: the count and everything that follows from it
+// (tlas_tail's scalars), the instances' BLASes, and an upload's invalidation, since an instance index names another object afterwards.
+int rt_set_instance_list(rt_ctx* c, uint32_t n, const rt_instance* instances, const float* bounds6)
+{
+	if (!c || !instances) return fail(c, RT_E_ARG, "rt_set_instance_list: null argument");
+	if (!c->sceneLoaded) return fail(c, RT_E_STATE, "rt_set_instance_list: no scene uploaded");
+	if (!c->S.useTLAS) return fail(c, RT_E_UNSUPPORTED, "rt_set_instance_list: the scene has no TLAS");
+	rt_ctx::InstanceState& I = c->instances;
+	const size_t nBlas = I.objBox.size();
+	// ---- everything that can be refused is refused here, before anything is queued ----
+	if (n < 1 || n > RT_TLAS_MAX) return fail(c, RT_E_ARG, "rt_set_instance_list: %u instances (a TLAS holds 1..%d)", n, RT_TLAS_MAX);
+	for (uint32_t k = 0; k < n; k++) {
+		const rt_instance& in = instances[k];
+		if (in.blas < 0 || (size_t)in.blas >= nBlas) return fail(c, RT_E_ARG, "rt_set_instance_list: instance %u names blas %d of %zu (a new BLAS needs rt_upload_scene)", k, in.blas, nBlas);
+		const int rc = check_instance(c, "rt_set_instance_list", k, in, bounds6 ? bounds6 + 6 * (size_t)k : nullptr);
+		if (rc != RT_OK) return rc;
+	}
+	// ---- the host's part: pack_instances' records, the reach of every instance (rt_layout.h instance_reach, f64) ----
+	std::vector<DInstance> inst(n);
+	std::vector<int> blasOf(n);
+	std::vector<Reach> reach(n);
+	std::vector<float> xform((size_t)12 * n);
+	for (uint32_t k = 0; k < n; k++) {
+		const rt_instance& in = instances[k];
+		memset(&inst[k], 0, sizeof(DInstance));
+		memcpy(inst[k].invT, in.inv_transform, 48), memcpy(inst[k].T, in.transform, 48);
+		inst[k].rootLink = c->blasRoot[(size_t)in.blas], inst[k].rootWide = I.rootWide[(size_t)in.blas];
+		inst[k].rootWide8 = I.wide8OK ? I.rootWide8[(size_t)in.blas] : RT_EMPTY;
+		blasOf[k] = in.blas;
+		memcpy(&xform[(size_t)12 * k], in.transform, 48);
+		reach[k] = instance_reach(I.objBox[(size_t)in.blas], in.inv_transform);
+	}
+	HIPCHK(c, hipSetDevice(c->device));
+	prof_begin(c, K_QUERY);
+	// ---- the new boxes, into scratch (I.which: the new list's BLASes, where k_instance_bounds reads them before the commit) ----
+	if (bounds6) HIPCHK(c, hipMemcpyAsync(I.boundsNew, bounds6, (size_t)24 * n, hipMemcpyHostToDevice, c->stream));
+	else {
+		HIPCHK(c, hipMemcpyAsync(I.xform, xform.data(), xform.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+		HIPCHK(c, hipMemcpyAsync(I.which, blasOf.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+		hipLaunchKernelGGL(k_instance_bounds, dim3(1), dim3(RT_TLAS_MAX), 0, c->stream, I.xform, (const int*)I.which, I.blasBox, (int)n, I.boundsNew, (const int*)nullptr);
+	}
+	const int rc = tlas_tail(c, "rt_set_instance_list", n, reach,
+		[&]() -> int {
+			I.inst.swap(inst), I.blasOf.swap(blasOf);
+			I.boundsKnown.assign(n, 1);
+			c->nInstances = (int)n;
+			HIPCHK(c, hipMemcpyAsync(I.instMut, I.inst.data(), (size_t)n * sizeof(DInstance), hipMemcpyHostToDevice, c->stream));
+			HIPCHK(c, hipMemcpyAsync(I.blasOfDev, I.blasOf.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+			return RT_OK;
+		},
+		[]() -> int { return RT_OK; }); // nothing of the scene has been touched yet
+	if (rc != RT_OK) return rc;
+	c->sceneGen++;                            // an upload's invalidation: the G-buffer (its instance indices renumber) and the primary-hit table ...
+	c->geomGen++, c->shapeGen++, c->topoGen++; // ... and a captured history at every level: an index no longer names the same object, nothing is carried
 	return RT_OK;
 }
 

@@ -100,7 +100,7 @@ static int triangles_tail(rt_ctx* c, const char* who, uint32_t blas, uint32_t n_
 			HIPCHK(c, hipMemcpyAsync(I.which, which.data(), which.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
 			hipLaunchKernelGGL(k_instance_bounds, dim3(1), dim3(RT_TLAS_MAX), 0, c->stream, I.xform, I.blasOfDev, I.blasBox, (int)which.size(), I.boundsNew, (const int*)I.which);
 		}
-		const int rc = tlas_tail(c, who, V.reach,
+		const int rc = tlas_tail(c, who, n, V.reach,
 			[&]() -> int {
 				for (int i : which) I.boundsKnown[(size_t)i] = 1;
 				wide_sync();

@@ -21,7 +21,9 @@ static int instances_keep(rt_ctx* c, const rt_scene_desc* d, const SceneLayout& 
 	rt_ctx::InstanceState& I = c->instances;
 	I = rt_ctx::InstanceState();
 	const uint n = d->n_instances;
+	const size_t room = RT_TLAS_MAX - (size_t)n; // rt_set_instance_list replaces the list by one of up to RT_TLAS_MAX instances: every array below has room for it from the start
 	I.inst = L.inst, I.instMut = instDev, I.reachMut = reachDev;
+	I.rootWide = L.rootWide, I.rootWide8 = L.rootWide8, I.wide8OK = L.wide8OK; // pack_instances' words, per BLAS
 	I.blasOf.resize(n), I.reach.resize(n), I.boundsKnown.assign(n, 0);
 	I.objBox.resize(d->n_blas), I.blasBox6.resize((size_t)6 * d->n_blas);
 	for (uint k = 0; k < d->n_blas; k++) {
@@ -45,16 +47,16 @@ static int instances_keep(rt_ctx* c, const rt_scene_desc* d, const SceneLayout& 
 		memcpy(&b6[6 * nd.blas], nd.aabb_min, 12), memcpy(&b6[6 * nd.blas + 3], nd.aabb_max, 12);
 		I.boundsKnown[nd.blas] = 1;
 	}
-	SCENE_ARRAY(&I.bounds, b6);
+	SCENE_ARRAY(&I.bounds, b6, 6 * room);
 	SCENE_ARRAY(&I.blasBox, I.blasBox6);
-	SCENE_ARRAY(&I.blasOfDev, I.blasOf);
-	HIPCHK(c, dalloc(c->sceneAllocs, &I.tlasKeep, (size_t)2 * n + 1));
-	HIPCHK(c, dalloc(c->sceneAllocs, &I.boundsNew, (size_t)6 * n));
-	HIPCHK(c, dalloc(c->sceneAllocs, &I.nodesNew, (size_t)2 * n + 1));
+	SCENE_ARRAY(&I.blasOfDev, I.blasOf, room);
+	HIPCHK(c, dalloc(c->sceneAllocs, &I.tlasKeep, (size_t)2 * RT_TLAS_MAX + 1));
+	HIPCHK(c, dalloc(c->sceneAllocs, &I.boundsNew, (size_t)6 * RT_TLAS_MAX));
+	HIPCHK(c, dalloc(c->sceneAllocs, &I.nodesNew, (size_t)2 * RT_TLAS_MAX + 1));
 	HIPCHK(c, dalloc(c->sceneAllocs, &I.used, 1));
-	HIPCHK(c, dalloc(c->sceneAllocs, &I.reachIn, n));
-	HIPCHK(c, dalloc(c->sceneAllocs, &I.xform, (size_t)12 * n));
-	HIPCHK(c, dalloc(c->sceneAllocs, &I.which, n));
+	HIPCHK(c, dalloc(c->sceneAllocs, &I.reachIn, (size_t)RT_TLAS_MAX));
+	HIPCHK(c, dalloc(c->sceneAllocs, &I.xform, (size_t)12 * RT_TLAS_MAX));
+	HIPCHK(c, dalloc(c->sceneAllocs, &I.which, (size_t)RT_TLAS_MAX));
 	HIPCHK(c, dalloc(c->sceneAllocs, &I.boxUndo, 6));
 	return RT_OK;
 }
@@ -115,9 +117,9 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
 	DScene S;
 	memset(&S, 0, sizeof(S));
 	float* dp = nullptr;
-	// rt_set_instances rebuilds the TLAS as tlas::build's, n pair records for n instances (rt_instances.h): the tail of pairs[] and reach[]
-	// have room for them from the start
-	const size_t tlasRoom = d->use_tlas && (int)d->n_instances > L.tlasPairs ? (size_t)((int)d->n_instances - L.tlasPairs) : 0;
+	// rt_set_instances rebuilds the TLAS as tlas::build's, n pair records for n instances (rt_instances.h), and rt_set_instance_list
+	// replaces the list by one of up to RT_TLAS_MAX: the tail of pairs[] and reach[] have room for that many records from the start
+	const size_t tlasRoom = d->use_tlas && RT_TLAS_MAX > L.tlasPairs ? (size_t)(RT_TLAS_MAX - L.tlasPairs) : 0;
 	SCENE_ARRAY(&dp, L.pairs, 16 + tlasRoom * 16);
 	S.pairs = (const float4*)dp;
 	SCENE_ARRAY(&dp, L.prims, 16);
@@ -151,7 +153,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
 	S.stackRows = L.stackRows;
 	if (d->use_tlas) {
 		DInstance* di = nullptr;
-		SCENE_ARRAY(&di, L.inst);
+		SCENE_ARRAY(&di, L.inst, RT_TLAS_MAX - L.inst.size()); // (check_desc: at most RT_TLAS_MAX instances)
 		S.inst = di;
 		SCENE_ARRAY(&dp, L.brute);
 		S.brute = (const float4*)dp;

@@ -5,7 +5,7 @@
 //   rt_layout.h         the scene layout as a value: build_layout, host arithmetic only (no hip* call, no rt_ctx)
 //   rt_api_upload.inc   rt_upload_scene: build_layout's arrays copied to the device; rt_layout_*
 //   rt_api_build.inc    device builders, refit
-//   rt_api_instances.inc rt_set_instances (kernels: rt_instances.h), rt_download_tlas, rt_scene_array
+//   rt_api_instances.inc rt_set_instances, rt_set_instance_list (kernels: rt_instances.h), rt_download_tlas, rt_scene_array
 //   rt_api_triangles.inc rt_set_triangles (kernels: rt_triangles.h), rt_blas_array
 //   rt_api_vertices.inc rt_set_mesh_indices, rt_set_vertices, rt_set_vertices_device (kernel: rt_vertices.h)
 //   rt_api_materials.inc rt_set_lights, rt_set_materials, rt_set_sky (kernel: rt_materials.h)
@@ -149,12 +149,14 @@ struct rt_ctx {
 	// Host: a mirror of inst[], per instance its BLAS and its reach (rt_layout.h instance_reach), per BLAS its object box (f64) and its
 	// local box (f32, bvh::bounds), the uploaded TLAS until the first update replaces it, the RT_LAYOUT_SCALARS words.  Device (scene
 	// pool): every instance's world box and the TLAS nodes the context walks, the local boxes, and the scratch a call builds into.
+	// Every per-instance array on the device has room for RT_TLAS_MAX instances: rt_set_instance_list changes their number.
 	struct InstanceState {
 		std::vector<DInstance> inst;
 		std::vector<int> blasOf;
 		std::vector<Reach> reach;
 		std::vector<ObjectBox> objBox;
 		std::vector<float> blasBox6;
+		std::vector<uint> rootWide, rootWide8; bool wide8OK = false; // per BLAS, what pack_instances put into a record of the upload (rt_set_instance_list)
 		std::vector<char> boundsKnown; // the instance had a leaf in the uploaded TLAS, or has been set since
 		std::vector<rt_tlas_node> uploaded;
 		bool built = false; // tlasKeep holds a tlas::build of the context's own

@@ -161,6 +161,8 @@ void rth_mat4_inverse(const float* m, float* out) { mat4 a; memcpy(a.cell, m, 64
 static const bvh* pick(const Scene& sc, int blas)
 {
 	if (blas < 0) return sc.b;
+	// a committed scene's own numbering first: after Scene::SetInstanceList the order of first use may be another
+	for (uint i = 0; i < sc.bvhCount; i++) if (sc.bvhList[i].blas->owner == &sc && sc.bvhList[i].blas->blasIndex == blas) return sc.bvhList[i].blas;
 	// distinct BLASes in order of first use by an instance (matches Scene::Describe)
 	std::vector<const bvh*> seen;
 	for (uint i = 0; i < sc.bvhCount; i++) {
@@ -345,6 +347,13 @@ int rth_renderer_commit_look(void* h, int which)
 	GUARD(r, which == 0 ? r->r->CommitLights() : which == 1 ? r->r->CommitMaterials() : r->r->CommitSky());
 	return 0;
 }
+// Renderer::CommitInstanceList: the replaced list (rth_scene_set_instance_list) sent on, the next Tick clears
+int rth_renderer_commit_instance_list(void* h)
+{
+	RthRenderer* r = (RthRenderer*)h;
+	GUARD(r, r->r->CommitInstanceList());
+	return 0;
+}
 int rth_renderer_carried_pixels(void* h) { return ((RthRenderer*)h)->r->carriedPixels; }
 int rth_renderer_active_pixels(void* h) { return ((RthRenderer*)h)->r->activePixels; }
 const float* rth_renderer_accumulator(void* h) { return &((RthRenderer*)h)->r->accumulator[0].x; }
@@ -381,6 +390,24 @@ int rth_scene_commit_instances(void* h)
 {
 	RthScene* s = (RthScene*)h;
 	GUARD(s, s->sc->CommitInstances());
+	return 0;
+}
+// Scene::SetInstanceList: the instance array and the TLAS replaced by n fresh instances (meshIdx, transforms: rth_build_tlas's); then
+// Scene::CommitInstanceList / Renderer::CommitInstanceList sends the list on
+int rth_scene_set_instance_list(void* h, int nInst, const int* meshIdx, const float* transforms)
+{
+	RthScene* s = (RthScene*)h;
+	if (nInst < 0) { s->err = "rth_scene_set_instance_list: a negative count"; return -1; }
+	std::vector<int> mi(meshIdx, meshIdx + nInst);
+	std::vector<mat4> T((size_t)nInst);
+	for (int i = 0; i < nInst; i++) memcpy(T[i].cell, transforms + 16 * i, 64);
+	GUARD(s, s->sc->SetInstanceList(mi, T));
+	return 0;
+}
+int rth_scene_commit_instance_list(void* h)
+{
+	RthScene* s = (RthScene*)h;
+	GUARD(s, s->sc->CommitInstanceList());
 	return 0;
 }
 // The triangles of mesh 'mesh' rewritten from n * 9 vertex floats (n must be the mesh's triangle count): vertices and Triangles as

@@ -310,6 +310,17 @@ public:
 	// nodesUsed from rt_download_tlas, so that tl is the tree the device walks.  Throws without useTLAS (RT_E_UNSUPPORTED) and for what
 	// rt_set_instances refuses.  The accumulator is the caller's to clear (Renderer: camera.SetChange(true) before the next Tick).
 	void CommitInstances();
+	// Adding, removing and re-pointing instances without a re-upload (rt_set_instance_list).  CommitInstanceList: call it after REPLACING
+	// the instance array and the TLAS object -- bvhList / bvhCount / Transforms and tl = new tlas(bvhList, bvhCount), 1..256 instances,
+	// every one over a bvh the committed scene holds (a new mesh needs Commit).  It sends the whole list with each bvhInstance's own
+	// 'bounds' to ctx and every context of CommitAlso and refreshes tl from rt_download_tlas, as CommitInstances does.  Throws without
+	// useTLAS and for what rt_set_instance_list refuses.  A bvh left without an instance stays on the device and can be named again.
+	// SetInstanceList does the replacing: fresh bvhInstances (meshOfInstance[i] names the mesh as BuildTLAS does; the mesh must have been
+	// given a bvh by BuildTLAS), their transforms, a new tlas built on the host.  It sends nothing.
+	// (Describe() numbers the BLASes by first use in bvhList and leaves out one without an instance: after a list edit it describes what a
+	// new Commit would upload, which holds the committed contexts' BLASes in the committed order only while the list's first uses keep it.)
+	void SetInstanceList(const std::vector<int>& meshOfInstance, const std::vector<mat4>& transforms);
+	void CommitInstanceList();
 	// Deforming a mesh without a re-upload (rt_set_triangles): call it after rewriting the triangles of the mesh(es) under 'bv' (same
 	// count; Triangle::update or new Triangles).  It runs the host bvh::Refit() and refreshes bv->bounds, sends all of bv's triangles to
 	// ctx and every context of CommitAlso, and -- the library's choice, stated as in CommitInstances' counterpart rt_set_instances with
@@ -497,6 +508,9 @@ public:
 	void CommitLights();
 	void CommitMaterials();
 	void CommitSky();
+	// Scene::CommitInstanceList along the same path: it commits and the next Tick clears.  No carry either: an instance index names
+	// another object afterwards, and the device ends a captured history at every level.
+	void CommitInstanceList();
 	float4* accumulator = nullptr; // host copy, refreshed by Tick
 	uint32_t* screenPixels = nullptr; // Surface::pixels analogue (template/precomp.h:134)
 	Scene scene;
@@ -524,7 +538,7 @@ private:
 	rt_camera sampledCam{};           // ... and of the last adaptive Tick: the camera the accumulator's samples were taken with
 	bool CaptureForCarry();           // CommitInstances' and CommitTriangles' common head
 	void CommitDeformation(bvh* bv, bool fromVertices); // CommitTriangles and CommitVertices
-	void CommitLook(void (Scene::*commit)());           // CommitLights, CommitMaterials and CommitSky
+	void CommitLook(void (Scene::*commit)());           // CommitLights, CommitMaterials, CommitSky and CommitInstanceList
 	bool motionPending = false;       // CommitInstances / CommitTriangles captured a history and changed the scene: the next adaptive Tick carries across it
 	bool deformPending = false;       // ... and one of the changes was a deformation: the carry is rt_reproject_deform
 	bool clearPending = false;        // CommitInstances moved instances without a capture, or Commit() followed one: the next Tick clears, with no carry

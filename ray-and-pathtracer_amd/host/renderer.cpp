@@ -177,6 +177,7 @@ void Renderer::CommitLook(void (Scene::*commit)())
 void Renderer::CommitLights() { CommitLook(&Scene::CommitLights); }
 void Renderer::CommitMaterials() { CommitLook(&Scene::CommitMaterials); }
 void Renderer::CommitSky() { CommitLook(&Scene::CommitSky); }
+void Renderer::CommitInstanceList() { CommitLook(&Scene::CommitInstanceList); }
 
 void Renderer::SyncCamera()
 {

@@ -422,25 +422,83 @@ void Scene::SetTime(float t)
 	for (rt_ctx* o : alsoCtx) check(o, rt_set_time(o, t));
 }
 
+// every instance as the C ABI's record, with its BLAS in the numbering of the committed description (set by Commit) and its own 'bounds'
+static void flatten_instances(Scene& s, std::vector<rt_instance>& in, std::vector<float>& b6)
+{
+	in.resize(s.bvhCount), b6.resize((size_t)6 * s.bvhCount);
+	for (uint i = 0; i < s.bvhCount; i++) {
+		in[i].blas = s.bvhList[i].blas->blasIndex;
+		memcpy(in[i].transform, s.bvhList[i].matTransform.cell, 64);
+		memcpy(in[i].inv_transform, s.bvhList[i].invTransform.cell, 64);
+		put3(&b6[6 * i], s.bvhList[i].bounds.bmin), put3(&b6[6 * i + 3], s.bvhList[i].bounds.bmax);
+		s.Transforms[i] = s.bvhList[i].matTransform;
+	}
+}
+// tl becomes the tree the device walks (tl has 2 n + 1 nodes of room: tlas::tlas)
+static void download_tlas(Scene& s)
+{
+	static_assert(sizeof(TLASNode) == sizeof(rt_tlas_node), "TLASNode must match rt_tlas_node");
+	uint32_t used = 0;
+	check(s.ctx, rt_download_tlas(s.ctx, (rt_tlas_node*)s.tl->tlasNode, &used));
+	s.tl->nodesUsed = used;
+}
+
 void Scene::CommitInstances()
 {
 	if (!ctx) throw std::runtime_error("Scene: Commit() has not been called");
 	if (!useTLAS || !tl) throw std::runtime_error("rt_amd: Scene::CommitInstances: the scene has no TLAS (RT_E_UNSUPPORTED)");
-	std::vector<rt_instance> in(bvhCount);
-	std::vector<float> b6((size_t)6 * bvhCount);
-	for (uint i = 0; i < bvhCount; i++) {
-		in[i].blas = bvhList[i].blas->blasIndex; // the order Describe() flattened them in (set by Commit)
-		memcpy(in[i].transform, bvhList[i].matTransform.cell, 64);
-		memcpy(in[i].inv_transform, bvhList[i].invTransform.cell, 64);
-		put3(&b6[6 * i], bvhList[i].bounds.bmin), put3(&b6[6 * i + 3], bvhList[i].bounds.bmax);
-		Transforms[i] = bvhList[i].matTransform;
-	}
+	std::vector<rt_instance> in;
+	std::vector<float> b6;
+	flatten_instances(*this, in, b6);
 	check(ctx, rt_set_instances(ctx, 0, bvhCount, in.data(), b6.data()));
 	for (rt_ctx* o : alsoCtx) check(o, rt_set_instances(o, 0, bvhCount, in.data(), b6.data()));
-	static_assert(sizeof(TLASNode) == sizeof(rt_tlas_node), "TLASNode must match rt_tlas_node");
-	uint32_t used = 0;
-	check(ctx, rt_download_tlas(ctx, (rt_tlas_node*)tl->tlasNode, &used)); // tl has 2 n + 1 nodes of room (tlas::tlas)
-	tl->nodesUsed = used;
+	download_tlas(*this);
+}
+
+void Scene::SetInstanceList(const std::vector<int>& meshOfInstance, const std::vector<mat4>& transforms)
+{
+	if (!useTLAS || !tl) throw std::runtime_error("rt_amd: Scene::SetInstanceList: the scene has no TLAS (RT_E_UNSUPPORTED)");
+	if (meshOfInstance.size() != transforms.size() || meshOfInstance.empty() || meshOfInstance.size() > 256) throw std::runtime_error("rt_amd: Scene::SetInstanceList: a TLAS holds 1..256 instances");
+	const uint n = (uint)meshOfInstance.size();
+	std::vector<bvh*> blasOf(n, nullptr);
+	for (uint i = 0; i < n; i++) {
+		const int mi = meshOfInstance[i];
+		if (mi < 0 || mi >= (int)meshes.size()) throw std::runtime_error("rt_amd: Scene::SetInstanceList: bad mesh index");
+		for (size_t k = blasOwned.size(); k-- > 0 && !blasOf[i];) if (blasOwned[k]->mesh == &meshes[mi]) blasOf[i] = blasOwned[k]; // the latest BuildTLAS's
+		if (!blasOf[i]) throw std::runtime_error("rt_amd: Scene::SetInstanceList: the mesh has no bvh (BuildTLAS makes one per mesh it is given)");
+	}
+	bvhInstance* list = new bvhInstance[n];
+	mat4* T = new mat4[n];
+	for (uint i = 0; i < n; i++) {
+		T[i] = transforms[i];
+		list[i] = bvhInstance(blasOf[i]);
+		list[i].SetTransform(T[i]);
+		list[i].owner = blasOf[i]->owner, list[i].index = (int)i;
+	}
+	tlas* t = new tlas(list, (int)n);
+	t->owner = tl->owner;
+	t->build();
+	delete tl;
+	delete[] bvhList;
+	delete[] Transforms;
+	tl = t, bvhList = list, Transforms = T, bvhCount = n;
+}
+
+void Scene::CommitInstanceList()
+{
+	if (!ctx) throw std::runtime_error("Scene: Commit() has not been called");
+	if (!useTLAS || !tl) throw std::runtime_error("rt_amd: Scene::CommitInstanceList: the scene has no TLAS (RT_E_UNSUPPORTED)");
+	if (bvhCount < 1 || bvhCount > 256 || tl->blas != bvhList || tl->blasCount != bvhCount) throw std::runtime_error("rt_amd: Scene::CommitInstanceList: tl is not a tlas over bvhList (1..256 instances)");
+	for (uint i = 0; i < bvhCount; i++)
+		if (!bvhList[i].blas || bvhList[i].blas->owner != this || bvhList[i].blas->blasIndex < 0) throw std::runtime_error("rt_amd: Scene::CommitInstanceList: instance of a bvh the committed scene does not hold (a new BLAS needs Commit)");
+	std::vector<rt_instance> in;
+	std::vector<float> b6;
+	flatten_instances(*this, in, b6);
+	check(ctx, rt_set_instance_list(ctx, bvhCount, in.data(), b6.data()));
+	for (rt_ctx* o : alsoCtx) check(o, rt_set_instance_list(o, bvhCount, in.data(), b6.data()));
+	for (uint i = 0; i < bvhCount; i++) bvhList[i].owner = this, bvhList[i].index = (int)i;
+	tl->owner = this;
+	download_tlas(*this);
 }
 
 // what CommitTriangles and CommitVertices do on the host before the device call: bvh::Refit and bvh::bounds (bvh.cpp:48-49) from the refitted root
@@ -462,9 +520,7 @@ static void refresh_instances(Scene& s, bvh* bv)
 		mat4 M = s.bvhList[i].matTransform;
 		s.bvhList[i].SetTransform(M);
 	}
-	uint32_t used = 0;
-	check(s.ctx, rt_download_tlas(s.ctx, (rt_tlas_node*)s.tl->tlasNode, &used));
-	s.tl->nodesUsed = used;
+	download_tlas(s);
 }
 
 void Scene::CommitTriangles(bvh* bv)

@@ -39,7 +39,7 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_set_pixel_filter", "rt_get_pixel_filter", "rt_sample_rays",
               "rt_set_lens", "rt_get_lens", "rt_focus_at",
               "rt_layout_build", "rt_layout_array", "rt_layout_free",
-              "rt_set_instances", "rt_download_tlas", "rt_scene_array",
+              "rt_set_instances", "rt_set_instance_list", "rt_download_tlas", "rt_scene_array",
               "rt_set_triangles", "rt_blas_array",
               "rt_set_mesh_indices", "rt_set_vertices", "rt_set_vertices_device",
               "rt_set_lights", "rt_set_materials", "rt_set_sky"]
@@ -269,6 +269,7 @@ def rt_lib():
         L.rt_layout_array.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.rt_layout_free.argtypes = [C.c_void_p]
         L.rt_set_instances.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.rt_set_instance_list.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.rt_download_tlas.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_scene_array.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         L.rt_set_triangles.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
@@ -413,6 +414,18 @@ class HostScene:
         """Scene::CommitInstances: every instance's matrices and (accumulating) bounds through rt_set_instances, to every committed context;
         the scene's tlas is then the tree the device walks.  Needs a committed scene."""
         self._chk(self.L.rth_scene_commit_instances(self.h))
+
+    def set_instance_list(self, instances):
+        """Scene::SetInstanceList: the instance array and the tlas replaced by fresh instances, (mesh index, row-major mat4) each as
+        build_tlas takes them; every mesh named must have been part of build_tlas.  commit_instance_list() sends the list to the device"""
+        idx = np.array([i for i, _ in instances], dtype=np.int32)
+        T = np.ascontiguousarray(np.stack([np.asarray(t, dtype=np.float32).reshape(16) for _, t in instances]))
+        self._chk(self.L.rth_scene_set_instance_list(self.h, len(idx), _p(idx), _p(T)))
+
+    def commit_instance_list(self):
+        """Scene::CommitInstanceList: the whole (replaced) instance list with the instances' own bounds through rt_set_instance_list, to
+        every committed context; the scene's tlas is then the tree the device walks.  Needs a committed scene."""
+        self._chk(self.L.rth_scene_commit_instance_list(self.h))
 
     def set_mesh_vertices(self, mesh, v9):
         """the triangles of mesh 'mesh' rewritten from (n, 9) vertices (n: its triangle count), as mesh_raw makes them; objIdx and material
@@ -710,6 +723,11 @@ class HostRenderer:
         the next adaptive Tick carries the samples across the move (rt_reproject_motion), otherwise it clears"""
         self._chk(self.L.rth_renderer_commit_instances(self.h))
 
+    def commit_instance_list(self):
+        """rapt::Renderer::CommitInstanceList: the scene's replaced instance list (scene.set_instance_list) sent on, and the next Tick
+        clears (there is no carry across a list edit: an instance index names another object afterwards)"""
+        self._chk(self.L.rth_renderer_commit_instance_list(self.h))
+
     def commit_triangles(self, blas=-1):
         """rapt::Renderer::CommitTriangles of BLAS 'blas' (scene.commit_triangles' numbering; -1: the scene BVH): the mesh's rewritten
         triangles (scene.set_mesh_vertices) sent on; with reproject and adaptive set the next adaptive Tick carries the samples across
@@ -836,6 +854,15 @@ class HostRenderer:
         b = None if bounds6 is None else np.ascontiguousarray(bounds6, dtype=np.float32).reshape(-1, 6)
         assert b is None or len(b) == len(ins)
         return int(self.rt.rt_set_instances(self.ctx, int(first), len(ins), _p(ins) if len(ins) else None, None if b is None else _p(b)))
+
+    def set_instance_list(self, instances, bounds6=None):
+        """rt_set_instance_list: the whole instance list replaced by 'instances', an RT_INSTANCE_DTYPE array of 1..256 records whose blas
+        may be any uploaded BLAS; bounds6 (n, 6) their world boxes, or None: the device computes the box of a fresh instance for each.
+        Returns the rt_status (0: done)."""
+        ins = np.ascontiguousarray(instances, dtype=RT_INSTANCE_DTYPE).reshape(-1)
+        b = None if bounds6 is None else np.ascontiguousarray(bounds6, dtype=np.float32).reshape(-1, 6)
+        assert b is None or len(b) == len(ins)
+        return int(self.rt.rt_set_instance_list(self.ctx, len(ins), _p(ins) if len(ins) else None, None if b is None else _p(b)))
 
     def download_tlas(self):
         """rt_download_tlas: the TLAS the context walks, as (nodes_used, 8) uint32 like build_tlas"""
