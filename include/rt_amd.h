@@ -954,7 +954,9 @@ int rt_set_sky(rt_ctx* ctx, const uint8_t* pixels, int32_t w, int32_t h, int32_t
  *                       holds one round further for the bounce table (RT_BOUNCE_TABLE, default on): the ray a glass
  *                       or metal primary hit scatters is answered from it, still one rays_nearest query with its
  *                       light_tests / brute_tests; the walk of its at most two rays per table record is tallied
- *                       by the counting launch that builds it, and a current table adds none */
+ *                       by the counting launch that builds it, and a current table adds none.  And for the chain
+ *                       tables (RT_BOUNCE_DEPTH 2-4): while every hit of a path so far was glass or metal, the ray of
+ *                       rounds 2 .. depth is answered the same way, from levels built behind the bounce table */
 #define RT_COUNT_OFF 0
 #define RT_COUNT_REFERENCE 1
 #define RT_COUNT_EXECUTED 2

@@ -69,6 +69,10 @@ rt_ctx* rt_create(int device, int width, int height)
 		c->dense.gridShadeBounce = resident((const void*)k_shade_s<false, true>);
 		c->dense.gridShadeDirect = resident((const void*)k_shade_s<false, false, true>);
 		c->dense.gridShadeDirectBounce = resident((const void*)k_shade_s<false, true, true>);
+		c->dense.gridChain = std::min(resident((const void*)k_chain_table<false>), resident((const void*)k_chain_table<true>));
+		c->dense.gridShadeChain = resident((const void*)k_shade_s<false, false, false, true>);
+		c->dense.gridShadeBounceChain = resident((const void*)k_shade_s<false, true, false, true>);
+		c->dense.gridShadeDirectBounceChain = resident((const void*)k_shade_s<false, true, true, true>);
 		c->dense.gridLight = resident((const void*)k_light_s<false>);
 		c->dense.gridLightDirect = resident((const void*)k_light_s<true>);
 		int q = std::min(c->slot.gridConnect, c->slot.gridExtend);
@@ -260,11 +264,11 @@ const char* rt_build_info(void)
 const char* rt_tuning_info(rt_ctx* c)
 {
 	if (!c) return "";
-	char buf[768];
-	snprintf(buf, sizeof(buf), "stream=%d decide=%d fuse=%d refill=%d refill_any=%d stepmin=%d stepmin_any=%d stepmin_xform=%d pairagain=%d pairagain_any=%d drain=%d drain_any=%d shade_lds=%d gamma_lut=%d exact_gamma=%d defer_gamma=%d wide=%d wide8=%d mega=%d mega_levels=%d mega_lpt=%d qlearn=%d tlas_lds=%d stack_rows=%d slots=%d primary_table=%d primary_table_min=%d bounce_table=%d round0_entries=%d",
+	char buf[1024];
+	snprintf(buf, sizeof(buf), "stream=%d decide=%d fuse=%d refill=%d refill_any=%d stepmin=%d stepmin_any=%d stepmin_xform=%d pairagain=%d pairagain_any=%d drain=%d drain_any=%d shade_lds=%d gamma_lut=%d exact_gamma=%d defer_gamma=%d wide=%d wide8=%d mega=%d mega_levels=%d mega_lpt=%d qlearn=%d tlas_lds=%d stack_rows=%d slots=%d primary_table=%d primary_table_min=%d bounce_table=%d round0_entries=%d bounce_depth=%d bounce_depth_min=%d bounce_cap=%ld",
 	         c->knobs.stream, c->knobs.decide, c->knobs.fuse, RT_REFILL, RT_REFILL_ANY, RT_STEPMIN, RT_STEPMIN_ANY, RT_STEPMIN_XFORM,
 	         RT_PAIRAGAIN, RT_PAIRAGAIN_ANY, RT_DRAIN_LANES, RT_DRAIN_LANES_ANY, c->knobs.shadeLds, c->S.gammaLut ? 1 : 0, c->knobs.exactGamma, c->knobs.deferGamma, c->S.wide ? 1 : 0, c->S.wide8 ? 1 : 0, c->knobs.mega, c->knobs.megaLevels, c->knobs.megaLpt, c->Qt.on,
-	         c->S.tlasLds, c->S.stackRows, slot_budget(c), c->knobs.primaryTable, c->knobs.tableMin, c->knobs.bounceTable, c->knobs.round0Entries);
+	         c->S.tlasLds, c->S.stackRows, slot_budget(c), c->knobs.primaryTable, c->knobs.tableMin, c->knobs.bounceTable, c->knobs.round0Entries, c->knobs.bounceDepth, c->knobs.chainMin, c->knobs.chainCap);
 	c->tuningInfo = buf;
 	return c->tuningInfo.c_str();
 }

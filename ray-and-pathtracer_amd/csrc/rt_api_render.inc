@@ -383,15 +383,64 @@ static void launch_connect_s(rt_ctx* c, hipStream_t st, const StreamState& T, in
 // resets the accumulator anyway).
 // The bounce table (rt_stream.h BounceTable) is built right behind it, from its records, inside the same profile entry, and is current
 // exactly when it is (*bounce); a scene without a glass or metal material has none.
-static int primary_table_for(rt_ctx* c, const RenderParams& R, hipStream_t st, bool* use, bool* bounce)
+// The chain tables (rt_stream.h ChainLevel), levels 2 .. RT_BOUNCE_DEPTH, are built behind the bounce table on the same stream, work heads,
+// spill buffer and status word, inside the same profile entry -- at a threshold of their own, RT_BOUNCE_DEPTH_MIN times the primary table's:
+// a batch that has to rebuild pays 1-3 more builds for walks that shorten only over many frames.  When the threshold is crossed after levels
+// 0-1 were built, the levels are built then, as an entry of their own.  *chain: the levels a batch may read, 1 (the bounce table) .. depth.
+static int build_chain_tables(rt_ctx* c, hipStream_t st)
 {
 	rt_ctx::DenseState& d = c->dense;
-	*use = false, *bounce = false;
+	const size_t records = (size_t)(c->width + 2) * (size_t)(c->height + 2);
+	const int depth = c->knobs.bounceDepth;
+	const size_t cap = c->knobs.chainCap < 0 ? records : std::min((size_t)c->knobs.chainCap, (size_t)0x3FFFFFFF);
+	if (!d.chainCount) HIPCHK(c, dalloc(d.tabAllocs, &d.chainCount, (size_t)4));
+	for (int k = 2; k <= depth; k++) {
+		ChainLevel& L = d.chain[k - 2];
+		if (L.A) continue;
+		HIPCHK(c, dalloc(d.tabAllocs, &L.A, cap)); HIPCHK(c, dalloc(d.tabAllocs, &L.B, cap));
+		HIPCHK(c, dalloc(d.tabAllocs, &L.RO, cap)); HIPCHK(c, dalloc(d.tabAllocs, &L.RD, cap));
+		HIPCHK(c, dalloc(d.tabAllocs, &L.parent, cap));
+		L.count = d.chainCount + (k - 2), L.cap = (int)cap;
+	}
+	HIPCHK(c, hipMemsetAsync(d.chainCount, 0, 4 * sizeof(int), st));
+	// (a capacity of 0: every link of the bounce table is the 0 k_bounce_table wrote, and no level has a record)
+	for (int k = 2; k <= depth && cap > 0; k++) {
+		const ChainLevel& L = d.chain[k - 2];
+		const ChainLevel up = k == 2 ? ChainLevel{} : d.chain[k - 3];
+		const size_t nUp = k == 2 ? 2 * records : cap;
+		hipLaunchKernelGGL(k_chain_link, dim3((unsigned)((nUp + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, st, c->S, k == 2 ? d.btab.B : up.B, k == 2 ? (const int*)nullptr : (const int*)up.count, (int)nUp, L);
+		HIPCHK(c, hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), st)); // the same work heads again
+		const int grid = std::min((int)((cap + RT_CHUNK - 1) / RT_CHUNK / 4 + 1), d.gridChain);
+		if (c->counting) hipLaunchKernelGGL(k_chain_table<true>, dim3(grid), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, d.btab, up, L, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
+		else hipLaunchKernelGGL(k_chain_table<false>, dim3(grid), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, d.btab, up, L, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
+	}
+	d.chainLevels = depth, d.chainGen = c->sceneGen;
+	return RT_OK;
+}
+static int primary_table_for(rt_ctx* c, const RenderParams& R, hipStream_t st, bool* use, bool* bounce, int* chain)
+{
+	rt_ctx::DenseState& d = c->dense;
+	*use = false, *bounce = false, *chain = 1;
+	const bool wantChain = c->knobs.bounceDepth > 1 && c->knobs.bounceTable != 0 && !c->Qt.on; // (the sampler's shade reads no table)
 	// (a filter kind: the samples of a pixel take distinct rays, which no table of the frame's integer-pixel rays holds; such a batch does
 	// not count towards a rebuild either)
 	if (!c->knobs.primaryTable || R.customO || R.filter != RT_FILTER_REFERENCE) return RT_OK;
-	if (d.tableGen == c->sceneGen) { *use = true, *bounce = d.bounceGen == c->sceneGen; return RT_OK; }
 	const size_t records = (size_t)(c->width + 2) * (size_t)(c->height + 2);
+	const unsigned long long chainAt = (unsigned long long)c->knobs.chainMin * (unsigned long long)c->knobs.tableMin * records;
+	if (d.tableGen == c->sceneGen) {
+		*use = true, *bounce = d.bounceGen == c->sceneGen;
+		if (*bounce && wantChain && d.chainGen != c->sceneGen) { // levels 0-1 are current, the deeper ones not yet: the samples keep counting
+			d.tablePending += R.nSamples;
+			if (d.tablePending >= chainAt) {
+				prof_begin(c, K_QUERY, st);
+				const int rc = build_chain_tables(c, st);
+				prof_end(c, st);
+				if (rc != RT_OK) return rc;
+			}
+		}
+		if (*bounce && wantChain && d.chainGen == c->sceneGen) *chain = d.chainLevels;
+		return RT_OK;
+	}
 	if (d.tablePendingGen != c->sceneGen) d.tablePendingGen = c->sceneGen, d.tablePending = 0;
 	d.tablePending += R.nSamples;
 	if (d.tablePending < (unsigned long long)c->knobs.tableMin * records) return RT_OK;
@@ -423,6 +472,11 @@ static int primary_table_for(rt_ctx* c, const RenderParams& R, hipStream_t st, b
 		if (c->counting) hipLaunchKernelGGL(k_bounce_table<true>, dim3(gridB), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, d.btab, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
 		else hipLaunchKernelGGL(k_bounce_table<false>, dim3(gridB), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, d.btab, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
 		d.bounceGen = c->sceneGen;
+		if (wantChain && d.tablePending >= chainAt) {
+			const int rc = build_chain_tables(c, st);
+			if (rc != RT_OK) { prof_end(c, st); return rc; }
+			*chain = d.chainLevels;
+		}
 	}
 	prof_end(c, st);
 	d.tableGen = c->sceneGen;
@@ -458,11 +512,14 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 	const int cnt = c->counting ? 1 : 0;
 	const int n = (int)R.nSamples;
 	bool table = false, bounce = false;
+	int chain = 1;
 	{
-		const int rc = primary_table_for(c, R, st, &table, &bounce);
+		const int rc = primary_table_for(c, R, st, &table, &bounce, &chain);
 		if (rc != RT_OK) return rc;
 	}
 	bounce = bounce && c->knobs.bounceTable != 0 && !c->Qt.on; // (the sampler's shade keeps emit_ray_s: the same bits either way)
+	// rounds 1 .. chainDepth - 1 read the chain tables (k_shade_s CHAIN), round 0 hands them their keys; a batch whose round 1 is its last has no use for them
+	const int chainDepth = bounce && rounds > 2 ? chain : 1;
 	// round 0 straight from the table (k_generate_c, k_shade_s / k_light_s TABLE0): no round-0 entry is written or read.  The pinhole ray is
 	// what the kernels rebuild from the pixel, and the sampler's shade keeps its entries; RT_ROUND0_ENTRIES=1 keeps them for everybody.
 	const bool direct = table && !c->Qt.on && !c->C.fisheye && c->knobs.round0Entries != 1;
@@ -500,7 +557,12 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 		if (pendingJoin) { HIPCHK(c, hipStreamWaitEvent(st, c->dense.join, 0)); pendingJoin = false; }
 		prof_begin(c, K_SHADE, st);
 		if (c->Qt.on) hipLaunchKernelGGL(k_shade_s<true>, dim3(c->dense.gridShade), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{}, 0, PrimaryTable{});
-		else if (direct && round == 0 && bounce && !last) hipLaunchKernelGGL((k_shade_s<false, true, true>), dim3(c->dense.gridShadeDirectBounce), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, c->dense.btab, c->knobs.bounceTable, c->dense.tab);
+		else if (direct && round == 0 && chainDepth > 1) hipLaunchKernelGGL((k_shade_s<false, true, true, true>), dim3(c->dense.gridShadeDirectBounceChain), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, c->dense.btab, c->knobs.bounceTable, c->dense.tab);
+		else if (round == 0 && chainDepth > 1) hipLaunchKernelGGL((k_shade_s<false, true, false, true>), dim3(c->dense.gridShadeBounceChain), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, c->dense.btab, c->knobs.bounceTable, PrimaryTable{});
+		else if (round > 0 && round < chainDepth && !last) {
+			const ChainLevel& L = c->dense.chain[round - 1]; // level round + 1
+			hipLaunchKernelGGL((k_shade_s<false, false, false, true>), dim3(c->dense.gridShadeChain), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{ L.A, L.B, L.cap, 0 }, c->knobs.bounceTable, PrimaryTable{});
+		} else if (direct && round == 0 && bounce && !last) hipLaunchKernelGGL((k_shade_s<false, true, true>), dim3(c->dense.gridShadeDirectBounce), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, c->dense.btab, c->knobs.bounceTable, c->dense.tab);
 		else if (direct && round == 0) hipLaunchKernelGGL((k_shade_s<false, false, true>), dim3(c->dense.gridShadeDirect), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{}, 0, c->dense.tab);
 		else if (bounce && round == 0 && !last) hipLaunchKernelGGL((k_shade_s<false, true>), dim3(c->dense.gridShadeBounce), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, c->dense.btab, c->knobs.bounceTable, PrimaryTable{});
 		else hipLaunchKernelGGL(k_shade_s<false>, dim3(c->dense.gridShade), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{}, 0, PrimaryTable{});
@@ -537,7 +599,7 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 	}
 	if (hc[3] != 0) (void)hipMemsetAsync(T.counts + 3, 0, sizeof(int), st);
 	const int rc = decode_status(c, hc[3], FAM_WAVEFRONT);
-	if (rc != RT_OK) { c->dense.tableGen = 0, c->dense.bounceGen = 0; return rc; } // (the trouble may have been the table build's)
+	if (rc != RT_OK) { c->dense.tableGen = 0, c->dense.bounceGen = 0, c->dense.chainGen = 0; return rc; } // (the trouble may have been the table build's)
 	HIPCHK(c, hipGetLastError());
 	return RT_OK;
 }

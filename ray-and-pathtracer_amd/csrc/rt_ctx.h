@@ -83,6 +83,17 @@ struct Knobs {
 	int bounceTable = 7;   // RT_BOUNCE_TABLE: (tests) which first-bounce rays off a glass or metal primary hit shade(0) answers from the bounce table
 	                       // (rt_stream.h BounceTable) instead of tracing them: bit 0 metal, bit 1 glass refraction, bit 2 glass reflection; 0: none,
 	                       // and no table is built
+	int bounceDepth = 4;   // RT_BOUNCE_DEPTH: 1-4, the levels of specular bounces answered from tables: 1 the bounce table alone; d: rounds 1 .. d - 1 also read
+	                       // the chain tables (rt_stream.h ChainLevel: the rays of paths whose every hit so far was glass or metal).  The same frames at
+	                       // every depth; RT_BOUNCE_TABLE's mask bits mean the same at every level
+	int chainMin = 1;      // RT_BOUNCE_DEPTH_MIN: levels >= 2 are built once RT_PRIMARY_TABLE_MIN times this many camera samples per primary record have
+	                       // been asked for since the tables went stale (1: with the first two levels; 0 with RT_PRIMARY_TABLE_MIN=0: everything in the
+	                       // first batch).  1080p, bench scene: levels 2-4 build in 1.4 ms; a batch that rebuilds everything is 1.3 ms behind depth 1
+	                       // at 1-2 frames, 0.7 at 12, 0.5 at 16, 0.26 ahead at 24 (profiles/ab_chain_table.txt), and a camera at rest has the build back
+	                       // eleven one-frame batches later.  A later build (2) makes what a context's counting launch tallies depend on how many
+	                       // samples it rendered before, which tests/test_gpu_look.py holds equal to a fresh context's: the default keeps one rule
+	long chainCap = -1;    // RT_BOUNCE_CAP: (tests) records a level >= 2 holds; default one per primary record (the bench frame uses 0.14-0.19;
+	                       // a camera inside glass can ask for 2^k).  Children that do not fit are traced as at depth 1
 	int round0Entries = 0; // RT_ROUND0_ENTRIES: 0 round 0 of a batch with a current primary table shades straight from the table (k_generate_c writes class
 	                       // bytes only; rt_stream.h k_shade_s TABLE0), 1 generate copies the records into round-0 entries first (k_generate_t),
 	                       // 2 (tests) as 0, and the entry arrays nobody may read are filled with 0xFF bytes behind every such generate
@@ -101,6 +112,9 @@ static void read_knobs(Knobs& k)
 	k.mixedMax = (unsigned)num("RT_MIXED_MAX", 10000000);
 	k.primaryTable = num("RT_PRIMARY_TABLE", 1) != 0, k.tableMin = (int)std::max(0l, num("RT_PRIMARY_TABLE_MIN", 12));
 	{ const char* e = getenv("RT_BOUNCE_TABLE"); k.bounceTable = e ? (int)atol(e) & 7 : 7; } // (a test-tier mask read beside num(): tests/support.py KNOBS is the list of the num() knobs, and tests/test_gpu_bounce_table.py clears this one itself)
+	{ const char* e = getenv("RT_BOUNCE_DEPTH"); const long v = e ? atol(e) : 4; k.bounceDepth = v < 1 ? 1 : (v > 4 ? 4 : (int)v); } // (beside num() as well: tests/test_gpu_chain_table.py clears these three itself)
+	{ const char* e = getenv("RT_BOUNCE_DEPTH_MIN"); k.chainMin = e ? (int)std::max(0l, atol(e)) : 1; }
+	{ const char* e = getenv("RT_BOUNCE_CAP"); k.chainCap = e ? std::max(0l, atol(e)) : -1; }
 	{ const char* e = getenv("RT_ROUND0_ENTRIES"); const long v = e ? atol(e) : 0; k.round0Entries = v == 1 || v == 2 ? (int)v : 0; } // (beside num() too: tests/test_gpu_round0_direct.py clears it itself)
 	if (k.exactGamma) k.deferGamma = 1; // the exact form lives where samples are read (k_accumulate), not in the shading kernels
 	// the scheduling thresholds are compile-time constants since round 4 (rt_scene_dev.h): a sweep script that still sets them in
@@ -245,6 +259,14 @@ struct rt_ctx {
 		unsigned long long bounceGen = 0;
 		int gridBounce = 0, gridShadeBounce = 0; // resident blocks of k_bounce_table and of the shade launch that reads it
 		int gridShadeDirect = 0, gridShadeDirectBounce = 0, gridLightDirect = 0; // ... and of the round-0 launches that read the primary table (TABLE0)
+		// The chain tables (rt_stream.h ChainLevel): chain[k - 2] is level k = 2 .. 4, built behind the bounce table from its records once the
+		// batch's samples are worth it (primary_table_for); levels 2 .. chainLevels are current while chainGen == sceneGen.  chainCount: the
+		// levels' record counters on the device.  In tabAllocs with the other tables.
+		ChainLevel chain[3] = {};
+		int* chainCount = nullptr;
+		int chainLevels = 1;
+		unsigned long long chainGen = 0;
+		int gridChain = 0, gridShadeChain = 0, gridShadeBounceChain = 0, gridShadeDirectBounceChain = 0; // resident blocks of k_chain_table and of the CHAIN shade launches
 		void free_state() { free_pool(allocs); cap = 0; }
 		void destroy()
 		{

@@ -328,18 +328,11 @@ struct BounceTable {
 	int n, w; // primary records (2 n records here) and the primary table's row length
 };
 #define BT_PRESENT 0x100
-// the ray of (record i, branch): false when there is none (the primary ray ends, its hit is diffuse, or no sample can take the branch)
-__device__ __forceinline__ bool bounce_ray(const DScene& S, const DCamera& C, const PrimaryTable& P, int i, int branch, f3& nO, f3& nD)
+// the ray a glass or metal hit (material m, normal, t) of the ray (O, D) scatters on 'branch': false when there is none (the hit is
+// diffuse, or no sample can take the branch)
+__device__ __forceinline__ bool specular_ray(const DMaterial& m, const f3& O, const f3& D, const f3& normal, float t, int branch, f3& nO, f3& nD)
 {
-	const int4 b = P.B[i];
-	if (b.z & PT_FINISHED) return false;
-	const DMaterial m = S.mats[b.y];
 	if (m.type != 3 && m.type != 2) return false;
-	const float4 a = P.A[i];
-	f3 O, D;
-	primary_ray(C, i % P.w - 1, i / P.w - 1, O, D);
-	const f3 normal = xyz(a);
-	const float t = a.w;
 	const f3 I = O + t * D; // ray.IntersectionPoint(), as k_shade_s
 	const f3 W(1.0f);
 	f3 E(1.0f), nW, o(0.0f), d(0.0f);
@@ -354,6 +347,18 @@ __device__ __forceinline__ bool bounce_ray(const DScene& S, const DCamera& C, co
 	}
 	if (have) nO = o, nD = d;
 	return have;
+}
+// the ray of (record i, branch): false when there is none (the primary ray ends, its hit is diffuse, or no sample can take the branch)
+__device__ __forceinline__ bool bounce_ray(const DScene& S, const DCamera& C, const PrimaryTable& P, int i, int branch, f3& nO, f3& nD)
+{
+	const int4 b = P.B[i];
+	if (b.z & PT_FINISHED) return false;
+	const DMaterial m = S.mats[b.y];
+	if (m.type != 3 && m.type != 2) return false;
+	const float4 a = P.A[i];
+	f3 O, D;
+	primary_ray(C, i % P.w - 1, i / P.w - 1, O, D);
+	return specular_ray(m, O, D, xyz(a), a.w, branch, nO, nD);
 }
 struct BouncePolicy {
 	const DScene& S; const DCamera& C; const PrimaryTable& P; const BounceTable& Bt; float t_min; int* flag;
@@ -393,6 +398,139 @@ __global__ void __launch_bounds__(RT_BLOCK) k_bounce_table(DScene S, DCamera C, 
 	uint rays = 0;
 	BouncePolicy pol{ S, C, P, Bt, mode_t_min(1), flag };
 	trace_persistent<false, COUNT, false>(S, pol, 2 * Bt.n, heads, t_min, tuning, ldsStack, spill, flag, lc, rays);
+	if (COUNT) flush_counters(counters, lc, 0, 0);
+}
+
+// ---- the chain tables: levels 2 .. RT_BOUNCE_DEPTH ----------------------------------------------------------------------
+// The argument does not stop at round 1.  While every hit of a path so far was glass or metal, no draw has entered an nO or nD: the
+// round-k ray is one of at most 2^k rays per primary record, and these are the long rays (58 / 47 steps per ray leaving glass / metal,
+// 14 off a diffuse surface).  Level 1 is the BounceTable, dense.  A level k >= 2 is COMPACT: a record exists only for a child of a
+// specular hit of level k - 1, and B.w of a record of level k >= 1 -- 0 until k_chain_link has run over its level -- is the LINK:
+// 1 + the index in level k + 1 of its first child, 0 for none.  Children per specular hit: metal one; glass the refraction at the
+// link's index and the reflection one behind it (the refraction's record stays absent when kr < 1 fails, as in bounce_ray).
+//   A, B    as the BounceTable's, B.w the link
+//   RO, RD  (build only) the record's world ray: load writes it, store hands it to resolve_hit, the next level's load starts from it
+//   parent  (build only) x = the record of the level above, y = the branch; x < 0: the slot nobody got (below)
+// k_chain_link hands out the indices with one atomic per block, so the order of records differs from build to build and nothing
+// depends on it.  A level holds cap records; children that do not fit -- both of a glass hit or neither -- leave link 0, and shade
+// traces such a ray as it always did: a missing record is never wrong, only slower.
+// Bit equality, by induction on the level.  Shade of round k - 1 computes the ray of an entry answered from record r of level k - 1
+// by metal_bounce / glass_hit + glass_refracted / glass_reflected on O, D (the entry's: the nO, nD the round before wrote, to the
+// bit), normal and t (hitN: r's A), the material (hitId: r's B.y) and I = O + t * D.  The build's load runs the same functions
+// (specular_ray, which is bounce_ray's body) on r's world ray -- level 1: bounce_ray of the primary record, which is shade(0)'s nO, nD
+// by the level-1 argument above; level >= 2: RO, RD of r, which by induction is the entry's O, D -- and on r's A and B, under
+// -ffp-contract=off.  W, E and the draw enter the weights only.  So the child's ray is the ray shade would hand to emit_ray_s, and
+// its record what extend would have stored for it: head tests, walk and resolve_hit (on the world ray) are the same calls.
+struct ChainLevel {
+	float4* A;
+	int4* B;
+	float4* RO;
+	float4* RD;
+	int2* parent;
+	int* count; // records handed out so far; runs past cap when children did not fit
+	int cap;
+};
+// Links level 'up' (its B; n records, or min(*upCount, n) of a compact level) to level L: every present record whose hit is glass or
+// metal gets its children's indices.  The request of a block is one atomicAdd; a record's children sit at the block's base + the
+// requests of the lanes before it.  The only hole this can leave below cap is the last slot, when a glass pair started there: its
+// parent is marked -1 by the lane that saw it.
+__global__ void __launch_bounds__(RT_BLOCK) k_chain_link(DScene S, int4* upB, const int* upCount, int n, ChainLevel L)
+{
+	__shared__ int waveSum[RT_BLOCK / 64];
+	__shared__ int blockBase;
+	if (upCount) n = min(*upCount, n);
+	const int i = (int)(blockIdx.x * RT_BLOCK + threadIdx.x);
+	const int lane = (int)(threadIdx.x & 63), wib = (int)(threadIdx.x >> 6);
+	int nc = 0;
+	if (i < n) {
+		const int4 b = upB[i];
+		if ((b.z & BT_PRESENT) && (b.z & CL_CONT)) { // a surface: b.y is a material
+			const int type = S.mats[b.y].type;
+			nc = type == 3 ? 2 : (type == 2 ? 1 : 0);
+		}
+	}
+	int inc = nc;
+	for (int o = 1; o < 64; o <<= 1) {
+		const int t = __shfl_up(inc, o);
+		if (lane >= o) inc += t;
+	}
+	if (lane == 63) waveSum[wib] = inc;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		int tot = 0;
+		for (int w = 0; w < RT_BLOCK / 64; w++) tot += waveSum[w];
+		blockBase = tot > 0 ? atomicAdd(L.count, tot) : 0;
+	}
+	__syncthreads();
+	if (i >= n) return;
+	int base = blockBase + inc - nc;
+	for (int w = 0; w < wib; w++) base += waveSum[w];
+	int link = 0;
+	if (nc > 0) {
+		if (base >= 0 && base + nc <= L.cap) {
+			L.parent[base] = make_int2(i, 0);
+			if (nc == 2) L.parent[base + 1] = make_int2(i, 1);
+			link = base + 1;
+		} else if (base >= 0 && base < L.cap) L.parent[base] = make_int2(-1, 0); // (base == cap - 1, nc == 2)
+	}
+	upB[i].w = link;
+}
+struct ChainPolicy {
+	const DScene& S; const DCamera& C; const PrimaryTable& P; const BounceTable& Bt; const ChainLevel& Up; const ChainLevel& L; float t_min; int* flag;
+	__device__ __forceinline__ int slot_of(int w) const { return w; }
+	__device__ __forceinline__ bool load(int w, f3& O, f3& D, float& tm, HitRef& head) const
+	{
+		const int2 pr = L.parent[w];
+		const bool from1 = Up.A == nullptr; // the level above is the bounce table
+		RT_CHECK(w >= 0 && w < L.cap && pr.x < (from1 ? 2 * Bt.n : Up.cap) && (pr.y == 0 || pr.y == 1), 29, flag);
+		bool have = pr.x >= 0;
+		f3 o(0.0f), d(0.0f), nO(0.0f), nD(0.0f);
+		if (have) {
+			float4 a;
+			int4 b;
+			if (from1) {
+				const int branch = pr.x >= Bt.n ? 1 : 0;
+				have = bounce_ray(S, C, P, pr.x - branch * Bt.n, branch, o, d);
+				a = Bt.A[pr.x], b = Bt.B[pr.x];
+			} else {
+				o = xyz(Up.RO[pr.x]), d = xyz(Up.RD[pr.x]);
+				a = Up.A[pr.x], b = Up.B[pr.x];
+			}
+			if (have && (b.z & BT_PRESENT) && (b.z & CL_CONT)) {
+				const DMaterial m = S.mats[b.y];
+				have = specular_ray(m, o, d, xyz(a), a.w, pr.y, nO, nD);
+			} else have = false;
+		}
+		if (!have) { L.B[w] = make_int4(0, 0, 0, 0); return false; }
+		L.RO[w] = mk4(nO, 0.0f), L.RD[w] = mk4(nD, 0.0f);
+		O = nO, D = nD;
+		tm = 1e34f; // Ray constructor default, as emit_ray_s
+		LaneCounters unused;
+		find_nearest_head<false>(S, O, D, t_min, tm, head, unused);
+		return true;
+	}
+	__device__ __forceinline__ void store(int w, const HitRef& hit, const f3&, const f3&) const
+	{
+		const f3 O = xyz(L.RO[w]), D = xyz(L.RD[w]); // (the walk's O and D may be an instance's)
+		int objIdx, mat, matType;
+		f3 normal;
+		resolve_hit(S, hit, O, D, objIdx, mat, normal, &matType);
+		const int flags = BT_PRESENT | hit_class(S, objIdx, mat, 0, matType) | (hit_class(S, objIdx, mat, 1, matType) << 4);
+		L.A[w] = mk4(normal, hit.t);
+		L.B[w] = make_int4(objIdx, mat, flags, 0);
+	}
+};
+// One launch per level >= 2 right behind k_chain_link of the level above, over the records that got a parent; counting launches as
+// k_primary_table.  A level whose parent level holds no specular hit finds a count of 0 and traces nothing.
+template <bool COUNT>
+__global__ void __launch_bounds__(RT_BLOCK) k_chain_table(DScene S, DCamera C, PrimaryTable P, BounceTable Bt, ChainLevel Up, ChainLevel L, float t_min, int tuning, uint* spill, int* heads, int* flag, DCounters* counters)
+{
+	__shared__ __attribute__((aligned(16))) uint ldsStack[RT_LDS_WORDS];
+	LaneCounters lc;
+	lc.clear();
+	uint rays = 0;
+	ChainPolicy pol{ S, C, P, Bt, Up, L, mode_t_min(1), flag };
+	trace_persistent<false, COUNT, false>(S, pol, min(*L.count, L.cap), heads, t_min, tuning, ldsStack, spill, flag, lc, rays);
 	if (COUNT) flush_counters(counters, lc, 0, 0);
 }
 
@@ -602,10 +740,17 @@ __device__ __forceinline__ void load_tables(DScene& S, ShadeTables& L, int enabl
 // primary table P (the index out of the same sample_primary_pixel call), O is the camera position and D the pinhole ray of the integer
 // pixel: primary_ray_f on the ints k_primary_table and k_generate_t hand to primary_ray, so the bits are theirs.  The shadow record
 // refers to the table record instead of the entry (shX.x: k_light_s TABLE0).  Always launched with round 0 and fresh set.
-template <bool QL, bool BOUNCE = false, bool TABLE0 = false>
+// CHAIN: a batch whose chain tables (ChainLevel) are current.  An entry answered from a record of level k carries that record's link as
+// its key in W.w, which is free while the sampler is off (written 0 otherwise, and loaded by every later shade anyway); key 0: no table.
+// With BOUNCE (round 0) the kernel only adds the key it read from the level-1 record.  Without (round r, 1 <= r < depth), Bt is level
+// r + 1 with n = its capacity: a glass or metal hit of an entry with a key takes the child key - 1 + branch under the same mask bits, and a
+// present child answers the ray as the bounce table does in round 0, its own link the new key; every other ray goes to emit_ray_s with key 0.
+template <bool QL, bool BOUNCE = false, bool TABLE0 = false, bool CHAIN = false>
 __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_WAVES) k_shade_s(DScene S0, DCamera C, RenderParams R, StreamState T, int round, int fresh, int last, int lastNext, int decide, int ldsTables, int counting, QTable Qt, BounceTable Bt, int bounceMask, PrimaryTable P)
 {
 	static_assert(!(QL && TABLE0), "the sampler's round 0 keeps its entries");
+	static_assert(!(QL && CHAIN), "W.w is the sampler's key word");
+	constexpr bool READ = CHAIN && !BOUNCE; // a round >= 1 that reads a chain level
 	__shared__ ShadeTables tables;
 	uint nDecided = 0;
 	uint qOld = 0; // QL: the words this lane's rewards were added to, or-ed (q_reward: bit 31 = a count field past its limit)
@@ -676,7 +821,8 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 			f3 nO(0.0f), nD(0.0f), nW(0.0f);
 			uint nextKey = 0;       // QL: (cell, patch) + 1 of the ray this hit scatters
 			bool deadSample = false; // QL: the guided direction points below the surface: nothing to trace
-			int bounceRec = -1;      // BOUNCE: the bounce table's record of the scattered ray
+			int bounceRec = -1;      // BOUNCE: the bounce table's record of the scattered ray; READ: the chain level's
+			const int chainKey = READ && !fresh ? __float_as_int(w4.w) : 0; // READ: the link of the record this entry's hit came from
 			// QL: the key word travels in W.w: bits 0-30 the (cell, patch) + 1 that sent this ray, bit 31 "this sample pays rewards"
 			const uint keyWord = QL ? (fresh ? (((__float_as_uint(e4.w) & Qt.learnMask) == 0) ? RT_Q_LEARNER : 0u) : __float_as_uint(w4.w)) : 0u;
 			const bool learner = (keyWord & RT_Q_LEARNER) != 0;
@@ -699,15 +845,18 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 					if (g.kr < RandomFloat(seed)) {
 						glass_refracted(g, m, I, D, W, E, nO, nD, nW);
 						if (BOUNCE && (bounceMask & 2)) bounceRec = primaryRec;
+						if (READ && (bounceMask & 2) && chainKey > 0) bounceRec = chainKey - 1;
 					} else {
 						glass_reflected(g, m, I, D, W, nO, nD, nW);
 						if (BOUNCE && (bounceMask & 4)) bounceRec = primaryRec + Bt.n;
+						if (READ && (bounceMask & 4) && chainKey > 0) bounceRec = chainKey;
 					}
 					if (childTraces) segmentEnds = false;
 					else Lsum = Lsum + untraced_child(nW);
 				} else if (m.type == 2) { // METAL, renderer.cpp:192-197
 					metal_bounce(true, col, I, D, normal, W, E, nO, nD, nW);
 					if (BOUNCE && (bounceMask & 1)) bounceRec = primaryRec;
+					if (READ && (bounceMask & 1) && chainKey > 0) bounceRec = chainKey - 1;
 					if (childTraces) segmentEnds = false;
 					else Lsum = Lsum + untraced_child(nW);
 				} else { // DIFFUSE, renderer.cpp:156-191
@@ -762,14 +911,17 @@ __global__ void __launch_bounds__(RT_BLOCK, QL ? RT_SHADE_Q_WAVES : RT_SHADE_S_W
 					if constexpr (BOUNCE) {
 						RT_CHECK(fresh && primaryRec >= 0 && primaryRec < Bt.n && bounceRec < 2 * Bt.n, 27, &T.counts[SC_FLAG]);
 						if (primaryRec >= 0 && primaryRec < Bt.n && bounceRec >= 0) bb = Bt.B[bounceRec]; // (bounceRec is primaryRec or primaryRec + n)
+					} else if constexpr (READ) {
+						RT_CHECK(!fresh && round > 0 && bounceRec < Bt.n, 30, &T.counts[SC_FLAG]);
+						if (bounceRec >= 0 && bounceRec < Bt.n) bb = Bt.B[bounceRec];
 					}
-					if (BOUNCE && (bb.z & BT_PRESENT)) {
+					if ((BOUNCE || READ) && (bb.z & BT_PRESENT)) {
 						// what emit_ray_s writes for a ray it decided
 						const float4 ba = Bt.A[bounceRec];
 						T.hitN[pout][p.x] = ba;
 						T.hitId[pout][p.x] = make_int2(bb.x, bb.y);
 						T.O[pout][p.x] = mk4(nO, ba.w), T.D[pout][p.x] = mk4(nD, 0.0f); // (w: extend's, which never sees this entry)
-						T.W[pout][p.x] = mk4(nW, __uint_as_float(nextKey | (keyWord & RT_Q_LEARNER)));
+						T.W[pout][p.x] = mk4(nW, CHAIN ? __int_as_float(bb.w) : __uint_as_float(nextKey | (keyWord & RT_Q_LEARNER)));
 						T.cls[pout][p.x] = (unsigned char)(CL_LIVE | ((lastNext ? bb.z >> 4 : bb.z) & 15));
 						nDecided++;
 					} else {
