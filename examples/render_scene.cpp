@@ -6,12 +6,14 @@
 //   g++ -std=c++17 -O2 examples/render_scene.cpp -Iray-and-pathtracer_amd/host \
 //       -Lray-and-pathtracer_amd/host -lrapt_host -Lray-and-pathtracer_amd/csrc -lrt_amd \
 //       -Wl,-rpath,$PWD/ray-and-pathtracer_amd/host -Wl,-rpath,$PWD/ray-and-pathtracer_amd/csrc -o render_scene
-//   ./render_scene scene.rapt out.ppm 640 360 path 16 [all | d0,d1,...] [--filter reference|point|box|tent] [--aperture R --focus D | --focus-pixel X,Y] [--spin DEG [--carry]]
+//   ./render_scene scene.rapt out.ppm 640 360 path 16 [all | d0,d1,...] [--filter reference|point|box|tent] [--aperture R --focus D | --focus-pixel X,Y] [--shutter DX,DY,DZ] [--spin DEG [--carry]]
 // The optional last argument spreads every Tick over several GPUs (one rt_ctx and one host thread per device,
 // rows interleaved, rt_gather_rows into device d0): "all" = every visible device.  --filter (anywhere after the frame count) sets
 // Renderer::pixelFilter: the sub-pixel camera samples of path mode (rt_set_pixel_filter; default: the reference's truncated jitter).
 // --aperture R (path mode, with a --filter other than reference) gives the camera a thin lens of radius R (Renderer::lensRadius, rt_set_lens)
 // focused at --focus D, or on what pixel X,Y sees with --focus-pixel X,Y (Renderer::FocusAt, rt_focus_at), which also prints that distance.
+// --shutter DX,DY,DZ (path mode, with a --filter other than reference): camera motion blur.  The camera translates by that vector over the
+// exposure, all four points (Renderer::shutter / shutterCamera, rt_set_shutter): every sample is taken at a time of its own.
 // --spin DEG (a TLAS scene): before the last frame instance 0 is turned by DEG degrees about y (bvhInstance::SetTransform) and sent on with
 // Scene::CommitInstances (rt_set_instances: no re-upload); that Tick clears, so the image is the moved scene's.
 // --carry (path mode with --spin only; refused otherwise): the Ticks are adaptive with Renderer::reproject set and the move goes through Renderer::CommitInstances,
@@ -28,7 +30,7 @@ using namespace rapt;
 
 int main(int argc, char** argv)
 {
-	if (argc < 7) { fprintf(stderr, "usage: %s scene.rapt out.ppm width height whitted|path frames [all | d0,d1,...] [--filter reference|point|box|tent] [--aperture R --focus D | --focus-pixel X,Y] [--spin DEG [--carry]]\n", argv[0]); return 2; }
+	if (argc < 7) { fprintf(stderr, "usage: %s scene.rapt out.ppm width height whitted|path frames [all | d0,d1,...] [--filter reference|point|box|tent] [--aperture R --focus D | --focus-pixel X,Y] [--shutter DX,DY,DZ] [--spin DEG [--carry]]\n", argv[0]); return 2; }
 	int filter = RT_FILTER_REFERENCE;
 	float spin = 0;
 	bool carry = false;
@@ -52,6 +54,15 @@ int main(int argc, char** argv)
 		if (ap) aperture = (float)atof(argv[a + 1]);
 		if (fo) focus = (float)atof(argv[a + 1]);
 		if (fp && sscanf(argv[a + 1], "%d,%d", &focusX, &focusY) != 2) { fprintf(stderr, "--focus-pixel X,Y\n"); return 2; }
+		for (int b = a; b + 2 < argc; b++) argv[b] = argv[b + 2];
+		argc -= 2, a--;
+	}
+	float shutterMove[3] = { 0, 0, 0 };
+	bool shutter = false;
+	for (int a = 7; a + 1 < argc; a++) {
+		if (strcmp(argv[a], "--shutter") != 0) continue;
+		if (sscanf(argv[a + 1], "%f,%f,%f", &shutterMove[0], &shutterMove[1], &shutterMove[2]) != 3) { fprintf(stderr, "--shutter DX,DY,DZ\n"); return 2; }
+		shutter = true;
 		for (int b = a; b + 2 < argc; b++) argv[b] = argv[b + 2];
 		argc -= 2, a--;
 	}
@@ -90,6 +101,13 @@ int main(int argc, char** argv)
 			if (!(focus > 0)) aperture = 0;
 		}
 		app.lensRadius = aperture, app.focusDistance = focus;
+		if (shutter) {
+			const float3 move(shutterMove[0], shutterMove[1], shutterMove[2]);
+			app.shutterCamera = app.camera; // the camera at shutter close: the open camera, translated
+			app.shutterCamera.camPos = app.camera.camPos + move, app.shutterCamera.topLeft = app.camera.topLeft + move;
+			app.shutterCamera.topRight = app.camera.topRight + move, app.shutterCamera.bottomLeft = app.camera.bottomLeft + move;
+			app.shutter = true;
+		}
 		const int ticks = path ? frames : 1;
 		for (int f = 0; f < ticks; f++) {
 			if (spin != 0 && f == ticks - 1) {

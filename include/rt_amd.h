@@ -257,6 +257,49 @@ typedef struct { float radius; float focus_distance; } rt_lens;   /* radius 0: o
 int rt_set_lens(rt_ctx* ctx, const rt_lens* lens);     /* NULL: off */
 int rt_get_lens(const rt_ctx* ctx, rt_lens* out);
 int rt_focus_at(rt_ctx* ctx, int x, int y, float* distance_out);
+/* ---- shutter: camera motion blur for path-mode camera samples ------------------------------------------------------------------
+ * Every path sample of a batch is otherwise taken at one instant, through the context's one rt_camera record.  rt_set_shutter makes that
+ * record the camera at shutter OPEN and gives the context a second record, the camera at shutter CLOSE: every path-mode camera sample
+ * draws a time tau of its own in [0, 1] and looks through the camera interpolated to that time.  The reference has no shutter: this is
+ * the library's own definition, restated in numpy by tests/shutter_ref.py.  A NULL record switches the shutter off (a context's
+ * default): no time is drawn and every bit is the pixel filter's and the lens's.
+ * Definition of camera sample (pixel (x, y), frame f, seed_base) with the shutter on; all arithmetic f32, IEEE divide and square root, no
+ * contraction; s, StreamSeed, RandomFloat, o(), dot, cross, normalize and RT_LENS_TRIES are rt_set_pixel_filter's and rt_set_lens's above;
+ * X0 is any of the twelve floats cam_pos, top_left, top_right, bottom_left of the context's camera, X1 the same float of cam_close:
+ *   the path's random stream: StreamSeed(s), nothing drawn (unchanged)
+ *   js = StreamSeed(~s)
+ *   BOX / TENT: u1 = RandomFloat(js); u2 = RandomFloat(js); dx = o(u1); dy = o(u2)        (POINT: no draw, dx = dy = 0)
+ *   tau = RandomFloat(js)                    (behind the filter's draws, in front of the lens's; the CLOSED interval [0, 1])
+ *   X(tau) = X0 + tau * (X1 - X0)            per float, for all twelve
+ *   without a lens: the pixel filter's ray -- GetPrimaryRay's P and D on u = (x + dx) * (1.0f / width), v = (y + dy) * (1.0f / height) --
+ *     computed on the camera X(tau): O = cam(tau), D = normalize(P - cam(tau));
+ *   with a lens (radius > 0): rt_set_lens's ray on the camera X(tau).  The rejection pairs continue on js behind tau, and lam is
+ *     evaluated per sample on the device, lam = focus_distance / (fabsf(dot(E, N)) / sqrtf(dot(N, N))) with A, B, N, E of X(tau).
+ *     (With the shutter off lam stays the host's number, and every bit is what rt_set_lens alone gives.)
+ * tau = 1.0f does not give X1's bits in general (X0 + (X1 - X0) rounds twice).  A closing record that equals the open camera gives
+ * X(tau) = X0 exactly (X1 - X0 = 0); it still consumes the tau draw, so without a lens its rays are the pixel filter's bit for bit, but
+ * with a lens the lens point comes from later draws and it is NOT bit-equal to the shutter switched off.
+ * The shutter applies to the RT_MODE_PATH camera samples of rt_render, rt_render_rows, rt_render_active and rt_render_budget and to
+ * rt_sample_rays; Whitted mode, rt_trace_batch*, rt_render_aovs, rt_primary_hits and rt_focus_at ignore it.  A sample stays a function of
+ * (seed_base, pixel, frame, kind, lens, shutter) and is accumulated into its own pixel: split calls, row shards, lists, budget plans, the
+ * statistics and rt_gather_* compose with it as with the lens.  From those calls, with the shutter on, RT_E_UNSUPPORTED (never a silent
+ * still camera):
+ *   - kind RT_FILTER_REFERENCE (the lens's rule: its jitter lives on the path's own stream and the hit tables serve that mode);
+ *   - a fisheye open camera;
+ *   - with a lens: lam at the open or at the closing camera not finite and > 0;
+ *   - (the Q-learning sampler is refused with any filter kind already).
+ * rt_set_shutter: RT_E_ARG, checked before the context is touched, for a float among cam_close's twelve that is not finite and for
+ * cam_close->fisheye != 0; view_angle and y_angle are not looked at.  It does not clear the accumulator, does not make the G-buffer
+ * stale, does not end a captured history and drops no list or plan.  rt_set_camera keeps the shutter: the closing record is the
+ * caller's to update when the open camera moves.  The record is copied to the device on the context's stream.
+ * rt_get_shutter returns 1 (on; *out = the record as it was set), 0 (off; *out untouched) or a negative rt_status.
+ * Limits: camera motion only -- objects do not blur (moving instances and deforming meshes would need a time in the traversal state).
+ * The G-buffer, both denoisers, the three reprojections and rt_focus_at see the camera at shutter open.  A pixel that the motion sweeps
+ * over several surfaces mixes surfaces its G-buffer record does not describe: the denoisers' edge stops are too sharp there, and a carry
+ * moves its samples as if the camera stood still at shutter open.  The time is uniform and unstratified: no shutter efficiency curve,
+ * no rolling shutter. */
+int rt_set_shutter(rt_ctx* ctx, const rt_camera* cam_close);   /* NULL: off (a context's default) */
+int rt_get_shutter(const rt_ctx* ctx, rt_camera* out);         /* 1: on, *out = the record; 0: off, *out untouched; < 0: an rt_status */
 /* memset of the accumulator (renderer.cpp:9, :274) */
 int rt_clear(rt_ctx* ctx);
 /* rows [y0, y1) of the float4 accumulator -> host (Renderer::accumulator, renderer.h:98) */

@@ -89,6 +89,8 @@ rt_ctx* rt_create(int device, int width, int height)
 	ok = ok && hipMemset(c->counters, 0, 2 * sizeof(DCounters)) == hipSuccess;
 	ok = ok && hipHostMalloc((void**)&c->hostCounts, 32 * sizeof(int)) == hipSuccess;
 	ok = ok && hipMalloc((void**)&c->gammaLut, 256 * sizeof(float)) == hipSuccess;
+	ok = ok && hipMalloc((void**)&c->shutterDev, sizeof(ShutterCam)) == hipSuccess;
+	ok = ok && hipMemset(c->shutterDev, 0, sizeof(ShutterCam)) == hipSuccess;
 	if (ok) {
 		const int exact = c->knobs.exactGamma; // rt_kernels.h gamma_powf
 		ok = hipMemcpyToSymbol(HIP_SYMBOL(g_exactGamma), &exact, sizeof(int), 0, hipMemcpyHostToDevice) == hipSuccess;
@@ -132,6 +134,7 @@ void rt_destroy(rt_ctx* c)
 	free_pool(c->recordAllocs);
 	free_pool(c->historyAllocs);
 	if (c->gammaLut) (void)hipFree(c->gammaLut);
+	if (c->shutterDev) (void)hipFree(c->shutterDev);
 	if (c->flags) (void)hipFree(c->flags);
 	if (c->counters) (void)hipFree(c->counters);
 	if (c->hostCounts) (void)hipHostFree(c->hostCounts);

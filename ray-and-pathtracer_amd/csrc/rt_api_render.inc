@@ -667,6 +667,15 @@ static void screen_normal(const DCamera& C, float* N)
 	for (int i = 0; i < 3; i++) A[i] = C.topRight[i] - C.topLeft[i], B[i] = C.bottomLeft[i] - C.topLeft[i];
 	N[0] = A[1] * B[2] - A[2] * B[1], N[1] = A[2] * B[0] - A[0] * B[2], N[2] = A[0] * B[1] - A[1] * B[0];
 }
+// lam = focus_distance / screen_dist of a pinhole camera, as include/rt_amd.h defines it (rt_set_lens)
+static float lens_lam(const DCamera& C, float focusDistance)
+{
+	float N[3], E[3];
+	screen_normal(C, N);
+	for (int i = 0; i < 3; i++) E[i] = C.topLeft[i] - C.camPos[i];
+	const float screenDist = fabsf(host_dot(E, N)) / sqrtf(host_dot(N, N));
+	return focusDistance / screenDist;
+}
 // rt_set_lens's rules for a call that takes path-mode camera samples (include/rt_amd.h), and the lens's one derived number:
 // *lam = focus_distance / screen_dist, or 0 with the lens off
 static int lens_check(rt_ctx* c, const char* fn, float* lam)
@@ -676,28 +685,45 @@ static int lens_check(rt_ctx* c, const char* fn, float* lam)
 	if (c->pixelFilter == RT_FILTER_REFERENCE)
 		return fail(c, RT_E_UNSUPPORTED, "%s: a lens (rt_set_lens) with RT_FILTER_REFERENCE: the reference's jitter lives on the path's own stream; set a kind with rt_set_pixel_filter first", fn);
 	if (c->C.fisheye) return fail(c, RT_E_UNSUPPORTED, "%s: a lens (rt_set_lens) under a fisheye camera", fn);
-	float N[3], E[3];
-	screen_normal(c->C, N);
-	for (int i = 0; i < 3; i++) E[i] = c->C.topLeft[i] - c->C.camPos[i];
-	const float screenDist = fabsf(host_dot(E, N)) / sqrtf(host_dot(N, N));
-	const float l = c->lens.focus_distance / screenDist;
+	const float l = lens_lam(c->C, c->lens.focus_distance);
 	if (!(std::isfinite(l) && l > 0.0f)) return fail(c, RT_E_UNSUPPORTED, "%s: a lens (rt_set_lens) over a degenerate screen rectangle (focus_distance / screen_dist = %g)", fn, (double)l);
 	*lam = l;
 	return RT_OK;
 }
-// rt_set_pixel_filter's and rt_set_lens's rules for a path-mode render call (include/rt_amd.h); fn: the entry point the caller came through
+// rt_set_shutter's rules for a call that takes path-mode camera samples (include/rt_amd.h), behind a lens_check that passed: with a
+// lens, lam is a number of every sample's own camera, which the device computes, and *lam becomes what the device computes it from,
+// the focus distance itself (set_lens)
+static int shutter_check(rt_ctx* c, const char* fn, float* lam)
+{
+	if (!c->shutterOn) return RT_OK;
+	if (c->pixelFilter == RT_FILTER_REFERENCE)
+		return fail(c, RT_E_UNSUPPORTED, "%s: a shutter (rt_set_shutter) with RT_FILTER_REFERENCE: the reference's jitter lives on the path's own stream; set a kind with rt_set_pixel_filter first", fn);
+	if (c->C.fisheye) return fail(c, RT_E_UNSUPPORTED, "%s: a shutter (rt_set_shutter) under a fisheye camera", fn);
+	if (c->lens.radius > 0.0f) {
+		DCamera close = c->C;
+		memcpy(close.camPos, c->shutterCam.cam_pos, 12), memcpy(close.topLeft, c->shutterCam.top_left, 12);
+		memcpy(close.topRight, c->shutterCam.top_right, 12), memcpy(close.bottomLeft, c->shutterCam.bottom_left, 12);
+		const float l = lens_lam(close, c->lens.focus_distance);
+		if (!(std::isfinite(l) && l > 0.0f)) return fail(c, RT_E_UNSUPPORTED, "%s: a lens (rt_set_lens) over a degenerate screen rectangle of the shutter's closing camera (rt_set_shutter; focus_distance / screen_dist = %g)", fn, (double)l);
+		*lam = c->lens.focus_distance;
+	}
+	return RT_OK;
+}
+// rt_set_pixel_filter's, rt_set_lens's and rt_set_shutter's rules for a path-mode render call (include/rt_amd.h); fn: the entry point the caller came through
 static int filter_check(rt_ctx* c, const char* fn, float* lam)
 {
-	const int rc = lens_check(c, fn, lam);
+	int rc = lens_check(c, fn, lam);
+	if (rc == RT_OK) rc = shutter_check(c, fn, lam);
 	if (rc != RT_OK || c->pixelFilter == RT_FILTER_REFERENCE) return rc;
 	if (c->Qt.on) return fail(c, RT_E_UNSUPPORTED, "%s: a pixel filter with the Q-learning sampler on (its learn_mask is defined on the post-jitter state)", fn);
 	if (c->C.fisheye && c->pixelFilter != RT_FILTER_POINT) return fail(c, RT_E_UNSUPPORTED, "%s: RT_FILTER_BOX / RT_FILTER_TENT under a fisheye camera", fn);
 	return RT_OK;
 }
-// the lens of a batch of camera samples (lam: filter_check's / lens_check's)
+// the lens and the shutter of a batch of camera samples (lam: filter_check's, or lens_check's and shutter_check's; R.mode is set)
 static void set_lens(const rt_ctx* c, RenderParams& R, float lam)
 {
 	if (lam > 0.0f) R.lensRadius = c->lens.radius, R.lensLam = lam;
+	if (c->shutterOn && R.mode == RT_MODE_PATH) R.shutter = c->shutterDev;
 }
 
 // Frames [frame0, frame0 + nframes) of one tile of pixels -- tilePixels of them: the rows row_first + k * row_stride of rt_render_rows, or
@@ -838,7 +864,8 @@ int rt_sample_rays(rt_ctx* c, uint32_t frame, uint32_t seed_base, int y0, int y1
 	if (c->C.fisheye && c->pixelFilter > RT_FILTER_POINT) return fail(c, RT_E_UNSUPPORTED, "rt_sample_rays: RT_FILTER_BOX / RT_FILTER_TENT under a fisheye camera");
 	float lam = 0.0f;
 	{
-		const int lrc = lens_check(c, "rt_sample_rays", &lam);
+		int lrc = lens_check(c, "rt_sample_rays", &lam);
+		if (lrc == RT_OK) lrc = shutter_check(c, "rt_sample_rays", &lam);
 		if (lrc != RT_OK) return lrc;
 	}
 	HIPCHK(c, hipSetDevice(c->device));
@@ -879,6 +906,34 @@ int rt_get_lens(const rt_ctx* c, rt_lens* out)
 	if (!c || !out) return RT_E_ARG;
 	*out = c->lens;
 	return RT_OK;
+}
+
+// ---- shutter (include/rt_amd.h) --------------------------------------------------------------------
+int rt_set_shutter(rt_ctx* c, const rt_camera* cam_close)
+{
+	if (!c) return fail(c, RT_E_ARG, "rt_set_shutter: null context");
+	if (!cam_close) { c->shutterOn = false; return RT_OK; } // (the record stays: nothing reads it with the shutter off)
+	if (cam_close->fisheye != 0) return fail(c, RT_E_ARG, "rt_set_shutter: a fisheye closing camera");
+	ShutterCam rec;
+	memcpy(rec.camPos, cam_close->cam_pos, 12), memcpy(rec.topLeft, cam_close->top_left, 12);
+	memcpy(rec.topRight, cam_close->top_right, 12), memcpy(rec.bottomLeft, cam_close->bottom_left, 12);
+	const float* f = (const float*)&rec;
+	for (int i = 0; i < 12; i++)
+		if (!std::isfinite(f[i])) return fail(c, RT_E_ARG, "rt_set_shutter: float %d of the closing camera's twelve is %g", i, (double)f[i]);
+	// the device's record, on the context's stream: batches launched before see the record before.  (The copy of a host record this small
+	// is staged before the call returns, so 'rec' may leave.)  The accumulator, the G-buffer, a captured history, a list and a plan do
+	// not depend on it.
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipMemcpyAsync(c->shutterDev, &rec, sizeof(rec), hipMemcpyHostToDevice, c->stream));
+	c->shutterCam = *cam_close, c->shutterOn = true;
+	return RT_OK;
+}
+int rt_get_shutter(const rt_ctx* c, rt_camera* out)
+{
+	if (!c || !out) return RT_E_ARG;
+	if (!c->shutterOn) return 0;
+	*out = c->shutterCam;
+	return 1;
 }
 
 // Autofocus: Camera::GetPrimaryRay(x, y) on the host -- primary_ray_f's operations on whole coordinates, the bits k_primary_aovs gives the

@@ -220,6 +220,12 @@ struct rt_ctx {
 	bool cameraSet = false;
 	int pixelFilter = RT_FILTER_REFERENCE; // rt_set_pixel_filter: the kind of the path-mode camera samples (RenderParams::filter of their batches)
 	rt_lens lens{ 0.0f, 1.0f }; // rt_set_lens: the thin lens of the path-mode camera samples (radius 0: off); lens_params puts it into a batch's RenderParams
+	// rt_set_shutter: the camera at shutter close of the path-mode camera samples (C above is the camera at shutter open).  shutterDev is
+	// its twelve floats on the device (allocated by rt_create, written by rt_set_shutter on the stream); set_lens puts its address into a
+	// batch's RenderParams while shutterOn
+	bool shutterOn = false;
+	rt_camera shutterCam{};
+	ShutterCam* shutterDev = nullptr;
 	// accumulator
 	float4* accum = nullptr;
 	bool accumOwned = true;

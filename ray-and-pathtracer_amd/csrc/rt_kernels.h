@@ -36,6 +36,9 @@ struct DCamera {
 	int width, height;
 };
 
+// rt_set_shutter's record of a context: the twelve floats of the camera at shutter close, in device memory (rt_ctx::shutterDev)
+struct ShutterCam { float camPos[3], topLeft[3], topRight[3], bottomLeft[3]; };
+
 struct PathState {
 	float4* O[2];    // ray origin xyz, w = ray.t on entry (tmax); double buffered by round parity
 	float4* D[2];    // ray direction xyz
@@ -71,8 +74,13 @@ struct RenderParams {
 	// Nothing reads customD without customO set, and camera_sample() alone reads the lens.  (RenderParams has no padding left, and a
 	// longer DCamera or RenderParams would move the arguments of every kernel that takes one behind it.)
 	union { const float* customD; struct { float lensRadius, lensLam; }; };
-	float4* customOut; int customDepth;
-	float customE[3];  // rt_trace_batch_energy: the 'energy' argument of Trace / Sample
+	float4* customOut;
+	// customO is the tag of these sixteen bytes too: caller rays have their start depth and rt_trace_batch_energy's 'energy' argument of
+	// Trace / Sample here, camera samples (customO null) the address of the context's closing camera (rt_set_shutter; null: the shutter is
+	// off).  Every read of customDepth and customE is behind customO, and camera_sample() alone reads the shutter.  (customOut is a tag of
+	// its own -- 'if (R.customOut)' -- and cannot be shared.)  With the shutter on, lensLam above holds the lens's focus_distance itself:
+	// lam depends on the sample's time and shutter_ray() computes it.
+	union { struct { int customDepth; float customE[3]; }; const ShutterCam* shutter; };
 	uint permShift;    // rt_mega.h: log2 of the tile the permutation deals out
 	uint permMul;      // rt_mega.h: work item w is sample (w * permMul) % nSamples (0: w itself), see run_whitted_mega
 	int finishInline;  // path mode with a slot per sample: nothing to resume and no sample to pull when a segment ends,
@@ -86,6 +94,10 @@ struct RenderParams {
 	const uint* pixelList; // rt_render_active: tile pixel lp is pixel pixelList[lp] (tilePixels = the list's length); nullptr: the row mapping
 	const uint2* plan;     // rt_render_budget (rt_budget.h): sample sid is { pixel, frame - frame0 } = plan[sid]; nullptr: frame-major over the tile
 };
+
+// (kernel arguments behind a RenderParams must not move: the record keeps its size and the place of every field)
+static_assert(sizeof(RenderParams) == 136 && offsetof(RenderParams, customDepth) == 80 && offsetof(RenderParams, customE) == 84 && offsetof(RenderParams, permShift) == 96,
+              "RenderParams: the shutter's address shares the bytes of customDepth and customE");
 
 #define ST_ACTIVE 1      // has a ray for extend + shade
 #define ST_SHADOW 2      // diffuse hit: connect + light
@@ -393,7 +405,7 @@ __device__ __forceinline__ void lens_point(uint& js, float& a, float& b)
 // to occupancy steps.  Inlined, the loop and the two normalisations took k_finish from 89 to 97 VGPRs (5 -> 4 waves) and
 // k_sample_general from 166 to 175 (3 -> 2), profiles/lens_kernel_asm_diff.json.
 struct LensRay { float ox, oy, oz, dx, dy, dz; };
-__device__ __noinline__ LensRay lens_ray(f3 camPos, f3 TL, f3 TR, f3 BL, float u, float v, float radius, float lam, uint js)
+__device__ __forceinline__ LensRay lens_ray_body(f3 camPos, f3 TL, f3 TR, f3 BL, float u, float v, float radius, float lam, uint js)
 {
 	float a, b;
 	lens_point(js, a, b);
@@ -404,16 +416,49 @@ __device__ __noinline__ LensRay lens_ray(f3 camPos, f3 TL, f3 TR, f3 BL, float u
 	const f3 D = normalize(F - O);
 	return LensRay{ O.x, O.y, O.z, D.x, D.y, D.z };
 }
+__device__ __noinline__ LensRay lens_ray(f3 camPos, f3 TL, f3 TR, f3 BL, float u, float v, float radius, float lam, uint js)
+{
+	return lens_ray_body(camPos, TL, TR, BL, u, v, radius, lam, js);
+}
+// rt_set_shutter's ray (include/rt_amd.h): the sample's time tau from the jitter stream, behind the filter's draws and in front of the
+// lens's; the camera at that time, each of the twelve floats X0 + tau * (X1 - X0); then the pinhole ray through (u, v) of that camera's
+// screen rectangle (primary_ray_f's operations) or, with a lens, lens_ray on it with the lam of that camera.  A called function with
+// everything passed by value, for lens_ray's reason; the closing camera is read here, through the one address every lane has.  It is a
+// leaf: the lens's body is inlined, because a call from here to lens_ray gave every kernel that starts camera samples a stack (16 bytes of
+// scratch in k_generate_s and k_sample_rays, which had none).
+__device__ __noinline__ LensRay shutter_ray(f3 camPos, f3 TL, f3 TR, f3 BL, const ShutterCam* close, float u, float v, float radius, float focus, uint js)
+{
+	const float tau = RandomFloat(js);
+	camPos = camPos + tau * (f3(close->camPos[0], close->camPos[1], close->camPos[2]) - camPos);
+	TL = TL + tau * (f3(close->topLeft[0], close->topLeft[1], close->topLeft[2]) - TL);
+	TR = TR + tau * (f3(close->topRight[0], close->topRight[1], close->topRight[2]) - TR);
+	BL = BL + tau * (f3(close->bottomLeft[0], close->bottomLeft[1], close->bottomLeft[2]) - BL);
+	const f3 A = TR - TL, B = BL - TL;
+	if (__float_as_int(radius) > 0) {
+		const f3 N = cross(A, B), E = TL - camPos;
+		const float lam = focus / (fabsf(dot(E, N)) / sqrtf(dot(N, N)));
+		return lens_ray_body(camPos, TL, TR, BL, u, v, radius, lam, js);
+	}
+	const f3 P = TL + u * A + v * B;
+	const f3 D = normalize(P - camPos);
+	return LensRay{ camPos.x, camPos.y, camPos.z, D.x, D.y, D.z };
+}
 // radius > 0, as a compare of the float's bits: the host stores a finite radius >= 0 (rt_set_lens), and an integer compare of a kernel
 // argument stays on the scalar unit
 __device__ __forceinline__ bool lens_on(const RenderParams& R) { return __float_as_int(R.lensRadius) > 0; }
-// The ONE place that reads R.filter and the lens: camera sample (x, y, frame) of a path batch -> the state its path's random stream starts
+// the shutter of a launch of camera samples: a kernel argument's compare with null, on the scalar unit like lens_on's
+__device__ __forceinline__ bool shutter_on(const RenderParams& R) { return R.shutter != nullptr; }
+// The ONE place that reads R.filter, the lens and the shutter: camera sample (x, y, frame) of a path batch -> the state its path's random stream starts
 // in and its ray.  REFERENCE (renderer.cpp:263-278): the stream's first two draws are the jitter, truncated by primary_ray's int parameters.
 // A filter kind (include/rt_amd.h rt_set_pixel_filter): the path's stream starts at StreamSeed(s) with nothing drawn, the jitter has
 // the stream StreamSeed(~s) of its own, and the ray goes through (x + dx, y + dy); with a lens (rt_set_lens, radius > 0) it leaves from a
 // point of the lens disk drawn from the same jitter stream.  R.filter and R.lensRadius are the same for every lane of a launch.
 // The lens has a branch of its own BESIDE the pinhole filter's, which stays the parent's: folded into it (one jitter, then lens or
 // pinhole) k_sample_general took 169 VGPRs, one past its third wave; apart it takes 167 and k_finish its parent's 89.
+// The shutter (rt_set_shutter; R.shutter, the same for every lane of a launch too) has a third branch in front of those two, which stay
+// as they are: every sample looks through the camera interpolated to a time of its own, drawn behind the filter's draws.
+// SHUTTER = false leaves the third branch out: for k_whitted_level alone (sample_primary below).
+template <bool SHUTTER = true>
 __device__ __forceinline__ void camera_sample(const DCamera& C, const RenderParams& R, int x, int y, uint frame, f3& O, f3& D, uint& seed)
 {
 	const uint s = R.seedBase + (uint)(y * C.width + x) + frame * (uint)(C.width * C.height);
@@ -423,6 +468,17 @@ __device__ __forceinline__ void camera_sample(const DCamera& C, const RenderPara
 		float newX = x + (RandomFloat(seed) * 2 - 1);
 		float newY = y + (RandomFloat(seed) * 2 - 1);
 		px = (int)newX, py = (int)newY; // jitter truncated by the int parameters (renderer.cpp:276-278)
+	} else if (SHUTTER && shutter_on(R)) { // (never under a fisheye camera or with the reference's jitter: the host refuses a shutter there)
+		uint js = StreamSeed(~s);
+		float fx = (float)x, fy = (float)y;
+		if (R.filter != RT_FILTER_POINT) {
+			const float u1 = RandomFloat(js), u2 = RandomFloat(js);
+			fx = (float)x + filter_offset(R.filter, u1), fy = (float)y + filter_offset(R.filter, u2);
+		}
+		const LensRay l = shutter_ray(f3(C.camPos[0], C.camPos[1], C.camPos[2]), f3(C.topLeft[0], C.topLeft[1], C.topLeft[2]), f3(C.topRight[0], C.topRight[1], C.topRight[2]),
+		                              f3(C.bottomLeft[0], C.bottomLeft[1], C.bottomLeft[2]), R.shutter, fx * (1.0f / C.width), fy * (1.0f / C.height), R.lensRadius, R.lensLam, js);
+		O = f3(l.ox, l.oy, l.oz), D = f3(l.dx, l.dy, l.dz);
+		return;
 	} else if (lens_on(R)) { // (never under a fisheye camera or with the reference's jitter: the host refuses a lens there)
 		uint js = StreamSeed(~s);
 		float fx = (float)x, fy = (float)y;
@@ -443,6 +499,11 @@ __device__ __forceinline__ void camera_sample(const DCamera& C, const RenderPara
 	primary_ray(C, px, py, O, D); // ONE call for the reference's pixel and POINT's: the fisheye body is compiled once per caller
 }
 // camera sample 'sid' of the pool (renderer.cpp:263-278): its seed, jitter and primary ray; deterministic in (R, C, sid)
+// SHUTTER = false: k_whitted_level (rt_mega.h) serves Whitted batches only and never takes the camera_sample branch, but what it compiles
+// of it decides its scratch at the 128 VGPRs it is bound to: 128 bytes with the lens's branch alone (the parent's code, instruction for
+// instruction), 224 with the shutter's beside it, 192 with whitted_primary below -- and the 192-byte form measured 2.4 % slower on a
+// 1080p Whitted frame (2.57 against 2.51 ms, alternated).  So that kernel keeps compiling exactly what it compiled before the shutter.
+template <bool SHUTTER = true>
 __device__ __forceinline__ void sample_primary(const DCamera& C, const RenderParams& R, uint sid, f3& O, f3& D, uint& seed)
 {
 	int x, y;
@@ -451,11 +512,11 @@ __device__ __forceinline__ void sample_primary(const DCamera& C, const RenderPar
 	if (R.mode == 0) {
 		seed = StreamSeed(R.seedBase + (uint)(y * C.width + x) + frame * (uint)(C.width * C.height));
 		primary_ray(C, x, y, O, D);
-	} else camera_sample(C, R, x, y, frame, O, D, seed);
+	} else camera_sample<SHUTTER>(C, R, x, y, frame, O, D, seed);
 }
 // sample_primary's Whitted case alone, for k_whitted_mega (rt_mega.h), which serves Whitted batches only and needs no seed: compiling the
-// path branch it never takes cost it 16 to 64 bytes of scratch once the lens joined that branch.  (k_whitted_level keeps sample_primary:
-// with this function it would gain 16 bytes of scratch, with sample_primary it loses 48.)
+// path branch it never takes cost it 16 to 64 bytes of scratch once the lens joined that branch.  (k_whitted_level keeps sample_primary,
+// without the shutter's branch: see there.)
 __device__ __forceinline__ void whitted_primary(const DCamera& C, const RenderParams& R, uint sid, f3& O, f3& D)
 {
 	int x, y;

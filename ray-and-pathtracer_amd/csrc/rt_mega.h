@@ -342,7 +342,7 @@ struct WhittedLevelPolicy {
 		if (V.level == 0) {
 			uint sid, seed;
 			if (!sample_of(work, sid)) return false;
-			sample_primary(C, R, sid, O, D, seed);
+			sample_primary<false>(C, R, sid, O, D, seed); // (<false>: the code this kernel had before the shutter, rt_kernels.h sample_primary)
 			M.W[gl] = make_float4(1, 1, 1, __int_as_float(start_depth(R)));
 			M.E[gl] = make_float4(1, 1, 1, 0);
 			M.L[gl] = make_float4(0, 0, __uint_as_float(sid), __uint_as_float((uint)__builtin_amdgcn_s_memrealtime())); // key 0; w: when the lane took the sample

@@ -306,6 +306,21 @@ int rth_renderer_set_lens(void* h, float radius, float focusDistance)
 	try { r->r->SyncLens(); } catch (const std::exception& e) { r->r->lensRadius = r0, r->r->focusDistance = f0; r->err = e.what(); return -1; }
 	return 0;
 }
+// Renderer::shutter / shutterCamera (p: the closing camera's cam_pos, top_left, top_right, bottom_left, twelve floats; null: off), sent to
+// every context at once like the lens; a refused record leaves the shutter before
+int rth_renderer_set_shutter(void* h, const float* p)
+{
+	RthRenderer* r = (RthRenderer*)h;
+	const bool on0 = r->r->shutter;
+	const Camera cam0 = r->r->shutterCamera;
+	r->r->shutter = p != nullptr;
+	if (p) {
+		Camera& k = r->r->shutterCamera;
+		k.camPos = float3(p[0], p[1], p[2]), k.topLeft = float3(p[3], p[4], p[5]), k.topRight = float3(p[6], p[7], p[8]), k.bottomLeft = float3(p[9], p[10], p[11]);
+	}
+	try { r->r->SyncShutter(); } catch (const std::exception& e) { r->r->shutter = on0, r->r->shutterCamera = cam0; r->err = e.what(); return -1; }
+	return 0;
+}
 int rth_renderer_focus_at(void* h, int x, int y, float* out)
 {
 	RthRenderer* r = (RthRenderer*)h;

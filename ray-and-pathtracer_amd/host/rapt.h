@@ -431,6 +431,15 @@ public:
 	float focusDistance = 1.0f;
 	void SyncLens();                  // the lens -> every context, now (Tick does it anyway)
 	float FocusAt(int x, int y);      // rt_focus_at of context 0 under 'camera' (sent first) and the committed scene: 0 where the pixel sees the sky; sets nothing
+	// Shutter of the path-mode camera samples (rt_set_shutter): with 'shutter' set, 'camera' is the camera at shutter open and the four
+	// points of shutterCamera the camera at shutter close; every sample looks through the camera interpolated to a time of its own.
+	// (shutterCamera's fisheye members are not sent; its change flag is not looked at.)  Tick sends the shutter with the camera, the filter
+	// and the lens, and treats a change of it between two path Ticks as it treats a change of lens: it clears, with no reprojection carry.
+	// A shutter needs a pixelFilter other than REFERENCE and a pinhole camera: otherwise the path Tick throws (RT_E_UNSUPPORTED).
+	// (The G-buffer, the denoisers, the carries and FocusAt see the camera at shutter open: include/rt_amd.h rt_set_shutter, "Limits".)
+	bool shutter = false;
+	Camera shutterCamera;
+	void SyncShutter();               // the shutter -> every context, now (Tick does it anyway)
 	// Denoised preview (path mode only): Tick refreshes the G-buffer when something changed (rt_render_aovs, 0.001f as Sample), filters the
 	// mean with rt_denoise and shows rt_resolve_denoised in screenPixels; 'accumulator' stays the raw download.  Off: Tick is unchanged.
 	// (The G-buffer's ray of a pixel is GetPrimaryRay(x, y): in reference mode one of the up to four integer-pixel rays its samples take,
@@ -533,6 +542,11 @@ private:
 	int sampledFilter = RT_FILTER_REFERENCE; // pixelFilter of the last path Tick: the kind the accumulator's samples were taken with
 	rt_lens sampledLens{ 0.0f, 1.0f }; // ... and the lens of the last path Tick
 	bool LensChanged() const { return lensRadius != sampledLens.radius || (lensRadius > 0.0f && focusDistance != sampledLens.focus_distance); }
+	bool sampledShutter = false;      // ... and its shutter: on or off, and the closing record while on
+	rt_camera sampledShutterCam{};
+	rt_camera ShutterRecord() const;  // shutterCamera's four points as the record rt_set_shutter takes
+	bool ShutterChanged() const;
+	void ShutterSampled();            // the shutter of this path Tick becomes the sampled one
 	rt_camera syncedCam{};            // the record of the last SyncCamera
 	bool lastTickAdaptive = false;    // the last Tick was TickAdaptive: the accumulator holds its samples, taken under sampledCam
 	rt_camera sampledCam{};           // ... and of the last adaptive Tick: the camera the accumulator's samples were taken with

@@ -203,6 +203,38 @@ void Renderer::SyncLens()
 	for (rt_ctx* k : ctxs) check(k, rt_set_lens(k, &l));
 }
 
+rt_camera Renderer::ShutterRecord() const
+{
+	rt_camera c;
+	memset(&c, 0, sizeof(c));
+	const Camera& k = shutterCamera;
+	c.cam_pos[0] = k.camPos.x, c.cam_pos[1] = k.camPos.y, c.cam_pos[2] = k.camPos.z;
+	c.top_left[0] = k.topLeft.x, c.top_left[1] = k.topLeft.y, c.top_left[2] = k.topLeft.z;
+	c.top_right[0] = k.topRight.x, c.top_right[1] = k.topRight.y, c.top_right[2] = k.topRight.z;
+	c.bottom_left[0] = k.bottomLeft.x, c.bottom_left[1] = k.bottomLeft.y, c.bottom_left[2] = k.bottomLeft.z;
+	return c;
+}
+
+void Renderer::SyncShutter()
+{
+	const rt_camera c = ShutterRecord();
+	for (rt_ctx* k : ctxs) check(k, rt_set_shutter(k, shutter ? &c : nullptr));
+}
+
+bool Renderer::ShutterChanged() const
+{
+	if (shutter != sampledShutter) return true;
+	if (!shutter) return false;
+	const rt_camera c = ShutterRecord();
+	return memcmp(&c, &sampledShutterCam, sizeof(c)) != 0;
+}
+
+void Renderer::ShutterSampled()
+{
+	sampledShutter = shutter;
+	if (shutter) sampledShutterCam = ShutterRecord();
+}
+
 float Renderer::FocusAt(int x, int y)
 {
 	if (!ctx) Init();
@@ -238,9 +270,10 @@ void Renderer::Tick(float /*deltaTime*/)
 	const int it = scene.GetIterationNumber();
 	SyncPixelFilter();
 	SyncLens();
-	// (a path Tick under another filter kind or lens than the last one's: like a camera change)
-	const bool camChanged = camera.GetChange() || (!scene.raytracer && (pixelFilter != sampledFilter || LensChanged()));
-	if (!scene.raytracer) sampledFilter = pixelFilter, sampledLens = { lensRadius, focusDistance };
+	SyncShutter();
+	// (a path Tick under another filter kind, lens or shutter than the last one's: like a camera change)
+	const bool camChanged = camera.GetChange() || (!scene.raytracer && (pixelFilter != sampledFilter || LensChanged() || ShutterChanged()));
+	if (!scene.raytracer) sampledFilter = pixelFilter, sampledLens = { lensRadius, focusDistance }, ShutterSampled();
 	if (camChanged && !scene.raytracer) {
 		scene.SetIterationNumber(1);
 		for (rt_ctx* k : ctxs) check(k, rt_clear(k)); // accumulator[...] = float3(0) for every pixel (:273-275)
@@ -302,10 +335,11 @@ void Renderer::TickAdaptive()
 	scene.totIterationNumber++;
 	const int it = scene.GetIterationNumber();
 	const int n = (int)ctxs.size();
-	const bool filterChanged = pixelFilter != sampledFilter || LensChanged(); // like a camera change, without a carry: the carried samples would be the old kind's or the old lens's
+	const bool filterChanged = pixelFilter != sampledFilter || LensChanged() || ShutterChanged(); // like a camera change, without a carry: the carried samples would be the old kind's, the old lens's or the old shutter's
 	SyncPixelFilter();
 	SyncLens();
-	sampledFilter = pixelFilter, sampledLens = { lensRadius, focusDistance };
+	SyncShutter();
+	sampledFilter = pixelFilter, sampledLens = { lensRadius, focusDistance }, ShutterSampled();
 	const bool motion = motionPending; // CommitInstances captured the history and moved the instances: carry with rt_reproject_motion
 	const bool deform = deformPending; // ... CommitTriangles deformed a mesh as well: rt_reproject_deform, which subsumes the other two carries
 	motionPending = deformPending = false;

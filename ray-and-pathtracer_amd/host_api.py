@@ -38,6 +38,7 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_select_active_dilated", "rt_select_budget_dilated",
               "rt_set_pixel_filter", "rt_get_pixel_filter", "rt_sample_rays",
               "rt_set_lens", "rt_get_lens", "rt_focus_at",
+              "rt_set_shutter", "rt_get_shutter",
               "rt_layout_build", "rt_layout_array", "rt_layout_free",
               "rt_set_instances", "rt_set_instance_list", "rt_download_tlas", "rt_scene_array",
               "rt_set_triangles", "rt_blas_array",
@@ -62,6 +63,12 @@ class RtQlearnParams(C.Structure):
 
 class RtLens(C.Structure):
     _fields_ = [("radius", C.c_float), ("focus_distance", C.c_float)]
+
+
+class RtCamera(C.Structure):
+    """include/rt_amd.h rt_camera"""
+    _fields_ = [("cam_pos", C.c_float * 3), ("top_left", C.c_float * 3), ("top_right", C.c_float * 3), ("bottom_left", C.c_float * 3),
+                ("fisheye", C.c_int32), ("view_angle", C.c_float), ("y_angle", C.c_float)]
 
 
 class RtDenoiseParams(C.Structure):
@@ -264,6 +271,8 @@ def rt_lib():
         L.rt_set_lens.argtypes = [C.c_void_p, C.c_void_p]
         L.rt_get_lens.argtypes = [C.c_void_p, C.c_void_p]
         L.rt_focus_at.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.rt_set_shutter.argtypes = [C.c_void_p, C.c_void_p]
+        L.rt_get_shutter.argtypes = [C.c_void_p, C.c_void_p]
         L.rt_layout_build.restype = C.c_void_p
         L.rt_layout_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.rt_layout_array.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -677,6 +686,26 @@ class HostRenderer:
         d = C.c_float(0.0)
         self._chk(self.L.rth_renderer_focus_at(self.h, int(x), int(y), C.byref(d)))
         return np.float32(d.value)
+
+    def set_shutter(self, cam_pos, top_left, top_right, bottom_left):
+        """rapt::Renderer::shutter / shutterCamera, sent to every context at once: the camera at shutter close of the path-mode camera
+        samples (the renderer's camera is the one at shutter open)"""
+        rec = np.ascontiguousarray(np.concatenate([np.asarray(v, np.float32).reshape(3) for v in (cam_pos, top_left, top_right, bottom_left)]))
+        self._chk(self.L.rth_renderer_set_shutter(self.h, _p(rec)))
+
+    def clear_shutter(self):
+        """rapt::Renderer::shutter = false on every context: the samples of a batch are taken at one instant again"""
+        self._chk(self.L.rth_renderer_set_shutter(self.h, None))
+
+    def shutter(self):
+        """rt_get_shutter of context 0: the closing camera (4, 3) float32 -- cam_pos, top_left, top_right, bottom_left -- or None (off)"""
+        c = RtCamera()
+        rc = int(self.rt.rt_get_shutter(self.ctx, C.byref(c)))
+        if rc < 0:
+            self._rt(rc)
+        if rc == 0:
+            return None
+        return np.float32([list(c.cam_pos), list(c.top_left), list(c.top_right), list(c.bottom_left)])
 
     def sample_rays(self, frame, seed_base=0x12345678, y0=0, y1=None):
         """rt_sample_rays: the camera rays (O, D), each (rows * width, 3), of frame 'frame' of the path samples under the context's filter"""
