@@ -494,4 +494,127 @@ void orc_mat4_trs(const float* t, float s, float rx, float ry, float rz, float* 
 	memcpy(out, M.cell, 64);
 }
 
+// ---- leaf entry points: the oracle's own functions, one call per case ---------------------------
+// The same signatures as oracle/ref/ref_leaf.cpp exports for the reference's compiled code (ref_*), so
+// tests/test_ref_leaf_cpu.py drives both with one caller and compares the answers bit for bit.
+static void put3(float* p, const float3& v) { p[0] = v.x, p[1] = v.y, p[2] = v.z; }
+static Triangle leaf_tri(const float* v) { return Triangle(7, 0, f3(v), f3(v + 3), f3(v + 6)); }
+static void leaf_hit(const Ray& r, int i, int* hit, float* t, float* nrm) { hit[i] = r.objIdx, t[i] = r.t, put3(nrm + 3 * i, r.hitNormal); }
+// light[12]: pos(3) strength col(3) radius normal(3) raytracer -- AreaLight's constructor, template/scene.h:97-103
+static Light leaf_area(const float* L)
+{
+	Light a;
+	a.kind = 0, a.objIdx = 7, a.pos = f3(L), a.strength = L[3], a.col = f3(L + 4), a.radius = L[7], a.radius2 = L[7] * L[7];
+	a.area = 2 * a.radius2 * PI, a.normal = f3(L + 8), a.raytracer = L[11] != 0;
+	return a;
+}
+// light[8]: pos(3) strength normal(3) r -- DirectionalLight's constructor, template/scene.h:146-148
+static Light leaf_dir(const float* L)
+{
+	Light d;
+	d.kind = 1, d.objIdx = 7, d.pos = f3(L), d.strength = L[3], d.col = float3(1), d.normal = f3(L + 4);
+	d.sinAngle = x_sinf(L[7] * PI / 2);
+	return d;
+}
+void orc_leaf_tri_ctor(int n, const float* v9, float* N, float* centroid)
+{
+	for (int i = 0; i < n; i++) { Triangle t = leaf_tri(v9 + 9 * i); put3(N + 3 * i, t.N), put3(centroid + 3 * i, t.centroid); }
+}
+void orc_leaf_tri_intersect(int n, const float* v9, const float* O, const float* D, const float* tmax, const float* tmin, int* hit, float* t, float* nrm)
+{
+	for (int i = 0; i < n; i++) { Ray r(f3(O + 3 * i), f3(D + 3 * i), tmax[i]); leaf_tri(v9 + 9 * i).Intersect(r, tmin[i]); leaf_hit(r, i, hit, t, nrm); }
+}
+void orc_leaf_tri_occluding(int n, const float* v9, const float* O, const float* D, const float* tmax, const float* tmin, int* occ)
+{
+	for (int i = 0; i < n; i++) { Ray r(f3(O + 3 * i), f3(D + 3 * i), tmax[i]); occ[i] = leaf_tri(v9 + 9 * i).IsOccluding(r, tmin[i]); }
+}
+void orc_leaf_sphere_intersect(int n, const float* pos, const float* rad, const float* O, const float* D, const float* tmax, const float* tmin, int* hit, float* t, float* nrm)
+{
+	for (int i = 0; i < n; i++) { Ray r(f3(O + 3 * i), f3(D + 3 * i), tmax[i]); Sphere(7, 0, f3(pos + 3 * i), rad[i]).Intersect(r, tmin[i]); leaf_hit(r, i, hit, t, nrm); }
+}
+void orc_leaf_sphere_occluding(int n, const float* pos, const float* rad, const float* O, const float* D, const float* tmax, const float* tmin, int* occ)
+{
+	for (int i = 0; i < n; i++) { Ray r(f3(O + 3 * i), f3(D + 3 * i), tmax[i]); occ[i] = Sphere(7, 0, f3(pos + 3 * i), rad[i]).IsOccluding(r, tmin[i]); }
+}
+void orc_leaf_sphere_normal(int n, const float* pos, const float* rad, const float* I, float* nrm)
+{
+	// Sphere::GetNormal (template/scene.h:382-385), as Sphere::Intersect applies it to the hit point
+	for (int i = 0; i < n; i++) { Sphere s(7, 0, f3(pos + 3 * i), rad[i]); put3(nrm + 3 * i, (f3(I + 3 * i) - s.pos) * s.invr); }
+}
+void orc_leaf_plane_intersect(int n, const float* N, const float* d, const float* O, const float* D, const float* tmax, const float* tmin, int* hit, float* t, float* nrm)
+{
+	for (int i = 0; i < n; i++) { Ray r(f3(O + 3 * i), f3(D + 3 * i), tmax[i]); Plane(7, 0, f3(N + 3 * i), d[i]).Intersect(r, tmin[i]); leaf_hit(r, i, hit, t, nrm); }
+}
+void orc_leaf_plane_occluding(int n, const float* N, const float* d, const float* O, const float* D, const float* tmax, const float* tmin, int* occ)
+{
+	for (int i = 0; i < n; i++) { Ray r(f3(O + 3 * i), f3(D + 3 * i), tmax[i]); occ[i] = Plane(7, 0, f3(N + 3 * i), d[i]).IsOccluding(r, tmin[i]); }
+}
+void orc_leaf_area_intersect(int n, const float* L, const float* O, const float* D, const float* tmax, const float* tmin, int* hit, float* t, float* nrm)
+{
+	for (int i = 0; i < n; i++) { Ray r(f3(O + 3 * i), f3(D + 3 * i), tmax[i]); leaf_area(L + 12 * i).Intersect(r, tmin[i]); leaf_hit(r, i, hit, t, nrm); }
+}
+void orc_leaf_area_intensity(int n, const float* L, const float* p, const float* nrm, const float* from, float* rgb)
+{
+	for (int i = 0; i < n; i++) put3(rgb + 3 * i, leaf_area(L + 12 * i).GetLightIntensityAt(f3(p + 3 * i), f3(nrm + 3 * i), f3(from + 3 * i)));
+}
+void orc_leaf_area_position(int n, const float* L, const unsigned* seedIn, float* pos, unsigned* seedOut)
+{
+	for (int i = 0; i < n; i++) { uint s = seedIn[i]; put3(pos + 3 * i, leaf_area(L + 12 * i).GetLightPosition(s)); seedOut[i] = s; }
+}
+void orc_leaf_dir_ctor(int n, const float* L, float* sinAngle)
+{
+	for (int i = 0; i < n; i++) sinAngle[i] = leaf_dir(L + 8 * i).sinAngle;
+}
+void orc_leaf_dir_intensity(int n, const float* L, const float* p, float* rgb)
+{
+	for (int i = 0; i < n; i++) put3(rgb + 3 * i, leaf_dir(L + 8 * i).GetLightIntensityAt(f3(p + 3 * i), float3(0, 1, 0), float3(0)));
+}
+void orc_leaf_glass_fresnel(int n, const float* I, const float* N, const float* ior, float* kr)
+{
+	for (int i = 0; i < n; i++) { float k = 0; glass_fresnel(f3(I + 3 * i), f3(N + 3 * i), ior[i], k); kr[i] = k; }
+}
+void orc_leaf_glass_refract(int n, const float* D, const float* N, const float* ratio, float* out)
+{
+	for (int i = 0; i < n; i++) put3(out + 3 * i, glass_refract(f3(D + 3 * i), f3(N + 3 * i), ratio[i]));
+}
+// m[6]: albedo(3) ks kd n; a material built with raytracer == true (no draw)
+void orc_leaf_diffuse_scatter(int n, const float* m, const float* O, const float* D, const float* t, const float* lightDir, const float* lightInt,
+                              const float* nrm, const float* energyIn, float* att, float* energyOut, float* scatO)
+{
+	for (int i = 0; i < n; i++) {
+		const float* M = m + 6 * i;
+		Material d;
+		d.type = DIFFUSE, d.albedo = f3(M), d.col = float3(1), d.specu = M[3], d.diffu = M[4], d.N = (int)M[5], d.raytracer = true;
+		Ray r(f3(O + 3 * i), f3(D + 3 * i), t[i]);
+		float3 a(0), dir(0), e = f3(energyIn + 3 * i);
+		uint seed = 1;
+		diffuse_scatter(d, r, a, dir, f3(lightDir + 3 * i), f3(lightInt + 3 * i), f3(nrm + 3 * i), e, seed);
+		put3(att + 3 * i, a), put3(energyOut + 3 * i, e), put3(scatO + 3 * i, r.IntersectionPoint()); // :615: the scattered ray starts at the hit point
+	}
+}
+void orc_leaf_metal_scatter(int n, const float* O, const float* D, const float* t, const float* nrm, float* outO, float* outD, int* ret)
+{
+	for (int i = 0; i < n; i++) {
+		Ray r(f3(O + 3 * i), f3(D + 3 * i), t[i]);
+		float3 nn = f3(nrm + 3 * i);
+		Ray s = metal_scatter(r, nn);
+		ret[i] = dot(s.D, nn) > 0; // :634
+		put3(outO + 3 * i, s.O), put3(outD + 3 * i, s.D);
+	}
+}
+// cam[15]: camPos(3) topLeft(3) topRight(3) bottomLeft(3) fishEye viewAngle yAngle; the reference's fixed 600 x 400
+void orc_leaf_camera_rays(const float* cam, int n, const int* xs, const int* ys, float* O, float* D)
+{
+	Camera c;
+	c.camPos = f3(cam), c.topLeft = f3(cam + 3), c.topRight = f3(cam + 6), c.bottomLeft = f3(cam + 9);
+	c.fishEye = cam[12] != 0, c.viewAngle = cam[13], c.yAngle = cam[14];
+	for (int i = 0; i < n; i++) { Ray r = c.GetPrimaryRay(xs[i], ys[i]); put3(O + 3 * i, r.O), put3(D + 3 * i, r.D); }
+}
+void orc_leaf_sky_color(int w, int h, int nch, const unsigned char* px, int n, const float* D, float* rgb)
+{
+	Scene s;
+	s.skydome.assign(px, px + (size_t)w * h * nch), s.skydomeX = w, s.skydomeY = h, s.skydomeN = nch;
+	for (int i = 0; i < n; i++) put3(rgb + 3 * i, s.GetSkyColor(Ray(f3(D + 3 * i), f3(D + 3 * i))));
+}
+
 } // extern "C"
