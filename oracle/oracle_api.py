@@ -90,6 +90,83 @@ def qlearn_reward_fixed(R):
     return out
 
 
+class ScanPrims:
+    """Arrays of primitives for the scan helpers (orc_scan_*): triangles v9 (n, 9) with optional stored normals tri_n (n, 3), spheres
+    (n, 4) pos + r, planes (n, 4) N + d, ids (n_tri + n_sph + n_pla, 2) obj and mat in that order; nobox: the spheres and planes are
+    brute-force primitives without a box."""
+
+    def __init__(self, v9=None, tri_n=None, spheres=None, planes=None, ids=None, nobox=False):
+        f = np.float32
+        self.v9 = np.zeros((0, 9), f) if v9 is None else np.ascontiguousarray(v9, f).reshape(-1, 9)
+        self.tri_n = None if tri_n is None else np.ascontiguousarray(tri_n, f).reshape(-1, 3)
+        self.spheres = np.zeros((0, 4), f) if spheres is None else np.ascontiguousarray(spheres, f).reshape(-1, 4)
+        self.planes = np.zeros((0, 4), f) if planes is None else np.ascontiguousarray(planes, f).reshape(-1, 4)
+        self.n = len(self.v9) + len(self.spheres) + len(self.planes)
+        self.ids = np.zeros((self.n, 2), np.int32) if ids is None else np.ascontiguousarray(ids, np.int32).reshape(-1, 2)
+        assert len(self.ids) == self.n and (self.tri_n is None or len(self.tri_n) == len(self.v9))
+        self.nobox = bool(nobox)
+
+    def _args(self):
+        return (len(self.v9), _p(self.v9), None if self.tri_n is None else _p(self.tri_n), len(self.spheres), _p(self.spheres),
+                len(self.planes), _p(self.planes), _p(self.ids), int(self.nobox))
+
+
+def _rays(O, D, tmax):
+    O = np.ascontiguousarray(O, dtype=np.float32).reshape(-1, 3)
+    D = np.ascontiguousarray(D, dtype=np.float32).reshape(-1, 3)
+    tm = np.full(len(O), 1e34, np.float32) if tmax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (len(O),)))
+    return O, D, tm
+
+
+def scan_nearest(prims, O, D, tmax, t_min, T, gate=None, got=None, nrm_m=None):
+    """orc_scan_nearest: every primitive's leaf Intersect against every ray.  T: the answer under test per ray (the slab test's ray.t);
+    gate: a uint8 per ray that closes the filter where 0; got: dict(obj, mat, normal) whose bits a full witness must carry; nrm_m: the
+    instance transform a hit normal goes through.  Returns dict(t_all, t_next, t_flt, wit_t, wit_full)."""
+    O, D, tm = _rays(O, D, tmax)
+    n = len(O)
+    T = np.ascontiguousarray(np.broadcast_to(np.asarray(T, np.float32), (n,)))
+    g = None if gate is None else np.ascontiguousarray(gate, np.uint8)
+    go = gm = gn = None
+    if got is not None:
+        go = np.ascontiguousarray(got["obj"], np.int32)
+        gm = np.ascontiguousarray(got["mat"], np.int32) if "mat" in got else None  # (a query that reports no material or normal)
+        gn = np.ascontiguousarray(got["normal"], np.float32).reshape(-1, 3) if "normal" in got else None
+    M = None if nrm_m is None else np.ascontiguousarray(nrm_m, np.float32).reshape(16)
+    t_all, t_next, t_flt = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+    wit_t, wit_full = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    lib().orc_scan_nearest(*prims._args(), n, _p(O), _p(D), _p(tm), C.c_float(t_min), _p(T), None if g is None else _p(g),
+                           None if go is None else _p(go), None if gm is None else _p(gm), None if gn is None else _p(gn),
+                           None if M is None else _p(M), _p(t_all), _p(t_next), _p(t_flt), _p(wit_t), _p(wit_full))
+    return dict(t_all=t_all, t_next=t_next, t_flt=t_flt, wit_t=wit_t, wit_full=wit_full)
+
+
+def scan_occluded(prims, O, D, tmax, t_min, gate=None):
+    """orc_scan_occluded: dict(occ_all, occ_flt), a bool per ray"""
+    O, D, tm = _rays(O, D, tmax)
+    g = None if gate is None else np.ascontiguousarray(gate, np.uint8)
+    a, f = np.zeros(len(O), np.uint8), np.zeros(len(O), np.uint8)
+    lib().orc_scan_occluded(*prims._args(), len(O), _p(O), _p(D), _p(tm), C.c_float(t_min), None if g is None else _p(g), _p(a), _p(f))
+    return dict(occ_all=a.astype(bool), occ_flt=f.astype(bool))
+
+
+def slab(O, D, t, box6):
+    """IntersectAABB per ray with ray.t = t against box6 ((6,): one box for all, (n, 6): one per ray): tmin, or 1e30 for a miss"""
+    O, D, t = _rays(O, D, t)
+    b = np.ascontiguousarray(box6, np.float32)
+    out = np.zeros(len(O), np.float32)
+    lib().orc_slab_batch(len(O), _p(O), _p(D), _p(t), int(b.ndim == 2), _p(b), _p(out))
+    return out
+
+
+def instance_ray(O, D, inv_t):
+    """world rays -> instance rays through TransformPosition / TransformVector of the instance's inverse transform"""
+    O, D, _ = _rays(O, D, None)
+    M = np.ascontiguousarray(inv_t, np.float32).reshape(16)
+    oO, oD = np.zeros_like(O), np.zeros_like(D)
+    lib().orc_leaf_instance_ray(len(O), _p(O), _p(D), _p(M), _p(oO), _p(oD))
+    return oO, oD
+
+
 class OracleScene:
     """Scene builder + queries over the CPU restatement (oracle)."""
 

@@ -617,4 +617,148 @@ void orc_leaf_sky_color(int w, int h, int nch, const unsigned char* px, int n, c
 	for (int i = 0; i < n; i++) put3(rgb + 3 * i, s.GetSkyColor(Ray(f3(D + 3 * i), f3(D + 3 * i))));
 }
 
+// ---- scan: every primitive against every ray, no tree, no stack, no order -------------------------
+// The second statement of FindNearest / IsOccluded that tests/scan_ref.py words (rules A, B and the two occlusion rules): the pinned leaf
+// bodies above over arrays of primitives, and the one box fact a tree may use, IntersectAABB of a primitive's OWN box.  Nothing of bvh,
+// bvhInstance or tlas is named here but IntersectAABB.
+// Primitives: triangles v9 (+ optional stored normals triN, else Triangle's own), spheres pos + r, planes N + d; ids: (obj, mat) per
+// primitive in that order.  flags bit 0: spheres and planes carry no box (the brute-force primitives of a TLAS scene).
+struct ScanPrims {
+	std::vector<Triangle> tri; std::vector<Sphere> sph; std::vector<Plane> pla;
+	std::vector<float3> bmin, bmax; // own boxes: triangle min / max of its vertices, sphere pos -/+ r, plane as bvh::UpdateNodeBounds (Q1)
+	bool nobox = false;
+	size_t size() const { return tri.size() + sph.size() + pla.size(); }
+};
+static ScanPrims scan_prims(int nTri, const float* v9, const float* triN, int nSph, const float* sph4, int nPla, const float* pla4, const int* ids, int flags)
+{
+	ScanPrims P;
+	P.nobox = (flags & 1) != 0;
+	for (int i = 0; i < nTri; i++, ids += 2) {
+		Triangle t(ids[0], ids[1], f3(v9 + 9 * i), f3(v9 + 9 * i + 3), f3(v9 + 9 * i + 6));
+		if (triN) t.N = f3(triN + 3 * i);
+		P.tri.push_back(t);
+		P.bmin.push_back(t_fminf(t_fminf(t.v0, t.v1), t.v2)), P.bmax.push_back(t_fmaxf(t_fmaxf(t.v0, t.v1), t.v2));
+	}
+	for (int i = 0; i < nSph; i++, ids += 2) {
+		Sphere s(ids[0], ids[1], f3(sph4 + 4 * i), sph4[4 * i + 3]);
+		P.sph.push_back(s);
+		P.bmin.push_back(s.pos - float3(s.r)), P.bmax.push_back(s.pos + float3(s.r));
+	}
+	for (int i = 0; i < nPla; i++, ids += 2) {
+		Plane q(ids[0], ids[1], f3(pla4 + 4 * i), pla4[4 * i + 3]);
+		P.pla.push_back(q);
+		float3 n = normalize(q.N), lo(-1e30f), hi(1e30f);
+		if (n.x + n.y + n.z == 1 && (n.x == 1 || n.y == 1 || n.z == 1)) { // Q1: a slab at coordinate 0
+			if (n.x == 1) lo.x = hi.x = 0; else if (n.y == 1) lo.y = hi.y = 0; else lo.z = hi.z = 0;
+		}
+		P.bmin.push_back(lo), P.bmax.push_back(hi);
+	}
+	return P;
+}
+static inline void scan_leaf(const ScanPrims& P, size_t p, Ray& r, float t_min)
+{
+	if (p < P.tri.size()) P.tri[p].Intersect(r, t_min);
+	else if (p < P.tri.size() + P.sph.size()) P.sph[p - P.tri.size()].Intersect(r, t_min);
+	else P.pla[p - P.tri.size() - P.sph.size()].Intersect(r, t_min);
+}
+static inline bool scan_leaf_occ(const ScanPrims& P, size_t p, const Ray& r, float t_min)
+{
+	if (p < P.tri.size()) return P.tri[p].IsOccluding(r, t_min);
+	else if (p < P.tri.size() + P.sph.size()) return P.sph[p - P.tri.size()].IsOccluding(r, t_min);
+	else return P.pla[p - P.tri.size() - P.sph.size()].IsOccluding(r, t_min);
+}
+static inline bool scan_box(const ScanPrims& P, size_t p, const Ray& r, float rayT)
+{
+	if (P.nobox && p >= P.tri.size()) return true;
+	Ray b = r;
+	b.t = rayT;
+	return IntersectAABB(b, P.bmin[p], P.bmax[p]) != 1e30f;
+}
+static inline unsigned fbits(float x) { unsigned u; memcpy(&u, &x, 4); return u; }
+// the scan's own thread count: orc_render / orc_tick leave omp_set_num_threads at what their caller asked for (often 1), and a scan is
+// rays x primitives.  OMP_NUM_THREADS where it is set, else the processors, 16 at most.
+static int scan_threads()
+{
+	const char* e = getenv("OMP_NUM_THREADS");
+	int n = e ? atoi(e) : omp_get_num_procs();
+	return n < 1 ? 1 : n > 16 ? 16 : n;
+}
+// Per ray i, each primitive's leaf Intersect on a fresh Ray(O, D, tmax[i]) at t_min:
+//   tAll[i]  the nearest leaf t over all primitives (1e30f: none hit); tNext[i] the nearest one that is farther than tAll[i] (1e30f: none)
+//   tFlt[i]  the nearest leaf t over those whose own box passes IntersectAABB with ray.t = T[i], and gate[i] != 0 (gate NULL: all open)
+//   witT[i]  the first primitive whose leaf t has T[i]'s bits (-1: none)
+//   witFull[i]  the first such primitive whose obj, mat and normal bits are gotObj / gotMat / gotN's too (-1: none; gotMat, gotN NULL: not
+//            compared, for a query that reports neither); nrmM (16 floats or
+//            NULL): the normal is normalize(TransformVector(hitNormal, nrmM)) as bvhInstance::BIntersect leaves it
+void orc_scan_nearest(int nTri, const float* v9, const float* triN, int nSph, const float* sph4, int nPla, const float* pla4, const int* ids, int flags,
+                      int n, const float* O, const float* D, const float* tmax, float t_min, const float* T, const unsigned char* gate,
+                      const int* gotObj, const int* gotMat, const float* gotN, const float* nrmM,
+                      float* tAll, float* tNext, float* tFlt, int* witT, int* witFull)
+{
+	const ScanPrims P = scan_prims(nTri, v9, triN, nSph, sph4, nPla, pla4, ids, flags);
+	mat4 M;
+	if (nrmM) memcpy(M.cell, nrmM, 64);
+	const size_t N = P.size();
+	const int nt = scan_threads();
+#pragma omp parallel for schedule(dynamic, 16) num_threads(nt)
+	for (int i = 0; i < n; i++) {
+		float best = 1e30f, next = 1e30f, bestF = 1e30f;
+		int wT = -1, wF = -1;
+		const Ray base(f3(O + 3 * i), f3(D + 3 * i), tmax[i]);
+		for (size_t p = 0; p < N; p++) {
+			Ray r = base;
+			scan_leaf(P, p, r, t_min);
+			if (!(r.t < base.t)) continue; // every leaf body accepts only t < ray.t
+			if (r.t < best) next = best, best = r.t;
+			else if (r.t > best && r.t < next) next = r.t;
+			if ((!gate || gate[i]) && r.t < bestF && scan_box(P, p, base, T[i])) bestF = r.t;
+			if (fbits(r.t) == fbits(T[i])) {
+				if (wT < 0) wT = (int)p;
+				if (wF < 0 && gotObj) {
+					float3 nn = nrmM ? normalize(TransformVector(r.hitNormal, M)) : r.hitNormal;
+					if (r.objIdx == gotObj[i] && (!gotMat || r.mat == gotMat[i]) &&
+					    (!gotN || (fbits(nn.x) == fbits(gotN[3 * i]) && fbits(nn.y) == fbits(gotN[3 * i + 1]) && fbits(nn.z) == fbits(gotN[3 * i + 2])))) wF = (int)p;
+				}
+			}
+		}
+		tAll[i] = best, tNext[i] = next, tFlt[i] = bestF, witT[i] = wT, witFull[i] = wF;
+	}
+}
+// Per ray i, each primitive's leaf IsOccluding on Ray(O, D, tmax[i]) at t_min: occAll[i] some primitive occludes; occFlt[i] some primitive
+// occludes while its own box passes IntersectAABB with ray.t = tmax[i], and gate[i] != 0
+void orc_scan_occluded(int nTri, const float* v9, const float* triN, int nSph, const float* sph4, int nPla, const float* pla4, const int* ids, int flags,
+                       int n, const float* O, const float* D, const float* tmax, float t_min, const unsigned char* gate,
+                       unsigned char* occAll, unsigned char* occFlt)
+{
+	const ScanPrims P = scan_prims(nTri, v9, triN, nSph, sph4, nPla, pla4, ids, flags);
+	const size_t N = P.size();
+	const int nt = scan_threads();
+#pragma omp parallel for schedule(dynamic, 16) num_threads(nt)
+	for (int i = 0; i < n; i++) {
+		const Ray r(f3(O + 3 * i), f3(D + 3 * i), tmax[i]);
+		bool any = false, anyF = false;
+		for (size_t p = 0; p < N && !anyF; p++) {
+			if (!scan_leaf_occ(P, p, r, t_min)) continue;
+			any = true;
+			if ((!gate || gate[i]) && scan_box(P, p, r, r.t)) anyF = true;
+		}
+		occAll[i] = any, occFlt[i] = anyF;
+	}
+}
+// IntersectAABB of ray i with ray.t = t[i] against box6[i] (perRay) or box6[0]: min then max
+void orc_slab_batch(int n, const float* O, const float* D, const float* t, int perRay, const float* box6, float* out)
+{
+	for (int i = 0; i < n; i++) {
+		const float* b = box6 + (perRay ? 6 * i : 0);
+		out[i] = IntersectAABB(Ray(f3(O + 3 * i), f3(D + 3 * i), t[i]), f3(b), f3(b + 3));
+	}
+}
+// world ray -> instance ray, as bvhInstance::BIntersect / IsOccluded do it (bvhInstance.cpp:6-7, 26-27): no normalisation, t keeps its meaning
+void orc_leaf_instance_ray(int n, const float* O, const float* D, const float* invT, float* outO, float* outD)
+{
+	mat4 M;
+	memcpy(M.cell, invT, 64);
+	for (int i = 0; i < n; i++) put3(outO + 3 * i, TransformPosition(f3(O + 3 * i), M)), put3(outD + 3 * i, TransformVector(f3(D + 3 * i), M));
+}
+
 } // extern "C"
