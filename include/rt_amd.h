@@ -162,6 +162,17 @@ enum { RT_LAYOUT_PAIRS = 0, RT_LAYOUT_PRIMS, RT_LAYOUT_WIDE, RT_LAYOUT_WIDE8, RT
 rt_layout* rt_layout_build(const rt_scene_desc* desc, int wide, int wide8, int tlas_lds);
 int rt_layout_array(const rt_layout* layout, int which, const void** data, size_t* bytes);
 void rt_layout_free(rt_layout* layout);
+/* Which kernel instantiations the dense path-mode pipeline launches for a batch, and which any-hit walk a queue of shadow rays takes: the
+ * host's decisions (csrc/rt_forms.h) without a device or a context, for tests/test_forms_cpu.py.
+ * rt_launch_form: facts = { primary table current, bounce table current, chain levels the batch may read (1-4), RT_BOUNCE_TABLE != 0,
+ *   RT_ROUND0_ENTRIES, sampler on, fisheye camera, rounds }; round in [0, rounds).  out = { generate kernel (0 k_generate_c, 1 k_generate_t,
+ *   2 k_generate_s), k_shade_s's template bits (1 QL, 2 BOUNCE, 4 TABLE0, 8 CHAIN), k_light_s's TABLE0 over this round's shadow records,
+ *   the same over the round before's (the launch of a mixed round; -1 at round 0), shade's BounceTable argument (0 empty, 1 the bounce
+ *   table, 2 chain level round + 1), its PrimaryTable argument (0 empty, 1 the table), whether it is handed the RT_BOUNCE_TABLE mask,
+ *   fresh }.  RT_E_ARG: a null pointer, a round or a level count out of range; RT_E_STATE: a combination no kernel was built for.
+ * rt_any_hit_walk: 0 binary, 1 counting, 2 4-wide, 4 8-wide (3 is the walk over the list a wide walk hands back: never chosen). */
+int rt_launch_form(const int32_t* facts, int round, int32_t* out);
+int rt_any_hit_walk(int counting, int wide, int wide8);
 
 /* ---- the pixel loop ---------------------------------------------------------------------------- */
 /* Replaces the pixel loop of Renderer::Tick (renderer.cpp:259-285) for frames

@@ -1,9 +1,10 @@
 // librt_amd.so: implementation of the C ABI in include/rt_amd.h for gfx950.
 // This file: context, camera, accumulator access, counters and timers, build / tuning info; the other units of the library
-// (scene upload, whose host-only layout builder is rt_layout.h, device builders, instance updates, relighting, the render loops, gather, batch queries, the Q-learning sampler, the output stage's helpers, the denoisers, adaptive sampling, budgeted passes, reprojection) are the rt_api_*.inc files
+// (scene upload, whose host-only layout builder is rt_layout.h, device builders, instance updates, relighting, the camera-sample settings, the render loops, gather, batch queries, the Q-learning sampler, the output stage's helpers, the denoisers, adaptive sampling, budgeted passes, reprojection) are the rt_api_*.inc files
 // included below -- one translation unit, see rt_ctx.h.
 #include "rt_ctx.h"
 #include "rt_layout.h"
+#include "rt_forms.h"
 
 extern "C" {
 
@@ -50,35 +51,30 @@ rt_ctx* rt_create(int device, int width, int height)
 		// kernel): a block that had to wait for a slot would find its share of the queue already taken
 		const int capBlocks = RT_GRID_CAP; // (measurement builds: -DRT_GRID_CAP=4 halves the resident blocks of every persistent kernel)
 		auto resident = [&](const void* fn) { int b = 0; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, fn, RT_BLOCK, 0) != hipSuccess || b < 1) b = 1; if (b > 8) b = 8; if (capBlocks >= 1 && b > capBlocks) b = capBlocks; return b * prop.multiProcessorCount; };
-		const int e0 = std::min(resident((const void*)k_extend<false, false>), resident((const void*)k_extend<false, true>)), e1 = std::min(resident((const void*)k_extend<true, false>), resident((const void*)k_extend<true, true>));
-		const int c0 = resident((const void*)k_connect<false>), c1 = resident((const void*)k_connect<true>);
-		c->slot.gridExtend = e0 < e1 ? e0 : e1, c->slot.gridConnect = c0 < c1 ? c0 : c1;
-		c->slot.gridConnectWide = resident((const void*)k_connect<false, true>);
-		c->slot.gridLeftover = std::min(resident((const void*)k_connect<false, false, true>), prop.multiProcessorCount); // a short list: one block per CU is plenty
-		c->dense.gridExtend = std::min(resident((const void*)k_extend_s<false>), resident((const void*)k_extend_s<true>));
-		c->dense.gridConnect = std::min(resident((const void*)k_connect_s<false>), resident((const void*)k_connect_s<true>));
-		c->dense.gridConnectWide = resident((const void*)k_connect_s<false, true>);
-		c->dense.gridLeftover = std::min(resident((const void*)k_connect_s<false, false, true>), prop.multiProcessorCount);
-		c->dense.gridConnectWide8 = resident((const void*)k_connect_s<false, false, false, true>);
+		// the grids of a family, under the family's index; a twin (COUNT) pair shares the smaller of its two
+		auto fill = [&](auto& tab, int* grids, int n) { for (int i = 0; i < n; i++) grids[i] = tab[i] ? resident((const void*)tab[i]) : 0; };
+		auto pair = [&](auto& tab) { return std::min(resident((const void*)tab[0]), resident((const void*)tab[1])); };
+		auto walks = [&](auto& tab, int* grids) {
+			fill(tab, grids, WALK_FORMS);
+			grids[WALK_BINARY] = grids[WALK_COUNTING] = std::min(grids[WALK_BINARY], grids[WALK_COUNTING]);
+			grids[WALK_LISTED] = std::min(grids[WALK_LISTED], prop.multiProcessorCount); // a short list: one block per CU is plenty
+		};
+		c->slot.gridExtend = std::min(pair(kExtend[0]), pair(kExtend[1]));
+		walks(kConnect, c->slot.gridConnect);
+		c->dense.gridExtend = pair(kExtendS);
+		walks(kConnectS, c->dense.gridConnect);
 		c->dense.gridTraverse = resident((const void*)k_traverse_s);
-		c->dense.gridTable = std::min(resident((const void*)k_primary_table<false>), resident((const void*)k_primary_table<true>));
-		c->dense.gridBounce = std::min(resident((const void*)k_bounce_table<false>), resident((const void*)k_bounce_table<true>));
+		c->dense.gridTable = pair(kPrimaryTable), c->dense.gridBounce = pair(kBounceTable), c->dense.gridChain = pair(kChainTable);
 		c->mega.grid = resident((const void*)k_whitted_mega);
 		c->level.grid = resident((const void*)k_whitted_level);
-		c->dense.gridShade = std::min(resident((const void*)k_shade_s<false>), resident((const void*)k_shade_s<true>));
-		c->dense.gridShadeBounce = resident((const void*)k_shade_s<false, true>);
-		c->dense.gridShadeDirect = resident((const void*)k_shade_s<false, false, true>);
-		c->dense.gridShadeDirectBounce = resident((const void*)k_shade_s<false, true, true>);
-		c->dense.gridChain = std::min(resident((const void*)k_chain_table<false>), resident((const void*)k_chain_table<true>));
-		c->dense.gridShadeChain = resident((const void*)k_shade_s<false, false, false, true>);
-		c->dense.gridShadeBounceChain = resident((const void*)k_shade_s<false, true, false, true>);
-		c->dense.gridShadeDirectBounceChain = resident((const void*)k_shade_s<false, true, true, true>);
-		c->dense.gridLight = resident((const void*)k_light_s<false>);
-		c->dense.gridLightDirect = resident((const void*)k_light_s<true>);
-		int q = std::min(c->slot.gridConnect, c->slot.gridExtend);
-		const void* qk[9] = { (const void*)k_query_nearest<false>, (const void*)k_query_nearest<true>, (const void*)k_query_occluded<false>, (const void*)k_query_occluded<true>, (const void*)k_primary_hits<false>, (const void*)k_primary_hits<true>,
-		                      (const void*)k_query_occluded<false, true>, (const void*)k_query_occluded<false, false, true>, (const void*)k_query_occluded<false, false, false, true> };
-		for (int i = 0; i < 9; i++) { const int r = resident(qk[i]); if (r < q) q = r; }
+		fill(kShadeS, c->dense.gridShade, SHADE_FORMS);
+		c->dense.gridShade[0] = c->dense.gridShade[SHADE_QL] = std::min(c->dense.gridShade[0], c->dense.gridShade[SHADE_QL]); // the plain shade and the sampler's share one
+		fill(kLightS, c->dense.gridLight, LIGHT_FORMS);
+		// one grid for every query kernel
+		int q = std::min(c->slot.gridConnect[WALK_BINARY], c->slot.gridExtend);
+		q = std::min(q, std::min(resident((const void*)kQueryNearest[0][1]), resident((const void*)kQueryNearest[1][1])));
+		q = std::min(q, pair(kPrimaryHits));
+		for (int w = 0; w < WALK_FORMS; w++) q = std::min(q, resident((const void*)kQueryOccluded[w]));
 		c->gridQuery = q;
 		c->gridAovs = std::min(q, std::min(resident((const void*)k_primary_aovs<false>), resident((const void*)k_primary_aovs<true>)));
 	}
@@ -169,6 +165,7 @@ int rt_set_camera(rt_ctx* c, const rt_camera* cam)
 #include "rt_api_triangles.inc"
 #include "rt_api_vertices.inc"
 #include "rt_api_materials.inc"
+#include "rt_api_camera.inc"
 #include "rt_api_render.inc"
 #include "rt_api_output.inc"
 

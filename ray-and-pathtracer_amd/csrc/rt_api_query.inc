@@ -1,6 +1,6 @@
 // Batch queries: Scene::FindNearest / IsOccluded / GetSkyColor and the members below scene level for n caller rays, primary-hit maps.  Included by rt_api.hip.
 // ---- batch queries -------------------------------------------------------------------------------
-static int query_grid(rt_ctx* c, int n) { int g = (n + RT_CHUNK - 1) / RT_CHUNK / 4 + 1; return g > c->gridQuery ? c->gridQuery : g; }
+static int query_grid(rt_ctx* c, int n) { return short_grid((size_t)n, c->gridQuery, RT_CHUNK); }
 
 // the scene as a query of the given scope sees it: rooted at the accelerator, one BLAS or one instance
 static int scoped_scene(rt_ctx* c, int scope, int index, DScene& S, const char* who)
@@ -48,14 +48,7 @@ int rt_intersect_scope(rt_ctx* c, int scope, int index, int n, const float* O, c
 		(void)hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), c->stream); // work heads
 		section_probe_reset(c->stream);
 		prof_begin(c, K_QUERY);
-		const bool head = scope == RT_SCOPE_SCENE;
-		if (c->counting) {
-			if (head) hipLaunchKernelGGL((k_query_nearest<true, true>), dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, S, n, dO, dD, dT, t_min, tuning(c), dH, c->spill, c->flags, c->counters);
-			else hipLaunchKernelGGL((k_query_nearest<true, false>), dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, S, n, dO, dD, dT, t_min, tuning(c), dH, c->spill, c->flags, c->counters);
-		} else {
-			if (head) hipLaunchKernelGGL((k_query_nearest<false, true>), dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, S, n, dO, dD, dT, t_min, tuning(c), dH, c->spill, c->flags, c->counters);
-			else hipLaunchKernelGGL((k_query_nearest<false, false>), dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, S, n, dO, dD, dT, t_min, tuning(c), dH, c->spill, c->flags, c->counters);
-		}
+		hipLaunchKernelGGL(kQueryNearest[c->counting ? 1 : 0][scope == RT_SCOPE_SCENE ? 1 : 0], dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, S, n, dO, dD, dT, t_min, tuning(c), dH, c->spill, c->flags, c->counters);
 		prof_end(c);
 		if (!c->counting) section_probe_print(c->stream, "query", n);
 		e = hipStreamSynchronize(c->stream);
@@ -105,8 +98,8 @@ int rt_occluded_scope(rt_ctx* c, int scope, int index, int n, const float* O, co
 	unsigned char* dR = nullptr;
 	uint* dL = nullptr;
 	int rc = RT_OK;
-	const bool wide8Walk = !c->counting && S.wide8;
-	const bool wideWalk = !c->counting && (c->S.wide || wide8Walk);
+	const int walk = any_hit_walk(c->counting != 0, c->S.wide != nullptr, S.wide8 != nullptr); // (the context's 4-wide nodes, the scope's 8-wide ones: DESIGN.md section 3)
+	const bool wideWalk = walk_is_wide(walk);
 	hipError_t e = dalloc(tmp, &dO, (size_t)3 * n);
 	if (e == hipSuccess) e = dalloc(tmp, &dD, (size_t)3 * n);
 	if (e == hipSuccess && tmax) e = dalloc(tmp, &dT, (size_t)n);
@@ -118,15 +111,12 @@ int rt_occluded_scope(rt_ctx* c, int scope, int index, int n, const float* O, co
 	if (e == hipSuccess) {
 		(void)hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), c->stream); // work heads
 		prof_begin(c, K_QUERY);
-		if (c->counting) hipLaunchKernelGGL((k_query_occluded<true>), dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, S, n, dO, dD, dT, tuning(c), dR, c->spill, c->flags, c->counters + 1, dL);
-		else if (!wideWalk) hipLaunchKernelGGL((k_query_occluded<false>), dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, S, n, dO, dD, dT, tuning(c), dR, c->spill, c->flags, c->counters + 1, dL);
-		else {
-			// the 4-wide walk, then the binary walk over the rays it handed back (not clean: normally none)
-			(void)hipMemsetAsync(c->flags + 2, 0, sizeof(int), c->stream);
-			if (wide8Walk) hipLaunchKernelGGL((k_query_occluded<false, false, false, true>), dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, S, n, dO, dD, dT, tuning(c), dR, c->spill, c->flags, c->counters + 1, dL);
-			else hipLaunchKernelGGL((k_query_occluded<false, true>), dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, S, n, dO, dD, dT, tuning(c), dR, c->spill, c->flags, c->counters + 1, dL);
+		if (wideWalk) (void)hipMemsetAsync(c->flags + 2, 0, sizeof(int), c->stream);
+		hipLaunchKernelGGL(kQueryOccluded[walk], dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, S, n, dO, dD, dT, tuning(c), dR, c->spill, c->flags, c->counters + 1, dL);
+		if (wideWalk) {
+			// the binary walk over the rays the wide walk handed back (not clean: normally none)
 			(void)hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), c->stream);
-			hipLaunchKernelGGL((k_query_occluded<false, false, true>), dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, S, n, dO, dD, dT, tuning(c), dR, c->spill, c->flags, c->counters + 1, dL);
+			hipLaunchKernelGGL(kQueryOccluded[WALK_LISTED], dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, S, n, dO, dD, dT, tuning(c), dR, c->spill, c->flags, c->counters + 1, dL);
 		}
 		prof_end(c);
 		e = hipStreamSynchronize(c->stream);
@@ -153,8 +143,7 @@ int rt_primary_hits(rt_ctx* c, float t_min, int32_t* obj_out, float* t_out)
 	if (e == hipSuccess) {
 		(void)hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), c->stream); // work heads
 		prof_begin(c, K_QUERY);
-		if (c->counting) hipLaunchKernelGGL(k_primary_hits<true>, dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, t_min, tuning(c), dO, dT, c->spill, c->flags, c->counters);
-		else hipLaunchKernelGGL(k_primary_hits<false>, dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, t_min, tuning(c), dO, dT, c->spill, c->flags, c->counters);
+		hipLaunchKernelGGL(kPrimaryHits[c->counting ? 1 : 0], dim3(query_grid(c, n)), dim3(RT_BLOCK), 0, c->stream, c->S, c->C, t_min, tuning(c), dO, dT, c->spill, c->flags, c->counters);
 		prof_end(c);
 		e = hipStreamSynchronize(c->stream);
 	}

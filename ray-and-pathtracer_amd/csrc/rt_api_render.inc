@@ -71,20 +71,17 @@ static int segments_per_sample(int mode, int depth, int nLights)
 	return (1 << (depth < 12 ? depth : 12)) * (1 + nLights);
 }
 
-// Scene::IsOccluded for the shadow queue.  Counting launches walk like the reference; timed launches take the 4-wide
-// walk when the scene has wide nodes, followed by the binary walk over the (normally empty) list of rays the wide
-// walk handed back because they are not clean.
+// Scene::IsOccluded for the shadow queue, by the walk rt_forms.h chooses: a wide walk is followed by the binary walk over the (normally
+// empty) list of rays it handed back because they are not clean.
 static void launch_connect(rt_ctx* c, hipStream_t st, const PathState& P, const Queues& Q, int parity, uint* spill)
 {
 	// the any-hit walk has its own thresholds (RT_REFILL_ANY, RT_STEPMIN_ANY, RT_PAIRAGAIN_ANY)
 	const int tun = tuning(c);
-	if (c->counting) hipLaunchKernelGGL((k_connect<true>), dim3(c->slot.gridConnect), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, tun, spill, c->counters + 1);
-	else if (!c->S.wide) hipLaunchKernelGGL((k_connect<false>), dim3(c->slot.gridConnect), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, tun, spill, c->counters + 1);
-	else {
-		hipLaunchKernelGGL((k_connect<false, true>), dim3(c->slot.gridConnectWide), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, tun, spill, c->counters + 1);
-		hipLaunchKernelGGL(k_round_begin, dim3(1), dim3(1), 0, st, Q, 0, 0, 4);
-		hipLaunchKernelGGL((k_connect<false, false, true>), dim3(c->slot.gridLeftover), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, tun, spill, c->counters + 1);
-	}
+	const int walk = any_hit_walk(c->counting != 0, c->S.wide != nullptr, false); // (no 8-wide walk over slots)
+	hipLaunchKernelGGL(kConnect[walk], dim3(c->slot.gridConnect[walk]), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, tun, spill, c->counters + 1);
+	if (!walk_is_wide(walk)) return;
+	hipLaunchKernelGGL(k_round_begin, dim3(1), dim3(1), 0, st, Q, 0, 0, 4);
+	hipLaunchKernelGGL(kConnect[WALK_LISTED], dim3(c->slot.gridConnect[WALK_LISTED]), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, tun, spill, c->counters + 1);
 }
 // The round loop of the slot wavefront (rt_kernels.h), shared by rt_render_rows and rt_trace_batch: Whitted rounds (RT_MEGA=0 and
 // counting launches), path batches with fewer slots than samples, RT_COUNT_REFERENCE launches, RT_STREAM=0.  One kernel at a time on
@@ -118,7 +115,7 @@ static int run_rounds(rt_ctx* c, const RenderParams& R, int maxRounds, int known
 		step_count_begin(c, st, P.nSlots);
 		prof_begin(c, K_EXTEND, st);
 		{
-			auto extendKernel = c->counting ? (allActive ? k_extend<true, true> : k_extend<true, false>) : (allActive ? k_extend<false, true> : k_extend<false, false>);
+			auto extendKernel = kExtend[c->counting ? 1 : 0][allActive ? 1 : 0];
 			hipLaunchKernelGGL(extendKernel, dim3(c->slot.gridExtend), dim3(RT_BLOCK), 0, st, c->S, P, Q, parity, t_min, tuning(c), c->spill, c->counters);
 		}
 		prof_end(c, st);
@@ -362,18 +359,12 @@ static int ensure_stream_state(rt_ctx* c, int n)
 static void launch_connect_s(rt_ctx* c, hipStream_t st, const StreamState& T, int round, uint* spill)
 {
 	const int tun = tuning(c);
-	if (c->counting) hipLaunchKernelGGL((k_connect_s<true>), dim3(c->dense.gridConnect), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
-	else if (c->S.wide8) {
-		// the 8-wide quantised walk, then the binary walk over the rays it handed back (not clean: normally none)
-		hipLaunchKernelGGL((k_connect_s<false, false, false, true>), dim3(c->dense.gridConnectWide8), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
-		hipLaunchKernelGGL(k_stream_begin, dim3(1), dim3(1), 0, st, T);
-		hipLaunchKernelGGL((k_connect_s<false, false, true>), dim3(c->dense.gridLeftover), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
-	} else if (!c->S.wide) hipLaunchKernelGGL((k_connect_s<false>), dim3(c->dense.gridConnect), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
-	else {
-		hipLaunchKernelGGL((k_connect_s<false, true>), dim3(c->dense.gridConnectWide), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
-		hipLaunchKernelGGL(k_stream_begin, dim3(1), dim3(1), 0, st, T);
-		hipLaunchKernelGGL((k_connect_s<false, false, true>), dim3(c->dense.gridLeftover), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
-	}
+	const int walk = any_hit_walk(c->counting != 0, c->S.wide != nullptr, c->S.wide8 != nullptr);
+	hipLaunchKernelGGL(kConnectS[walk], dim3(c->dense.gridConnect[walk]), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
+	if (!walk_is_wide(walk)) return;
+	// the binary walk over the rays the wide walk handed back (not clean: normally none)
+	hipLaunchKernelGGL(k_stream_begin, dim3(1), dim3(1), 0, st, T);
+	hipLaunchKernelGGL(kConnectS[WALK_LISTED], dim3(c->dense.gridConnect[WALK_LISTED]), dim3(RT_BLOCK), 0, st, c->S, T, round, tun, spill, c->counters + 1);
 }
 // Does round 0 of this batch read the primary-hit table (rt_stream.h)?  A current table is read; a stale one is rebuilt -- on the batch's
 // stream, before generate, with no synchronisation: its status word is the round pipeline's -- once the camera samples asked for since it
@@ -409,10 +400,8 @@ static int build_chain_tables(rt_ctx* c, hipStream_t st)
 		const ChainLevel up = k == 2 ? ChainLevel{} : d.chain[k - 3];
 		const size_t nUp = k == 2 ? 2 * records : cap;
 		hipLaunchKernelGGL(k_chain_link, dim3((unsigned)((nUp + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, st, c->S, k == 2 ? d.btab.B : up.B, k == 2 ? (const int*)nullptr : (const int*)up.count, (int)nUp, L);
-		HIPCHK(c, hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), st)); // the same work heads again
-		const int grid = std::min((int)((cap + RT_CHUNK - 1) / RT_CHUNK / 4 + 1), d.gridChain);
-		if (c->counting) hipLaunchKernelGGL(k_chain_table<true>, dim3(grid), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, d.btab, up, L, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
-		else hipLaunchKernelGGL(k_chain_table<false>, dim3(grid), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, d.btab, up, L, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
+		const int rc = build_table(c, st, kChainTable, cap, d.gridChain, -1, d.tab, d.btab, up, L);
+		if (rc != RT_OK) return rc;
 	}
 	d.chainLevels = depth, d.chainGen = c->sceneGen;
 	return RT_OK;
@@ -461,16 +450,10 @@ static int primary_table_for(rt_ctx* c, const RenderParams& R, hipStream_t st, b
 		B.n = (int)records, B.w = c->width + 2;
 		d.btab = B;
 	}
-	HIPCHK(c, hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), st)); // work heads
-	const int grid = std::min((int)((records + RT_CHUNK - 1) / RT_CHUNK / 4 + 1), d.gridTable); // a short queue does not need the whole grid
-	prof_begin(c, K_QUERY, st); // (the profile's query slot: a build is one launch there)
-	if (c->counting) hipLaunchKernelGGL(k_primary_table<true>, dim3(grid), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
-	else hipLaunchKernelGGL(k_primary_table<false>, dim3(grid), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
+	int brc = build_table(c, st, kPrimaryTable, records, d.gridTable, K_QUERY, d.tab); // (the profile's query slot: a build is one launch there)
+	if (brc == RT_OK && withBounce) brc = build_table(c, st, kBounceTable, 2 * records, d.gridBounce, -1, d.tab, d.btab);
+	if (brc != RT_OK) return brc;
 	if (withBounce) {
-		HIPCHK(c, hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), st)); // the same work heads, for the second launch
-		const int gridB = std::min((int)((2 * records + RT_CHUNK - 1) / RT_CHUNK / 4 + 1), d.gridBounce);
-		if (c->counting) hipLaunchKernelGGL(k_bounce_table<true>, dim3(gridB), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, d.btab, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
-		else hipLaunchKernelGGL(k_bounce_table<false>, dim3(gridB), dim3(RT_BLOCK), 0, st, c->S, c->C, d.tab, d.btab, 0.001f, tuning(c), c->spill, c->flags + 16, &d.T.counts[SC_FLAG], c->counters);
 		d.bounceGen = c->sceneGen;
 		if (wantChain && d.tablePending >= chainAt) {
 			const int rc = build_chain_tables(c, st);
@@ -517,16 +500,14 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 		const int rc = primary_table_for(c, R, st, &table, &bounce, &chain);
 		if (rc != RT_OK) return rc;
 	}
-	bounce = bounce && c->knobs.bounceTable != 0 && !c->Qt.on; // (the sampler's shade keeps emit_ray_s: the same bits either way)
-	// rounds 1 .. chainDepth - 1 read the chain tables (k_shade_s CHAIN), round 0 hands them their keys; a batch whose round 1 is its last has no use for them
-	const int chainDepth = bounce && rounds > 2 ? chain : 1;
-	// round 0 straight from the table (k_generate_c, k_shade_s / k_light_s TABLE0): no round-0 entry is written or read.  The pinhole ray is
-	// what the kernels rebuild from the pixel, and the sampler's shade keeps its entries; RT_ROUND0_ENTRIES=1 keeps them for everybody.
-	const bool direct = table && !c->Qt.on && !c->C.fisheye && c->knobs.round0Entries != 1;
+	// which instantiation each launch of the batch takes: rt_forms.h
+	const DenseBatch batch{ table, bounce, chain, c->knobs.bounceTable != 0, c->knobs.round0Entries, c->Qt.on != 0, c->C.fisheye != 0, rounds };
+	const bool direct = batch.direct();
+	const dim3 perEntry((n + RT_BLOCK - 1) / RT_BLOCK);
+	const int gen = generate_form(batch);
 	prof_begin(c, K_GENERATE, st);
-	if (direct) hipLaunchKernelGGL(k_generate_c, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, c->dense.tab, rounds == 1 ? 1 : 0, cnt);
-	else if (table) hipLaunchKernelGGL(k_generate_t, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, c->dense.tab, rounds == 1 ? 1 : 0, cnt);
-	else hipLaunchKernelGGL(k_generate_s, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, rounds == 1 ? 1 : 0, c->knobs.decide, cnt);
+	if (gen == GENERATE_S) hipLaunchKernelGGL(k_generate_s, perEntry, dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, rounds == 1 ? 1 : 0, c->knobs.decide, cnt);
+	else hipLaunchKernelGGL(kGenerateTab[gen], perEntry, dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, c->dense.tab, rounds == 1 ? 1 : 0, cnt);
 	prof_end(c, st);
 	if (direct && c->knobs.round0Entries == 2) { // (tests) whoever still read a round-0 entry would see NaNs and ids of -1
 		HIPCHK(c, hipMemsetAsync(T.O[0], 0xFF, (size_t)n * sizeof(float4), st));
@@ -534,6 +515,11 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 		HIPCHK(c, hipMemsetAsync(T.hitN[0], 0xFF, (size_t)n * sizeof(float4), st));
 		HIPCHK(c, hipMemsetAsync(T.hitId[0], 0xFF, (size_t)n * sizeof(int2), st));
 	}
+	// light over the shadow records of round 'of'
+	auto light = [&](hipStream_t on, int of, int lastArg) {
+		const int f = light_form(batch, of);
+		hipLaunchKernelGGL(kLightS[f], dim3(c->dense.gridLight[f]), dim3(RT_BLOCK), 0, on, c->S, R, T, of, lastArg, c->knobs.shadeLds, c->C, f ? c->dense.tab : PrimaryTable{});
+	};
 	bool pendingJoin = false;
 	for (int round = 0; round < rounds; round++) {
 		const int last = round + 1 == rounds ? 1 : 0, lastNext = round + 2 == rounds ? 1 : 0;
@@ -542,30 +528,25 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 			tail_probe_reset(st);
 			prof_begin(c, K_EXTEND, st);
 			if (mixed && round > 0) hipLaunchKernelGGL(k_traverse_s, dim3(c->dense.gridTraverse), dim3(RT_BLOCK), 0, st, c->S, T, round, last, t_min, tuning(c), c->spill);
-			else if (c->counting) hipLaunchKernelGGL((k_extend_s<true>), dim3(c->dense.gridExtend), dim3(RT_BLOCK), 0, st, c->S, T, round & 1, last, t_min, tuning(c), c->spill, c->counters);
-			else hipLaunchKernelGGL((k_extend_s<false>), dim3(c->dense.gridExtend), dim3(RT_BLOCK), 0, st, c->S, T, round & 1, last, t_min, tuning(c), c->spill, c->counters);
+			else hipLaunchKernelGGL(kExtendS[cnt], dim3(c->dense.gridExtend), dim3(RT_BLOCK), 0, st, c->S, T, round & 1, last, t_min, tuning(c), c->spill, c->counters);
 			prof_end(c, st);
 			tail_probe_print(st, "extend_s", round);
 		}
 		if (mixed && round > 0) { // the shadow answers of the round before came with this round's hits
 			prof_begin(c, K_SHADE, st);
-			if (direct && round == 1) hipLaunchKernelGGL(k_light_s<true>, dim3(c->dense.gridLightDirect), dim3(RT_BLOCK), 0, st, c->S, R, T, round - 1, 0, c->knobs.shadeLds, c->C, c->dense.tab);
-			else hipLaunchKernelGGL(k_light_s<false>, dim3(c->dense.gridLight), dim3(RT_BLOCK), 0, st, c->S, R, T, round - 1, 0, c->knobs.shadeLds, c->C, PrimaryTable{});
+			light(st, round - 1, 0);
 			prof_end(c, st);
 		}
 		hipLaunchKernelGGL(k_assign, dim3(grid / 2), dim3(RT_COMPACT_BLOCK), 0, st, T, round);
 		if (pendingJoin) { HIPCHK(c, hipStreamWaitEvent(st, c->dense.join, 0)); pendingJoin = false; }
+		// shade: the form's bits say which tables it is handed (rt_forms.h); a chain round reads level round + 1
+		const int f = shade_form(batch, round), bt = shade_bt(f);
+		if (!kShadeS[f]) return fail(c, RT_E_STATE, "run_rounds_stream: no k_shade_s of form %d (round %d of %d)", f, round, rounds);
+		const ChainLevel& L = c->dense.chain[bt == BT_CHAIN ? round - 1 : 0];
+		const BounceTable Bt = bt == BT_BOUNCE ? c->dense.btab : bt == BT_CHAIN ? BounceTable{ L.A, L.B, L.cap, 0 } : BounceTable{};
 		prof_begin(c, K_SHADE, st);
-		if (c->Qt.on) hipLaunchKernelGGL(k_shade_s<true>, dim3(c->dense.gridShade), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{}, 0, PrimaryTable{});
-		else if (direct && round == 0 && chainDepth > 1) hipLaunchKernelGGL((k_shade_s<false, true, true, true>), dim3(c->dense.gridShadeDirectBounceChain), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, c->dense.btab, c->knobs.bounceTable, c->dense.tab);
-		else if (round == 0 && chainDepth > 1) hipLaunchKernelGGL((k_shade_s<false, true, false, true>), dim3(c->dense.gridShadeBounceChain), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, c->dense.btab, c->knobs.bounceTable, PrimaryTable{});
-		else if (round > 0 && round < chainDepth && !last) {
-			const ChainLevel& L = c->dense.chain[round - 1]; // level round + 1
-			hipLaunchKernelGGL((k_shade_s<false, false, false, true>), dim3(c->dense.gridShadeChain), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{ L.A, L.B, L.cap, 0 }, c->knobs.bounceTable, PrimaryTable{});
-		} else if (direct && round == 0 && bounce && !last) hipLaunchKernelGGL((k_shade_s<false, true, true>), dim3(c->dense.gridShadeDirectBounce), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, c->dense.btab, c->knobs.bounceTable, c->dense.tab);
-		else if (direct && round == 0) hipLaunchKernelGGL((k_shade_s<false, false, true>), dim3(c->dense.gridShadeDirect), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{}, 0, c->dense.tab);
-		else if (bounce && round == 0 && !last) hipLaunchKernelGGL((k_shade_s<false, true>), dim3(c->dense.gridShadeBounce), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, 1, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, c->dense.btab, c->knobs.bounceTable, PrimaryTable{});
-		else hipLaunchKernelGGL(k_shade_s<false>, dim3(c->dense.gridShade), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt, BounceTable{}, 0, PrimaryTable{});
+		hipLaunchKernelGGL(kShadeS[f], dim3(c->dense.gridShade[f]), dim3(RT_BLOCK), 0, st, c->S, c->C, R, T, round, round == 0 ? 1 : 0, last, lastNext, c->knobs.decide, c->knobs.shadeLds, cnt, c->Qt,
+		                   Bt, shade_masked(f) ? c->knobs.bounceTable : 0, shade_tab(f) ? c->dense.tab : PrimaryTable{});
 		prof_end(c, st);
 		if (mixed && !last) continue; // this round's shadow rays ride in the next round's traversal launch
 		if (twoStreams) {
@@ -576,8 +557,7 @@ static int run_rounds_stream(rt_ctx* c, const RenderParams& R, int rounds)
 		launch_connect_s(c, sb, T, round, twoStreams ? c->dense.sideSpill : c->spill);
 		prof_end(c, sb);
 		prof_begin(c, K_SHADE, sb);
-		if (direct && round == 0) hipLaunchKernelGGL(k_light_s<true>, dim3(c->dense.gridLightDirect), dim3(RT_BLOCK), 0, sb, c->S, R, T, round, last, c->knobs.shadeLds, c->C, c->dense.tab);
-		else hipLaunchKernelGGL(k_light_s<false>, dim3(c->dense.gridLight), dim3(RT_BLOCK), 0, sb, c->S, R, T, round, last, c->knobs.shadeLds, c->C, PrimaryTable{});
+		light(sb, round, last);
 		prof_end(c, sb);
 		if (twoStreams) { HIPCHK(c, hipEventRecord(c->dense.join, sb)); pendingJoin = true; }
 	}
@@ -655,75 +635,6 @@ static int stats_clear(rt_ctx* c)
 	HIPCHK(c, hipMemsetAsync(c->stats.sumY, 0, n * sizeof(float), c->stream));
 	HIPCHK(c, hipMemsetAsync(c->stats.sumYY, 0, n * sizeof(float), c->stream));
 	return RT_OK;
-}
-
-// dot and cross as include/rt_amd.h defines them (rt_reproject), on the host: this translation unit is compiled with -ffp-contract=off
-// (csrc/Makefile), so these are the bits the definition of rt_set_lens names
-static float host_dot(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-// N = cross(TR - TL, BL - TL) of the camera's screen rectangle
-static void screen_normal(const DCamera& C, float* N)
-{
-	float A[3], B[3];
-	for (int i = 0; i < 3; i++) A[i] = C.topRight[i] - C.topLeft[i], B[i] = C.bottomLeft[i] - C.topLeft[i];
-	N[0] = A[1] * B[2] - A[2] * B[1], N[1] = A[2] * B[0] - A[0] * B[2], N[2] = A[0] * B[1] - A[1] * B[0];
-}
-// lam = focus_distance / screen_dist of a pinhole camera, as include/rt_amd.h defines it (rt_set_lens)
-static float lens_lam(const DCamera& C, float focusDistance)
-{
-	float N[3], E[3];
-	screen_normal(C, N);
-	for (int i = 0; i < 3; i++) E[i] = C.topLeft[i] - C.camPos[i];
-	const float screenDist = fabsf(host_dot(E, N)) / sqrtf(host_dot(N, N));
-	return focusDistance / screenDist;
-}
-// rt_set_lens's rules for a call that takes path-mode camera samples (include/rt_amd.h), and the lens's one derived number:
-// *lam = focus_distance / screen_dist, or 0 with the lens off
-static int lens_check(rt_ctx* c, const char* fn, float* lam)
-{
-	*lam = 0.0f;
-	if (!(c->lens.radius > 0.0f)) return RT_OK;
-	if (c->pixelFilter == RT_FILTER_REFERENCE)
-		return fail(c, RT_E_UNSUPPORTED, "%s: a lens (rt_set_lens) with RT_FILTER_REFERENCE: the reference's jitter lives on the path's own stream; set a kind with rt_set_pixel_filter first", fn);
-	if (c->C.fisheye) return fail(c, RT_E_UNSUPPORTED, "%s: a lens (rt_set_lens) under a fisheye camera", fn);
-	const float l = lens_lam(c->C, c->lens.focus_distance);
-	if (!(std::isfinite(l) && l > 0.0f)) return fail(c, RT_E_UNSUPPORTED, "%s: a lens (rt_set_lens) over a degenerate screen rectangle (focus_distance / screen_dist = %g)", fn, (double)l);
-	*lam = l;
-	return RT_OK;
-}
-// rt_set_shutter's rules for a call that takes path-mode camera samples (include/rt_amd.h), behind a lens_check that passed: with a
-// lens, lam is a number of every sample's own camera, which the device computes, and *lam becomes what the device computes it from,
-// the focus distance itself (set_lens)
-static int shutter_check(rt_ctx* c, const char* fn, float* lam)
-{
-	if (!c->shutterOn) return RT_OK;
-	if (c->pixelFilter == RT_FILTER_REFERENCE)
-		return fail(c, RT_E_UNSUPPORTED, "%s: a shutter (rt_set_shutter) with RT_FILTER_REFERENCE: the reference's jitter lives on the path's own stream; set a kind with rt_set_pixel_filter first", fn);
-	if (c->C.fisheye) return fail(c, RT_E_UNSUPPORTED, "%s: a shutter (rt_set_shutter) under a fisheye camera", fn);
-	if (c->lens.radius > 0.0f) {
-		DCamera close = c->C;
-		memcpy(close.camPos, c->shutterCam.cam_pos, 12), memcpy(close.topLeft, c->shutterCam.top_left, 12);
-		memcpy(close.topRight, c->shutterCam.top_right, 12), memcpy(close.bottomLeft, c->shutterCam.bottom_left, 12);
-		const float l = lens_lam(close, c->lens.focus_distance);
-		if (!(std::isfinite(l) && l > 0.0f)) return fail(c, RT_E_UNSUPPORTED, "%s: a lens (rt_set_lens) over a degenerate screen rectangle of the shutter's closing camera (rt_set_shutter; focus_distance / screen_dist = %g)", fn, (double)l);
-		*lam = c->lens.focus_distance;
-	}
-	return RT_OK;
-}
-// rt_set_pixel_filter's, rt_set_lens's and rt_set_shutter's rules for a path-mode render call (include/rt_amd.h); fn: the entry point the caller came through
-static int filter_check(rt_ctx* c, const char* fn, float* lam)
-{
-	int rc = lens_check(c, fn, lam);
-	if (rc == RT_OK) rc = shutter_check(c, fn, lam);
-	if (rc != RT_OK || c->pixelFilter == RT_FILTER_REFERENCE) return rc;
-	if (c->Qt.on) return fail(c, RT_E_UNSUPPORTED, "%s: a pixel filter with the Q-learning sampler on (its learn_mask is defined on the post-jitter state)", fn);
-	if (c->C.fisheye && c->pixelFilter != RT_FILTER_POINT) return fail(c, RT_E_UNSUPPORTED, "%s: RT_FILTER_BOX / RT_FILTER_TENT under a fisheye camera", fn);
-	return RT_OK;
-}
-// the lens and the shutter of a batch of camera samples (lam: filter_check's, or lens_check's and shutter_check's; R.mode is set)
-static void set_lens(const rt_ctx* c, RenderParams& R, float lam)
-{
-	if (lam > 0.0f) R.lensRadius = c->lens.radius, R.lensLam = lam;
-	if (c->shutterOn && R.mode == RT_MODE_PATH) R.shutter = c->shutterDev;
 }
 
 // Frames [frame0, frame0 + nframes) of one tile of pixels -- tilePixels of them: the rows row_first + k * row_stride of rt_render_rows, or
@@ -846,117 +757,4 @@ int rt_trace_batch_energy(rt_ctx* c, int mode, int n, const float* O, const floa
 		else for (int i = 0; i < n; i++) { rgb_out[3 * i] = out4[4 * i], rgb_out[3 * i + 1] = out4[4 * i + 1], rgb_out[3 * i + 2] = out4[4 * i + 2]; }
 	}
 	return rc;
-}
-
-// ---- pixel filter (include/rt_amd.h) ------------------------------------------------------------------
-int rt_set_pixel_filter(rt_ctx* c, int kind)
-{
-	if (!c || kind < RT_FILTER_REFERENCE || kind > RT_FILTER_TENT) return fail(c, RT_E_ARG, "rt_set_pixel_filter: kind %d", kind);
-	c->pixelFilter = kind; // neither the accumulator nor the G-buffer depends on it
-	return RT_OK;
-}
-int rt_get_pixel_filter(const rt_ctx* c) { return c ? c->pixelFilter : RT_E_ARG; }
-
-int rt_sample_rays(rt_ctx* c, uint32_t frame, uint32_t seed_base, int y0, int y1, float* O_out, float* D_out)
-{
-	if (!c || !O_out || !D_out) return fail(c, RT_E_ARG, "rt_sample_rays: null argument");
-	if (y0 < 0 || y1 > c->height || y0 >= y1) return fail(c, RT_E_ARG, "rt_sample_rays: rows [%d,%d) outside 0..%d", y0, y1, c->height);
-	if (c->C.fisheye && c->pixelFilter > RT_FILTER_POINT) return fail(c, RT_E_UNSUPPORTED, "rt_sample_rays: RT_FILTER_BOX / RT_FILTER_TENT under a fisheye camera");
-	float lam = 0.0f;
-	{
-		int lrc = lens_check(c, "rt_sample_rays", &lam);
-		if (lrc == RT_OK) lrc = shutter_check(c, "rt_sample_rays", &lam);
-		if (lrc != RT_OK) return lrc;
-	}
-	HIPCHK(c, hipSetDevice(c->device));
-	const size_t n = (size_t)c->width * (size_t)(y1 - y0);
-	float *dO = nullptr, *dD = nullptr;
-	std::vector<void*> tmp;
-	struct Guard { rt_ctx* c; std::vector<void*>& v; ~Guard() { (void)hipStreamSynchronize(c->stream); free_pool(v); } } guard{ c, tmp }; // every return path frees
-	HIPCHK(c, dalloc(tmp, &dO, 3 * n));
-	HIPCHK(c, dalloc(tmp, &dD, 3 * n));
-	RenderParams R;
-	memset(&R, 0, sizeof(R));
-	R.mode = RT_MODE_PATH, R.frame0 = frame, R.nSamples = (uint)n, R.tilePixels = (uint)n, R.seedBase = seed_base, R.rowFirst = y0, R.rowStride = 1;
-	R.sceneRt = -1, R.filter = c->pixelFilter;
-	set_lens(c, R, lam);
-	prof_begin(c, K_QUERY);
-	hipLaunchKernelGGL(k_sample_rays, dim3((unsigned)((n + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, c->stream, c->C, R, dO, dD);
-	prof_end(c);
-	HIPCHK(c, hipGetLastError());
-	HIPCHK(c, hipMemcpyAsync(O_out, dO, 12 * n, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(c, hipMemcpyAsync(D_out, dD, 12 * n, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	return RT_OK;
-}
-
-// ---- thin lens (include/rt_amd.h) ------------------------------------------------------------------
-int rt_set_lens(rt_ctx* c, const rt_lens* lens)
-{
-	if (!c) return fail(c, RT_E_ARG, "rt_set_lens: null context");
-	const rt_lens off = { 0.0f, c->lens.focus_distance };
-	const rt_lens l = lens ? *lens : off;
-	if (!std::isfinite(l.radius) || l.radius < 0.0f) return fail(c, RT_E_ARG, "rt_set_lens: radius %g", (double)l.radius);
-	if (l.radius > 0.0f && !(std::isfinite(l.focus_distance) && l.focus_distance > 0.0f)) return fail(c, RT_E_ARG, "rt_set_lens: focus_distance %g", (double)l.focus_distance);
-	c->lens = l; // the accumulator, the G-buffer, a captured history, a list and a plan do not depend on it
-	return RT_OK;
-}
-int rt_get_lens(const rt_ctx* c, rt_lens* out)
-{
-	if (!c || !out) return RT_E_ARG;
-	*out = c->lens;
-	return RT_OK;
-}
-
-// ---- shutter (include/rt_amd.h) --------------------------------------------------------------------
-int rt_set_shutter(rt_ctx* c, const rt_camera* cam_close)
-{
-	if (!c) return fail(c, RT_E_ARG, "rt_set_shutter: null context");
-	if (!cam_close) { c->shutterOn = false; return RT_OK; } // (the record stays: nothing reads it with the shutter off)
-	if (cam_close->fisheye != 0) return fail(c, RT_E_ARG, "rt_set_shutter: a fisheye closing camera");
-	ShutterCam rec;
-	memcpy(rec.camPos, cam_close->cam_pos, 12), memcpy(rec.topLeft, cam_close->top_left, 12);
-	memcpy(rec.topRight, cam_close->top_right, 12), memcpy(rec.bottomLeft, cam_close->bottom_left, 12);
-	const float* f = (const float*)&rec;
-	for (int i = 0; i < 12; i++)
-		if (!std::isfinite(f[i])) return fail(c, RT_E_ARG, "rt_set_shutter: float %d of the closing camera's twelve is %g", i, (double)f[i]);
-	// the device's record, on the context's stream: batches launched before see the record before.  (The copy of a host record this small
-	// is staged before the call returns, so 'rec' may leave.)  The accumulator, the G-buffer, a captured history, a list and a plan do
-	// not depend on it.
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, hipMemcpyAsync(c->shutterDev, &rec, sizeof(rec), hipMemcpyHostToDevice, c->stream));
-	c->shutterCam = *cam_close, c->shutterOn = true;
-	return RT_OK;
-}
-int rt_get_shutter(const rt_ctx* c, rt_camera* out)
-{
-	if (!c || !out) return RT_E_ARG;
-	if (!c->shutterOn) return 0;
-	*out = c->shutterCam;
-	return 1;
-}
-
-// Autofocus: Camera::GetPrimaryRay(x, y) on the host -- primary_ray_f's operations on whole coordinates, the bits k_primary_aovs gives the
-// pixel's ray -- then one ray through rt_intersect_batch (one launch, one query of the profile).
-int rt_focus_at(rt_ctx* c, int x, int y, float* distance_out)
-{
-	if (!c || !distance_out) return fail(c, RT_E_ARG, "rt_focus_at: null argument");
-	if (x < 0 || x >= c->width || y < 0 || y >= c->height) return fail(c, RT_E_ARG, "rt_focus_at: pixel (%d, %d) outside %d x %d", x, y, c->width, c->height);
-	if (!c->sceneLoaded) return fail(c, RT_E_STATE, "rt_focus_at: no scene uploaded");
-	if (c->C.fisheye) return fail(c, RT_E_UNSUPPORTED, "rt_focus_at: a fisheye camera");
-	const DCamera& C = c->C;
-	const float u = (float)x * (1.0f / C.width), v = (float)y * (1.0f / C.height);
-	float O[3], D[3], N[3];
-	for (int i = 0; i < 3; i++) {
-		const float P = C.topLeft[i] + u * (C.topRight[i] - C.topLeft[i]) + v * (C.bottomLeft[i] - C.topLeft[i]);
-		O[i] = C.camPos[i], D[i] = P - C.camPos[i];
-	}
-	const float invLen = 1.0f / sqrtf(host_dot(D, D));
-	for (int i = 0; i < 3; i++) D[i] = D[i] * invLen;
-	rt_hit hit;
-	const int rc = rt_intersect_batch(c, 1, O, D, nullptr, 0.001f, &hit);
-	if (rc != RT_OK) return rc;
-	screen_normal(C, N);
-	*distance_out = hit.obj_idx < 0 ? 0.0f : hit.t * (fabsf(host_dot(D, N)) / sqrtf(host_dot(N, N)));
-	return RT_OK;
 }

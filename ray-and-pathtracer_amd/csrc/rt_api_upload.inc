@@ -1,5 +1,5 @@
 // rt_upload_scene: the layout build_layout (rt_layout.h) makes of the reference-shaped arrays of include/rt_amd.h, copied to HBM and named in
-// DScene and the context; and the device-free rt_layout_* entry points, which hand the same layout to the caller.  Host code only.
+// DScene and the context; and the device-free entry points: rt_layout_*, which hand the same layout to the caller, and rt_launch_form (rt_forms.h).  Host code only.
 // Included by rt_api.hip (one translation unit).
 
 // scene_array (rt_ctx.h): a vector copied into a new array of the scene pool
@@ -226,3 +226,17 @@ int rt_layout_array(const rt_layout* o, int which, const void** data, size_t* by
 	return fail(nullptr, RT_E_ARG, "rt_layout_array: array %d", which);
 }
 void rt_layout_free(rt_layout* o) { delete o; }
+
+// ---- the launch forms without a device (include/rt_amd.h rt_launch_form; csrc/rt_forms.h) ------------------
+int rt_launch_form(const int32_t* facts, int round, int32_t* out)
+{
+	if (!facts || !out) return fail(nullptr, RT_E_ARG, "rt_launch_form: null argument");
+	const DenseBatch b{ facts[0] != 0, facts[1] != 0, facts[2], facts[3] != 0, facts[4], facts[5] != 0, facts[6] != 0, facts[7] };
+	if (b.chainLevels < 1 || b.chainLevels > 4 || b.rounds < 1 || round < 0 || round >= b.rounds) return fail(nullptr, RT_E_ARG, "rt_launch_form: round %d of %d, %d chain levels", round, b.rounds, b.chainLevels);
+	const int f = shade_form(b, round);
+	if (!kShadeS[f]) return fail(nullptr, RT_E_STATE, "rt_launch_form: no k_shade_s of form %d (round %d of %d)", f, round, b.rounds);
+	out[0] = generate_form(b), out[1] = f, out[2] = light_form(b, round), out[3] = round > 0 ? light_form(b, round - 1) : -1;
+	out[4] = shade_bt(f), out[5] = shade_tab(f) ? 1 : 0, out[6] = shade_masked(f) ? 1 : 0, out[7] = round == 0 ? 1 : 0;
+	return RT_OK;
+}
+int rt_any_hit_walk(int counting, int wide, int wide8) { return any_hit_walk(counting != 0, wide != 0, wide8 != 0); }

@@ -9,6 +9,8 @@
 //   rt_api_triangles.inc rt_set_triangles (kernels: rt_triangles.h), rt_blas_array
 //   rt_api_vertices.inc rt_set_mesh_indices, rt_set_vertices, rt_set_vertices_device (kernel: rt_vertices.h)
 //   rt_api_materials.inc rt_set_lights, rt_set_materials, rt_set_sky (kernel: rt_materials.h)
+//   rt_forms.h          which instantiation a launch takes, as pure functions (no hip* call, no rt_ctx); the kernel tables they index are below
+//   rt_api_camera.inc   the camera-sample settings: rt_set_pixel_filter, rt_set_lens, rt_set_shutter, rt_focus_at, rt_sample_rays and their checks
 //   rt_api_render.inc   rt_render*, rt_trace_batch*: round loops and batches
 //   rt_api_gather.inc   rt_gather_*
 //   rt_api_query.inc    batch queries
@@ -29,6 +31,7 @@
 #include "rt_vertices.h"
 #include "rt_materials.h"
 #include "rt_layout.h"
+#include "rt_forms.h"
 #include "rt_denoise.h"
 #include "rt_adaptive.h"
 #include "rt_budget.h"
@@ -46,6 +49,34 @@
 #include <vector>
 
 using namespace rtd;
+
+// ---- the kernel families (rt_forms.h) -----------------------------------------------------------
+// One table per family of instantiations that share a signature, indexed by the form rt_forms.h chooses; beside each, the context holds
+// the resident grids under the same index (rt_create fills them in a loop over the table).  A combination nobody launches is a null entry.
+// [COUNT]: the counting twin of a traversal kernel
+static const decltype(&k_extend<false, false>) kExtend[2][2] = { { k_extend<false, false>, k_extend<false, true> }, { k_extend<true, false>, k_extend<true, true> } }; // [COUNT][DENSE]
+static const decltype(&k_connect<false>) kConnect[WALK_FORMS] = { k_connect<false>, k_connect<true>, k_connect<false, true>, k_connect<false, false, true>, nullptr }; // (no 8-wide walk over slots)
+static const decltype(&k_extend_s<false>) kExtendS[2] = { k_extend_s<false>, k_extend_s<true> };
+static const decltype(&k_connect_s<false>) kConnectS[WALK_FORMS] = { k_connect_s<false>, k_connect_s<true>, k_connect_s<false, true>, k_connect_s<false, false, true>, k_connect_s<false, false, false, true> };
+static const decltype(&k_primary_table<false>) kPrimaryTable[2] = { k_primary_table<false>, k_primary_table<true> };
+static const decltype(&k_bounce_table<false>) kBounceTable[2] = { k_bounce_table<false>, k_bounce_table<true> };
+static const decltype(&k_chain_table<false>) kChainTable[2] = { k_chain_table<false>, k_chain_table<true> };
+static const decltype(&k_shade_s<false>) kShadeS[SHADE_FORMS] = {
+	k_shade_s<false>, k_shade_s<true>,                                 // 0, QL
+	k_shade_s<false, true>, nullptr,                                   // BOUNCE
+	k_shade_s<false, false, true>, nullptr,                            // TABLE0
+	k_shade_s<false, true, true>, nullptr,                             // BOUNCE | TABLE0
+	k_shade_s<false, false, false, true>, nullptr,                     // CHAIN
+	k_shade_s<false, true, false, true>, nullptr,                      // BOUNCE | CHAIN
+	nullptr, nullptr,                                                  // TABLE0 | CHAIN: round 0 of a chain batch hands out keys, so it has BOUNCE
+	k_shade_s<false, true, true, true>, nullptr,                       // BOUNCE | TABLE0 | CHAIN
+};
+static const decltype(&k_light_s<false>) kLightS[LIGHT_FORMS] = { k_light_s<false>, k_light_s<true> };
+static_assert(GENERATE_C == 0 && GENERATE_T == 1, "kGenerateTab is indexed by generate_form");
+static const decltype(&k_generate_c) kGenerateTab[2] = { k_generate_c, k_generate_t }; // GENERATE_C, GENERATE_T (k_generate_s reads no table: a signature of its own)
+static const decltype(&k_query_nearest<false, false>) kQueryNearest[2][2] = { { k_query_nearest<false, false>, k_query_nearest<false, true> }, { k_query_nearest<true, false>, k_query_nearest<true, true> } }; // [COUNT][HEAD]
+static const decltype(&k_query_occluded<false>) kQueryOccluded[WALK_FORMS] = { k_query_occluded<false>, k_query_occluded<true>, k_query_occluded<false, true>, k_query_occluded<false, false, true>, k_query_occluded<false, false, false, true> };
+static const decltype(&k_primary_hits<false>) kPrimaryHits[2] = { k_primary_hits<false>, k_primary_hits<true> };
 
 #ifndef RT_GRID_CAP
 #define RT_GRID_CAP 8
@@ -237,7 +268,7 @@ struct rt_ctx {
 		int stateSlots = 0, stateLights = -1;
 		bool statePend = false, stateWide = false;
 		std::vector<void*> allocs;
-		int gridExtend = 0, gridConnect = 0, gridConnectWide = 0, gridLeftover = 0; // resident blocks of the persistent traversal kernels (every wave owns a first chunk: none may wait for a slot)
+		int gridExtend = 0, gridConnect[WALK_FORMS] = {}; // resident blocks of the persistent traversal kernels (every wave owns a first chunk: none may wait for a slot); kExtend, kConnect
 		void free_state() { free_pool(allocs); stateSlots = 0; }
 	};
 	SlotState slot;
@@ -250,8 +281,9 @@ struct rt_ctx {
 		hipStream_t side = nullptr;
 		uint* sideSpill = nullptr;
 		hipEvent_t fork = nullptr, join = nullptr;
-		int gridExtend = 0, gridConnect = 0, gridConnectWide = 0, gridLeftover = 0, gridConnectWide8 = 0, gridTraverse = 0;
-		int gridShade = 0, gridLight = 0; // resident blocks of the grid-stride shading kernels (a second, partial round of blocks would run at low occupancy)
+		int gridExtend = 0, gridConnect[WALK_FORMS] = {}, gridTraverse = 0; // kExtendS, kConnectS, k_traverse_s
+		// resident blocks of the grid-stride shading kernels (a second, partial round of blocks would run at low occupancy): kShadeS, kLightS
+		int gridShade[SHADE_FORMS] = {}, gridLight[LIGHT_FORMS] = {};
 		// The primary-hit table (rt_stream.h PrimaryTable): Scene::FindNearest of every distinct camera ray of the frame, which round 0 of
 		// a batch fans out to its samples.  Current while tableGen == sceneGen (the G-buffer's rule below); it outlives batches and calls.
 		PrimaryTable tab{};
@@ -263,8 +295,7 @@ struct rt_ctx {
 		// current with it (bounceGen == sceneGen); a scene without such a material has none (in tabAllocs with the primary table)
 		BounceTable btab{};
 		unsigned long long bounceGen = 0;
-		int gridBounce = 0, gridShadeBounce = 0; // resident blocks of k_bounce_table and of the shade launch that reads it
-		int gridShadeDirect = 0, gridShadeDirectBounce = 0, gridLightDirect = 0; // ... and of the round-0 launches that read the primary table (TABLE0)
+		int gridBounce = 0; // resident blocks of k_bounce_table
 		// The chain tables (rt_stream.h ChainLevel): chain[k - 2] is level k = 2 .. 4, built behind the bounce table from its records once the
 		// batch's samples are worth it (primary_table_for); levels 2 .. chainLevels are current while chainGen == sceneGen.  chainCount: the
 		// levels' record counters on the device.  In tabAllocs with the other tables.
@@ -272,7 +303,7 @@ struct rt_ctx {
 		int* chainCount = nullptr;
 		int chainLevels = 1;
 		unsigned long long chainGen = 0;
-		int gridChain = 0, gridShadeChain = 0, gridShadeBounceChain = 0, gridShadeDirectBounceChain = 0; // resident blocks of k_chain_table and of the CHAIN shade launches
+		int gridChain = 0; // resident blocks of k_chain_table
 		void free_state() { free_pool(allocs); cap = 0; }
 		void destroy()
 		{
@@ -500,6 +531,17 @@ static void prof_cancel(rt_ctx* c)
 	(void)hipEventDestroy(c->timers.back().b);
 	c->timers.pop_back();
 	c->timerKind.pop_back();
+}
+// One build of a table of the dense pipeline (primary, bounce, chain: rt_api_render.inc) on the batch's stream: the work heads reset, a grid
+// for a queue of n rays, the COUNT twin on counting launches.  prof >= 0: the build opens a profile entry of that kind behind the reset (the
+// caller closes it).  args: the kernel's own, between the camera and t_min.
+template <class K, class... A>
+static int build_table(rt_ctx* c, hipStream_t st, const K (&twins)[2], size_t n, int resident, int prof, const A&... args)
+{
+	HIPCHK(c, hipMemsetAsync(c->flags + 16, 0, RT_HEADS * RT_HEAD_STRIDE * sizeof(int), st)); // work heads: every build starts them again
+	if (prof >= 0) prof_begin(c, prof, st);
+	hipLaunchKernelGGL(twins[c->counting ? 1 : 0], dim3(short_grid(n, resident, RT_CHUNK)), dim3(RT_BLOCK), 0, st, c->S, c->C, args..., 0.001f, tuning(c), c->spill, c->flags + 16, &c->dense.T.counts[SC_FLAG], c->counters);
+	return RT_OK;
 }
 static void prof_collect(rt_ctx* c)
 {

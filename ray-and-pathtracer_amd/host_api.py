@@ -39,7 +39,7 @@ RT_SYMBOLS = ["rt_device_count", "rt_create", "rt_destroy", "rt_last_error", "rt
               "rt_set_pixel_filter", "rt_get_pixel_filter", "rt_sample_rays",
               "rt_set_lens", "rt_get_lens", "rt_focus_at",
               "rt_set_shutter", "rt_get_shutter",
-              "rt_layout_build", "rt_layout_array", "rt_layout_free",
+              "rt_layout_build", "rt_layout_array", "rt_layout_free", "rt_launch_form", "rt_any_hit_walk",
               "rt_set_instances", "rt_set_instance_list", "rt_download_tlas", "rt_scene_array",
               "rt_set_triangles", "rt_blas_array",
               "rt_set_mesh_indices", "rt_set_vertices", "rt_set_vertices_device",
@@ -277,6 +277,8 @@ def rt_lib():
         L.rt_layout_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.rt_layout_array.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.rt_layout_free.argtypes = [C.c_void_p]
+        L.rt_launch_form.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rt_any_hit_walk.argtypes = [C.c_int, C.c_int, C.c_int]
         L.rt_set_instances.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.rt_set_instance_list.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.rt_download_tlas.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1297,6 +1299,25 @@ def layout(desc, wide=-1, wide8=0, tlas_lds=1):
         return out
     finally:
         L.rt_layout_free(h)
+
+
+LAUNCH_FORM_FIELDS = ["generate", "shade", "light", "light_mixed", "bt", "p", "masked", "fresh"]
+
+
+def launch_form(facts, rnd):
+    """rt_launch_form: what round 'rnd' of a dense path batch launches, as a dict named by LAUNCH_FORM_FIELDS.  facts: (primary table current,
+    bounce table current, chain levels, RT_BOUNCE_TABLE != 0, RT_ROUND0_ENTRIES, sampler on, fisheye, rounds).  Needs no device."""
+    L = rt_lib()
+    f, out = (C.c_int32 * 8)(*[int(v) for v in facts]), (C.c_int32 * 8)()
+    rc = L.rt_launch_form(f, int(rnd), out)
+    if rc != 0:
+        raise RuntimeError("rt_launch_form: %d: %s" % (rc, L.rt_last_error(None).decode()))
+    return dict(zip(LAUNCH_FORM_FIELDS, out))
+
+
+def any_hit_walk(counting, wide, wide8):
+    """rt_any_hit_walk: 0 binary, 1 counting, 2 4-wide, 4 8-wide.  Needs no device."""
+    return rt_lib().rt_any_hit_walk(int(counting), int(bool(wide)), int(bool(wide8)))
 
 
 def device_pci_bus_id(device):
