@@ -310,6 +310,21 @@ class OracleScene:
         self.L.orc_scope_occluded(self.h, scope, index, len(O), _p(O), _p(D), tm, _p(out))
         return out
 
+    def stack_peaks(self, O, D, tmax=None, any_hit=False, scope=0, index=0, t_min=1e-6):
+        """Per ray, the highest stack pointer its walk reached: dict(blas, tlas, stacked) of uint32 arrays.  blas / tlas: on the own
+        stack[64] of bvh::BIntersect (BIsOccluded with any_hit) / tlas::Intersect (IsOccluded); stacked: on one stack that holds both, the
+        TLAS pointer at an instance's entry + 1 + the pointer inside the BLAS, which is how the device keeps them (without a TLAS: blas).
+        scope 0: Scene::FindNearest / IsOccluded(Ray&), 1 .. 3 as scope_nearest.  A tally beside the walk; no result depends on it."""
+        O = np.ascontiguousarray(O, dtype=np.float32).reshape(-1, 3)
+        D = np.ascontiguousarray(D, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros((len(O), 3), dtype=np.uint32)
+        tm = None if tmax is None else _p(np.ascontiguousarray(tmax, dtype=np.float32))
+        if any_hit:
+            self.L.orc_peaks_occluded(self.h, int(scope), int(index), len(O), _p(O), _p(D), tm, _p(out))
+        else:
+            self.L.orc_peaks_nearest(self.h, int(scope), int(index), len(O), _p(O), _p(D), tm, C.c_float(t_min), _p(out))
+        return dict(blas=out[:, 0].copy(), tlas=out[:, 1].copy(), stacked=out[:, 2].copy())
+
     def sky_color(self, D):
         D = np.ascontiguousarray(D, dtype=np.float32).reshape(-1, 3)
         out = np.zeros((len(D), 3), dtype=np.float32)
@@ -373,6 +388,15 @@ class OracleRenderer:
         out = np.zeros((len(O), 3), dtype=np.float32)
         self.L.orc_trace_rays(self.h, mode, len(O), _p(O), _p(D), depth, _f3(energy), C.c_uint(seed_base), _p(out))
         return out
+
+    def trace_rays_peaks(self, mode, O, D, depth=4, energy=(1, 1, 1), seed_base=0x12345678):
+        """trace_rays, and per ray the peak stack pointers (OracleScene.stack_peaks) over every walk of its tree or path: (rgb, dict)"""
+        O = np.ascontiguousarray(O, dtype=np.float32).reshape(-1, 3)
+        D = np.ascontiguousarray(D, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros((len(O), 3), dtype=np.float32)
+        pk = np.zeros((len(O), 3), dtype=np.uint32)
+        self.L.orc_trace_rays_peaks(self.h, mode, len(O), _p(O), _p(D), depth, _f3(energy), C.c_uint(seed_base), _p(out), _p(pk))
+        return out, dict(blas=pk[:, 0].copy(), tlas=pk[:, 1].copy(), stacked=pk[:, 2].copy())
 
     def accumulator(self):
         out = np.zeros((self.hgt, self.w, 4), dtype=np.float32)

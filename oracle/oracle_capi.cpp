@@ -269,6 +269,41 @@ int orc_scope_occluded(void* h, int scope, int index, int n, const float* O, con
 	}
 	return 0;
 }
+// The peak stack pointers of each ray's walk (Counters::sp_blas, sp_tlas, sp_stacked: peaks[3 * i ..]), for the query orc_find_nearest_batch
+// (scope 0, with t_min) or orc_scope_nearest (scope 1 .. 3) makes of it.  A tally: the walks are the ones above, their results are not returned.
+static void peaks_out(const Counters& c, unsigned* p) { p[0] = c.sp_blas, p[1] = c.sp_tlas, p[2] = c.sp_stacked; }
+int orc_peaks_nearest(void* h, int scope, int index, int n, const float* O, const float* D, const float* tmax, float t_min, unsigned* peaks)
+{
+	const Scene& sc = ((OrcScene*)h)->sc;
+	Counters cnt;
+	for (int i = 0; i < n; i++) {
+		Ray r(f3(O + 3 * i), f3(D + 3 * i), tmax ? tmax[i] : 1e34f);
+		r.objIdx = -1;
+		cnt.clear_peaks();
+		if (scope == 0) sc.FindNearest(r, t_min, cnt);
+		else if (scope == 1) { if (sc.useTLAS) sc.tl->Intersect(r, cnt); else sc.b->Intersect(r, cnt); }
+		else if (scope == 2) (sc.useTLAS ? sc.blasList[index] : sc.b)->Intersect(r, cnt);
+		else sc.instances[index]->BIntersect(r, cnt);
+		peaks_out(cnt, peaks + 3 * i);
+	}
+	return 0;
+}
+// ... of orc_is_occluded_batch (scope 0) or orc_scope_occluded (scope 1 .. 3)
+int orc_peaks_occluded(void* h, int scope, int index, int n, const float* O, const float* D, const float* tmax, unsigned* peaks)
+{
+	const Scene& sc = ((OrcScene*)h)->sc;
+	Counters cnt;
+	for (int i = 0; i < n; i++) {
+		Ray r(f3(O + 3 * i), f3(D + 3 * i), tmax ? tmax[i] : 1e34f);
+		cnt.clear_peaks();
+		if (scope == 0) sc.IsOccluded(r, cnt);
+		else if (scope == 1) { if (sc.useTLAS) sc.tl->IsOccluded(r, cnt); else sc.b->IsOccluded(r, cnt); }
+		else if (scope == 2) (sc.useTLAS ? sc.blasList[index] : sc.b)->IsOccluded(r, cnt);
+		else sc.instances[index]->IsOccluded(r, cnt);
+		peaks_out(cnt, peaks + 3 * i);
+	}
+	return 0;
+}
 // Scene::GetSkyColor (template/scene.h:1312-1327) for n directions
 void orc_sky_color(void* h, int n, const float* D, float* rgb)
 {
@@ -414,16 +449,27 @@ int orc_tick(void* h, int* camChanged, unsigned frame, unsigned seedBase, int nt
 }
 // Renderer::Trace (mode 0) / Renderer::Sample (mode 1) on caller rays with a caller energy; ray i draws from the
 // stream StreamSeed(seedBase + i), as rt_trace_batch does
-void orc_trace_rays(void* h, int mode, int n, const float* O, const float* D, int depth, const float* energy, unsigned seedBase, float* rgb)
+static void trace_rays(void* h, int mode, int n, const float* O, const float* D, int depth, const float* energy, unsigned seedBase, float* rgb, unsigned* peaks)
 {
 	Renderer& r = ((OrcRenderer*)h)->r;
 	Counters cnt;
 	for (int i = 0; i < n; i++) {
 		uint seed = StreamSeed(seedBase + (uint)i);
 		Ray ray(f3(O + 3 * i), f3(D + 3 * i));
+		cnt.clear_peaks();
 		const float3 c = mode == 0 ? r.Trace(ray, depth, f3(energy), seed, cnt) : r.Sample(ray, depth, f3(energy), seed, cnt, 0, r.ql.on && (seed & r.ql.learnMask) == 0);
 		rgb[3 * i] = c.x, rgb[3 * i + 1] = c.y, rgb[3 * i + 2] = c.z;
+		if (peaks) peaks_out(cnt, peaks + 3 * i);
 	}
+}
+void orc_trace_rays(void* h, int mode, int n, const float* O, const float* D, int depth, const float* energy, unsigned seedBase, float* rgb)
+{
+	trace_rays(h, mode, n, O, D, depth, energy, seedBase, rgb, nullptr);
+}
+// ... and per ray the peak stack pointers over every walk of its tree or path (nearest-hit and shadow rays alike): peaks[3 * i ..]
+void orc_trace_rays_peaks(void* h, int mode, int n, const float* O, const float* D, int depth, const float* energy, unsigned seedBase, float* rgb, unsigned* peaks)
+{
+	trace_rays(h, mode, n, O, D, depth, energy, seedBase, rgb, peaks);
 }
 void orc_get_accumulator(void* h, float* out) { const Renderer& r = ((OrcRenderer*)h)->r; memcpy(out, r.accumulator.data(), r.accumulator.size() * 16); }
 // screen->pixels for iteration count 'it' (renderer.cpp:287-290)

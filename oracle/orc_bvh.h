@@ -377,7 +377,7 @@ struct bvh {
 				if (stackPtr == 0) break; else node = stack[--stackPtr];
 			} else {
 				node = c1;
-				if (dist2 != 1e30f) stack[stackPtr++] = c2;
+				if (dist2 != 1e30f) { stack[stackPtr++] = c2; cnt.note_blas(stackPtr); }
 			}
 		}
 	}
@@ -407,7 +407,7 @@ struct bvh {
 				if (stackPtr == 0) return false; else node = stack[--stackPtr];
 			} else {
 				node = c1;
-				if (dist2 != 1e30f) stack[stackPtr++] = c2;
+				if (dist2 != 1e30f) { stack[stackPtr++] = c2; cnt.note_blas(stackPtr); }
 			}
 		}
 	}
@@ -529,7 +529,9 @@ struct tlas {
 			const TLASNode& n = tlasNode[node];
 			if (n.isLeaf()) {
 				cnt.instance_visits++;
+				cnt.enter_instance(stackPtr);
 				blas[n.BLAS]->BIntersect(ray, cnt);
+				cnt.leave_instance();
 				if (stackPtr == 0) break; else node = stack[--stackPtr];
 				continue;
 			}
@@ -543,7 +545,7 @@ struct tlas {
 				if (stackPtr == 0) break; else node = stack[--stackPtr];
 			} else {
 				node = child1;
-				if (dist2 != 1e30f) stack[stackPtr++] = child2;
+				if (dist2 != 1e30f) { stack[stackPtr++] = child2; cnt.note_tlas(stackPtr); }
 			}
 		}
 	}
@@ -555,7 +557,10 @@ struct tlas {
 			const TLASNode& n = tlasNode[node];
 			if (n.isLeaf()) {
 				cnt.instance_visits++;
-				if (blas[n.BLAS]->IsOccluded(ray, cnt)) return true;
+				cnt.enter_instance(stackPtr);
+				const bool occluded = blas[n.BLAS]->IsOccluded(ray, cnt);
+				cnt.leave_instance();
+				if (occluded) return true;
 				if (stackPtr == 0) break; else node = stack[--stackPtr];
 				continue;
 			}
@@ -569,7 +574,7 @@ struct tlas {
 				if (stackPtr == 0) break; else node = stack[--stackPtr];
 			} else {
 				node = child1;
-				if (dist2 != 1e30f) stack[stackPtr++] = child2;
+				if (dist2 != 1e30f) { stack[stackPtr++] = child2; cnt.note_tlas(stackPtr); }
 			}
 		}
 		return false;

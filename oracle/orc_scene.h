@@ -29,11 +29,25 @@ struct Counters {
 	uint64_t brute_tests = 0;    // TLAS-mode brute force sphere / plane tests (template/scene.h:1260-1261)
 	uint64_t light_tests = 0;    // light->Intersect calls (template/scene.h:1257)
 	uint64_t tri_intersect_calls = 0; // Triangle::Intersect calls from BIntersect leaves (bvh.cpp:619): the figure gprof reports for the reference
+	// Peak stack pointers of the walks since the last clear_peaks(): a tally beside the walks, read by nothing that computes a result.
+	// sp_blas / sp_tlas: the highest stackPtr bvh::BIntersect / BIsOccluded and tlas::Intersect / IsOccluded reached on their own stack[64];
+	// sp_stacked: what ONE stack holding both would have reached, the TLAS pointer at an instance's entry + 1 (a marker to come back by) +
+	// the BLAS pointer inside it (the device's layout); without a TLAS it is sp_blas.
+	uint32_t sp_blas = 0, sp_tlas = 0, sp_stacked = 0;
+	uint32_t sp_base = 0; // entries below the BLAS walk that is running: 0 outside an instance, the TLAS pointer + 1 inside one
+	void clear_peaks() { sp_blas = sp_tlas = sp_stacked = sp_base = 0; }
+	void note_blas(uint32_t sp) { if (sp > sp_blas) sp_blas = sp; if (sp_base + sp > sp_stacked) sp_stacked = sp_base + sp; }
+	void note_tlas(uint32_t sp) { if (sp > sp_tlas) sp_tlas = sp; if (sp > sp_stacked) sp_stacked = sp; }
+	void enter_instance(uint32_t tlasSp) { sp_base = tlasSp + 1; note_blas(0); }
+	void leave_instance() { sp_base = 0; }
 	void add(const Counters& o)
 	{
 		inner_visits += o.inner_visits; prim_tests += o.prim_tests; tlas_inner += o.tlas_inner;
 		instance_visits += o.instance_visits; rays_nearest += o.rays_nearest; rays_occluded += o.rays_occluded;
 		brute_tests += o.brute_tests; light_tests += o.light_tests; tri_intersect_calls += o.tri_intersect_calls;
+		if (o.sp_blas > sp_blas) sp_blas = o.sp_blas;
+		if (o.sp_tlas > sp_tlas) sp_tlas = o.sp_tlas;
+		if (o.sp_stacked > sp_stacked) sp_stacked = o.sp_stacked;
 	}
 };
 

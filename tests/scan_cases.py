@@ -18,6 +18,7 @@ tlas_test2_BigB  0.0044 / 0.836 / 0.836  |  0.0034 / 0.712 / 0.712  |  0.0186 / 
 pretty_tlas_1    0.0010 / 0.748 / 0.748  |  0.0010 / 0.623 / 0.623  |  0.0010 / 0.562 / 0.562
 pretty_tlas_8    0.0010 / 0.763 / 0.763  |  0.0000 / 0.643 / 0.643  |  0.0010 / 0.569 / 0.569
 deep_tree        0.0078 / 0.731 / 0.731  |  0.0066 / 0.602 / 0.602  |  0.0322 / 0.638 / 0.638
+deep_chain       0.0000 / 0.821 / 0.821  |  0.0000 / 0.696 / 0.696  |  0.0000 / 0.618 / 0.618
 two_prims        0.0039 / 0.706 / 0.706  |  0.0029 / 0.599 / 0.599  |  0.0049 / 0.524 / 0.524
 one_leaf         0.0015 / 0.681 / 0.681  |  0.0010 / 0.564 / 0.564  |  0.0015 / 0.504 / 0.504
 moving           0.0034 / 0.725 / 0.725  |  0.0029 / 0.604 / 0.604  |  0.0083 / 0.536 / 0.536
@@ -100,6 +101,28 @@ def _deep_tree(b, scenes):
     b.build(2)
 
 
+def _deep_chain(b, scenes):
+    """the 24-triangle chain of tests/spill_cases.py with wider triangles (base -0.45 .. 1.45, apex at 1.25: four rays in five of the set
+    below hit one): under LONGESTAXIS a tree 24 levels deep that a ray along +x walks to the bottom, pushing the far leaf at every
+    level -- the walk's stack pointer peaks at 23, past the rows kept in LDS, and the deep walks are held to the tree-free rule too"""
+    import spill_cases
+    t = spill_cases.chain_tris(24)
+    t[:, 1], t[:, 4], t[:, 8] = -0.45, 1.45, 1.25
+    b.mesh_raw(1, b.diffuse(0.8, (1, 1, 1)), t)
+    b.build(2)
+
+
+def _chain_rays(name, o, rec):
+    """three in four along +x from in front of the chain (direction (1, +-1e-21, +-1e-21): finite, non-zero, no drift to speak of), the
+    others from between the last triangles and back along -x from beyond the far end, interleaved"""
+    import spill_cases
+    n = CASES[name]["n"]
+    rng = np.random.default_rng(sum(name.encode()) * 7919 + 1)
+    c = dict(spill_cases.CASES["chain_p23"])
+    O, D, _, _ = spill_cases._mix(rng, spill_cases._chain_parts(rng, c, n - 1 - 2 * (n // 8), n // 8))
+    return O, D
+
+
 def _two_prims(b, scenes):
     """a BLAS of two triangles under one instance that scales (x2.5), turns and moves it: the instance ray's direction is not unit"""
     m = b.mesh_raw(1, b.diffuse(0.8, (1, 1, 1)), np.array([[0, 0, 0, 1, 0, 0, 0, 1, 0.25], [0.2, 0.1, 0.5, 1.1, 0.3, 0.6, 0.1, 1.2, 0.4]], F32))
@@ -131,8 +154,8 @@ def _moving(b, scenes):
 # the deep tree's coplanar triangles leave a ray aimed at a vertex or an edge undecided more often than a mesh's, so it aims at centroids.
 # A ray stopped one ulp behind a hit in a box without thickness is undecided about one time in three (the plane's t is a quotient, the
 # slab's a product with the reciprocal), so the deep tree's 'hit_ulp' set places such a tmax on one ray of eight, not of four.
-def _case(fill, n, random=0.15, nonunit=0.5, targets=(1, 1, 1), ulp_every=4):
-    return dict(fill=fill, n=n, random=random, nonunit=nonunit, targets=targets, ulp_every=ulp_every)
+def _case(fill, n, random=0.15, nonunit=0.5, targets=(1, 1, 1), ulp_every=4, make=None):
+    return dict(fill=fill, n=n, random=random, nonunit=nonunit, targets=targets, ulp_every=ulp_every, make=make)
 
 
 CASES = {
@@ -144,12 +167,14 @@ CASES = {
     "pretty_tlas_1": _case(lambda b, s: s.pretty_tlas(b, 1), 2048),
     "pretty_tlas_8": _case(lambda b, s: s.pretty_tlas(b, 8), 1024),
     "deep_tree": _case(_deep_tree, 4096, 0.05, targets=(1, 1, 30), ulp_every=8),
+    "deep_chain": _case(_deep_chain, 4096, make=_chain_rays),  # its own rays: the mix below aims from every side and never walks deep
     "two_prims": _case(_two_prims, 2048, 0.05, targets=(1, 1, 4)),
     "one_leaf": _case(_one_leaf, 2048, 0.05, targets=(1, 1, 4)),
     "moving": _case(_moving, 4096),
 }
 LARGE = ("tlas_test2_BigB", "pretty_tlas_1", "pretty_tlas_8")  # 12 to 100 thousand triangles: fewer rays, and fewer repeats in the tests
 SMALL = ("mixed_small_s0", "mixed_small_s1", "mixed_small_s2", "mixed_small_s3", "deep_tree", "two_prims", "one_leaf")
+DEEP_WALKS = ("deep_chain",)  # (apart from SMALL: set_time would turn the chain about z, and its rays are made for the chain as it is)
 
 
 def fill(name, b, scenes):
@@ -221,6 +246,10 @@ def _nudge(d, rng):
 def make_rays(name, o, rec):
     """the case's ray set (O, D), seeded by its name"""
     case = CASES[name]
+    if case["make"]:
+        O, D = case["make"](name, o, rec)
+        assert np.isfinite(O).all() and np.isfinite(D).all() and (D != 0).all() and len(O) <= 8192, name
+        return O, D
     n, random_share = case["n"], case["random"]
     rng = np.random.default_rng(sum(name.encode()) * 7919 + 1)
     tris, sph = world_geometry(o, rec)

@@ -940,34 +940,64 @@ def test_more_than_eight_lights(scenes, oracle_api, host_api):
     r.close()
 
 
-def test_deep_tree_uses_the_spill_stack(oracle_api, host_api):
-    """A degenerate LONGESTAXIS tree over geometrically spaced triangles is deeper than the 15 stack
-    entries kept in LDS: the global spill part of the traversal stack must give the same hits."""
-    n = 40
-    tris = []
-    for i in range(n):
-        x = 2.0 ** i * 1e-6
-        tris.append([x, 0, 1, x, 1, 1, x * 1.1, 0, 1])
-    tris = np.array(tris, dtype=np.float32)
-    def fill(s):
-        m = s.diffuse(0.8, (1, 1, 1))
-        s.mesh_raw(1, m, tris)
-        s.build(2)  # LONGESTAXIS: halves the extent, peeling off one triangle per level
-    o = oracle_api.OracleScene(); fill(o)
-    r = host_api.HostRenderer(8, 8); fill(r.scene); r.commit()
-    assert o.bvh_dump(-1)["max_depth"] > 20
+STACK_ROWS_MAX = 14  # csrc/rt_scene_dev.h RT_STACK_ROWS_MAX at RT_LDS_WORDS = 5120: the stack entries a lane keeps in LDS, at most
+
+
+def deep_tree_fill(s):
+    """40 triangles, flat in z, geometrically spaced along x, under LONGESTAXIS: halves the extent, peeling off one triangle per level"""
+    tris = np.array([[x, 0, 1, x, 1, 1, x * 1.1, 0, 1] for x in (2.0 ** i * 1e-6 for i in range(40))], dtype=np.float32)
+    s.mesh_raw(1, s.diffuse(0.8, (1, 1, 1)), tris)
+    s.build(2)
+
+
+def deep_tree_rays_along_z():
     rng = np.random.default_rng(0)
     O = np.stack([rng.uniform(0, 600, 4000), rng.uniform(0, 1, 4000), np.zeros(4000)], 1).astype(np.float32)
     O[:, 0] = np.exp(rng.uniform(np.log(1e-6), np.log(600.0), 4000)).astype(np.float32)
     D = np.tile(np.array([[0, 0, 1]], np.float32), (4000, 1))
     D[:, 0] = rng.uniform(-0.05, 0.05, 4000).astype(np.float32)
     D /= np.linalg.norm(D, axis=1, keepdims=True).astype(np.float32)
+    return O, D
+
+
+def test_deep_tree_uses_the_spill_stack(oracle_api, host_api):
+    """Two degenerate LONGESTAXIS trees.  The first, 40 flat triangles met by rays along z, is 40 levels deep, but its walks never push:
+    the two children of every node are disjoint in x, so at most one is hit (tests/test_spill_cpu.py records the oracle's peak stack
+    pointer for these rays: 0).  It holds the descent through a deep chain of nodes, hits and occlusion flags, to the oracle.  The spill
+    half of the stack is reached by the second: the 24-triangle chain of tests/spill_cases.py under rays along +x, which pass every box
+    and push the far leaf at every level.  The oracle's peak there is 23, above the RT_STACK_ROWS_MAX entries kept in LDS, and the global
+    spill part of the traversal stack must give the same hits (tests/test_gpu_spill.py covers every walk and row split)."""
+    import spill_cases
+    o = oracle_api.OracleScene(); deep_tree_fill(o)
+    r = host_api.HostRenderer(8, 8); deep_tree_fill(r.scene); r.commit()
+    assert o.bvh_dump(-1)["max_depth"] > 20
+    O, D = deep_tree_rays_along_z()
     ref = o.find_nearest(O, D)
     got = r.find_nearest(O, D)
     assert (ref["obj"] != -1).sum() > 20
     assert np.array_equal(got["obj"], ref["obj"]) and np.array_equal(got["t"].view(np.uint32), ref["t"].view(np.uint32))
     assert np.array_equal(r.is_occluded(O, D), o.is_occluded(O, D)["occluded"])
     r.close()
+    o.close()
+    # the +x rays, on the tree they can walk to the bottom (the flat triangles above have boxes without thickness along the rays)
+    o = oracle_api.OracleScene(); spill_cases.fill("chain_p23", o)
+    r = host_api.HostRenderer(8, 8); spill_cases.fill("chain_p23", r.scene); r.commit()
+    R = spill_cases.rays("chain_p23")
+    O, D = R["O"], R["D"]
+    assert o.bvh_dump(-1)["max_depth"] > 20
+    for any_hit in (False, True):
+        assert o.stack_peaks(O, D, any_hit=any_hit)["stacked"].max() > STACK_ROWS_MAX
+    ref = o.find_nearest(O, D)
+    got = r.find_nearest(O, D)
+    assert (ref["obj"] != -1).sum() > 20
+    assert np.array_equal(got["obj"], ref["obj"]) and np.array_equal(got["t"].view(np.uint32), ref["t"].view(np.uint32))
+    assert np.array_equal(got["normal"][ref["obj"] != -1].view(np.uint32), ref["normal"][ref["obj"] != -1].view(np.uint32))
+    occ = o.is_occluded(O, D)["occluded"]
+    assert np.array_equal(r.is_occluded(O, D), occ)
+    r.set_counting(True)  # the reference's binary walk (the default any-hit walk of a scene BVH is the 4-wide one)
+    assert np.array_equal(r.is_occluded(O, D), occ)
+    r.close()
+    o.close()
 
 
 @pytest.mark.parametrize("name,kw", [("pretty_tlas", {"n_instances": 8}), ("pretty_tlas", {"n_instances": 3}), ("tlas_test2", {})])

@@ -18,11 +18,13 @@ import vertices_ref as vr
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 MODES = {"default": ({}, False), "counting": ({}, True), "tlas_in_global": ({"RT_TLAS_LDS": "0"}, False), "wide4": ({"RT_WIDE": "1"}, False),
-         "wide8": ({"RT_WIDE8": "1"}, False)}
+         "wide8": ({"RT_WIDE8": "1"}, False), "binary": ({"RT_WIDE": "0"}, False)}
 MODE_CASES = [(m, n) for n in sc.CASES for m in ("default", "counting")] + \
              [("tlas_in_global", n) for n in ("tlas_test2_BigB", "pretty_tlas_8", "two_prims", "moving")] + \
-             [("wide4", n) for n in ("mixed_small_s0", "deep_tree", "tlas_test2_BigB", "two_prims", "one_leaf")] + \
-             [("wide8", n) for n in ("deep_tree", "tlas_test2_BigB", "two_prims", "one_leaf")]  # (no 8-wide layout with spheres or planes in the tree)
+             [("wide4", n) for n in ("mixed_small_s0", "deep_tree", "deep_chain", "tlas_test2_BigB", "two_prims", "one_leaf")] + \
+             [("wide8", n) for n in ("deep_tree", "deep_chain", "tlas_test2_BigB", "two_prims", "one_leaf")] + \
+             [("binary", "deep_chain")]  # (no 8-wide layout with spheres or planes in the tree; binary: a scene BVH's any-hit walk is 4-wide by
+                                         # default, and on the chain only the binary one goes deep enough to spill)
 
 
 def _renderer(host_api, monkeypatch, scenes, name, env=None, w=16, h=8, device_build=False):
